@@ -7,7 +7,12 @@ image whose f64 planar pixels are ALREADY RESIDENT IN HBM when the timed region 
 `value`).  Default workload = the configuration the metric is quoted on ("256-color ICtCp +
 KMeans"): BASELINE.json configs[2], 4096x4096, K=256, ICtCp, KMeans 32 it / 512^2 samples, dither off.
 
-  python bench.py --gpus N --steps K --warmup W [--config c2|c3|c3full|c3sal|c4|c4map|c4km] [--no-cpu-baseline]
+  python bench.py --gpus N --steps K --warmup W [--config c2|c3|c3full|c3sal|c4|c4map|c4km] [--dump-outputs DIR]
+                  [--full [--no-cpu-baseline] [--no-extras] [--no-profile] [--extra-streams S]]
+
+A plain run sets up, warms up, times the K steps and prints the line: nothing else.  --full adds, all outside the timed
+region except the sampled kernel events: per-kernel HIP events (roofline, kernels), first_call, throughput_concurrent, the
+extras of the c3 run (north_star_kernels, host_to_host, content, ...) and the CPU baseline with its parity record.
 
 N > 1: one process per GPU (torch.distributed, backend nccl = RCCL); images are independent, so the
 ranks shard the batch with NO data-path collective ("scaling": "weak": every rank quantises its own
@@ -41,6 +46,25 @@ CONFIGS = {
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (spec)
 EVENT_SAMPLE = 4                      # the roofline kernel carries HIP events on every 4th launch inside the timed region (4 and the
                                       # 9 launches per image are coprime: every split level is sampled over the steps)
+DUMP_BYTES = 64 * 10 ** 6             # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path, pals, maps, n):
+    """--dump-outputs: what the timed path returned in its last step, one row per image of that step (every rank's, every
+    stream's).  palette.npy = the f64 palettes as returned; index_map.npy = the u8 index maps as float32, whole where they fit in
+    DUMP_BYTES, else the same fixed sample of pixels (seed 0, sorted) of every map, whose pixel numbers are index_map_pixels.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    pals = np.stack(pals).astype(np.float64)
+    np.save(os.path.join(path, "palette.npy"), pals)
+    room = DUMP_BYTES - pals.nbytes
+    if len(maps) * n * 4 <= room:
+        np.save(os.path.join(path, "index_map.npy"), np.stack(maps).astype(np.float32))
+        return
+    s = min(n, 1 << 21, room // (4 * len(maps) + 8))
+    px = np.sort(np.random.default_rng(0).choice(n, size=s, replace=False))
+    np.save(os.path.join(path, "index_map.npy"), np.stack([m[px] for m in maps]).astype(np.float32))
+    np.save(os.path.join(path, "index_map_pixels.npy"), px.astype(np.float64))
 
 
 class Runner:
@@ -651,9 +675,14 @@ def main():
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the untimed extras of the default run: north_star_kernels, host_to_host")
-    ap.add_argument("--no-profile", action="store_true", help="do not record per-kernel HIP events in the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps measure and check everything else the line reports: per-kernel HIP events (roofline, "
+                         "kernels), first_call, throughput_concurrent, the extras of the c3 run, cpu_baseline and parity")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what the last one returned (palettes, index maps) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline and parity")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the untimed extras of the c3 run: north_star_kernels, host_to_host, ...")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: do not record per-kernel HIP events in the timed region")
     ap.add_argument("--force-dist", action="store_true", help="take the torch.distributed (RCCL) path even with one rank")
     ap.add_argument("--oversubscribe", action="store_true",
                     help="TEST MODE, never a measurement of scaling: the N ranks share the GPUs the box has (rank r on device r mod count) and the "
@@ -664,7 +693,7 @@ def main():
                          "maps and palettes with them (reported as gather_check)")
     ap.add_argument("--streams", type=int, default=1, help="images quantised concurrently per GPU and step in the timed region")
     ap.add_argument("--extra-streams", type=int, default=6,
-                    help="after the timed region also measure throughput with this many concurrent images per GPU; reported "
+                    help="with --full: after the timed region also measure throughput with this many concurrent images per GPU; reported "
                          "separately as throughput_concurrent, never as `value` (0 = skip)")
     ap.add_argument("--kmeans-update", type=int, default=0, choices=[0, 1],
                     help="1: the order-free centroid update (patolette_amd_set_kmeans_update(1)): NOT the reference's bits and OUTSIDE north_star's "
@@ -672,6 +701,9 @@ def main():
                          "~0.02 %% of the index map follows (tests/test_gpu_kmeans_update.py); the line says so in config.kmeans_update and is "
                          "never the headline")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    profile = args.full and not args.no_profile
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: start the N ranks here (one process per GPU, RCCL), exactly as the driver's
@@ -726,8 +758,10 @@ def main():
     width, height, K, cs, niter, max_samples, dither, weighted, desc = cfg
     n = width * height
     S = max(1, args.streams)
-    S2 = max(0, args.extra_streams)
-    pool = max(S, min(S2, 3), min(3, args.steps))        # distinct images; more in flight than that re-use them (read-only)
+    S2 = max(0, args.extra_streams) if args.full else 0
+    # distinct images; more in flight than that re-use them (read-only).  The pool does not depend on --full: a plain run
+    # quantises the same images
+    pool = max(S, min(max(0, args.extra_streams), 3), min(3, args.steps))
     d_imgs, d_wts = [], []
     for i in range(pool):
         if weighted == "saliency":
@@ -773,7 +807,7 @@ def main():
     # roofline figure); the per-kernel table comes from one extra, untimed, fully timed step afterwards.
     dom_name = None
     for i in range(args.warmup):
-        if not args.no_profile and i == args.warmup - 1:
+        if profile and i == args.warmup - 1:
             _native.profile(True)
         run.step(i)
         if dist is not None:
@@ -786,14 +820,14 @@ def main():
             dist.gather(pw_t, gp, dst=0)
             torch.cuda.synchronize()
             del gl, gp
-    if not args.no_profile and args.warmup > 0:
+    if profile and args.warmup > 0:
         L.patolette_amd_synchronize()
         pw = _native.profile_results()
         if pw:
             dom_name = max(pw, key=lambda k: pw[k]["total_ms"])
         _native.profile(False)
     barrier()
-    if not args.no_profile:
+    if profile:
         _native.profile(True, only=dom_name, sample=EVENT_SAMPLE)
     gathered, works = [], []
     t0 = time.perf_counter()
@@ -816,16 +850,29 @@ def main():
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     stats = _native.last_stats()
+    if args.dump_outputs and rank == 0:
+        # taken before anything else runs: the untimed steps of --full reuse the result slots
+        last = args.warmup + args.steps - 1
+        if dist is None:
+            maps = []
+            for j in range(S):
+                m8 = np.empty(n, dtype=np.uint8)
+                assert L.patolette_amd_memcpy_d2h(m8.ctypes.data_as(C.c_void_p), map_ptr(last, j), n) == 0
+                maps.append(m8)
+            dump_outputs(args.dump_outputs, list(pals[last * S:(last + 1) * S]), maps, n)
+        else:
+            last_pals = [gl_p[r][(args.steps - 1) * S + j].cpu().numpy() for r in range(world) for j in range(S)]
+            dump_outputs(args.dump_outputs, last_pals, [gathered[-1][r][j].cpu().numpy() for r in range(world) for j in range(S)], n)
     # the palette a TIMED step produced for rank 0's image 0 (seed 0): what `parity` below holds to the oracle
     pal_timed = None
     for i in range(args.steps):
         if ((args.warmup + i) * S) % len(d_imgs) == 0:
             pal_timed = pals[(args.warmup + i) * S].copy()
             break
-    prof = _native.profile_results() if not args.no_profile else {}
+    prof = _native.profile_results() if profile else {}
     _native.profile(False)
     prof_full = prof
-    if not args.no_profile and dom_name is not None:
+    if profile and dom_name is not None:
         _native.profile(True)
         run.step(args.warmup + args.steps - 1)          # untimed: every kernel carries events
         L.patolette_amd_synchronize()
@@ -833,7 +880,7 @@ def main():
         _native.profile(False)
     # ---- what a FIRST call of an image size costs (the subsample list made again in every call), outside the timed region ----
     cold = None
-    if niter > 0 and S == 1 and args.steps > 0:
+    if args.full and niter > 0 and S == 1:
         prev = L.patolette_amd_set_subsample_cache(0)
         try:
             tt = []
@@ -953,7 +1000,7 @@ def main():
 
     # ---- extras of the default run, all outside the timed region ----
     ns_kernels = h2h = h2h_u8 = content = small = dflt = dcontent = None
-    if not args.no_extras and world == 1 and args.config == "c3":
+    if args.full and not args.no_extras and world == 1 and args.config == "c3":
         small = small_image(L, _native)
         dcontent = dither_content(L, _native)
         h2h = host_to_host(L, _native, cfg)
@@ -971,7 +1018,7 @@ def main():
     cpu = None
     parity = None
     dither_cmp = None
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         from oracle import binding as ob
         ncores = os.cpu_count() or 1
         sw, sh = width, height                                # the full workload (default config: ~10 + ~17 s; c4 / c4map: ~1 min a run)
@@ -1049,7 +1096,7 @@ def main():
                                            "between calls; a first call makes it on a helper thread beside conversion and the quantisers -- "
                                            "`first_call` is the same step with the list made again in every call; a pool of <= 3 distinct images "
                                            "rotates through the steps",
-                   "kernel_events_in_timed_region": ("none" if args.no_profile else
+                   "kernel_events_in_timed_region": ("none" if not profile else
                                                      ("dominant kernel only (%s), every %d-th launch (two event records cost ~12 us per launch); "
                                                       "per-kernel table from one extra untimed step" % (dom_name, EVENT_SAMPLE)
                                                       if dom_name else "all kernels")),

@@ -4,6 +4,7 @@
 Sources of truth, per file:
   color_ref.npz    outputs of the REFERENCE's own colour code: oracle/_ref/libref_color.so =
                    /root/reference/lib/src/color/*.c + lib/src/array/*.c compiled as they lie.
+  color_live_ref.json  SHA-256 digests of the same library's outputs on a 50 000-pixel image.
   eigen_lapack.npz outputs of LAPACK dsyev('V','L') from the OpenBLAS 0.3.28 that ships in this
                    image (scipy.linalg.lapack.dsyev) -- the third-party routine the reference
                    calls at lib/src/math/eigen.c:105-136.
@@ -21,6 +22,8 @@ Inputs are regenerated from the in-repo splitmix64 generator (orc_fill_*), so on
 and outputs are stored.  Nothing from /root/reference is copied: fixtures are data.
 """
 import ctypes as C
+import hashlib
+import json
 import os
 import sys
 
@@ -88,6 +91,26 @@ def make_color():
     out["cieluv_to_ictcp"] = chain
     np.savez_compressed(os.path.join(OUT, "color_ref.npz"), **out)
     print("color_ref.npz written")
+
+
+COLOR_LIVE_N, COLOR_LIVE_SEED = 50000, 77
+COLOR_LIVE = ["srgb_to_ictcp", "srgb_to_cieluv", "srgb_to_rec2020"]
+
+
+def bits_digest(a):
+    return hashlib.sha256(np.ascontiguousarray(a, dtype=np.float64).tobytes()).hexdigest()
+
+
+def make_color_live():
+    """color_live_ref.json: SHA-256 of the bits the reference's colour code returns for ob.image(50000, 77) -- a
+    bit-exact record of a larger input than color_ref.npz holds, in a few bytes."""
+    R = C.CDLL(REF_COLOR)
+    src = ob.image(COLOR_LIVE_N, COLOR_LIVE_SEED)
+    out = {"n": COLOR_LIVE_N, "seed": COLOR_LIVE_SEED, "sha256_of_f64_bits": {k: bits_digest(ref_convert(R, k, src)) for k in COLOR_LIVE}}
+    with open(os.path.join(OUT, "color_live_ref.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print("color_live_ref.json written")
 
 
 # ----------------------------------------------------------------------------- eigen
@@ -274,9 +297,11 @@ def make_pipeline():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["color", "eigen", "kmeans", "pipeline"]
+    which = sys.argv[1:] or ["color", "color_live", "eigen", "kmeans", "pipeline"]
     if "color" in which:
         make_color()
+    if "color_live" in which:
+        make_color_live()
     if "eigen" in which:
         make_eigen()
     if "kmeans" in which:
