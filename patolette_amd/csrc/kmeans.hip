@@ -1504,11 +1504,11 @@ __device__ __forceinline__ void km_block_replay(const float *blk, const float *w
 }
 // One block of up to 1024 samples (len of them real, the rest of the 1024 zero): the whole block at once; a block that fails (the
 // accumulator changes binade inside it, an exact tie) is taken quarter by quarter -- the quarters before and after a binade change hold
-// again on their own scale -- and only a failing QUARTER is replayed in order (quarters = false: the whole block is, as before round 4:
-// k_km_update 1082 -> 864 us at 67 M samples, 4.65 -> 3.42 ms over 32 iterations with a 30 % dominant colour)
-__device__ __forceinline__ void km_block_step(const float *blk, const float *wblk, const bool wx, const unsigned len, const bool quarters, float &acc, const int lane) {
+// again on their own scale -- and only a failing QUARTER is replayed in order (against replaying the whole block, as before round 4,
+// removed: k_km_update 1082 -> 864 us at 67 M samples, 4.65 -> 3.42 ms over 32 iterations with a 30 % dominant colour)
+__device__ __forceinline__ void km_block_step(const float *blk, const float *wblk, const bool wx, const unsigned len, float &acc, const int lane) {
     if (km_block_exact(blk, wblk, wx, 0, 4, acc, lane)) return;
-    if (quarters && len == 1024u) {
+    if (len == 1024u) {
         for (int q = 0; q < 4; q++)
             if (!km_block_exact(blk, wblk, wx, q, 1, acc, lane)) km_block_replay(blk, wblk, wx, (unsigned)q * 256u, (unsigned)(q + 1) * 256u, acc);
         return;
@@ -1521,8 +1521,7 @@ __device__ __forceinline__ void km_block_step(const float *blk, const float *wbl
 // then runs ITS chain over the four blocks from there -- 4 bytes per sample read per chain instead of 16 from memory, and the
 // in-order replays read the same buffer.  Two barriers per super-step; the next super-step's records are in flight meanwhile.
 template <bool W>
-__device__ __forceinline__ float km_chain_coop(const float4 *__restrict__ sorted, size_t lo, size_t hi, float *coop, int lane, int wid,
-                                               const bool km_quarters = true) {
+__device__ __forceinline__ float km_chain_coop(const float4 *__restrict__ sorted, size_t lo, size_t hi, float *coop, int lane, int wid) {
     constexpr int K = 16;
     constexpr size_t BS = (size_t)64 * K, SS = 4 * BS;
     const bool wx = W && wid < 3;                                          // weighted coordinate chain: acc = fma(x, w, acc)
@@ -1553,7 +1552,7 @@ __device__ __forceinline__ float km_chain_coop(const float4 *__restrict__ sorted
                 if (pos >= hi) break;                                      // wave-uniform
                 const size_t bend = pos + BS < hi ? pos + BS : hi;
                 const float *blk = mine + d * (int)BS, *wblk = wts + d * (int)BS;
-                km_block_step(blk, wblk, wx, (unsigned)(bend - pos), km_quarters, acc, lane);
+                km_block_step(blk, wblk, wx, (unsigned)(bend - pos), acc, lane);
             }
         }
         __syncthreads();                                                   // the buffer is rewritten by the next super-step
@@ -1568,7 +1567,7 @@ template <bool W>
 __device__ __forceinline__ float km_coop_lds(const float *mine, const float *wts, const unsigned n, const bool wx, float acc, const int lane) {
     constexpr unsigned BS = 1024;
     for (unsigned pos = 0; pos < n; pos += BS)
-        km_block_step(mine + pos, wts + pos, wx, pos + BS < n ? BS : n - pos, true, acc, lane);
+        km_block_step(mine + pos, wts + pos, wx, pos + BS < n ? BS : n - pos, acc, lane);
     return acc;
 }
 
@@ -1659,7 +1658,7 @@ __device__ __forceinline__ void km_update_finish(const int kidx, const int k, co
 template <bool W, bool BIGK = false>
 __global__ __launch_bounds__(256) void k_km_update(const float4 *__restrict__ sorted, const unsigned int *__restrict__ rowtot, int k,
                                                   unsigned long long nx, float *cent, float *hassign, float4 *c4,
-                                                  unsigned int *ticket, DevMT *mt, unsigned long long long_min, float *hs_mem, const int quarters) {
+                                                  unsigned int *ticket, DevMT *mt, unsigned long long long_min, float *hs_mem) {
     __shared__ float4 stage[4][2][64];
     extern __shared__ __attribute__((aligned(16))) float coop[];          // km_chain_coop: [4 components][4096 samples] when launched with it
     __shared__ float res[4];
@@ -1673,7 +1672,7 @@ __global__ __launch_bounds__(256) void k_km_update(const float4 *__restrict__ so
     const size_t lo = pre, hi = lo + rowtot[kidx];
     float acc = 0.f;
     if ((size_t)(hi - lo) >= long_min) {                                  // block-uniform (long_min is huge without the LDS buffer)
-        acc = km_chain_coop<W>(sorted, lo, hi, coop, lane, wid, quarters != 0);
+        acc = km_chain_coop<W>(sorted, lo, hi, coop, lane, wid);
     } else {
         if (wid == 0) acc = km_chain<W, 0>(sorted, lo, hi, stage[0], lane);
         else if (wid == 1) acc = km_chain<W, 1>(sorted, lo, hi, stage[1], lane);
@@ -1710,50 +1709,12 @@ __device__ __forceinline__ unsigned block_scan_incl_u32(const unsigned v, unsign
     return pre + inc;
 }
 
-// km_assign_one with two centroids per instruction: v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32 round each half like the scalar
-// instruction, so centroids 2p and 2p+1 (SIMD lanes l, l+1 of the reference's kernel) take four packed instructions instead of
-// eight; the pairwise table comes through the scalar cache like the plain one.
+// Packed pairs of centroids: v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32 round each half like the scalar instruction, so
+// centroids 2p and 2p+1 (SIMD lanes l, l+1 of the reference's kernel) take four packed instructions instead of eight; the
+// pairwise table comes through the scalar cache like the plain one.
 typedef float f2_t __attribute__((ext_vector_type(2)));
 typedef float f8_t __attribute__((ext_vector_type(8)));
 typedef const __attribute__((address_space(4))) f8_t *scalar_c8_t;
-__device__ __forceinline__ int km_assign_one_pk(const float x0, const float x1, const float x2, const scalar_c4_t c4, const scalar_c8_t c8, const int k) {
-    const f2_t m0 = {-2 * x0, -2 * x0}, m1 = {-2 * x1, -2 * x1}, m2 = {-2 * x2, -2 * x2};
-    const float xn = __builtin_fmaf(x2, x2, __builtin_fmaf(x0, x0, x1 * x1));
-    float ld[8]; int lb[8];
-#pragma unroll
-    for (int l = 0; l < 8; l++) { ld[l] = 3.402823466e+38F - xn; lb[l] = -l; }
-    const int ny_p = (k / 8) * 8;
-    for (int j = 0; j < ny_p; j += 8) {
-#pragma unroll
-        for (int l = 0; l < 8; l += 2) {
-            const f8_t y = c8[(j + l) >> 1];                    // wave-uniform address: scalar load
-            const f2_t y0 = {y[0], y[1]}, y1 = {y[2], y[3]}, y2 = {y[4], y[5]}, yw = {y[6], y[7]};
-            f2_t dp = m0 * y0;
-            dp = __builtin_elementwise_fma(m1, y1, dp);
-            dp = __builtin_elementwise_fma(m2, y2, dp);
-            dp = dp + yw;
-            if (dp[0] < ld[l]) { ld[l] = dp[0]; lb[l] = j; }
-            if (dp[1] < ld[l + 1]) { ld[l + 1] = dp[1]; lb[l + 1] = j; }
-        }
-    }
-    float cur_d = 3.402823466e+38F; unsigned cur_i = 0xFFFFFFFFu;
-#pragma unroll
-    for (int l = 0; l < 8; l++) {
-        const unsigned li = (unsigned)(lb[l] + l);
-        float cand = ld[l] + xn;
-        if (cand < 0) cand = 0;
-        if (cur_d > cand) { cur_d = cand; cur_i = li; }
-        else if (cur_d == cand && cur_i > li) cur_i = li;
-    }
-    for (int j0 = ny_p; j0 < k; j0++) {                     // simdlib_based.cpp:201-216
-        const auto y = c4[j0];
-        float dp = __builtin_fmaf(x2, y.z, __builtin_fmaf(x1, y.y, x0 * y.x));
-        float d = xn + y.w - 2 * dp;
-        if (d < 0) d = 0;
-        if (cur_d > d) { cur_d = d; cur_i = (unsigned)j0; }
-    }
-    return (int)cur_i;
-}
 
 // The same top-1 with HALF the instructions (the scan is what k_km_assign_sort spends its time on: sixteen wavefronts per CU at
 // ~1600 VALU instructions each, four cycles per instruction on a 16-lane SIMD = 13 us of an 18 us launch).  The reference's
@@ -1769,41 +1730,34 @@ __device__ __forceinline__ float km_min3(const float a, const float b, const flo
     asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
 }
-// NS samples per lane share every scalar load of the table.  What the scan waits for besides its arithmetic is the scalar cache:
+// What the scan waits for besides its arithmetic is the scalar cache:
 // scalar loads return out of order, so a wavefront waits for ALL it has issued before it computes (no overlap inside a
 // wavefront), and a round trip of eight 32-byte loads cost ~1000 cycles with sixteen wavefronts per CU asking.  The table unit of
 // sixteen centroids is therefore fetched as four 64-byte loads: 19 300 -> 15 100 cycles for the scan (s_memtime inside the kernel,
 // tools/diag/km_trace.py), of which 16 x 640 are the SIMD's own issue time.
-template <int NS>
-__device__ __forceinline__ void km_assign_min3(const float (&x0)[NS], const float (&x1)[NS], const float (&x2)[NS], const scalar_c4_t c4,
-                                               const scalar_c8_t c8, const float4 *c4s, const int k, int (&out)[NS]) {
-    f2_t m0[NS], m1[NS], m2[NS];
-    float xn[NS], ld[NS][8]; int lc[NS][8];
+__device__ __forceinline__ int km_assign_min3(const float x0, const float x1, const float x2, const scalar_c4_t c4,
+                                              const scalar_c8_t c8, const float4 *c4s, const int k) {
+    const f2_t m0 = {-2 * x0, -2 * x0}, m1 = {-2 * x1, -2 * x1}, m2 = {-2 * x2, -2 * x2};
+    const float xn = __builtin_fmaf(x2, x2, __builtin_fmaf(x0, x0, x1 * x1));
+    float ld[8]; int lc[8];
 #pragma unroll
-    for (int e = 0; e < NS; e++) {
-        m0[e] = f2_t{-2 * x0[e], -2 * x0[e]}; m1[e] = f2_t{-2 * x1[e], -2 * x1[e]}; m2[e] = f2_t{-2 * x2[e], -2 * x2[e]};
-        xn[e] = __builtin_fmaf(x2[e], x2[e], __builtin_fmaf(x0[e], x0[e], x1[e] * x1[e]));
-#pragma unroll
-        for (int l = 0; l < 8; l++) { ld[e][l] = 3.402823466e+38F - xn[e]; lc[e][l] = -1; }
-    }
+    for (int l = 0; l < 8; l++) { ld[l] = 3.402823466e+38F - xn; lc[l] = -1; }
     const int ny_p = (k / 8) * 8;
     const int U = ny_p >> 4;                                  // units of sixteen centroids; a trailing group of eight is "quarter" 4
     const int CUN = (U + 3) >> 2;                             // units per quarter
-    auto pair_dp = [&](const f8_t y, const int e) {
+    auto pair_dp = [&](const f8_t y) {
         const f2_t y0 = {y[0], y[1]}, y1 = {y[2], y[3]}, y2 = {y[4], y[5]}, yw = {y[6], y[7]};
-        f2_t dp = m0[e] * y0;
-        dp = __builtin_elementwise_fma(m1[e], y1, dp);
-        dp = __builtin_elementwise_fma(m2[e], y2, dp);
+        f2_t dp = m0 * y0;
+        dp = __builtin_elementwise_fma(m1, y1, dp);
+        dp = __builtin_elementwise_fma(m2, y2, dp);
         return dp + yw;
     };
     for (int c = 0; c < 4; c++) {
         const int u0 = c * CUN, u1 = u0 + CUN < U ? u0 + CUN : U;
         if (u0 >= u1) break;                                  // wave-uniform
-        float snap[NS][8];
+        float snap[8];
 #pragma unroll
-        for (int e = 0; e < NS; e++)
-#pragma unroll
-            for (int l = 0; l < 8; l++) snap[e][l] = ld[e][l];
+        for (int l = 0; l < 8; l++) snap[l] = ld[l];
         for (int u = u0; u < u1; u++) {
             const int p0 = u << 3;                            // pair index of centroid 16 u
             // the unit's 256 bytes as four 64-byte scalar loads (a scalar load is a round trip the wavefront cannot overlap with
@@ -1816,79 +1770,67 @@ __device__ __forceinline__ void km_assign_min3(const float (&x0)[NS], const floa
 #pragma unroll
             for (int l = 0; l < 8; l += 2) {
                 const f8_t ya = half(l < 4 ? q0 : q1, (l >> 1) & 1), yb = half(l < 4 ? q2 : q3, (l >> 1) & 1);
-#pragma unroll
-                for (int e = 0; e < NS; e++) {
-                    const f2_t a = pair_dp(ya, e), b = pair_dp(yb, e);
-                    ld[e][l] = km_min3(ld[e][l], a[0], b[0]);
-                    ld[e][l + 1] = km_min3(ld[e][l + 1], a[1], b[1]);
-                }
+                const f2_t a = pair_dp(ya), b = pair_dp(yb);
+                ld[l] = km_min3(ld[l], a[0], b[0]);
+                ld[l + 1] = km_min3(ld[l + 1], a[1], b[1]);
             }
         }
 #pragma unroll
-        for (int e = 0; e < NS; e++)
-#pragma unroll
-            for (int l = 0; l < 8; l++) lc[e][l] = ld[e][l] < snap[e][l] ? c : lc[e][l];
+        for (int l = 0; l < 8; l++) lc[l] = ld[l] < snap[l] ? c : lc[l];
     }
     if (ny_p & 8) {                                           // the trailing group of eight
         const int p0 = U << 3;
 #pragma unroll
         for (int l = 0; l < 8; l += 2) {
-            const f8_t ya = c8[p0 + (l >> 1)];
-#pragma unroll
-            for (int e = 0; e < NS; e++) {
-                const f2_t a = pair_dp(ya, e);
-                if (a[0] < ld[e][l]) { ld[e][l] = a[0]; lc[e][l] = 4; }
-                if (a[1] < ld[e][l + 1]) { ld[e][l + 1] = a[1]; lc[e][l + 1] = 4; }
-            }
+            const f2_t a = pair_dp(c8[p0 + (l >> 1)]);
+            if (a[0] < ld[l]) { ld[l] = a[0]; lc[l] = 4; }
+            if (a[1] < ld[l + 1]) { ld[l + 1] = a[1]; lc[l + 1] = 4; }
         }
     }
+    // merge of the lane trackers (simdlib_based.cpp:178-199): smallest clamped distance, smallest index among those attaining it
+    float cand[8];
+    float cur_d = 3.402823466e+38F;
 #pragma unroll
-    for (int e = 0; e < NS; e++) {
-        // merge of the lane trackers (simdlib_based.cpp:178-199): smallest clamped distance, smallest index among those attaining it
-        float cand[8];
-        float cur_d = 3.402823466e+38F;
+    for (int l = 0; l < 8; l++) { float cd = ld[l] + xn; if (cd < 0) cd = 0; cand[l] = cd; cur_d = cd < cur_d ? cd : cur_d; }
+    unsigned tm = 0u;
 #pragma unroll
-        for (int l = 0; l < 8; l++) { float cd = ld[e][l] + xn[e]; if (cd < 0) cd = 0; cand[l] = cd; cur_d = cd < cur_d ? cd : cur_d; }
-        unsigned tm = 0u;
+    for (int l = 0; l < 8; l++) tm |= cand[l] == cur_d ? (1u << l) : 0u;
+    unsigned cur_i = 0xFFFFFFFFu;
+    while (__any(tm != 0u)) {                                 // one trip unless a lane has two trackers tied
+        if (tm) {
+            const int l = __ffs((int)tm) - 1;
+            tm &= tm - 1u;
+            float target = ld[0]; int c = lc[0];
 #pragma unroll
-        for (int l = 0; l < 8; l++) tm |= cand[l] == cur_d ? (1u << l) : 0u;
-        unsigned cur_i = 0xFFFFFFFFu;
-        while (__any(tm != 0u)) {                             // one trip unless a lane has two trackers tied
-            if (tm) {
-                const int l = __ffs((int)tm) - 1;
-                tm &= tm - 1u;
-                float target = ld[e][0]; int c = lc[e][0];
-#pragma unroll
-                for (int q = 1; q < 8; q++) { target = l == q ? ld[e][q] : target; c = l == q ? lc[e][q] : c; }
-                unsigned idx = 0u;                            // a tracker that never went down holds index 0 (lb = -l)
-                if (c == 4) idx = (unsigned)((U << 4) + l);
-                else if (c >= 0) {
-                    const int u0 = c * CUN, u1 = u0 + CUN < U ? u0 + CUN : U;
-                    const int base = (u0 << 4) + l, lim = u1 << 4;
-                    for (int q = 2 * CUN - 1; q >= 0; q--) {  // descending: the first entry that attains the minimum wins
-                        const int j = base + 8 * q;
-                        if (j < lim) {
-                            const float4 y = c4s[j];
-                            float dp = (-2 * x0[e]) * y.x;
-                            dp = __builtin_fmaf(-2 * x1[e], y.y, dp);
-                            dp = __builtin_fmaf(-2 * x2[e], y.z, dp);
-                            dp = dp + y.w;
-                            if (dp == target) idx = (unsigned)j;
-                        }
+            for (int q = 1; q < 8; q++) { target = l == q ? ld[q] : target; c = l == q ? lc[q] : c; }
+            unsigned idx = 0u;                                // a tracker that never went down holds index 0 (lb = -l)
+            if (c == 4) idx = (unsigned)((U << 4) + l);
+            else if (c >= 0) {
+                const int u0 = c * CUN, u1 = u0 + CUN < U ? u0 + CUN : U;
+                const int base = (u0 << 4) + l, lim = u1 << 4;
+                for (int q = 2 * CUN - 1; q >= 0; q--) {      // descending: the first entry that attains the minimum wins
+                    const int j = base + 8 * q;
+                    if (j < lim) {
+                        const float4 y = c4s[j];
+                        float dp = (-2 * x0) * y.x;
+                        dp = __builtin_fmaf(-2 * x1, y.y, dp);
+                        dp = __builtin_fmaf(-2 * x2, y.z, dp);
+                        dp = dp + y.w;
+                        if (dp == target) idx = (unsigned)j;
                     }
                 }
-                cur_i = idx < cur_i ? idx : cur_i;
             }
+            cur_i = idx < cur_i ? idx : cur_i;
         }
-        for (int j0 = ny_p; j0 < k; j0++) {                   // simdlib_based.cpp:201-216
-            const auto y = c4[j0];
-            float dp = __builtin_fmaf(x2[e], y.z, __builtin_fmaf(x1[e], y.y, x0[e] * y.x));
-            float d = xn[e] + y.w - 2 * dp;
-            if (d < 0) d = 0;
-            if (cur_d > d) { cur_d = d; cur_i = (unsigned)j0; }
-        }
-        out[e] = cur_i < (unsigned)k ? (int)cur_i : 0;
     }
+    for (int j0 = ny_p; j0 < k; j0++) {                       // simdlib_based.cpp:201-216
+        const auto y = c4[j0];
+        float dp = __builtin_fmaf(x2, y.z, __builtin_fmaf(x1, y.y, x0 * y.x));
+        float d = xn + y.w - 2 * dp;
+        if (d < 0) d = 0;
+        if (cur_d > d) { cur_d = d; cur_i = (unsigned)j0; }
+    }
+    return cur_i < (unsigned)k ? (int)cur_i : 0;
 }
 
 #ifdef PAMD_KM_TRACE
@@ -1901,63 +1843,44 @@ __device__ unsigned long long g_km_trace[2][256][32];
 #define KM_TRACE0(kern, slot) do { } while (0)
 #endif
 
-// NS = samples per lane: 1 = sixteen wavefronts and the packed full scan (km_assign_one_pk, the round-3 form); 2 = eight wavefronts,
-// each taking two of the sixteen runs, with the min3 scan
-template <int NS>
-__global__ __launch_bounds__(1024 / NS) void k_km_assign_sort(KmSamples s, size_t nx, const float4 *__restrict__ c4, int k, const bool weighted,
-                                                              float4 *__restrict__ sorted_rec, unsigned short *__restrict__ offs,
-                                                              unsigned char *__restrict__ prev, unsigned int *flags, const bool min3) {
+// One sample per lane, sixteen wavefronts: each takes one of the block's sixteen runs of 64 consecutive samples
+__global__ __launch_bounds__(1024) void k_km_assign_sort(KmSamples s, size_t nx, const float4 *__restrict__ c4, int k, const bool weighted,
+                                                         float4 *__restrict__ sorted_rec, unsigned short *__restrict__ offs,
+                                                         unsigned char *__restrict__ prev, unsigned int *flags) {
     if (flags[0]) return;                                              // fixed point reached (k_km_prep's comment): nothing changes any more
     __shared__ unsigned char cnt[16][256];                             // members of (step, centroid): 64 at most
     __shared__ unsigned short stepbase[16][256];                       // start of centroid j's group + its members in earlier steps
     __shared__ unsigned int wsum[16];
     __shared__ float4 c4s[256];                                        // the centroid records once more, for per-lane reads (km_assign_min3)
-    constexpr int NT = 1024 / NS;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, step = threadIdx.x >> 6;        // step: the block's run of 64 consecutive samples this lane's sample is in
     KM_TRACE0(0, 0);
-    for (int i = threadIdx.x; i < 16 * 256 / 4; i += NT) reinterpret_cast<unsigned int *>(&cnt[0][0])[i] = 0u;
+    for (int i = threadIdx.x; i < 16 * 256 / 4; i += 1024) reinterpret_cast<unsigned int *>(&cnt[0][0])[i] = 0u;
     if ((int)threadIdx.x < k) c4s[threadIdx.x] = c4[threadIdx.x];
     __syncthreads();
     KM_TRACE0(0, 1);
     const scalar_c4_t t4 = (scalar_c4_t)(unsigned long long)c4;
     const scalar_c8_t t8 = (scalar_c8_t)(unsigned long long)(c4 + k);
     const size_t blk0 = (size_t)blockIdx.x * kKmSortBlock;
-    size_t i[NS]; bool v[NS]; float4 rec[NS]; int step[NS];
-#pragma unroll
-    for (int e = 0; e < NS; e++) {
-        step[e] = wv * NS + e;                                         // the block's run of 64 consecutive samples this lane's e-th sample is in
-        i[e] = blk0 + (size_t)step[e] * 64 + lane;
-        v[e] = i[e] < nx;
-        rec[e] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (v[e]) { rec[e].x = s.x[i[e]]; rec[e].y = s.y[i[e]]; rec[e].z = s.z[i[e]]; if (weighted) rec[e].w = s.w[i[e]]; }
-    }
+    const size_t i = blk0 + (size_t)step * 64 + lane;
+    const bool v = i < nx;
+    float4 rec = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (v) { rec.x = s.x[i]; rec.y = s.y[i]; rec.z = s.z[i]; if (weighted) rec.w = s.w[i]; }
 #ifdef PAMD_KM_TRACE
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     KM_TRACE0(0, 2);
     if (threadIdx.x == 0) g_km_trace[0][blockIdx.x & 255][24] = clock64();
 #endif
-    int a[NS];
-    if (NS == 1 && !min3) a[0] = v[0] ? km_assign_one_pk(rec[0].x, rec[0].y, rec[0].z, t4, t8, k) : 0;
-    else {
-        float x0[NS], x1[NS], x2[NS];
-#pragma unroll
-        for (int e = 0; e < NS; e++) { x0[e] = rec[e].x; x1[e] = rec[e].y; x2[e] = rec[e].z; }
-        km_assign_min3<NS>(x0, x1, x2, t4, t8, c4s, k, a);
+    int a = km_assign_min3(rec.x, rec.y, rec.z, t4, t8, c4s, k);
+    if (!v) a = 0;
+    if (v) {                                                           // a sample that changed sides marks both centroids dirty
+        const int old = prev[i];
+        if (old != a) { prev[i] = (unsigned char)a; flags[1 + old] = 1u; flags[1 + a] = 1u; }
     }
-    unsigned rk[NS];
-#pragma unroll
-    for (int e = 0; e < NS; e++) {
-        if (!v[e]) a[e] = 0;
-        if (v[e]) {                                                    // a sample that changed sides marks both centroids dirty
-            const int old = prev[i[e]];
-            if (old != a[e]) { prev[i[e]] = (unsigned char)a[e]; flags[1 + old] = 1u; flags[1 + a[e]] = 1u; }
-        }
-        const unsigned long long m = match_mask(a[e], 8, __ballot(v[e]));
-        rk[e] = (unsigned)__popcll(m & ((1ULL << lane) - 1ULL));       // rank among the step's samples of the same centroid
-        if (v[e] && rk[e] == 0u) cnt[step[e]][a[e]] = (unsigned char)__popcll(m);   // group leader
-    }
+    const unsigned long long m = match_mask(a, 8, __ballot(v));
+    const unsigned rk = (unsigned)__popcll(m & ((1ULL << lane) - 1ULL)); // rank among the step's samples of the same centroid
+    if (v && rk == 0u) cnt[step][a] = (unsigned char)__popcll(m);      // group leader
 #ifdef PAMD_KM_TRACE
-    if (lane == 0) g_km_trace[0][blockIdx.x & 255][8 + wv] = wall_clock64();
+    if (lane == 0) g_km_trace[0][blockIdx.x & 255][8 + step] = wall_clock64();
     if (threadIdx.x == 0) g_km_trace[0][blockIdx.x & 255][25] = clock64();
 #endif
     __syncthreads();
@@ -1980,9 +1903,7 @@ __global__ __launch_bounds__(1024 / NS) void k_km_assign_sort(KmSamples s, size_
     }
     __syncthreads();
     KM_TRACE0(0, 4);
-#pragma unroll
-    for (int e = 0; e < NS; e++)
-        if (v[e]) sorted_rec[blk0 + (unsigned)stepbase[step[e]][a[e]] + rk[e]] = rec[e];   // the sample itself: the update reads its members in runs
+    if (v) sorted_rec[blk0 + (unsigned)stepbase[step][a] + rk] = rec;   // the sample itself: the update reads its members in runs
 #ifdef PAMD_KM_TRACE
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     KM_TRACE0(0, 5);
@@ -2302,7 +2223,7 @@ void kmeans_iterate(KMeansWork &w, size_t nx, int k, bool weighted, int niter, h
         hipLaunchKernelGGL(k_km_bounds_fold, 1, 64, 0, s, w.bkeys.p, (KmGridDev *)w.grid.p);
     }
     // few samples: block-local sorts in the assignment kernel, one block per centroid collects its members (k_km_update_lists)
-    const size_t direct_max = getenv("PAMD_KM_DIRECT_MAX") ? (size_t)atoll(getenv("PAMD_KM_DIRECT_MAX")) : ((size_t)1 << 19);
+    constexpr size_t direct_max = (size_t)1 << 19;
     // (a cluster of up to 16 384 samples: its list is summed block-parallel in pieces of 4096 by k_km_update_lists -- a scene with a
     // few flat regions refines in 2.3 ms instead of 3.2; beyond that the global sort + k_km_update's long-chain form wins: a colour
     // covering 10 % / 30 % of the image 4.5 / 6.9 ms against 8.2 / 18.7, measured with the threshold swept over 4096 .. 131 072)
@@ -2319,24 +2240,20 @@ void kmeans_iterate(KMeansWork &w, size_t nx, int k, bool weighted, int niter, h
             HIP_CHECK(hipFuncSetAttribute((const void *)k_km_update_lists<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kKmDirectCap * 20));
         }
     }
-    static const bool mid_enabled = !(getenv("PAMD_KM_MID") && atoi(getenv("PAMD_KM_MID")) == 0);
-    const bool use_mid = use_lut && G == 64 && mid_enabled && k % 8 == 0;    // four-candidate table in LDS
+    const bool use_mid = use_lut && G == 64 && k % 8 == 0;    // four-candidate table in LDS
     if (use_mid) w.mid.reserve(32 * 32 * 32);
     // clusters of at least this many samples take the block-parallel exact chain (km_chain_coop)
     const unsigned long long long_min = getenv("PAMD_KM_LONG_MIN") ? (unsigned long long)atoll(getenv("PAMD_KM_LONG_MIN")) : 8192ULL;
-    static const int km_quarters = (getenv("PAMD_KM_QUARTERS") && atoi(getenv("PAMD_KM_QUARTERS")) == 0) ? 0 : 1;   // A/B of the quarter-wise retry
     for (int it = 0; it < niter; it++) {
         if (use_direct) {
             unsigned short *offs = (unsigned short *)w.table.p;              // 257 x blocks x 2 bytes
             const int sblocks = (int)ceil_div(nx, (size_t)kKmSortBlock);
             {
                 KTIME("k_km_assign", s, (weighted ? 32.0 : 28.0) * nx);
-                // 1 (default): sixteen wavefronts, one sample per lane, min3 scan; 2: eight wavefronts with two samples per lane (measured
-                // slower: 23 000 against 15 100 cycles for the scan -- a wavefront waits for its scalar loads, and with half the
-                // wavefronts per SIMD fewer of those waits overlap); 3: the round-3 scan (km_assign_one_pk: 23 500 cycles)
-                static const int per_lane = getenv("PAMD_KM_SCAN") ? atoi(getenv("PAMD_KM_SCAN")) : 1;
-                if (per_lane == 2) hipLaunchKernelGGL(k_km_assign_sort<2>, sblocks, 512, 0, s, ks, nx, w.c4.p, k, weighted, w.sorted.p, offs, (unsigned char *)w.assign.p, w.flags.p, true);
-                else hipLaunchKernelGGL(k_km_assign_sort<1>, sblocks, 1024, 0, s, ks, nx, w.c4.p, k, weighted, w.sorted.p, offs, (unsigned char *)w.assign.p, w.flags.p, per_lane == 1);
+                // sixteen wavefronts, one sample per lane, min3 scan (measured and removed: eight wavefronts with two samples per
+                // lane, 23 000 against 15 100 cycles for the scan -- a wavefront waits for its scalar loads, and with half the
+                // wavefronts per SIMD fewer of those waits overlap; the round-3 packed full scan, 23 500 cycles)
+                hipLaunchKernelGGL(k_km_assign_sort, sblocks, 1024, 0, s, ks, nx, w.c4.p, k, weighted, w.sorted.p, offs, (unsigned char *)w.assign.p, w.flags.p);
             }
             {
                 KTIME("k_km_update", s, 16.0 * nx);
@@ -2400,8 +2317,8 @@ void kmeans_iterate(KMeansWork &w, size_t nx, int k, bool weighted, int niter, h
                     HIP_CHECK(hipFuncSetAttribute((const void *)k_km_update<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 4096 * 4));
                     HIP_CHECK(hipFuncSetAttribute((const void *)k_km_update<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 4096 * 4));
                 }
-                if (weighted) hipLaunchKernelGGL((k_km_update<true, true>), k, 256, lds_up, s, w.sorted.p, w.rowtot.p, k, (unsigned long long)nx, w.cent.p, w.hassign.p, w.c4.p, w.ticket.p, w.mt.p, lm, w.hs.p, km_quarters);
-                else hipLaunchKernelGGL((k_km_update<false, true>), k, 256, lds_up, s, w.sorted.p, w.rowtot.p, k, (unsigned long long)nx, w.cent.p, w.hassign.p, w.c4.p, w.ticket.p, w.mt.p, lm, w.hs.p, km_quarters);
+                if (weighted) hipLaunchKernelGGL((k_km_update<true, true>), k, 256, lds_up, s, w.sorted.p, w.rowtot.p, k, (unsigned long long)nx, w.cent.p, w.hassign.p, w.c4.p, w.ticket.p, w.mt.p, lm, w.hs.p);
+                else hipLaunchKernelGGL((k_km_update<false, true>), k, 256, lds_up, s, w.sorted.p, w.rowtot.p, k, (unsigned long long)nx, w.cent.p, w.hassign.p, w.c4.p, w.ticket.p, w.mt.p, lm, w.hs.p);
             }
             continue;
         }
@@ -2409,9 +2326,7 @@ void kmeans_iterate(KMeansWork &w, size_t nx, int k, bool weighted, int niter, h
         {
             KTIME("k_km_scatter", s, (weighted ? 36.0 : 32.0) * nx - (use_mid ? 3.0 : 0.0) * nx);
             const unsigned char *a8 = (const unsigned char *)w.assign.p;               // k_km_assign_mid leaves one byte per sample
-            static const bool pair_on = !(getenv("PAMD_KM_PAIR") && atoi(getenv("PAMD_KM_PAIR")) == 0);
-            static const bool lds_sort_on = !(getenv("PAMD_KM_LDS_SORT") && atoi(getenv("PAMD_KM_LDS_SORT")) == 0);
-            if (use_mid && lds_sort_on && chunk_len >= 4096 && k <= 256) {
+            if (use_mid && chunk_len >= 4096 && k <= 256) {
                 constexpr size_t lds_ls = (size_t)(512 + 1024 + 4096 / 4 + 4 * 4096) * sizeof(unsigned int);
                 static PerDeviceOnce attr5;
                 if (attr5.first()) {
@@ -2420,7 +2335,7 @@ void kmeans_iterate(KMeansWork &w, size_t nx, int k, bool weighted, int niter, h
                 }
                 if (weighted) hipLaunchKernelGGL(k_km_scatter_lds<true>, nchunks, 256, lds_ls, s, ks, a8, nx, k, chunk_len, nchunks, w.table.p, w.rowtot.p, w.sorted.p);
                 else hipLaunchKernelGGL(k_km_scatter_lds<false>, nchunks, 256, lds_ls, s, ks, a8, nx, k, chunk_len, nchunks, w.table.p, w.rowtot.p, w.sorted.p);
-            } else if (use_mid && pair_on && chunk_len >= 2 * k) {
+            } else if (use_mid && chunk_len >= 2 * k) {
                 static PerDeviceOnce attr3;
                 if (attr3.first()) {
                     HIP_CHECK(hipFuncSetAttribute((const void *)k_km_scatter<true, unsigned char, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 9 * 256 * 4 + 4 * (256 + 64) * 16));
@@ -2442,8 +2357,8 @@ void kmeans_iterate(KMeansWork &w, size_t nx, int k, bool weighted, int niter, h
             const bool coop_on = nx >= long_min;
             const size_t lds_up = coop_on ? (size_t)4 * 4096 * sizeof(float) : 0;
             const unsigned long long lm = coop_on ? long_min : ~0ULL;
-            if (weighted) hipLaunchKernelGGL((k_km_update<true, false>), k, 256, lds_up, s, w.sorted.p, w.rowtot.p, k, (unsigned long long)nx, w.cent.p, w.hassign.p, w.c4.p, w.ticket.p, w.mt.p, lm, (float *)nullptr, km_quarters);
-            else hipLaunchKernelGGL((k_km_update<false, false>), k, 256, lds_up, s, w.sorted.p, w.rowtot.p, k, (unsigned long long)nx, w.cent.p, w.hassign.p, w.c4.p, w.ticket.p, w.mt.p, lm, (float *)nullptr, km_quarters);
+            if (weighted) hipLaunchKernelGGL((k_km_update<true, false>), k, 256, lds_up, s, w.sorted.p, w.rowtot.p, k, (unsigned long long)nx, w.cent.p, w.hassign.p, w.c4.p, w.ticket.p, w.mt.p, lm, (float *)nullptr);
+            else hipLaunchKernelGGL((k_km_update<false, false>), k, 256, lds_up, s, w.sorted.p, w.rowtot.p, k, (unsigned long long)nx, w.cent.p, w.hassign.p, w.c4.p, w.ticket.p, w.mt.p, lm, (float *)nullptr);
         }
     }
     HIP_CHECK(hipGetLastError());

@@ -751,8 +751,7 @@ static void launch_nn_lut(const double *d_colors, size_t plane_stride, size_t n,
     if (k <= 256) {
         w.lut.reserve((size_t)ncell * 32);
         unsigned char *l1 = w.lut.p, *l2 = w.lut.p + (size_t)ncell * 16;
-        static const bool mid_enabled = !(getenv("PAMD_NN_MID") && atoi(getenv("PAMD_NN_MID")) == 0);
-        const bool use_mid = g.G == 64 && mid_enabled;                      // large images: four-candidate table in LDS
+        const bool use_mid = g.G == 64;                                     // large images: four-candidate table in LDS
         if (use_mid) w.mid.reserve((size_t)(ncell / 8) + 257 * 4);        // the 32^3 table + the f32 records and margin behind it
         const int ncoarse = ncell / 64;
         w.clist.reserve((size_t)ncoarse * (1 + kCoarseMax) * 2);
@@ -763,23 +762,16 @@ static void launch_nn_lut(const double *d_colors, size_t plane_stride, size_t n,
         }
         if (use_mid) {
             if (n >> 32) throw HipError("patolette_amd: the LDS-table map kernel indexes pixels with 32 bits");
-            // one-byte maps: sixteen wavefronts per CU with four pixels per lane; PAMD_NN_WAVES=12 = twelve with six (9 KB of loads in
-            // flight per wavefront, 168 registers each): 294 against 281 us on the KMeans palette, level on the CIELuv one (interleaved
-            // launches, tools/diag/nn_ab.py).  (Four pixels per lane with 4- or 8-byte map elements spill.)
-            const int waves_env = getenv("PAMD_NN_WAVES") ? atoi(getenv("PAMD_NN_WAVES")) : 16;      // (read per call: an A/B alternates it)
-            auto go = [&](auto pc, auto wc) {
-                constexpr int P = decltype(pc)::value, WAVES = decltype(wc)::value;
-                static PerDeviceOnce attr_mid;
-                if (attr_mid.first()) HIP_CHECK(hipFuncSetAttribute((const void *)(k_nn_map_mid<OutT, P, WAVES>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mid_lds(WAVES)));
-                const int blocks = (int)std::min<size_t>((size_t)num_cus(), ceil_div(n, (size_t)64 * WAVES * P));
-                KTIME("k_nn_map", s, (24.0 + sizeof(OutT)) * n);
-                hipLaunchKernelGGL((k_nn_map_mid<OutT, P, WAVES>), blocks, 64 * WAVES, mid_lds(WAVES), s, d_colors, plane_stride, n, d_pal, k, g, (const unsigned int *)w.mid.p,
-                                   (const float4 *)(w.mid.p + ncell / 8), (const unsigned char *)l1, (const unsigned char *)l2, out);
-            };
-            if constexpr (sizeof(OutT) == 1) {
-                if (waves_env == 12) go(std::integral_constant<int, 6>{}, std::integral_constant<int, 12>{});
-                else go(std::integral_constant<int, 4>{}, std::integral_constant<int, 16>{});
-            } else go(std::integral_constant<int, 2>{}, std::integral_constant<int, 16>{});
+            // sixteen wavefronts per CU; one-byte maps with four pixels per lane (measured and removed: twelve wavefronts with six,
+            // 9 KB of loads in flight per wavefront, 168 registers each: 294 against 281 us on the KMeans palette, level on the
+            // CIELuv one, interleaved launches).  (Four pixels per lane with 4- or 8-byte map elements spill.)
+            constexpr int P = sizeof(OutT) == 1 ? 4 : 2, WAVES = 16;
+            static PerDeviceOnce attr_mid;
+            if (attr_mid.first()) HIP_CHECK(hipFuncSetAttribute((const void *)(k_nn_map_mid<OutT, P, WAVES>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mid_lds(WAVES)));
+            const int blocks = (int)std::min<size_t>((size_t)num_cus(), ceil_div(n, (size_t)64 * WAVES * P));
+            KTIME("k_nn_map", s, (24.0 + sizeof(OutT)) * n);
+            hipLaunchKernelGGL((k_nn_map_mid<OutT, P, WAVES>), blocks, 64 * WAVES, mid_lds(WAVES), s, d_colors, plane_stride, n, d_pal, k, g, (const unsigned int *)w.mid.p,
+                               (const float4 *)(w.mid.p + ncell / 8), (const unsigned char *)l1, (const unsigned char *)l2, out);
             return;
         }
         KTIME("k_nn_map", s, (24.0 + sizeof(OutT)) * n);
@@ -1313,10 +1305,10 @@ __global__ __launch_bounds__(64) void k_dither(const double *__restrict__ img, s
 // same way.  The warm-up of run b is the last `warm` pixels of run b - 1: the neighbouring column, no copy (warm <= run length).
 //   k_dither_order    rank -> linear pixel number: the only place that knows the Hilbert curve
 //   k_dither_streams  pixels into the transposed layout (tiles of 64 runs x 64 positions through LDS)
-//   k_dither_lanes<0> run b: zero queue `warm` pixels before t_b, the choices of the last sixteen warm-up steps -> side[b], of the run -> smap
+//   k_dither_lanes    run b: zero queue `warm` pixels before t_b, the choices of the last sixteen warm-up steps -> side[b], of the run -> smap
 //   k_dither_lane_check  boundary b is good iff side[b] equals the last sixteen choices of run b - 1; the others are listed
-//   k_dither_lanes<1> a listed run again from the queue rebuilt out of those choices and pixels (side[b] := what it read), until
-//                     sixteen consecutive choices equal what is there (the old chain met: the rest stands)
+//   k_dither_lane_repair  a listed run again, one wavefront each, from the queue rebuilt out of those choices and pixels (side[b] :=
+//                     what it read), until sixteen consecutive choices equal what is there (the old chain met: the rest stands)
 //   ... check / repair until a check lists nothing: nothing was written since the previous repair, every side[b] equals the
 //       map, and by induction over b (run 0 starts from the true zero queue) smap is the reference's chain
 //   k_dither_unpermute  out[pixel number of rank t_b + p] = smap(b, p)
@@ -1512,7 +1504,6 @@ __device__ __attribute__((noinline)) int dither_nearest_all(const double x, cons
     return best;
 }
 
-template <int MODE>
 __global__ __launch_bounds__(256) void k_dither_lanes(DitherLanes a, const double *__restrict__ pal /* planar (k,3), linear Rec2020 */, int k, DitherWeights wts) {
     extern __shared__ double lds[];
     double *praw = lds, *pwt = lds + 3 * k;                        // [3][k] raw palette; [3][k] scaled by the (float)-cast weights (riemersma.c:419-425)
@@ -1525,39 +1516,21 @@ __global__ __launch_bounds__(256) void k_dither_lanes(DitherLanes a, const doubl
     }
     __syncthreads();
     const unsigned gid = blockIdx.x * blockDim.x + threadIdx.x;
-    bool active;
-    unsigned b = 0;
-    if constexpr (MODE == 0) { active = gid < a.R.S; b = active ? gid : 0u; }
-    else { const unsigned nl = a.list[-1]; active = gid < nl; b = active ? a.list[gid] : 1u; }
+    const bool active = gid < a.R.S;
+    const unsigned b = active ? gid : 0u;
     const unsigned len = (unsigned)(a.R.t(b + 1) - a.R.t(b));       // this run
     const unsigned lp = b > 0 ? (unsigned)(a.R.t(b) - a.R.t(b - 1)) : 0u;   // the one before it
     // steps [0, wu) read the end of run b - 1 (the neighbouring column), steps [wu, wu + len) this run
-    const unsigned wu = MODE == 0 ? (b > 0 ? a.warm : 0u) : 0u;
+    const unsigned wu = b > 0 ? a.warm : 0u;
     const size_t own = a.R.idx(b, 0);
     size_t at = wu ? a.R.idx(b - 1, lp - wu) : own;                // where step 0 reads
-    if constexpr (MODE == 0) {
-        if (active && b > 0 && wu < 16) {                           // a warm-up of fewer than sixteen steps leaves no record to pass the check
-            for (int i = 0; i < 16; i++) a.side[16ull * b + i] = 0xFFFFu;
-        }
+    if (active && b > 0 && wu < 16) {                               // a warm-up of fewer than sixteen steps leaves no record to pass the check
+        for (int i = 0; i < 16; i++) a.side[16ull * b + i] = 0xFFFFu;
     }
 #define PAMD_DL_EACH(M) M(0) M(1) M(2) M(3) M(4) M(5) M(6) M(7) M(8) M(9) M(10) M(11) M(12) M(13) M(14) M(15)
 #define PAMD_DL_DECL(S) double q0_##S = 0.0, q1_##S = 0.0, q2_##S = 0.0;
     PAMD_DL_EACH(PAMD_DL_DECL)                                      // the error queue: slot s = the error of the run's step s (mod 16); named scalars: dither_slots.h
 #undef PAMD_DL_DECL
-    if constexpr (MODE == 1) {
-        if (active) {
-            // the queue as the chain holds it after the last sixteen pixels of run b - 1: original pixel - chosen colour, oldest first
-#define PAMD_DL_INIT(S)                                                                                                   \
-            {                                                                                                             \
-                const size_t rr = a.R.idx(b - 1, lp - 16 + S);                                                            \
-                const unsigned c = a.smap[rr];                                                                            \
-                a.side[16ull * b + S] = (unsigned short)c;                                                                \
-                q0_##S = a.sx[rr] - praw[c]; q1_##S = a.sy[rr] - praw[k + c]; q2_##S = a.sz[rr] - praw[2 * k + c];        \
-            }
-            PAMD_DL_EACH(PAMD_DL_INIT)
-#undef PAMD_DL_INIT
-        }
-    }
     const int G = a.g.G;
     const double lo0 = a.g.lo[0], lo1 = a.g.lo[1], lo2 = a.g.lo[2], in0 = a.g.inv[0], in1 = a.g.inv[1], in2 = a.g.inv[2];
     const double hi0 = a.hi[0], hi1 = a.hi[1], hi2 = a.hi[2];
@@ -1699,10 +1672,8 @@ __global__ __launch_bounds__(256) void k_dither_lanes(DitherLanes a, const doubl
     const unsigned nsteps = wu + len;
     unsigned st = 0;                                                // step number
     double c0 = 0, c1 = 0, c2 = 0;                                  // the pixel of step st, fetched one step ahead
-    int cm = 0;                                                     // MODE 1: and the choice smap holds for it
     bool on = active && nsteps > 0;
-    if (on) { c0 = a.sx[at]; c1 = a.sy[at]; c2 = a.sz[at]; if constexpr (MODE == 1) cm = (int)a.smap[at]; }
-    int streak = 0;                                                 // MODE 1: consecutive choices equal to what smap holds
+    if (on) { c0 = a.sx[at]; c1 = a.sy[at]; c2 = a.sz[at]; }
     // Sixteen steps a trip: the queue's slots are registers, the step that starts at slot j reads them in the order j, j + 1, ...
     // (dither_slots.h; with j a constant of the unrolled loop the macros' switches fold away).  One copy of the step selected by a
     // scalar branch on the slot was measured 10 % slower (a lone wavefront pays for every taken branch with a refill of its
@@ -1716,11 +1687,10 @@ __global__ __launch_bounds__(256) void k_dither_lanes(DitherLanes a, const doubl
 #pragma unroll
       for (int j = 0; j < 16; j++) {
         const double p0 = c0, p1 = c1, p2 = c2;
-        const int was = cm;
         const size_t cur = at;
         const bool nxt = on && st + 1 < nsteps;
         at = (st + 1 == wu) ? own : at + 64;                        // the run starts where the neighbour's column ends
-        if (nxt) { c0 = a.sx[at]; c1 = a.sy[at]; c2 = a.sz[at]; if constexpr (MODE == 1) cm = (int)a.smap[at]; }
+        if (nxt) { c0 = a.sx[at]; c1 = a.sy[at]; c2 = a.sz[at]; }
         e0 += l0 * wts.w[15]; e1 += l1 * wts.w[15]; e2 += l2 * wts.w[15];
         const double x = kRw * (p0 + e0), y = kGw * (p1 + e1), z = kBw * (p2 + e2);
         const NearestRec nr = nearest_request(x, y, z, on);
@@ -1731,16 +1701,11 @@ __global__ __launch_bounds__(256) void k_dither_lanes(DitherLanes a, const doubl
         if (on) {
             l0 = p0 - praw[bi]; l1 = p1 - praw[k + bi]; l2 = p2 - praw[2 * k + bi];       // riemersma.c:333-340
             PAMD_DL_QUEUE_PUSH(j, l0, l1, l2)
-            if constexpr (MODE == 0) {
-                if (st >= wu) a.smap[cur] = (unsigned char)bi;
-                else if (st + 16 >= wu) a.side[16ull * b + (st + 16 - wu)] = (unsigned short)bi;
-            } else {
-                if (was == bi) streak++;
-                else { streak = 0; a.smap[cur] = (unsigned char)bi; }
-            }
+            if (st >= wu) a.smap[cur] = (unsigned char)bi;
+            else if (st + 16 >= wu) a.side[16ull * b + (st + 16 - wu)] = (unsigned short)bi;
         }
         st++;
-        on = nxt && (MODE == 0 || streak < 16);
+        on = nxt;
       }
     }
 #undef PAMD_DL_EACH
@@ -1748,7 +1713,7 @@ __global__ __launch_bounds__(256) void k_dither_lanes(DitherLanes a, const doubl
     if ((threadIdx.x & 63) == 0) {
         atomicMax(&g_nn_stats[6], (unsigned long long)ws_exact); atomicMax(&g_nn_stats[7], (unsigned long long)ws_full);
         const unsigned wv = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-        if (MODE == 0 && wv < 4096u) { g_dl_wave[wv][0] = wall_clock64() - ws_t0; g_dl_wave[wv][1] = ws_exact; g_dl_wave[wv][2] = ws_trips; g_dl_wave[wv][3] = ws_long; }
+        if (wv < 4096u) { g_dl_wave[wv][0] = wall_clock64() - ws_t0; g_dl_wave[wv][1] = ws_exact; g_dl_wave[wv][2] = ws_trips; g_dl_wave[wv][3] = ws_long; }
     }
 #endif
 }
@@ -2100,9 +2065,6 @@ static bool launch_dither_lanes(const double *d_img, size_t plane_stride, int wh
     const double fw[3] = {(double)(float)kRw, (double)(float)kGw, (double)(float)kBw};
     NNGrid g, gw[2];
     g.G = npix >= ((size_t)1 << 20) ? 64 : 32;
-#ifdef PAMD_KM_TRACE
-    if (const char *e = getenv("PAMD_DITHER_GRID")) g.G = atoi(e) == 32 ? 32 : 64;      // diagnostic build: the records' grid
-#endif
     for (int c = 0; c < 3; c++) {
         double lo = INFINITY, hi = -INFINITY;
         for (int j = 0; j < k; j++) { const double v = h_pal[(size_t)c * k + j] * fw[c]; wp[(size_t)c * k + j] = v; lo = std::min(lo, v); hi = std::max(hi, v); }
@@ -2226,7 +2188,7 @@ static bool launch_dither_lanes(const double *d_img, size_t plane_stride, int wh
     const size_t lds = (size_t)6 * k * sizeof(double) + (size_t)k * sizeof(float4);
     {
         KTIME("k_dither", s, 25.0 * npix);
-        hipLaunchKernelGGL(k_dither_lanes<0>, (unsigned)ceil_div(S, 256), 256, lds, s, a, d_pal, k, wts);
+        hipLaunchKernelGGL(k_dither_lanes, (unsigned)ceil_div(S, 256), 256, lds, s, a, d_pal, k, wts);
     }
     HIP_CHECK(hipGetLastError());
     w.dither_segments = S; w.dither_repairs = 0; w.dither_rounds = 0; w.dither_through = 0; w.dither_jumps = 0; w.dither_solo = 0;
@@ -2258,12 +2220,9 @@ static bool launch_dither_lanes(const double *d_img, size_t plane_stride, int wh
         a.solo = solo ? 1 : 0;
         w.dither_repairs += solo ? 1 : nf;
         KTIME("k_dither_fix", s, 0.0);
-        // PAMD_DITHER_REPAIR=lanes: the listed runs 64 to a wavefront again (k_dither_lanes<1>), for comparison
-        static const bool repair_lanes = getenv("PAMD_DITHER_REPAIR") && !strcmp(getenv("PAMD_DITHER_REPAIR"), "lanes");
         const size_t lds_r = (size_t)6 * k * sizeof(double) + 3 * 128 * sizeof(double) + 128 * sizeof(unsigned) + 2048;   // + the history of choices
         const unsigned nblk = solo ? 1u : nf;
-        if (repair_lanes && !solo) hipLaunchKernelGGL(k_dither_lanes<1>, (unsigned)ceil_div((size_t)nf, 256), 256, lds, s, a, d_pal, k, wts);
-        else if (k <= 64) hipLaunchKernelGGL(k_dither_lane_repair<1>, nblk, 64, lds_r, s, a, d_pal, k, wts);
+        if (k <= 64) hipLaunchKernelGGL(k_dither_lane_repair<1>, nblk, 64, lds_r, s, a, d_pal, k, wts);
         else if (k <= 128) hipLaunchKernelGGL(k_dither_lane_repair<2>, nblk, 64, lds_r, s, a, d_pal, k, wts);
         else hipLaunchKernelGGL(k_dither_lane_repair<4>, nblk, 64, lds_r, s, a, d_pal, k, wts);
         HIP_CHECK(hipGetLastError());
@@ -2310,18 +2269,11 @@ static void launch_dither_t(int mode, unsigned blocks, const double *d_img, size
 #undef PAMD_DITHER1
 }
 
-static DitherConfig dither_settings() {
-    DitherConfig cfg = dither_cfg_snapshot();
-    if (const char *e = getenv("PAMD_DITHER_SEGMENTS")) cfg.segments = atoi(e);
-    if (const char *e = getenv("PAMD_DITHER_WARM")) cfg.warm = atoi(e);
-    if (const char *e = getenv("PAMD_DITHER_LANES")) cfg.lanes = atoi(e);
-    return cfg;
-}
 // One lane per run where the pruned search applies (8 <= K <= 256) and the image is large: the lane layout needs ~10^5 runs of a few
 // hundred pixels to fill the GPU and pays a gather, an un-permute and a repair round of fixed cost -- 2048^2: 2.3 ms against 1.6 ms
 // for one wavefront per run, 4096^2: 2.7 ms, 8192^2: 4.8 against 15.6 ms.  dither_layout(1) asks for it from 65 536 pixels on.
 bool dither_lane_layout(size_t width, size_t height, int k) {
-    const DitherConfig cfg = dither_settings();
+    const DitherConfig cfg = dither_cfg_snapshot();
     const size_t npix = width * height;
     if (!(k >= 8 && k <= 256) || cfg.segments == 1 || cfg.lanes == 0) return false;
     return cfg.lanes > 0 ? npix >= 65536 : npix >= ((size_t)1 << 23);
@@ -2335,7 +2287,7 @@ void launch_dither(const double *d_img, size_t plane_stride, int which, size_t w
     if (width * height >> 32) throw HipError("patolette_amd: the dither kernel numbers pixels with 32 bits");
     if (elem_bytes != 1 && elem_bytes != 4 && elem_bytes != 8) throw HipError("patolette_amd: map element size must be 1, 4 or 8");
     {
-        const DitherConfig cfg = dither_settings();
+        const DitherConfig cfg = dither_cfg_snapshot();
         // layout: what the caller decided when it chose the pixels' form (the knobs may change between its look and this one)
         if (layout >= 0 ? layout != 0 : dither_lane_layout(width, height, k)) {
             DitherWeights wts;
@@ -2391,7 +2343,7 @@ static void launch_dither_waves(const double *d_img, size_t plane_stride, size_t
     // Runs: two wavefronts per SIMD fill the issue slots of the chip (one chain alone uses ~2/3 of its SIMD's); never shorter than
     // the warm-up -- below that the speculative steps outnumber the useful ones.
     const size_t npix = width * height;
-    const DitherConfig cfg = dither_settings();
+    const DitherConfig cfg = dither_cfg_snapshot();
     DitherSeg sg{};
     sg.warm = cfg.warm >= 0 ? (unsigned)cfg.warm : 1024u;
     size_t S = cfg.segments > 0 ? (size_t)cfg.segments : (size_t)num_cus() * 8;

@@ -243,7 +243,7 @@ __device__ __forceinline__ double dpp_max_f64(const double v) {
 // (hm::lambda_max_bound x sum of weights: the scatter between two groups along their mean difference cannot exceed the node's
 // scatter along that direction; see leaf_bound).  init_kbase > 0: the call's first launch, which also sets the loop's state up
 // (the base clusters are nodes init_first .. init_first + init_kbase - 1).
-__global__ __launch_bounds__(256) void k_lq_children(NodeDev *nodes, LqCtl *c, const int call, const int eigen_bound, int init_kbase,
+__global__ __launch_bounds__(256) void k_lq_children(NodeDev *nodes, LqCtl *c, const int call, int init_kbase,
                                                      const int init_first, int init_nnodes, const int init_K, const GqOut *gq) {
     const bool init = init_kbase > 0;
     if (!init && c->h.done) return;
@@ -284,7 +284,7 @@ __global__ __launch_bounds__(256) void k_lq_children(NodeDev *nodes, LqCtl *c, c
     const bool single = d.gn <= 1ULL;
     const double sw = d.sw;
     if (single || !(sw > 0)) ub = 0;
-    else if (eigen_bound) {
+    else {
         double c6[6];
         for (int q = 0; q < 6; q++) c6[q] = cov[q] / sw;
         const double b = hm::lambda_max_bound(c6) * sw * (1.0 + 1e-9) + 1e-9 * cov[6];
@@ -313,7 +313,11 @@ __device__ __forceinline__ int block_excl_scan_256(const int v, int *sw /* [5] *
 // order-preserving 64-bit key of a priority (negative or NaN -> 0: below every threshold that matters)
 __device__ __forceinline__ unsigned long long lq_key(const double p) { return p > 0.0 ? (unsigned long long)__double_as_longlong(p) : 0ULL; }
 
-__global__ __launch_bounds__(256) void k_lq_select(NodeDev *nodes, LqCtl *c, const int call, const int e_lin, const int e_quad, const double beta) {
+// The split loops' speculation: of the leaves that could still matter, those whose priority is below kSpecBeta times the best of
+// them wait.  Swept 1/256 .. 1 on six kinds of content: 1/4 evaluates least (noise 514 -> 319 splits, lq -8 %).
+constexpr double kSpecBeta = 0.25;
+
+__global__ __launch_bounds__(256) void k_lq_select(NodeDev *nodes, LqCtl *c, const int call, const int e_lin, const int e_quad) {
     if (c->h.done) return;                                         // (set by an EARLIER launch only: every block of this one sees the same)
     const int tid = threadIdx.x, lane = tid & 63;
     const int cur = call & 1, nxt = cur ^ 1;
@@ -404,7 +408,7 @@ __global__ __launch_bounds__(256) void k_lq_select(NodeDev *nodes, LqCtl *c, con
     }
     const double thr = fmax(kDelta, tau * (1.0 - 1e-9));
     // ---- C. the leaves to evaluate: the children just made and what earlier rounds left waiting.  A leaf whose priority cannot reach
-    // tau never will (tau only grows): dropped for good.  Of the others, those far below the best of them wait (`beta`, the host-driven
+    // tau never will (tau only grows): dropped for good.  Of the others, those far below the best of them wait (kSpecBeta, the host-driven
     // loop's own rule and value: most of them fall below tau before their turn comes -- 500 evaluations a 256-colour palette without
     // the rule, ~330 with it); the best one is always taken, so every round evaluates something, and the loop ends when no leaf reaches
     // tau -- the set the replay needs is complete either way.  After 48 rounds everything that reaches tau is taken (a bound on the
@@ -418,7 +422,7 @@ __global__ __launch_bounds__(256) void k_lq_select(NodeDev *nodes, LqCtl *c, con
         return r.val < pp ? r.val : pp;
     };
     double thr2 = thr;
-    if (beta > 0.0 && c->h.rounds < 48) {
+    if (c->h.rounds < 48) {
         double u = -1.0;
         for (int i = tid; i < nleaves; i += 256) { const double pr = leaf_prio(c->leaves[i]); u = pr > u ? pr : u; }
 #pragma unroll
@@ -427,7 +431,7 @@ __global__ __launch_bounds__(256) void k_lq_select(NodeDev *nodes, LqCtl *c, con
         if (lane == 0) s_umax[tid >> 6] = u;
         __syncthreads();
         u = fmax(fmax(s_umax[0], s_umax[1]), fmax(s_umax[2], s_umax[3]));
-        if (beta * u > thr2) thr2 = beta * u;
+        if (kSpecBeta * u > thr2) thr2 = kSpecBeta * u;
     }
     int nkeep = 0, nr = 0;
     for (int base = 0; base < nleaves; base += 256) {
@@ -1247,8 +1251,6 @@ static bool node_axis(const HNode &h, double axis[3]) {
 // any two-way partition, so it bounds the benefit of the cut the reference will choose -- about three times tighter than
 // the distortion (the trace of S) for a roundish cluster.  The margins cover the roundings of the computed sums (~1e-15
 // relative to the distortion) with six orders to spare.
-static constexpr bool kUseEigenBound = true;
-static bool g_lq_eigen_bound = !(getenv("PAMD_LQ_EIGEN_BOUND") && atoi(getenv("PAMD_LQ_EIGEN_BOUND")) == 0);
 static void leaf_bound(HNode &h) {
     h.ub = h.dist;
     h.axis_state = 0;
@@ -1259,10 +1261,8 @@ static void leaf_bound(HNode &h) {
     double w[3];
     if (hm::eigen_sym3(a, w) != 0) { h.axis_state = -1; return; }
     h.axis[0] = a[6]; h.axis[1] = a[7]; h.axis[2] = a[8]; h.axis_state = 1;
-    if (kUseEigenBound && g_lq_eigen_bound) {
-        const double b = w[2] * h.sw * (1.0 + 1e-9) + 1e-9 * h.dist;
-        if (b == b && b < h.ub) h.ub = b;                          // NaN / larger: keep the distortion
-    }
+    const double b = w[2] * h.sw * (1.0 + 1e-9) + 1e-9 * h.dist;
+    if (b == b && b < h.ub) h.ub = b;                              // NaN / larger: keep the distortion
 }
 
 // --------------------------------------------------------------------------------------------
@@ -1405,7 +1405,7 @@ constexpr size_t kLqDeviceAutoPixels = (size_t)40 << 20;
 // yet).  Returns 0 (centres, stats filled in; the trace on request), -2 if the candidate tree outgrew the device's table (the caller
 // starts over on the host loop).
 static int lq_device_loop(Engine &E, size_t N, size_t K, bool weighted, bool inv_sums, const Bounds &bnd, const QuantBuffers &qlq, int kbase,
-                          int first_base, int nnodes, bool snake, std::vector<double> &centers, size_t &len, unsigned long long *max_members) {
+                          int first_base, int nnodes, std::vector<double> &centers, size_t &len, unsigned long long *max_members) {
     hipStream_t s = E.stream;
     const size_t lqs = (size_t)kNQ_LQ * 2 * kBuckets;
     const int ntA_ub = (int)ceil_div(N, (size_t)kTileA) + kLqRoundCap, ntP_ub = (int)ceil_div(N, (size_t)kTileP) + kLqRoundCap;
@@ -1417,11 +1417,9 @@ static int lq_device_loop(Engine &E, size_t N, size_t K, bool weighted, bool inv
     LqCtl *c = E.lqctl.p;
     LqHead *head = E.h_lqhead.p;
     for (int r = 0; r < kLqMaxRounds; r++) { head->round_px[r] = 0.0; head->round_nr[r] = 0.0; }
-    const int eigen_bound = (kUseEigenBound && g_lq_eigen_bound) ? 1 : 0;
     const RoundDyn *dyn = &c->dyn;
     const int *d_round = c->round_ids, *d_tP0 = c->tP0;
     int call = 0;                                                  // control calls so far: the parity selects the children list (LqCtl::cids)
-    static const double spec_beta_dev = getenv("PAMD_SPEC_BETA_DEV") ? atof(getenv("PAMD_SPEC_BETA_DEV")) : 0.25;   // 0: every leaf that reaches tau is evaluated at once
     // kbase < 0: the global quantiser ran on the device too (k_gq_control): the count of base clusters is in E.gqout, twelve at most
     const GqOut *gq = kbase < 0 ? (const GqOut *)E.gqout.p : nullptr;
     const int kb_ub = kbase < 0 ? kGqMaxK : kbase;
@@ -1429,11 +1427,11 @@ static int lq_device_loop(Engine &E, size_t N, size_t K, bool weighted, bool inv
         const bool first = call == 0;
         {
             KTIME("k_lq_children", s, 0.0);
-            if (first) hipLaunchKernelGGL(k_lq_children, (kb_ub + 3) / 4, 256, 0, s, E.nodes.p, c, call, eigen_bound, kb_ub, first_base, nnodes, (int)K, gq);
-            else hipLaunchKernelGGL(k_lq_children, 2 * kLqRoundCap / 4, 256, 0, s, E.nodes.p, c, call, eigen_bound, 0, 0, 0, 0, (const GqOut *)nullptr);
+            if (first) hipLaunchKernelGGL(k_lq_children, (kb_ub + 3) / 4, 256, 0, s, E.nodes.p, c, call, kb_ub, first_base, nnodes, (int)K, gq);
+            else hipLaunchKernelGGL(k_lq_children, 2 * kLqRoundCap / 4, 256, 0, s, E.nodes.p, c, call, 0, 0, 0, 0, (const GqOut *)nullptr);
         }
         KTIME("k_lq_select", s, 0.0);
-        hipLaunchKernelGGL(k_lq_select, 1 + (first ? (kb_ub + 3) / 4 : 2 * kLqRoundCap / 4), 256, 0, s, E.nodes.p, c, call, bnd.e_lin, bnd.e_quad, spec_beta_dev);
+        hipLaunchKernelGGL(k_lq_select, 1 + (first ? (kb_ub + 3) / 4 : 2 * kLqRoundCap / 4), 256, 0, s, E.nodes.p, c, call, bnd.e_lin, bnd.e_quad);
         HIP_CHECK(hipGetLastError());
         call++;
     };
@@ -1441,7 +1439,7 @@ static int lq_device_loop(Engine &E, size_t N, size_t K, bool weighted, bool inv
     auto round = [&]() {
         if (enq >= kLqMaxRounds) throw HipError("patolette_amd: split loop exceeded its round limit");
         const double *px_src = &head->round_px[enq], *nr_src = &head->round_nr[enq];
-        const bool rev = snake && (enq % 2 == 1);                  // the sweeps alternate their direction (see the host loop)
+        const bool rev = enq % 2 == 1;                             // the sweeps alternate their direction (see the host loop)
         // the round's set-up (tile lists, cleared bucket tables) rides on its first sweep; PAMD_LQ_SETUP_KERNEL=1: a launch of its own (A/B)
         static const bool setup_kernel = getenv("PAMD_LQ_SETUP_KERNEL") && atoi(getenv("PAMD_LQ_SETUP_KERNEL")) != 0;
         if (setup_kernel) {
@@ -1452,7 +1450,7 @@ static int lq_device_loop(Engine &E, size_t N, size_t K, bool weighted, bool inv
             const RoundLists rl{c->round_ids, c->tA0, c->tP0, E.tilesA.p, E.tilesP.p, E.hist.p, lqs, E.hsize.p, E.hcount.p};
             launch_minmax(qlq, E.tilesA.p, ntA_ub, 0, E.nodes.p, s, rev, dyn, px_src, &rl);
         }
-        launch_hist(qlq, false, E.tilesA.p, ntA_ub, 0, E.nodes.p, E.hist.p, E.hsize.p, E.hcount.p, s, snake && !rev, false, dyn, px_src);
+        launch_hist(qlq, false, E.tilesA.p, ntA_ub, 0, E.nodes.p, E.hist.p, E.hsize.p, E.hcount.p, s, !rev, false, dyn, px_src);
         launch_cut(weighted, E.nodes.p, d_round, kLqRoundCap, E.hist.p, E.hsize.p, E.hcount.p, E.lut.p, s, dyn, nr_src);
         launch_partition(qlq, E.tilesP.p, ntP_ub, 0, d_round, d_tP0, kLqRoundCap, E.nodes.p, E.lut.p, E.tilecnt.p, E.tileoff.p, true, s, inv_sums, rev, dyn, px_src);
         enq++;
@@ -1581,7 +1579,6 @@ static int quantize_clusters_run(Engine &E, size_t N, size_t K, bool weighted, c
     const int ntA0 = (int)ceil_div(N, (size_t)kTileA), ntP0 = (int)ceil_div(N, (size_t)kTileP);   // the root's tilings (gq_prepare)
     // every sweep over the pixels starts where the previous one stopped (see the split rounds below): the conversion wrote the
     // image front to back, so the root's moments are taken back to front, the extrema front to back, ...
-    static const bool snake = !(getenv("PAMD_SWEEP_SNAKE") && atoi(getenv("PAMD_SWEEP_SNAKE")) == 0);
     std::vector<NodeOut> got;
     bool mom_path = bnd.have_mom && !sh;                        // one sweep less: the directions of the following ones flip
     if (mom_path) {
@@ -1601,8 +1598,7 @@ static int quantize_clusters_run(Engine &E, size_t N, size_t K, bool weighted, c
             c6[q] = s2 - s1[ja[q]] * s1[jb[q]] / nn;
         }
         const long double tr = c6[0] + c6[3] + c6[5], tr2 = s2d[0] + s2d[1] + s2d[2];
-        static const bool guard = !(getenv("PAMD_ROOT_MOMENTS_GUARD") && atoi(getenv("PAMD_ROOT_MOMENTS_GUARD")) == 0);
-        if (guard && (!(tr > 1e-6L * tr2) || c6[0] < 0 || c6[3] < 0 || c6[5] < 0)) mom_path = false;
+        if (!(tr > 1e-6L * tr2) || c6[0] < 0 || c6[3] < 0 || c6[5] < 0) mom_path = false;
         else {
             for (int q = 0; q < 6; q++) hn[0].cov6[q] = (double)c6[q];
             hn[0].dist = (double)tr;
@@ -1611,7 +1607,7 @@ static int quantize_clusters_run(Engine &E, size_t N, size_t K, bool weighted, c
     if (!mom_path) {
         NodeIn d = make_nodedev(hn[0], bnd);
         put_nodes(E, {0}, {d});
-        launch_cov_nodes(qroot, E.cvt.p, E.tilesA.p, ntA0, N, E.nodes.p, s, snake);
+        launch_cov_nodes(qroot, E.cvt.p, E.tilesA.p, ntA0, N, E.nodes.p, s, true);
         if (sh) shard_exchange_acc(E, shard_upload_ids(E, {0}), 1);
         get_nodes(E, {0}, got);
         absorb_moments(hn[0], got[0]);
@@ -1632,9 +1628,9 @@ static int quantize_clusters_run(Engine &E, size_t N, size_t K, bool weighted, c
         put_nodes(E, {0}, {d});
     }
     const size_t hs = hist_slot_doubles();
-    launch_minmax(qroot, E.tilesA.p, ntA0, N, E.nodes.p, s, snake && mom_path);
+    launch_minmax(qroot, E.tilesA.p, ntA0, N, E.nodes.p, s, mom_path);
     if (sh) shard_exchange_keys(E, shard_upload_ids(E, {0}), 1);
-    launch_hist(qroot, true, E.tilesA.p, ntA0, N, E.nodes.p, E.hist.p, E.hsize.p, E.hcount.p, s, snake && !mom_path, Nt >= ((size_t)1 << 18));
+    launch_hist(qroot, true, E.tilesA.p, ntA0, N, E.nodes.p, E.hist.p, E.hsize.p, E.hcount.p, s, !mom_path, Nt >= ((size_t)1 << 18));
     if (sh) { comm_sum_dev(E, E.hist.p, hs, 0); comm_sum_dev(E, E.hcount.p, kBuckets, 2); }
     // The quantiser's decisions (global.c:189-298) on the device, the partition behind them without the host looking (k_gq_control):
     // one GPU, palettes of more than twelve colours (so that base clusters < K whatever the image), not verbose.  PAMD_GQ_DEVICE=0:
@@ -1652,8 +1648,8 @@ static int quantize_clusters_run(Engine &E, size_t N, size_t K, bool weighted, c
             HIP_CHECK(hipGetLastError());
         }
         launch_partition(qroot, E.tilesP.p, ntP0, N, E.round_nodes.p, E.node_tile0.p, 1, E.nodes.p, E.lut.p, E.tilecnt.p, E.tileoff.p, true, s, inv_sums,
-                         snake && mom_path, nullptr, nullptr, true);
-        launch_cov_children(qroot, E.tilesA.p, ntA0, N, E.nodes.p, s, snake && !mom_path, true);
+                         mom_path, nullptr, nullptr, true);
+        launch_cov_children(qroot, E.tilesA.p, ntA0, N, E.nodes.p, s, !mom_path, true);
         auto trace_header = [&]() {                              // (after a synchronisation)
             const GqOut &o = *E.h_gqout.p;
             E.trace_hdr.n_base = o.kbase;
@@ -1662,7 +1658,7 @@ static int quantize_clusters_run(Engine &E, size_t N, size_t K, bool weighted, c
         if (dev_eligible) {
             E.stats.ms_gq = now_ms() - t0;
             t0 = now_ms();
-            const int rc = lq_device_loop(E, N, K, weighted, inv_sums, bnd, qlq, -1, 1, 0, snake, centers, len, max_members);
+            const int rc = lq_device_loop(E, N, K, weighted, inv_sums, bnd, qlq, -1, 1, 0, centers, len, max_members);
             trace_header();
             E.stats.n_base_clusters = (size_t)E.h_gqout.p->kbase;
             if (rc != 0) return rc;
@@ -1767,16 +1763,16 @@ static int quantize_clusters_run(Engine &E, size_t N, size_t K, bool weighted, c
     E.h_bytes.reserve(kBuckets);                                // pinned: no synchronisation before the partition
     std::memcpy(E.h_bytes.p, lut.data(), kBuckets);
     HIP_CHECK(hipMemcpyAsync(E.lut.p, E.h_bytes.p, kBuckets, hipMemcpyHostToDevice, s));
-    launch_partition(qroot, E.tilesP.p, ntP0, N, E.round_nodes.p, E.node_tile0.p, 1, E.nodes.p, E.lut.p, E.tilecnt.p, E.tileoff.p, gq_binary, s, inv_sums, snake && mom_path);
+    launch_partition(qroot, E.tilesP.p, ntP0, N, E.round_nodes.p, E.node_tile0.p, 1, E.nodes.p, E.lut.p, E.tilecnt.p, E.tileoff.p, gq_binary, s, inv_sums, mom_path);
     if (sh) { hipLaunchKernelGGL(k_shard_children_local, 1, 64, 0, s, E.nodes.p, E.round_nodes.p, 1); HIP_CHECK(hipGetLastError()); }
-    if (!gq_binary) launch_cov_children(qroot, E.tilesA.p, ntA0, N, E.nodes.p, s, snake && !mom_path);
+    if (!gq_binary) launch_cov_children(qroot, E.tilesA.p, ntA0, N, E.nodes.p, s, !mom_path);
     if (sh) shard_exchange_acc(E, shard_upload_ids(E, base_ids), (int)base_ids.size());
     if (dev_eligible && (size_t)kbase < K) {
         // the split loop runs from the device: no synchronisation here, the control kernel takes the base clusters' moments itself
         E.stats.n_base_clusters = (size_t)kbase;
         E.stats.ms_gq = now_ms() - t0;
         t0 = now_ms();
-        const int rc = lq_device_loop(E, N, K, weighted, inv_sums, bnd, qlq, kbase, base_ids[0], (int)hn.size(), snake, centers, len, max_members);
+        const int rc = lq_device_loop(E, N, K, weighted, inv_sums, bnd, qlq, kbase, base_ids[0], (int)hn.size(), centers, len, max_members);
         if (rc != 0) return rc;
         E.stats.n_clusters = len;
         E.trace_hdr.n_clusters = (int32_t)len; E.trace_hdr.n_records = (int32_t)E.lq_commits.size();
@@ -1799,7 +1795,6 @@ static int quantize_clusters_run(Engine &E, size_t N, size_t K, bool weighted, c
     // ---------------- local quantiser (local.c:318-404) ----------------
     std::vector<int> result(base_ids);                          // frontier in the reference's order
     std::vector<int> leaves(base_ids);                          // candidate-tree nodes with moments but no split yet
-    static const double spec_beta = getenv("PAMD_SPEC_BETA") ? atof(getenv("PAMD_SPEC_BETA")) : 0.25;   // swept 1/256 .. 1 on six kinds of content: 1/4 evaluates least (noise 514 -> 319 splits, lq -8 %)
     size_t count = result.size();
     E.stats.split_evals = 0; E.stats.split_px = 0; E.stats.lq_rounds = 0;
     auto known = [&](const HNode &h) { return h.nosplit || h.gn <= 1 || h.split_done; };
@@ -1866,7 +1861,7 @@ static int quantize_clusters_run(Engine &E, size_t N, size_t K, bool weighted, c
             // upper bound of their benefit) is far below the current best benefit are left for later; the
             // exactness test above catches them if they ever become relevant.
             const double ref_b = std::max(best >= 0 ? bv : 0.0, max_unknown);
-            double thr = std::max(kDelta, spec_beta * ref_b);
+            double thr = std::max(kDelta, kSpecBeta * ref_b);
             {
                 // exact pruning: with R commits left, a leaf whose distortion is below the R-th largest
                 // KNOWN frontier benefit can never be chosen (its own and all its descendants' benefits are
@@ -1920,41 +1915,18 @@ static int quantize_clusters_run(Engine &E, size_t N, size_t K, bool weighted, c
             static const bool lq_trace = getenv("PAMD_LQ_TRACE") != nullptr;       // one line per split round on stderr
             if (lq_trace) fprintf(stderr, "patolette_amd: split round %zu: %d nodes, %zu pixels (%.2f of the image), %zu of %zu colours committed\n",
                                   E.stats.lq_rounds + 1, nr, rpx, (double)rpx / (double)(N ? N : 1), count, K);
-            // one packet, one copy: node records, ids, children ids, then per GROUP of nodes the tile prefixes of both tilings.
-            // One group = the whole round (the default).  PAMD_LQ_CHUNK_MB=m (experiment, profiles/r06_lq_chunk_major.txt): the round
-            // is issued chunk-major -- groups of nodes of <= m MB, each taken through minmax -> hist -> cut -> count -> scan -> scatter
-            // before the next group starts -- so that the second and third read of a node may find it in the Infinity Cache.
-            static const size_t chunk_mb = getenv("PAMD_LQ_CHUNK_MB") ? (size_t)atoi(getenv("PAMD_LQ_CHUNK_MB")) : 0;
-            std::vector<int> gb = {0};                              // group boundaries in todo[]
-            if (chunk_mb > 0 && !sh) {
-                const size_t cap_px = (chunk_mb << 20) / (planes * sizeof(double));
-                size_t acc = 0;
-                for (int r = 0; r < nr; r++) {
-                    const size_t n = hn[todo[r]].n;
-                    if (acc > 0 && acc + n > cap_px) { gb.push_back(r); acc = 0; }
-                    acc += n;
-                }
-            }
-            gb.push_back(nr);
-            const int ng = (int)gb.size() - 1;
+            // one packet, one copy: node records, ids, children ids, the tile prefixes of both tilings.  (Measured and removed:
+            // the round issued chunk-major, groups of nodes of a few MB each taken through minmax -> hist -> cut -> count -> scan ->
+            // scatter before the next group starts, so that the second and third read of a node may find it in the Infinity Cache;
+            // profiles/r06_lq_chunk_major.txt.)
             std::vector<int> cids;
             for (int id : todo) { cids.push_back(hn[id].left); cids.push_back(hn[id].right); }
-            std::vector<int> tAg, tPg;                               // the groups' prefixes one after the other (nrg + 1 entries each)
-            std::vector<size_t> g_off(ng), g_px(ng);
-            int ntA_max = 0, ntP_max = 0, nrg_max = 0;
-            for (int g = 0; g < ng; g++) {
-                g_off[g] = tAg.size();
-                int a = 0, b = 0; size_t px = 0;
-                tAg.push_back(0); tPg.push_back(0);
-                for (int r = gb[g]; r < gb[g + 1]; r++) {
-                    const unsigned long long n = hn[todo[r]].n;
-                    recs[r].slot = r - gb[g];
-                    a += (int)((n + kTileA - 1) / kTileA); b += (int)((n + kTileP - 1) / kTileP); px += n;
-                    tAg.push_back(a); tPg.push_back(b);
-                }
-                g_px[g] = px;
-                ntA_max = std::max(ntA_max, a); ntP_max = std::max(ntP_max, b); nrg_max = std::max(nrg_max, gb[g + 1] - gb[g]);
+            std::vector<int> tAg = {0}, tPg = {0};                   // the nodes' tile prefixes (nr + 1 entries each)
+            for (int id : todo) {
+                const unsigned long long n = hn[id].n;
+                tAg.push_back(tAg.back() + (int)((n + kTileA - 1) / kTileA)); tPg.push_back(tPg.back() + (int)((n + kTileP - 1) / kTileP));
             }
+            const int ntA = tAg[nr], ntP = tPg[nr];
             const size_t o_recs = 0, o_ids = o_recs + (size_t)nr * sizeof(NodeIn), o_cids = o_ids + (size_t)nr * sizeof(int),
                          o_tA = o_cids + cids.size() * sizeof(int), o_tP = o_tA + tAg.size() * sizeof(int),
                          pk_bytes = o_tP + tPg.size() * sizeof(int);
@@ -1967,41 +1939,36 @@ static int quantize_clusters_run(Engine &E, size_t N, size_t K, bool weighted, c
             lap(tm_packet);
             HIP_CHECK(hipMemcpyAsync(E.packet.p, E.h_packet.p, pk_bytes, hipMemcpyHostToDevice, s));
             const size_t lqs = (size_t)kNQ_LQ * 2 * kBuckets;
-            E.hist.reserve(std::max(hs, lqs * nrg_max)); E.hsize.reserve((size_t)nrg_max * kBuckets); E.hcount.reserve((size_t)nrg_max * kBuckets);
-            E.lut.reserve((size_t)nrg_max * kBuckets);
-            E.tilesA.reserve(ntA_max); E.tilesP.reserve(ntP_max);
-            E.tilecnt.reserve((size_t)ntP_max * kMaxChildren); E.tileoff.reserve((size_t)ntP_max * kMaxChildren);
+            E.hist.reserve(std::max(hs, lqs * nr)); E.hsize.reserve((size_t)nr * kBuckets); E.hcount.reserve((size_t)nr * kBuckets);
+            E.lut.reserve((size_t)nr * kBuckets);
+            E.tilesA.reserve(ntA); E.tilesP.reserve(ntP);
+            E.tilecnt.reserve((size_t)ntP * kMaxChildren); E.tileoff.reserve((size_t)ntP * kMaxChildren);
             // the sweeps of a round alternate their direction through the pixels (the first one runs against the partition that
-            // wrote them): each starts on what the previous one touched last.  PAMD_SWEEP_SNAKE=0: all forward
-            const bool rev = snake && (E.stats.lq_rounds % 2 == 1);     // (the base clusters' moments were taken back to front)
-            for (int g = 0; g < ng; g++) {
-                const int r0 = gb[g], nrg = gb[g + 1] - r0;
-                const int *d_ids = (const int *)(E.packet.p + o_ids) + r0;
-                const int *d_tA0 = (const int *)(E.packet.p + o_tA) + g_off[g], *d_tP0 = (const int *)(E.packet.p + o_tP) + g_off[g];
-                const int ntA = tAg[g_off[g] + nrg], ntP = tPg[g_off[g] + nrg];
-                const size_t gpx = g_px[g];
-                RoundSetup rs{(const NodeIn *)(E.packet.p + o_recs) + r0, d_ids, d_tA0, d_tP0, nrg, ntA, ntP,
-                              E.tilesA.p, E.tilesP.p, E.hist.p, lqs * nrg, E.hsize.p, E.hcount.p, (size_t)nrg * kBuckets};
-                {
-                    const size_t work = std::max<size_t>(std::max<size_t>(std::max<size_t>(ntP, lqs * nrg / 4), (size_t)nrg * kNodeResetElems), 256);
-                    hipLaunchKernelGGL(k_round_setup, (unsigned)std::min<size_t>((work + 255) / 256, 2048), 256, 0, s, E.nodes.p, rs);
-                    HIP_CHECK(hipGetLastError());
-                }
-                launch_minmax(qlq, E.tilesA.p, ntA, gpx, E.nodes.p, s, rev);
-                if (sh) shard_exchange_keys(E, d_ids, nrg);
-                launch_hist(qlq, false, E.tilesA.p, ntA, gpx, E.nodes.p, E.hist.p, E.hsize.p, E.hcount.p, s, snake && !rev);
-                if (sh) {
-                    comm_sum_dev(E, E.hist.p, lqs * nrg, 0);
-                    if (weighted) comm_sum_dev(E, E.hsize.p, (size_t)nrg * kBuckets, 1);
-                    comm_sum_dev(E, E.hcount.p, (size_t)nrg * kBuckets, 2);
-                }
-                launch_cut(weighted, E.nodes.p, d_ids, nrg, E.hist.p, E.hsize.p, E.hcount.p, E.lut.p, s);
-                launch_partition(qlq, E.tilesP.p, ntP, gpx, d_ids, d_tP0, nrg, E.nodes.p, E.lut.p, E.tilecnt.p, E.tileoff.p, true, s, inv_sums, rev);
-                if (sh) {
-                    hipLaunchKernelGGL(k_shard_children_local, (nrg + 63) / 64, 64, 0, s, E.nodes.p, d_ids, nrg);
-                    HIP_CHECK(hipGetLastError());
-                    shard_exchange_acc(E, (const int *)(E.packet.p + o_cids) + 2 * r0, 2 * nrg);
-                }
+            // wrote them): each starts on what the previous one touched last
+            const bool rev = E.stats.lq_rounds % 2 == 1;     // (the base clusters' moments were taken back to front)
+            const int *d_ids = (const int *)(E.packet.p + o_ids);
+            const int *d_tA0 = (const int *)(E.packet.p + o_tA), *d_tP0 = (const int *)(E.packet.p + o_tP);
+            RoundSetup rs{(const NodeIn *)(E.packet.p + o_recs), d_ids, d_tA0, d_tP0, nr, ntA, ntP,
+                          E.tilesA.p, E.tilesP.p, E.hist.p, lqs * nr, E.hsize.p, E.hcount.p, (size_t)nr * kBuckets};
+            {
+                const size_t work = std::max<size_t>(std::max<size_t>(std::max<size_t>(ntP, lqs * nr / 4), (size_t)nr * kNodeResetElems), 256);
+                hipLaunchKernelGGL(k_round_setup, (unsigned)std::min<size_t>((work + 255) / 256, 2048), 256, 0, s, E.nodes.p, rs);
+                HIP_CHECK(hipGetLastError());
+            }
+            launch_minmax(qlq, E.tilesA.p, ntA, rpx, E.nodes.p, s, rev);
+            if (sh) shard_exchange_keys(E, d_ids, nr);
+            launch_hist(qlq, false, E.tilesA.p, ntA, rpx, E.nodes.p, E.hist.p, E.hsize.p, E.hcount.p, s, !rev);
+            if (sh) {
+                comm_sum_dev(E, E.hist.p, lqs * nr, 0);
+                if (weighted) comm_sum_dev(E, E.hsize.p, (size_t)nr * kBuckets, 1);
+                comm_sum_dev(E, E.hcount.p, (size_t)nr * kBuckets, 2);
+            }
+            launch_cut(weighted, E.nodes.p, d_ids, nr, E.hist.p, E.hsize.p, E.hcount.p, E.lut.p, s);
+            launch_partition(qlq, E.tilesP.p, ntP, rpx, d_ids, d_tP0, nr, E.nodes.p, E.lut.p, E.tilecnt.p, E.tileoff.p, true, s, inv_sums, rev);
+            if (sh) {
+                hipLaunchKernelGGL(k_shard_children_local, (nr + 63) / 64, 64, 0, s, E.nodes.p, d_ids, nr);
+                HIP_CHECK(hipGetLastError());
+                shard_exchange_acc(E, (const int *)(E.packet.p + o_cids), 2 * nr);
             }
             lap(tm_enqueue);
             get_nodes_dev(E, (const int *)(E.packet.p + o_cids), (int)cids.size(), got);
@@ -2247,8 +2214,7 @@ static ConvertPlan convert_plan(const Engine &E, const patolette__QuantizationOp
     if (p.which == PAMD_SRGB_TO_ICTCP) p.sumk = make_bink(1, rootP);
     else if (p.which == PAMD_SRGB_TO_CIELUV) p.sumk = make_bink(8, rootP);
     // one GPU: the raw second moments ride along too (products < 1, resp. < 2^16), and the root's covariance needs no sweep
-    static const bool mom_on = !(getenv("PAMD_ROOT_MOMENTS") && atoi(getenv("PAMD_ROOT_MOMENTS")) == 0);
-    if (!E.shard && mom_on) {
+    if (!E.shard) {
         if (p.which == PAMD_SRGB_TO_ICTCP) p.momk = make_bink(1, rootP);
         else if (p.which == PAMD_SRGB_TO_CIELUV) p.momk = make_bink(16, rootP);
     }

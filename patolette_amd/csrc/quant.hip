@@ -205,7 +205,7 @@ __global__ __launch_bounds__(512) void k_hist(QuantBuffers qb, const Tile *__res
     // from_end: the blocks take their runs of tiles from the end of the list -- each sweep of a split round starts where the
     // previous one stopped, on the lines that are still in the caches (k_minmax)
     const int per = (ntiles + nblk - 1) / nblk;
-    const int bid = (from_end & 1) ? nblk - 1 - (int)blockIdx.x : (int)blockIdx.x;
+    const int bid = from_end ? nblk - 1 - (int)blockIdx.x : (int)blockIdx.x;
     const int tfirst = bid * per, tlast = min(ntiles, tfirst + per);
     for (int ti = tfirst; ti < tlast; ti++) {
         const Tile t = tiles[ti];
@@ -278,9 +278,6 @@ __global__ __launch_bounds__(512) void k_hist(QuantBuffers qb, const Tile *__res
                     left &= ~m;
                 }
             }
-#ifdef PAMD_KM_TRACE
-            if (from_end & 2) { if (pv[0] == 1.2345e300) h[b] = pv[1] + pv[2] + pv[3] + pv[4] + pv[5]; direct = false; }   // diagnostic: the kernel without its LDS atomics
-#endif
             if (direct) {
                 atomicAdd(&cnt[b], 1u);
 #pragma unroll
@@ -749,48 +746,31 @@ __global__ __launch_bounds__(1024) void k_scan(const int *__restrict__ round_nod
     if (threadIdx.x == 0) nd.cbegin[nch] = base;
 }
 
-// INV (with COV): every product is split onto the exact grids before it is added, so the children's moments no longer depend
-// on where the tile boundaries fall -- the same bits for any tiling, hence for any way of dealing an image out over several
-// GPUs (patolette_amd_slice).  The default adds each thread's products in plain f64 first (a fixed order for a fixed tiling:
-// deterministic, but the roundings move with the tile boundaries) and splits the 14 partials once per run of tiles.
-template <bool W, bool COV, bool INV = false>
-__global__ __launch_bounds__(256, INV ? 4 : 5) void k_scatter(QuantBuffers qb, const Tile *__restrict__ tiles, int ntiles, NodeDev *nodes,
+// The general partition: every child of a node gets its pixels in tile order (k_count / k_scan above give the offsets).
+// A block walks consecutive tiles (the tiles of one node are consecutive).
+template <bool W>
+__global__ __launch_bounds__(256, 5) void k_scatter(QuantBuffers qb, const Tile *__restrict__ tiles, int ntiles, NodeDev *nodes,
                                                     const unsigned char *__restrict__ lut, const unsigned long long *__restrict__ tileoff,
                                                     const int from_end) {
     constexpr int R = kTileP / 256;
     __shared__ unsigned long long off[R][4][kMaxChildren];
-    __shared__ double sm[28 * 4];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const unsigned long long ltmask = (1ULL << lane) - 1ULL;
-    // A block walks consecutive tiles (the tiles of one node are consecutive).  COV: each thread sums its products per
-    // child and quantity in plain f64 -- a fixed set of pixels in a fixed order for a given tiling, so deterministic --
-    // and the 14 per-thread partials are split onto the exact grids, reduced over the block and added atomically only
-    // when the node changes or the block is done.
     if ((from_end & 4) && nodes[0].nchild == 2) return;      // gated launch (launch_partition): the binary kernel has this partition
     const int per = (ntiles + (int)gridDim.x - 1) / (int)gridDim.x;
     const int bid = (from_end & 1) ? (int)gridDim.x - 1 - (int)blockIdx.x : (int)blockIdx.x;
     const int tfirst = bid * per, tlast = min(ntiles, tfirst + per);
-    constexpr int NP = INV ? 14 : 7;
-    double pl[NP], pr[NP];
-    if constexpr (COV) {
-#pragma unroll
-        for (int i = 0; i < NP; i++) { pl[i] = 0; pr[i] = 0; }
-    }
     for (int ti = tfirst; ti < tlast; ti++) {
         const Tile t = tiles[ti];
         const NodeDev &nd = nodes[t.node];
         const unsigned char *l = lut + (size_t)nd.slot * kBuckets;
-        const int nch = nd.nchild, split = nd.split;
+        const int nch = nd.nchild;
         unsigned cr[R];                                      // child (low byte) | rank within the wave << 8
 #pragma unroll
         for (int r = 0; r < R; r++) {
             unsigned i = r * 256 + threadIdx.x;
             int ch = 255;
-            if (i < t.count) {
-                const unsigned short b = qb.bkt[t.start + i];
-                if constexpr (COV) ch = (int)b > split ? 1 : 0;              // binary split: k_cut's table is b > split
-                else ch = (int)l[b];
-            }
+            if (i < t.count) ch = (int)l[qb.bkt[t.start + i]];
             unsigned rk = 0;
             for (int k = 0; k < nch; k++) {
                 unsigned long long m = __ballot(ch == k);
@@ -800,19 +780,7 @@ __global__ __launch_bounds__(256, INV ? 4 : 5) void k_scatter(QuantBuffers qb, c
             cr[r] = (unsigned)ch | (rk << 8);
         }
         __syncthreads();
-        if constexpr (COV) {
-            // binary split: the 2 x (R x 4) per-wave counts are turned into offsets by one wavefront (lane = child * 32 + entry,
-            // 32-lane prefix) instead of two threads walking 32 LDS entries each while the block waits
-            static_assert(R * 4 == 32, "one 32-lane group per child");
-            if (threadIdx.x < 64) {
-                const int k = lane >> 5, e = lane & 31;
-                const unsigned long long c = off[e >> 2][e & 3][k];
-                unsigned long long inc = c;
-#pragma unroll
-                for (int o = 1; o < 32; o <<= 1) { const unsigned long long t2 = __shfl_up(inc, o, 32); if (e >= o) inc += t2; }
-                off[e >> 2][e & 3][k] = tileoff[(size_t)ti * kMaxChildren + k] + inc - c;
-            }
-        } else if ((int)threadIdx.x < nch) {
+        if ((int)threadIdx.x < nch) {
             unsigned long long run = tileoff[(size_t)ti * kMaxChildren + threadIdx.x];
             for (int r = 0; r < R; r++)
                 for (int w = 0; w < 4; w++) { unsigned long long c = off[r][w][threadIdx.x]; off[r][w][threadIdx.x] = run; run += c; }
@@ -820,16 +788,6 @@ __global__ __launch_bounds__(256, INV ? 4 : 5) void k_scatter(QuantBuffers qb, c
         __syncthreads();
         const double *sx = qb.buf[nd.buf], *sy = sx + qb.N, *sz = sy + qb.N, *sw = sz + qb.N;
         double *dx = qb.buf[1 - nd.buf], *dy = dx + qb.N, *dz = dy + qb.N, *dw = dz + qb.N;
-        // COV (binary splits only): the children's centred moments are accumulated while their pixels pass through
-        // registers -- pca.c:62-101 / cluster.c:111-152 about the child means k_cut already wrote
-        double m0[2], m1[2], m2[2];
-        BinK kinv{0.0, 0.0};
-        if constexpr (COV) {
-            const NodeDev &c0 = nodes[nd.child0], &c1 = nodes[nd.child0 + 1];
-            m0[0] = c0.mean[0]; m1[0] = c0.mean[1]; m2[0] = c0.mean[2];
-            m0[1] = c1.mean[0]; m1[1] = c1.mean[1]; m2[1] = c1.mean[2];
-            if constexpr (INV) kinv = nd.kquad;
-        }
 #pragma unroll
         for (int r = 0; r < R; r++) {
             const int ch = (int)(cr[r] & 255u);
@@ -841,69 +799,28 @@ __global__ __launch_bounds__(256, INV ? 4 : 5) void k_scatter(QuantBuffers qb, c
                 if constexpr (W) w = sw[src];
                 dx[dst] = x; dy[dst] = y; dz[dst] = z;
                 if constexpr (W) dw[dst] = w;
-                if constexpr (COV) {
-                    const bool right = ch != 0;
-                    const double rf = right ? 1.0 : 0.0, lf = right ? 0.0 : 1.0;      // q * {0,1} exact, x + (+-0) = x
-                    const double ex = x - (right ? m0[1] : m0[0]), ey = y - (right ? m1[1] : m1[0]), ez = z - (right ? m2[1] : m2[0]);
-                    const double wx = w * ex, wy = w * ey, wz = w * ez;
-                    const double q[7] = {wx * ex, wy * ex, wz * ex, wy * ey, wz * ey, wz * ez, ((ex * ex + ey * ey) + ez * ez) * w};
-                    if constexpr (INV) {
-#pragma unroll
-                        for (int i = 0; i < 7; i++) {
-                            double v0, v1;
-                            bin_split(q[i], kinv, v0, v1);
-                            pl[2 * i] = __builtin_fma(v0, lf, pl[2 * i]); pl[2 * i + 1] = __builtin_fma(v1, lf, pl[2 * i + 1]);
-                            pr[2 * i] = __builtin_fma(v0, rf, pr[2 * i]); pr[2 * i + 1] = __builtin_fma(v1, rf, pr[2 * i + 1]);
-                        }
-                    } else {
-#pragma unroll
-                        for (int i = 0; i < 7; i++) { pl[i] = __builtin_fma(q[i], lf, pl[i]); pr[i] = __builtin_fma(q[i], rf, pr[i]); }
-                    }
-                }
-            }
-        }
-        if constexpr (COV) {
-            const bool flush = (ti + 1 == tlast) || tiles[ti + 1].node != t.node;       // block-uniform
-            if (flush) {
-                const BinK kq = nd.kquad;
-                double a[28];
-                if constexpr (INV) {
-#pragma unroll
-                    for (int i = 0; i < 14; i++) { a[i] = pl[i]; a[14 + i] = pr[i]; pl[i] = 0; pr[i] = 0; }
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 7; i++) {
-                        bin_split(pl[i], kq, a[2 * i], a[2 * i + 1]);
-                        bin_split(pr[i], kq, a[14 + 2 * i], a[14 + 2 * i + 1]);
-                        pl[i] = 0; pr[i] = 0;
-                    }
-                }
-                block_sum<28>(a, sm);
-                if (threadIdx.x == 0) {
-                    for (int side = 0; side < 2; side++) {
-                        NodeDev &ch = nodes[nd.child0 + side];
-                        for (int i = 0; i < 7; i++) {
-                            if (a[14 * side + 2 * i] != 0.0) unsafeAtomicAdd(&ch.acc[blockIdx.x & (kSlots - 1)][i][0], a[14 * side + 2 * i]);
-                            if (a[14 * side + 2 * i + 1] != 0.0) unsafeAtomicAdd(&ch.acc[blockIdx.x & (kSlots - 1)][i][1], a[14 * side + 2 * i + 1]);
-                        }
-                    }
-                }
             }
         }
         __syncthreads();                                     // `off` is rewritten by the next tile
     }
 }
 
-// The binary splits of the local quantiser (every sweep of k_scatter<., true, .> above), software-pipelined.  That kernel
-// makes one memory round trip after another -- eight bucket loads, then eight times (three pixel loads, wait, three stores),
-// the stores counted in the same in-order vmcnt as the loads -- and spends 81 % of its wavefront time parked with ~30 KB in
+// The binary splits of the local quantiser, software-pipelined, with the children's centred moments accumulated while their
+// pixels pass through registers.  The round-trip-per-round form it replaced (removed; it is in the history) made one memory
+// round trip after another -- eight bucket loads, then eight times (three pixel loads, wait, three stores),
+// the stores counted in the same in-order vmcnt as the loads -- and spent 81 % of its wavefront time parked with ~30 KB in
 // flight per CU, which is what 4.4 TB/s needs at ~2 us of latency and no more.  Here a wavefront issues ALL of a tile's
 // pixel loads (24, 32 with weights) first, then the NEXT tile's bucket loads; the offsets are worked out while the pixels
 // are on their way, and the next tile's ranks at the end of the trip, behind this tile's stores.  Nothing is waited for out
 // of issue order (gfx9's vmcnt retires loads and stores in the order they were issued: a wait for a late load is a wait
 // for everything before it), and what a trip hands to the next are ALU results (ranks, scalar offsets), never a load's
 // destination: a register copy of one, moved by the allocator behind the next trip's loads, would wait for this trip's stores.
-// Same pixels per thread, same order of the per-thread sums, same flush: bit-identical moments and layout.
+// Each thread sums its products per child and quantity in plain f64 -- a fixed set of pixels in a fixed order for a given
+// tiling, so deterministic -- and the 14 per-thread partials are split onto the exact grids, reduced over the block and
+// added atomically only when the node changes or the block is done.
+// INV: every product is split onto the exact grids before it is added, so the children's moments no longer depend on where
+// the tile boundaries fall -- the same bits for any tiling, hence for any way of dealing an image out over several GPUs
+// (patolette_amd_slice).
 template <bool W, bool INV>
 __global__ __launch_bounds__(256, (W || INV) ? 2 : 3) void k_scatter_bin(QuantBuffers qb, const Tile *__restrict__ tiles, int ntiles, NodeDev *nodes,
                                                                         const NodeDev *__restrict__ nodes_ro,
@@ -1185,11 +1102,7 @@ static void launch_hist_t(const QuantBuffers &qb, const Tile *d_tiles, int ntile
     // resident blocks per CU by LDS footprint (4 for the local quantiser's 29 KB, 1 for the global quantiser's 82+ KB);
     // each block walks its run of tiles and flushes once per node run
     const int g = std::min(ntiles, 256 * (GQ ? 1 : 4));
-    int fe = from_end ? 1 : 0;
-#ifdef PAMD_KM_TRACE
-    if (getenv("PAMD_HIST_NOATOMIC") && atoi(getenv("PAMD_HIST_NOATOMIC"))) fe |= 2;     // diagnostic: time the kernel without its LDS atomics (wrong results)
-#endif
-    hipLaunchKernelGGL((k_hist<W, GQ>), g, 512, lds, s, qb, d_tiles, ntiles, d_nodes, d_hist, d_hsize, d_hcount, fe, dyn);
+    hipLaunchKernelGGL((k_hist<W, GQ>), g, 512, lds, s, qb, d_tiles, ntiles, d_nodes, d_hist, d_hsize, d_hcount, from_end ? 1 : 0, dyn);
     HIP_CHECK(hipGetLastError());
 }
 
@@ -1320,32 +1233,21 @@ void launch_partition(const QuantBuffers &qb, const Tile *d_ptiles, int nptiles,
     if (nptiles) {
         KTIME_DYN(fuse_cov ? "k_scatter_cov" : "k_scatter", s, (qb.weighted ? 66.0 : 50.0), px, px_src);
         if (fuse_cov) {
-            static const bool v1 = getenv("PAMD_SCATTER_V1") && atoi(getenv("PAMD_SCATTER_V1")) != 0;   // the round-trip-per-round kernel (A/B)
-            if (!v1 || dyn || gated) {
-                const int gb = std::min(nptiles, 256 * ((invariant || qb.weighted) ? 2 : 3));
-                if (invariant) {
-                    if (qb.weighted) hipLaunchKernelGGL((k_scatter_bin<true, true>), gb, 256, 0, s, qb, d_ptiles, nptiles, d_nodes, (const NodeDev *)d_nodes, d_tileoff, fe, dyn);
-                    else hipLaunchKernelGGL((k_scatter_bin<false, true>), gb, 256, 0, s, qb, d_ptiles, nptiles, d_nodes, (const NodeDev *)d_nodes, d_tileoff, fe, dyn);
-                } else if (qb.weighted) hipLaunchKernelGGL((k_scatter_bin<true, false>), gb, 256, 0, s, qb, d_ptiles, nptiles, d_nodes, (const NodeDev *)d_nodes, d_tileoff, fe, dyn);
-                else hipLaunchKernelGGL((k_scatter_bin<false, false>), gb, 256, 0, s, qb, d_ptiles, nptiles, d_nodes, (const NodeDev *)d_nodes, d_tileoff, fe, dyn);
-                HIP_CHECK(hipGetLastError());
-                if (gated) {
-                    const int fg = (from_end ? 1 : 0) | 4;
-                    if (qb.weighted) hipLaunchKernelGGL((k_scatter<true, false>), nptiles, 256, 0, s, qb, d_ptiles, nptiles, d_nodes, d_lut, d_tileoff, fg);
-                    else hipLaunchKernelGGL((k_scatter<false, false>), nptiles, 256, 0, s, qb, d_ptiles, nptiles, d_nodes, d_lut, d_tileoff, fg);
-                    HIP_CHECK(hipGetLastError());
-                }
-                return;
-            }
-            const int g = std::min(nptiles, 256 * (invariant ? 4 : 5));   // resident blocks per CU, each loops over its run of tiles
+            const int gb = std::min(nptiles, 256 * ((invariant || qb.weighted) ? 2 : 3));
             if (invariant) {
-                if (qb.weighted) hipLaunchKernelGGL((k_scatter<true, true, true>), g, 256, 0, s, qb, d_ptiles, nptiles, d_nodes, d_lut, d_tileoff, fe);
-                else hipLaunchKernelGGL((k_scatter<false, true, true>), g, 256, 0, s, qb, d_ptiles, nptiles, d_nodes, d_lut, d_tileoff, fe);
-            } else if (qb.weighted) hipLaunchKernelGGL((k_scatter<true, true>), g, 256, 0, s, qb, d_ptiles, nptiles, d_nodes, d_lut, d_tileoff, fe);
-            else hipLaunchKernelGGL((k_scatter<false, true>), g, 256, 0, s, qb, d_ptiles, nptiles, d_nodes, d_lut, d_tileoff, fe);
+                if (qb.weighted) hipLaunchKernelGGL((k_scatter_bin<true, true>), gb, 256, 0, s, qb, d_ptiles, nptiles, d_nodes, (const NodeDev *)d_nodes, d_tileoff, fe, dyn);
+                else hipLaunchKernelGGL((k_scatter_bin<false, true>), gb, 256, 0, s, qb, d_ptiles, nptiles, d_nodes, (const NodeDev *)d_nodes, d_tileoff, fe, dyn);
+            } else if (qb.weighted) hipLaunchKernelGGL((k_scatter_bin<true, false>), gb, 256, 0, s, qb, d_ptiles, nptiles, d_nodes, (const NodeDev *)d_nodes, d_tileoff, fe, dyn);
+            else hipLaunchKernelGGL((k_scatter_bin<false, false>), gb, 256, 0, s, qb, d_ptiles, nptiles, d_nodes, (const NodeDev *)d_nodes, d_tileoff, fe, dyn);
+            if (gated) {
+                HIP_CHECK(hipGetLastError());
+                const int fg = (from_end ? 1 : 0) | 4;
+                if (qb.weighted) hipLaunchKernelGGL((k_scatter<true>), nptiles, 256, 0, s, qb, d_ptiles, nptiles, d_nodes, d_lut, d_tileoff, fg);
+                else hipLaunchKernelGGL((k_scatter<false>), nptiles, 256, 0, s, qb, d_ptiles, nptiles, d_nodes, d_lut, d_tileoff, fg);
+            }
         } else {
-            if (qb.weighted) hipLaunchKernelGGL((k_scatter<true, false>), nptiles, 256, 0, s, qb, d_ptiles, nptiles, d_nodes, d_lut, d_tileoff, fe);
-            else hipLaunchKernelGGL((k_scatter<false, false>), nptiles, 256, 0, s, qb, d_ptiles, nptiles, d_nodes, d_lut, d_tileoff, fe);
+            if (qb.weighted) hipLaunchKernelGGL((k_scatter<true>), nptiles, 256, 0, s, qb, d_ptiles, nptiles, d_nodes, d_lut, d_tileoff, fe);
+            else hipLaunchKernelGGL((k_scatter<false>), nptiles, 256, 0, s, qb, d_ptiles, nptiles, d_nodes, d_lut, d_tileoff, fe);
         }
     }
     HIP_CHECK(hipGetLastError());

@@ -323,7 +323,6 @@ struct MbdArgs {
     int rows, cols;
     unsigned int *progress;
     unsigned int *stalled;           // set when a strip gave up waiting for the one above it
-    int hs;                          // chunks per flag handshake with the neighbouring strips
 };
 
 __device__ __forceinline__ float wave_shr1(float from_above, float v) {
@@ -409,14 +408,15 @@ __global__ __launch_bounds__(64) void k_mbd_scan(MbdArgs a) {
         }
     };
     // The handshake with the strip above (a spin on its progress flag and an acquire fence) and with the strip below (a release
-    // fence and a flag store) can be made once per a.hs chunks; the strip then lags its neighbour by two windows of hs * kChunk
-    // steps instead of three chunks.  Measured at 4096 x 4096: a handshake costs ~0.7 us, a step ~90 ns, so hs = 2 trades
-    // 2 100 more steps for half the handshakes and comes out even (1.37 ms per pass either way); hs = 3, 4 are slower.
-    auto chunk_begin = [&](int t0, bool handshake) -> bool {             // true: gave up waiting
+    // fence and a flag store) is made once per chunk.  Measured and removed: once per hs chunks, the strip then lagging its
+    // neighbour by two windows of hs * kChunk steps instead of three chunks.  At 4096 x 4096 a handshake costs ~0.7 us, a step
+    // ~90 ns, so hs = 2 traded 2 100 more steps for half the handshakes and came out even (1.37 ms per pass either way); hs = 3,
+    // 4 were slower.
+    auto chunk_begin = [&](int t0) -> bool {                             // true: gave up waiting
         // steps t0 .. t0+kChunk-1 of lane 0 consume scan columns t0 .. t0+kChunk-1 of the row above the strip
         if (t0 >= Cn) return false;
-        if (strip > 0 && handshake) {
-            const unsigned int need = (unsigned int)min(Cn, t0 + a.hs * kChunk);
+        if (strip > 0) {
+            const unsigned int need = (unsigned int)min(Cn, t0 + kChunk);
             // bounded: the strip above always makes progress when all strips are resident (a few hundred single-wave
             // blocks), but a spin must never be able to hang the device -- past ~2 s the pass gives up and reports it
             unsigned spins = 0;
@@ -445,8 +445,8 @@ __global__ __launch_bounds__(64) void k_mbd_scan(MbdArgs a) {
     // so they have landed when the flag handshake at the block boundary drains the memory counter.
 #pragma unroll
     for (int j = 0; j < kChunk; j++) ring[j] = p[SD * j];
-    for (int t0 = 0, ci = 0; t0 < T; t0 += kChunk, ci = ci + 1 == a.hs ? 0 : ci + 1) {
-        if (chunk_begin(t0, ci == 0)) {                                           // let the strips below give up quickly too
+    for (int t0 = 0; t0 < T; t0 += kChunk) {
+        if (chunk_begin(t0)) {                                           // let the strips below give up quickly too
             if (lane == 0) __hip_atomic_store(&a.progress[strip], 0xFFFFFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             return;
         }
@@ -473,7 +473,7 @@ __global__ __launch_bounds__(64) void k_mbd_scan(MbdArgs a) {
                 visit(t0 + j, q + SD * j, ring[j], false, false);
             }
         }
-        if (ci + 1 == a.hs) chunk_end(t0 + kChunk - 1);
+        chunk_end(t0 + kChunk - 1);
 #pragma unroll
         for (int j = 0; j < kChunk; j++) ring[j] = next[j];
     }
@@ -532,7 +532,6 @@ static SkewGeom mbd_geometry(SalWork &w, int rows, int cols) {
 static void run_mbd_scans(SalWork &w, int rows, int cols, int iters, hipStream_t s, const float4 *st_rowmajor, float *d_out) {
     const int strips_f = (int)ceil_div((size_t)rows - 2, 64), strips_i = (int)ceil_div((size_t)rows - 3, 64);
     w.progress.reserve((size_t)strips_f + 1);                // [strips] progress + [1] stall flag
-    static const int hs = getenv("PAMD_MBD_HS") ? std::max(1, atoi(getenv("PAMD_MBD_HS"))) : 1;
     const SkewGeom geo = mbd_geometry(w, rows, cols);
     const int groups = ((rows + 126) >> 6) + 1;
     const size_t cells = (size_t)groups * geo.dn * 64;
@@ -540,7 +539,7 @@ static void run_mbd_scans(SalWork &w, int rows, int cols, int iters, hipStream_t
         KTIME("k_mbd_skew", s, 32.0 * rows * cols);
         hipLaunchKernelGGL(k_mbd_skew, stream_grid(cells), 256, 0, s, st_rowmajor, rows, cols, geo, groups, w.skew.p);
     }
-    MbdArgs ma{w.skew.p, geo, rows, cols, w.progress.p, w.progress.p + strips_f, hs};
+    MbdArgs ma{w.skew.p, geo, rows, cols, w.progress.p, w.progress.p + strips_f};
     w.d_stall = w.progress.p + strips_f;
     HIP_CHECK(hipMemsetAsync(w.d_stall, 0, sizeof(unsigned int), s));
     for (int pass = 0; pass < iters; pass++) {

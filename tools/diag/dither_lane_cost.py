@@ -1,6 +1,6 @@
 """Where a step of k_dither_lanes goes (diagnostic build: make -C patolette_amd/csrc TRACE=1; timings only, the maps of the
 flagged variants are wrong): the speculative launch's time with the record load made independent of the query (flag 4), without
-the exact pass (flag 8), both, and with the 32^3 grid.  usage: dither_lane_cost.py [side=4096]"""
+the exact pass (flag 8), and both.  usage: dither_lane_cost.py [side=4096]"""
 import ctypes as C
 import os
 import subprocess
@@ -35,9 +35,9 @@ if len(sys.argv) > 2 and sys.argv[2] == "child":
     pr = native.profile_results()
     raw.patolette_amd_debug_nn_flags(0)
     st = native.last_stats()
-    print("flags %d grid %s: k_dither (speculative launch) %.3f ms; runs %d" % (flags, os.environ.get("PAMD_DITHER_GRID", "64"), pr["k_dither"]["total_ms"], st["dither_segments"]))
+    print("flags %d: k_dither (speculative launch) %.3f ms; runs %d" % (flags, pr["k_dither"]["total_ms"], st["dither_segments"]))
     sys.exit(0)
 side = sys.argv[1] if len(sys.argv) > 1 else "4096"
-for flags, grid in ((0, "64"), (16, "64"), (24, "64")):
-    env = dict(os.environ, DLC_FLAGS=str(flags), PAMD_DITHER_GRID=grid)
+for flags in (0, 16, 24):
+    env = dict(os.environ, DLC_FLAGS=str(flags))
     subprocess.run([sys.executable, __file__, side, "child"], env=env, timeout=300)

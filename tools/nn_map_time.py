@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Mean launch time of the palette-map kernel on the two 67 MP geometries it is judged on -- `c4km` (ICtCp + KMeans palette) and
 `c4map` (BASELINE configs[3]: CIELuv + weights, no KMeans) -- and a checksum of the index map, for the library variant the
-environment selects (PAMD_NN_WAVES, PAMD_LIB_DIR): python tools/nn_map_time.py [steps]"""
+environment selects (PAMD_LIB_DIR): python tools/nn_map_time.py [steps]"""
 import ctypes as C
 import os
 import sys
@@ -36,5 +36,5 @@ for name, opts, wts in (("c4km", _native.QuantizationOptions(False, False, 2, 2,
     m8 = np.empty(n, dtype=np.uint8)
     L.patolette_amd_memcpy_d2h(m8.ctypes.data_as(C.c_void_p), dmap, n)
     us = 1e3 * r["total_ms"] / r["launches"]
-    print("%-6s k_nn_map %7.1f us x%d  %.3f of 8 TB/s   map crc %08x  (PAMD_NN_WAVES=%s)"
-          % (name, us, r["launches"], 25.0 * n / (us * 1e-6) / 8e12, zlib.crc32(m8.tobytes()), os.environ.get("PAMD_NN_WAVES", "default")), flush=True)
+    print("%-6s k_nn_map %7.1f us x%d  %.3f of 8 TB/s   map crc %08x"
+          % (name, us, r["launches"], 25.0 * n / (us * 1e-6) / 8e12, zlib.crc32(m8.tobytes())), flush=True)
