@@ -199,7 +199,7 @@ int patolette_amd_set_kmeans_update(int mode);
  * kernels, the sweep kernels read their sizes from device memory, which candidate nodes to evaluate is decided by a rule that
  * provably never skips a node the greedy loop commits, and the greedy loop of local.c:347-390 is replayed once, on the host, over
  * the evaluated tree; the host synchronises once per image instead of once per round.  Taken for palettes of up to 256 colours
- * on one GPU.  mode 2 (default): for images below 12 Mpixel, where the nine host turns are a third of the call; 1: wherever it
+ * on one GPU.  mode 2 (default): for images below 40 Mi pixels (40 x 2^20), where it is at least as fast; 1: wherever it
  * applies; 0: the host-driven loop everywhere (what sliced images, larger palettes and verbose calls always take).  Same
  * decisions and results either way (the children's moments may differ in their last bit: DESIGN.md 4.2).  Process-wide; returns
  * the previous setting.  Environment: PAMD_LQ_DEVICE=0|1|2. */
@@ -343,8 +343,23 @@ size_t patolette_amd_last_cluster_centers(double *out, size_t capacity_rows);
 /* TESTS ONLY: make the quantisers take a deliberately WRONG decision, to show that tests/tie_prover.py tells a tie from a bug.
  * 0 = none (default); 1 = the cut one occupied bucket past the arg-max of local.c:171; 2 = the greedy step takes the second
  * best cluster (local.c:277-307); 3 = the cut at the LAST maximum of the objective instead of the first (a member of the tie
- * set: differs from the reference only where the objective is exactly tied).  Process-wide; returns the previous setting. */
+ * set: differs from the reference only where the objective is exactly tied); 4 = NOT a wrong decision: the device-driven split
+ * loop reports its node table full after three rounds, so the call starts over on the host-driven loop (what a candidate tree
+ * too large for the table does; the result must not change).  Process-wide; returns the previous setting. */
 int patolette_amd_debug_fault(int which);
+
+/* TESTS ONLY: make the workspace's history visible.  A result must not depend on what the engine's buffers held before (another
+ * image's state, another engine's freed memory).  Bit 0 (poison): every fresh allocation of f64 / f32 device memory, and of f64
+ * pinned host memory, starts as quiet NaN, and so do the floating-point fields of the node table and of the split loop's control
+ * state; integer memory (indices, counts, keys) is never touched, so a stray read cannot become an address.  A NaN that reaches a
+ * result turns a silent dependence on memory contents into a visible mismatch.  Bit 1: count the workspace growths that free or
+ * move an allocation while the calling engine's streams still hold queued work (patolette_amd_debug_late_growths).  A count above
+ * zero is a definite hazard; a zero count is only evidence, since queued work may finish before the check.  Bit 2: name each such
+ * growth on stderr.  Process-wide; applies to later allocations; returns the previous flags.  Off: one relaxed atomic load per
+ * growth.  Environment default: PAMD_DEBUG_WORKSPACE=<flags>, read once when the library loads. */
+int patolette_amd_debug_workspace(int flags);
+/* late growths counted since the library loaded (bit 1 of patolette_amd_debug_workspace) */
+unsigned long long patolette_amd_debug_late_growths(void);
 
 /* ---- per-kernel timing with HIP events on the launch stream ------------------------------ */
 void patolette_amd_profile_enable(int on);   /* also resets the accumulated numbers */

@@ -127,6 +127,8 @@ SYMBOLS = {
     "patolette_amd_last_split_trace": (C.c_size_t, [C.POINTER(SplitTrace), C.POINTER(SplitRecord), C.c_size_t]),
     "patolette_amd_last_cluster_centers": (C.c_size_t, [dp, C.c_size_t]),
     "patolette_amd_debug_fault": (C.c_int, [C.c_int]),
+    "patolette_amd_debug_workspace": (C.c_int, [C.c_int]),
+    "patolette_amd_debug_late_growths": (C.c_ulonglong, []),
     "patolette_amd_set_split_loop": (C.c_int, [C.c_int]),
     "patolette_amd_profile_enable": (None, [C.c_int]),
     "patolette_amd_profile_only": (None, [C.c_char_p]),

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstddef>
 #include <cstdint>
 #include <cstdio>
@@ -75,24 +76,66 @@ struct ScopedKernel {
 #define KTIME_DYN(name, stream, per_unit, units, src) \
     pamd::ScopedKernel PAMD_CAT(_ktime_scope_, __LINE__)(name, stream, (src) ? (double)(per_unit) : (double)(per_unit) * (double)(units), src)
 
+// ---- workspace debugging (patolette_amd_debug_workspace, TESTS ONLY) ----
+// bit 0: fresh f64 / f32 memory of a DevBuf (and f64 of a PinBuf) starts as quiet NaN (all bytes 0xFF), the floating-point
+// fields of the record types with a WsPoison hook likewise; integer memory is never touched.  bit 1: count growths that free
+// or move an allocation while the calling engine's streams still hold queued work.  bit 2: also name each such growth on stderr.
+// Off: one relaxed load per growth.  Environment default: PAMD_DEBUG_WORKSPACE (read once, at library load).
+constexpr int kWsPoison = 1, kWsCount = 2, kWsLog = 4;
+extern std::atomic<int> g_debug_ws;
+extern std::atomic<unsigned long long> g_late_growths;
+// the streams of the engine the calling thread runs (set by WsGuard in the run paths; pointers, so that a stream made later counts)
+struct WsStreams { const hipStream_t *s[2] = {nullptr, nullptr}; };
+WsStreams &ws_streams();
+struct WsGuard {
+    WsStreams prev;
+    WsGuard(const hipStream_t *a, const hipStream_t *b) : prev(ws_streams()) { ws_streams().s[0] = a; ws_streams().s[1] = b; }
+    ~WsGuard() { ws_streams() = prev; }
+    WsGuard(const WsGuard &) = delete;
+    WsGuard &operator=(const WsGuard &) = delete;
+};
+void ws_growth(size_t bytes, const char *file, int line);              // an existing allocation is about to be freed or moved
+void ws_poison_dev(void *p, size_t bytes);                             // 0xFF bytes; complete when it returns
+void ws_poison_dev_rows(void *p, size_t pitch, size_t width, size_t rows);   // `width` bytes at the start of every `pitch`-byte row
+inline void ws_poison_host(double *p, size_t n) { for (size_t i = 0; i < n; i++) p[i] = __builtin_nan(""); }
+// per element type: what a fresh stretch [a, b) of elements gets under bit 0.  Default: nothing (integers, records without a hook)
+template <typename T> struct WsPoison {
+    static void dev(T *, size_t, size_t) {}
+    static void host(T *, size_t, size_t) {}
+};
+template <> struct WsPoison<double> {
+    static void dev(double *p, size_t a, size_t b) { ws_poison_dev(p + a, (b - a) * sizeof(double)); }
+    static void host(double *p, size_t a, size_t b) { ws_poison_host(p + a, b - a); }
+};
+template <> struct WsPoison<float> {
+    static void dev(float *p, size_t a, size_t b) { ws_poison_dev(p + a, (b - a) * sizeof(float)); }
+    static void host(float *, size_t, size_t) {}
+};
+
 // ---- simple device buffer with capacity reuse ----
 template <typename T>
 struct DevBuf {
     T *p = nullptr;
     size_t cap = 0;
-    void reserve(size_t n) {
+    void reserve(size_t n, const char *file = __builtin_FILE(), int line = __builtin_LINE()) {
         if (n <= cap) return;
+        const int dbg = g_debug_ws.load(std::memory_order_relaxed);
+        if (dbg && p) ws_growth(n * sizeof(T), file, line);
         if (p) (void)hipFree(p);
         p = nullptr; cap = 0;
         HIP_CHECK(hipMalloc((void **)&p, n * sizeof(T)));
         cap = n;
+        if (dbg & kWsPoison) WsPoison<T>::dev(p, 0, n);
     }
     // grow keeping the first `keep` elements
-    void grow(size_t n, size_t keep) {
+    void grow(size_t n, size_t keep, const char *file = __builtin_FILE(), int line = __builtin_LINE()) {
         if (n <= cap) return;
+        const int dbg = g_debug_ws.load(std::memory_order_relaxed);
+        if (dbg && p) ws_growth(n * sizeof(T), file, line);
         T *q = nullptr;
         size_t ncap = n + n / 2;
         HIP_CHECK(hipMalloc((void **)&q, ncap * sizeof(T)));
+        if (dbg & kWsPoison) WsPoison<T>::dev(q, keep, ncap);
         if (p && keep) HIP_CHECK(hipMemcpy(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice));
         if (p) (void)hipFree(p);
         p = q; cap = ncap;
@@ -109,12 +152,15 @@ template <typename T>
 struct PinBuf {
     T *p = nullptr;
     size_t cap = 0;
-    void reserve(size_t n) {
+    void reserve(size_t n, const char *file = __builtin_FILE(), int line = __builtin_LINE()) {
         if (n <= cap) return;
+        const int dbg = g_debug_ws.load(std::memory_order_relaxed);
+        if (dbg && p) ws_growth(n * sizeof(T), file, line);
         if (p) (void)hipHostFree(p);
         p = nullptr; cap = 0;
         HIP_CHECK(hipHostMalloc((void **)&p, n * sizeof(T), hipHostMallocDefault));
         cap = n;
+        if (dbg & kWsPoison) WsPoison<T>::host(p, 0, n);
     }
     ~PinBuf() { if (p) (void)hipHostFree(p); }
     PinBuf() = default;

@@ -2354,7 +2354,7 @@ static void launch_dither_waves(const double *d_img, size_t plane_stride, size_t
     sg.S = (unsigned)S;
     w.dither_segments = S; w.dither_repairs = 0; w.dither_rounds = 0; w.dither_through = 0; w.dither_jumps = 0; w.dither_solo = 0;
     if (S > 1) {
-        w.dside.reserve(16 * S + 16);
+        w.dside.reserve(16 * std::max(S, (size_t)num_cus() * 8) + 16);   // the default cap at once: no regrowth behind queued work
         w.hrep.reserve(2);
         sg.side = w.dside.p;
         sg.repairs = w.dside.p + 16 * S;

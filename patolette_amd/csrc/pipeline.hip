@@ -47,6 +47,31 @@ void launch_fill_weights(double *d, size_t n, uint64_t seed, hipStream_t s);
 // --------------------------------------------------------------------------------------------
 // (never destroyed: HIP objects must not be released after the runtime has shut down)
 KernelTimer &ktimer() { static thread_local KernelTimer *t = new KernelTimer; return *t; }
+
+// patolette_amd_debug_workspace (tests only; common.h)
+std::atomic<int> g_debug_ws{getenv("PAMD_DEBUG_WORKSPACE") ? atoi(getenv("PAMD_DEBUG_WORKSPACE")) & (kWsPoison | kWsCount | kWsLog) : 0};
+std::atomic<unsigned long long> g_late_growths{0};
+WsStreams &ws_streams() { static thread_local WsStreams w; return w; }
+void ws_growth(size_t bytes, const char *file, int line) {
+    const int dbg = g_debug_ws.load(std::memory_order_relaxed);
+    if (!(dbg & (kWsCount | kWsLog))) return;
+    bool queued = false;                                   // (work that completes before this query goes unseen: a zero count is evidence only)
+    for (const hipStream_t *sp : ws_streams().s)
+        if (sp && *sp && hipStreamQuery(*sp) == hipErrorNotReady) queued = true;
+    if (!queued) return;
+    g_late_growths.fetch_add(1);
+    if (dbg & kWsLog) fprintf(stderr, "patolette_amd: workspace growth to %zu bytes while work is queued (%s:%d)\n", bytes, file, line);
+}
+void ws_poison_dev(void *p, size_t bytes) {
+    if (!bytes) return;
+    HIP_CHECK(hipMemsetAsync(p, 0xFF, bytes, nullptr));
+    HIP_CHECK(hipStreamSynchronize(nullptr));
+}
+void ws_poison_dev_rows(void *p, size_t pitch, size_t width, size_t rows) {
+    if (!width || !rows) return;
+    HIP_CHECK(hipMemset2DAsync(p, pitch, 0xFF, width, rows, nullptr));
+    HIP_CHECK(hipStreamSynchronize(nullptr));
+}
 int KernelTimer::id_of(const char *name) {
     for (size_t i = 0; i < names.size(); i++) if (names[i] == name) return (int)i;
     names.emplace_back(name); total_ms.push_back(0); total_bytes.push_back(0); launches.push_back(0);
@@ -228,6 +253,19 @@ struct LqCtl {                                        // device memory
     LqRec nrec[kLqNodeCap];                           // -> host: the replay's table
     LqCen ncen[kLqNodeCap];                           // -> host: centres
 };
+// patolette_amd_debug_workspace bit 0: the control state's floating-point fields start as NaN (its integers stay as allocated)
+template <> struct WsPoison<LqCtl> {
+    static void dev(LqCtl *p, size_t a, size_t b) {
+        for (size_t i = a; i < b; i++) {
+            char *c = reinterpret_cast<char *>(p + i);
+            ws_poison_dev(c + offsetof(LqCtl, h) + offsetof(LqHead, tau), sizeof(double) * (1 + 2 * kLqMaxRounds));
+            ws_poison_dev(c + offsetof(LqCtl, np), sizeof(LqCtl::np));
+            ws_poison_dev_rows(c + offsetof(LqCtl, nrec), sizeof(LqRec), sizeof(double), kLqNodeCap);
+            ws_poison_dev(c + offsetof(LqCtl, ncen), sizeof(LqCtl::ncen));
+        }
+    }
+    static void host(LqCtl *, size_t, size_t) {}
+};
 
 // wave-wide maximum of a double through DPP row shifts and row broadcasts (lanes without a source keep their own value)
 template <int CTRL, int ROW_MASK>
@@ -254,6 +292,7 @@ __global__ __launch_bounds__(256) void k_lq_children(NodeDev *nodes, LqCtl *c, c
         c->K = init_K; c->M = init_K - init_kbase; c->nleaves = 0; c->ncids[0] = init_kbase; c->dyn = RoundDyn{0, 0, 0, 0};
         c->h.done = 0; c->h.error = 0; c->h.rounds = 0; c->h.nnodes = init_nnodes; c->h.neval = 0; c->h.split_evals = 0ULL; c->h.split_px = 0ULL;
         c->h.tau = 0.0;
+        for (int r = 0; r < kLqMaxRounds; r++) { c->h.round_px[r] = 0.0; c->h.round_nr[r] = 0.0; }
         if (gq && gq->error) { c->h.done = 1; c->h.error = 3; c->ncids[0] = 0; }
         // the records below the base clusters (the root) belong to no candidate: k_lq_select's rank count runs over ALL records below
         // nnodes, and what an earlier call or the allocator left there must not pass for an evaluated node (a stale record with a large
@@ -1400,6 +1439,37 @@ std::atomic<int> g_lq_device{getenv("PAMD_LQ_DEVICE") ? atoi(getenv("PAMD_LQ_DEV
 std::atomic<int> g_gq_device{getenv("PAMD_GQ_DEVICE") ? atoi(getenv("PAMD_GQ_DEVICE")) : 1};
 constexpr size_t kLqDeviceAutoPixels = (size_t)40 << 20;
 
+static bool lq_device_eligible(const Engine &E, size_t N, size_t K, bool verbose, bool allow_device) {
+    const int lq_mode = g_lq_device.load(std::memory_order_relaxed);
+    return allow_device && (lq_mode == 1 || (lq_mode == 2 && N < kLqDeviceAutoPixels)) && !E.shard && !verbose && K <= (size_t)kLqDevMaxK;
+}
+
+// What the quantisers of a call on an image of N pixels will reserve -- gq_prepare's tables, the node table and, when the call may
+// take the device-driven split loop, that loop's tables at their caps (lq_device_loop) -- reserved before the call enqueues
+// anything.  DevBuf::reserve frees the old allocation: never while queued work may still use it (the host-driven loop grows its
+// staging only after a synchronisation, see upload_tiles).  A no-op on every later call at this size.
+static void ws_prepare(Engine &E, size_t N, size_t K, bool weighted, bool verbose) {
+    const size_t planes = weighted ? 4 : 3;
+    const bool lq_dev = lq_device_eligible(E, N, K, verbose, true);
+    const size_t slack = lq_dev ? (size_t)kLqRoundCap : 0, ntA = ceil_div(N, (size_t)kTileA) + slack, ntP = ceil_div(N, (size_t)kTileP) + slack;
+    const size_t tables = lq_dev ? (size_t)kLqRoundCap * kBuckets : (size_t)kBuckets;
+    E.cvt.reserve(planes * N); E.cstats.reserve(1);
+    E.bufA.reserve(planes * N + 64); E.bufB.reserve(planes * N + 64); E.bkt.reserve(N);
+    E.tilesA.reserve(ntA); E.tilesP.reserve(ntP);
+    E.tilecnt.reserve(ntP * kMaxChildren); E.tileoff.reserve(ntP * kMaxChildren);
+    E.round_nodes.reserve(1); E.node_tile0.reserve(2); E.h_round.reserve(kBuckets);
+    E.hist.reserve(std::max(hist_slot_doubles(), lq_dev ? (size_t)kNQ_LQ * 2 * kBuckets * kLqRoundCap : 0));
+    E.hsize.reserve(tables); E.hcount.reserve(tables); E.lut.reserve(tables);
+    E.nodes.reserve(std::max<size_t>(4 * K + 64, lq_dev ? (size_t)kLqNodeCap : 0));
+    E.h_dbl.reserve(16 * kBuckets * 2 + 64);
+    E.gq.reserve(1); E.gqout.reserve(1); E.h_gqout.reserve(1); E.h_gq.reserve(1);
+    const size_t nput = kGqMaxK + 1;                               // put_nodes / get_nodes of the global quantiser: the root and its base clusters
+    E.stage_in.reserve(nput); E.stage_out.reserve(nput); E.ids.reserve(nput); E.h_stage_in.reserve(nput); E.h_stage_out.reserve(nput);
+    E.h_ids.reserve(nput); E.h_ids_get.reserve(nput);
+    E.h_cent.reserve(3 * K);                                       // KMeans: the centroids' pinned copy
+    if (lq_dev) { E.lqctl.reserve(1); E.h_lqhead.reserve(1); E.h_lqrec.reserve(kLqNodeCap); E.h_lqcen.reserve(kLqNodeCap); }
+}
+
 // The local quantiser driven from the device (k_lq_children / k_lq_select above).  In: the base clusters are nodes first_base ..
 // first_base + kbase - 1 of the table with their segments, means and moment accumulators complete on the stream (no synchronisation
 // yet).  Returns 0 (centres, stats filled in; the trace on request), -2 if the candidate tree outgrew the device's table (the caller
@@ -1458,11 +1528,14 @@ static int lq_device_loop(Engine &E, size_t N, size_t K, bool weighted, bool inv
     };
     control();                                                     // the base clusters' moments and bounds, round 1
     int want = (E.lq_hint_N == N && E.lq_hint_K == K && E.lq_hint_rounds > 0) ? E.lq_hint_rounds : 9;
+    const bool fault_full = g_debug_fault.load(std::memory_order_relaxed) == 4;
+    if (fault_full) want = 3;
     for (;;) {
         while (enq < want) round();
         hipLaunchKernelGGL(k_lq_export, 16, 256, 0, s, (const LqCtl *)c, head, E.h_lqrec.p, E.h_lqcen.p);
         HIP_CHECK(hipGetLastError());
         E.sync();
+        if (fault_full) return -2;                                 // patolette_amd_debug_fault(4): the table "filled up" after three rounds
         if (head->done) break;
         want = enq + 2;
     }
@@ -1544,8 +1617,7 @@ static int quantize_clusters_run(Engine &E, size_t N, size_t K, bool weighted, c
     if (E.prep_N != N || E.prep_planes != planes) gq_prepare(E, N, weighted);   // (the stage-level entry points come here unprepared)
     E.prep_N = 0;
     // PAMD_LQ_DEVICE=0: the host-driven split loop everywhere (A/B, and what sliced images, K > 256 and verbose calls always take)
-    const int lq_mode = g_lq_device.load(std::memory_order_relaxed);
-    const bool dev_eligible = allow_device && (lq_mode == 1 || (lq_mode == 2 && N < kLqDeviceAutoPixels)) && !sh && !verbose && K <= (size_t)kLqDevMaxK;
+    const bool dev_eligible = lq_device_eligible(E, N, K, verbose, allow_device);
     E.nodes.reserve(std::max<size_t>(4 * K + 64, dev_eligible ? (size_t)kLqNodeCap : 0));
     std::vector<HNode> hn;
     hn.reserve(4 * K + 64);
@@ -1931,6 +2003,14 @@ static int quantize_clusters_run(Engine &E, size_t N, size_t K, bool weighted, c
                          o_tA = o_cids + cids.size() * sizeof(int), o_tP = o_tA + tAg.size() * sizeof(int),
                          pk_bytes = o_tP + tPg.size() * sizeof(int);
             E.h_packet.reserve(pk_bytes); E.packet.reserve(pk_bytes);
+            // the round's tables and the children's pinned records: grown here, while the stream is idle (the last round ended with
+            // get_nodes_dev's synchronisation), not behind the packet's copy
+            const size_t lqs = (size_t)kNQ_LQ * 2 * kBuckets;
+            E.hist.reserve(std::max(hs, lqs * nr)); E.hsize.reserve((size_t)nr * kBuckets); E.hcount.reserve((size_t)nr * kBuckets);
+            E.lut.reserve((size_t)nr * kBuckets);
+            E.tilesA.reserve(ntA); E.tilesP.reserve(ntP);
+            E.tilecnt.reserve((size_t)ntP * kMaxChildren); E.tileoff.reserve((size_t)ntP * kMaxChildren);
+            E.h_stage_out.reserve(cids.size());
             std::memcpy(E.h_packet.p + o_recs, recs.data(), (size_t)nr * sizeof(NodeIn));
             std::memcpy(E.h_packet.p + o_ids, ids.data(), (size_t)nr * sizeof(int));
             std::memcpy(E.h_packet.p + o_cids, cids.data(), cids.size() * sizeof(int));
@@ -1938,11 +2018,6 @@ static int quantize_clusters_run(Engine &E, size_t N, size_t K, bool weighted, c
             std::memcpy(E.h_packet.p + o_tP, tPg.data(), tPg.size() * sizeof(int));
             lap(tm_packet);
             HIP_CHECK(hipMemcpyAsync(E.packet.p, E.h_packet.p, pk_bytes, hipMemcpyHostToDevice, s));
-            const size_t lqs = (size_t)kNQ_LQ * 2 * kBuckets;
-            E.hist.reserve(std::max(hs, lqs * nr)); E.hsize.reserve((size_t)nr * kBuckets); E.hcount.reserve((size_t)nr * kBuckets);
-            E.lut.reserve((size_t)nr * kBuckets);
-            E.tilesA.reserve(ntA); E.tilesP.reserve(ntP);
-            E.tilecnt.reserve((size_t)ntP * kMaxChildren); E.tileoff.reserve((size_t)ntP * kMaxChildren);
             // the sweeps of a round alternate their direction through the pixels (the first one runs against the partition that
             // wrote them): each starts on what the previous one touched last
             const bool rev = E.stats.lq_rounds % 2 == 1;     // (the base clusters' moments were taken back to front)
@@ -2004,6 +2079,7 @@ static int quantize_clusters_run(Engine &E, size_t N, size_t K, bool weighted, c
 
 static int quantize_clusters(Engine &E, size_t N, size_t K, bool weighted, const Bounds &bnd,
                              std::vector<double> &centers, size_t &len, bool verbose = false, unsigned long long *max_members = nullptr) {
+    WsGuard wg(&E.stream, &E.stream2);
     int rc = quantize_clusters_run(E, N, K, weighted, bnd, centers, len, verbose, max_members, true);
     if (rc == -2) {                                             // the device-driven loop ran out of node records: once more, host-driven
         E.prep_N = 0;
@@ -2228,8 +2304,10 @@ static void run_device(Engine &E, size_t width, size_t height, Pixels px, const 
     const size_t N = width * height;
     const bool weighted = d_weights != nullptr;
     const double t_start = now_ms();
+    WsGuard wg(&E.stream, &E.stream2);
     E.stats = patolette_amd__Stats{};
     E.prep_N = 0;
+    ws_prepare(E, N, K, weighted, opt->verbose);
     if (opt->kmeans_niter > 0) subsample_start(E, E.shard ? E.shard->total : N, K, opt->kmeans_max_samples);
     // S1: colour conversion into the working image (x|y|z|w planar), patolette.c:201-207
     double t0 = now_ms();
@@ -2430,7 +2508,11 @@ static void run_host(Engine &E, size_t width, size_t height, const double *data,
     // d_map_out: leave the narrow index map (u8 for K <= 256, else u32) in HBM there instead of widening it into palette_map
     const size_t N = width * height;
     double t0 = now_ms();
+    WsGuard wg(&E.stream, &E.stream2);
     E.src.reserve(3 * N);
+    if (weights) E.wsrc.reserve(N);
+    else if (tile_size > 0.0) { E.wsal.reserve(N); saliency_reserve(E.sal, width, height); }
+    ws_prepare(E, N, K, weights || tile_size > 0.0, opt->verbose);   // (the workspace as run_device will want it: nothing is queued yet)
     // Large images go up in pieces and what a piece completes is converted (on a second stream) while the next one is on the link:
     // the conversion (0.5 ms of a 4096^2 image's 7 ms upload) disappears behind the copy.  Its statistics are exact sums and keyed
     // extrema, so the chunking changes no bit.  With derived weights too: the saliency stage reads the sRGB source, which stays where it is.
@@ -2525,11 +2607,15 @@ static void run_u8(Engine &E, size_t width, size_t height, const unsigned char *
     const size_t N = width * height;
     hipStream_t s = E.stream;
     double t0 = now_ms();
+    WsGuard wg(&E.stream, &E.stream2);
+    if (!weights && tile_size > 0.0) { E.wsal.reserve(N); saliency_reserve(E.sal, width, height); }
+    ws_prepare(E, N, K, weights || tile_size > 0.0, opt->verbose);   // (as run_host)
     const unsigned char *d_px = pixels;
     const double *d_w = weights;
     bool converted = false;
     if (!on_device) {
         E.src8.reserve(N * (size_t)channels);
+        if (weights) E.wsrc.reserve(N);
         d_px = E.src8.p;
         // as run_host: a large image goes up in four pieces of whole pixels, each converted (second stream) while the next is on the link
         const size_t chunk_min = getenv("PAMD_UPLOAD_CHUNK_MIN") ? (size_t)atoll(getenv("PAMD_UPLOAD_CHUNK_MIN")) : ((size_t)1 << 21);
@@ -3193,6 +3279,8 @@ int patolette_amd_dither(const double *colors, size_t width, size_t height, cons
 }
 
 int patolette_amd_debug_fault(int which) { return g_debug_fault.exchange(which); }
+int patolette_amd_debug_workspace(int flags) { return g_debug_ws.exchange(flags & (kWsPoison | kWsCount | kWsLog)); }
+unsigned long long patolette_amd_debug_late_growths(void) { return g_late_growths.load(); }
 int patolette_amd_set_split_loop(int mode) { return g_lq_device.exchange(mode < 0 || mode > 2 ? 2 : mode); }
 int patolette_amd_set_global_quantiser(int on_device) { return g_gq_device.exchange(on_device ? 1 : 0); }
 void patolette_amd_dither_config(int segments, int warm) { dither_config(segments, warm); }

@@ -63,6 +63,17 @@ struct NodeDev {
     double acc[kSlots][7][2];
 };
 
+// patolette_amd_debug_workspace bit 0: a fresh node table's floating-point fields start as NaN (its integers stay as allocated)
+template <> struct WsPoison<NodeDev> {
+    static void dev(NodeDev *p, size_t a, size_t b) {
+        char *c = reinterpret_cast<char *>(p + a);
+        ws_poison_dev_rows(c + offsetof(NodeDev, axis), sizeof(NodeDev), offsetof(NodeDev, klin) - offsetof(NodeDev, axis), b - a);   // axis, mean, sw
+        ws_poison_dev_rows(c + offsetof(NodeDev, cov6), sizeof(NodeDev), offsetof(NodeDev, cbegin) - offsetof(NodeDev, cov6), b - a); // cov6, dist, ub
+        ws_poison_dev_rows(c + offsetof(NodeDev, acc), sizeof(NodeDev), sizeof(NodeDev::acc), b - a);
+    }
+    static void host(NodeDev *, size_t, size_t) {}
+};
+
 __device__ __forceinline__ void node_reset_outputs(NodeDev &d) {
     for (int i = 0; i < kSlots; i++) { d.minkey[i] = ~0ULL; d.maxkey[i] = 0ULL; }
     for (int i = 0; i < kSlots; i++) for (int q = 0; q < 7; q++) { d.acc[i][q][0] = 0; d.acc[i][q][1] = 0; }

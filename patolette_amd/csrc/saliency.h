@@ -33,6 +33,8 @@ struct SalWork {
 // error codes of the stage
 constexpr int kSalOk = 0, kSalBadShape = -2, kSalSingular = -3;
 
+// the stage's workspace for an image of this size, reserved before the caller enqueues anything (no regrowth behind queued work)
+void saliency_reserve(SalWork &w, size_t width, size_t height);
 // Returns kSalBadShape without touching the device when the reference's get_weights cannot process the
 // shape.  On success d_weights (width*height f64, device) holds 1 + sal^2 * N / tile_size^2.
 // d_f64 planar (channels >= 0) or (N,3) row-major (channels < 0); d_u8 interleaved with `channels` bytes per pixel

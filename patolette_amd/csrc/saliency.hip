@@ -531,7 +531,7 @@ static SkewGeom mbd_geometry(SalWork &w, int rows, int cols) {
 // d_out: the barrier distance, row-major
 static void run_mbd_scans(SalWork &w, int rows, int cols, int iters, hipStream_t s, const float4 *st_rowmajor, float *d_out) {
     const int strips_f = (int)ceil_div((size_t)rows - 2, 64), strips_i = (int)ceil_div((size_t)rows - 3, 64);
-    w.progress.reserve((size_t)strips_f + 1);                // [strips] progress + [1] stall flag
+    w.progress.reserve(std::max<size_t>((size_t)strips_f + 1, 1025));   // [strips] progress + [1] stall flag (65 536 rows at once: no regrowth behind queued work)
     const SkewGeom geo = mbd_geometry(w, rows, cols);
     const int groups = ((rows + 126) >> 6) + 1;
     const size_t cells = (size_t)groups * geo.dn * 64;
@@ -568,6 +568,13 @@ int mbd_device(SalWork &w, const float *h_img, size_t rows, size_t cols, int ite
     HIP_CHECK(hipStreamSynchronize(s));
     if (stalled) throw HipError("patolette_amd: the raster scan gave up waiting for a strip (device oversubscribed?)");
     return kSalOk;
+}
+
+void saliency_reserve(SalWork &w, size_t width, size_t height) {
+    const size_t n = width * height;
+    w.tmp.reserve(n); w.lab.reserve(3 * n); w.s.reserve(n);
+    (void)mbd_geometry(w, (int)height, (int)width);
+    w.dev.reserve(1); w.host.reserve(1);
 }
 
 int saliency_weights(SalWork &w, const double *d_f64, const unsigned char *d_u8, int channels, size_t width, size_t height,

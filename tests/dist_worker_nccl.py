@@ -59,7 +59,19 @@ def main():
         for i, r in enumerate(res):
             one = p.quantize(w, h, images[i], K, **kw)
             same = one[0] and np.array_equal(r[1], one[1]) and r[2].dtype == np.uint8 and np.array_equal(r[2], one[2])
-            notes.append("image %d %s" % (i, "same" if same else "DIFFERS"))
+            if same:
+                notes.append("image %d same" % i)
+            else:
+                # which side is wrong: both against a third call on a fresh workspace
+                L.patolette_amd_release_workspace()
+                fresh = p.quantize(w, h, images[i], K, **kw)
+
+                def side(res):
+                    if not (res[0] and fresh[0]):
+                        return "failed (%s / %s)" % (res[-1], fresh[-1])
+                    return "palette max diff %.3g, map mismatches %d" % (np.max(np.abs(res[1] - fresh[1])),
+                                                                         int(np.sum(res[2].astype(np.int64) != fresh[2].astype(np.int64))))
+                notes.append("image %d DIFFERS: batch vs fresh call: %s; separate call vs fresh call: %s" % (i, side(r), side(one)))
             ok = ok and same
         for im, r in zip(small, res8):
             one = p.quantize_u8(im, 24, dither=True, kmeans_niter=2)

@@ -13,8 +13,16 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture
 def loop(gpu):
-    yield lambda on_device: gpu.patolette_amd_set_split_loop(on_device)
-    gpu.patolette_amd_set_split_loop(1)
+    found = []
+
+    def set_mode(on_device):
+        prev = gpu.patolette_amd_set_split_loop(on_device)
+        if not found:
+            found.append(prev)
+        return prev
+    yield set_mode
+    if found:
+        gpu.patolette_amd_set_split_loop(found[0])
 
 
 def _same_decisions(ta, tb):
@@ -89,8 +97,16 @@ def test_device_driven_loop_at_bench_sizes(gpu, native, ob, loop):
 
 @pytest.fixture
 def gq(gpu):
-    yield lambda on_device: gpu.patolette_amd_set_global_quantiser(on_device)
-    gpu.patolette_amd_set_global_quantiser(1)
+    found = []
+
+    def set_mode(on_device):
+        prev = gpu.patolette_amd_set_global_quantiser(on_device)
+        if not found:
+            found.append(prev)
+        return prev
+    yield set_mode
+    if found:
+        gpu.patolette_amd_set_global_quantiser(found[0])
 
 
 def _blobs(rng, n, nblobs, spread):
