@@ -105,6 +105,37 @@ void patolette_amd_u8_device(size_t width, size_t height, const unsigned char *d
                              unsigned char *palette_u8, void *d_palette_map, int map_elem_bytes,
                              unsigned char *d_quantized, int *exit_code);
 
+/* ---- RGBA images: a transparent palette slot, an alpha-aware dither ---------------------------
+ * pixels: width*height interleaved 8-bit RGBA.  Pixel i is TRANSPARENT iff alpha_i < alpha_threshold (an integer in [0, 256]);
+ * every other pixel is OPAQUE.  M = number of opaque pixels, N = width*height.
+ *   M == N (no transparent pixel; always for alpha_threshold 0): bit for bit what patolette_amd_u8() returns for the RGB bytes with
+ *       the same options (f64 palette, palette bytes, map); palette_rgba[:, 3] = 255 on used rows; *transparent_index = -1.
+ *   0 < M < N: index 0 is the transparent entry -- f64 palette row 0 = (0, 0, 0), palette_rgba[0] = (0, 0, 0, 0),
+ *       *transparent_index = 0.  Rows 1 .. palette_size-1 are what patolette() returns with palette_size-1 colours for the (M, 3)
+ *       list of opaque pixels in row-scan order (their weights, in the same order; same options); unused rows -1 in the f64 palette
+ *       and (0, 0, 0, 0) in palette_rgba.  Map: 0 for a transparent pixel, 1 + that call's nearest-entry index for an opaque one; with
+ *       dithering, 1 + the choice of the reference's Riemersma walk over the width x height image on which transparent pixels are
+ *       treated exactly like positions outside the image (not dithered, the error queue unchanged): the chain visits the opaque
+ *       pixels in Hilbert order.
+ *   M == 0: success; row 0 is the transparent entry, every other row unused; the map is all 0; *transparent_index = 0.
+ * quantized: width*height x 4 interleaved = palette_rgba[palette_map] (opaque pixels have alpha 255).
+ * weights: NULL or N values, of which the opaque pixels' are used.  tile_size > 0 and no weights: the saliency weights are computed
+ * over the full image's RGB exactly as patolette_amd_u8() computes them (the RGB hidden under transparent pixels reaches the
+ * saliency map too), then restricted to the opaque pixels.  palette_only: the palettes as above, no map.
+ * Exit codes: as patolette_amd_u8(); -3 also for palette_size < 2 when opaque and transparent pixels are both present; -1 for an
+ * alpha_threshold outside [0, 256] (patolette_amd_last_error says why).  map_elem_bytes: 1, 2, 4 or 8, able to hold palette_size-1.
+ * Every output but exit_code may be NULL.  The *_device flavour takes device pointers for pixels / weights / palette_map /
+ * quantized (palette_map and quantized aligned to their element size, as hipMalloc returns them); palette, palette_rgba and
+ * transparent_index stay host memory. */
+void patolette_amd_rgba(size_t width, size_t height, const unsigned char *pixels, int alpha_threshold, const double *weights,
+                        double tile_size, size_t palette_size, const patolette__QuantizationOptions *options, double *palette,
+                        unsigned char *palette_rgba, void *palette_map, int map_elem_bytes, unsigned char *quantized,
+                        int *transparent_index, int *exit_code);
+void patolette_amd_rgba_device(size_t width, size_t height, const unsigned char *d_pixels, int alpha_threshold, const double *d_weights,
+                               double tile_size, size_t palette_size, const patolette__QuantizationOptions *options, double *palette,
+                               unsigned char *palette_rgba, void *d_palette_map, int map_elem_bytes, unsigned char *d_quantized,
+                               int *transparent_index, int *exit_code);
+
 /* ---- batch of independent images (SURVEY.md 8(b) "Batch extension") -----------------------
  * count images of identical width x height; data[i] / weights[i] (weights may be NULL or hold
  * NULL entries) / tile_size / palettes[i] / palette_maps[i] / exit_codes[i] as for

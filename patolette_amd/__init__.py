@@ -9,7 +9,8 @@ constants.  The work behind it runs in hand-written HIP kernels on gfx950 throug
 `tile_size > 0` derives the saliency weights on the GPU as the reference's binding does on the CPU
 (patolette.pyx:203-313).  Additive (not in the reference): the `weights=` keyword (explicit
 per-pixel weights instead of the saliency-derived ones), `saliency_weights`, `quantize_batch`, the 8-bit adaptor `quantize_u8` and its
-batch form `quantize_u8_batch`.
+batch form `quantize_u8_batch`, and `quantize_rgba` for RGBA images: a palette built from the visible pixels only, one reserved
+transparent index, and a dither that walks past transparent pixels as the reference's walks past positions outside the image.
 """
 import ctypes as C
 
@@ -213,6 +214,108 @@ def _quantize_u8_torch(image, palette_size, dither, palette_only, color_space, t
     return (True, palette_u8, pmap, quant, palette, message)
 
 
+def _rgba_args(palette_size, alpha_threshold, dither, palette_only, color_space, kmeans_niter, kmeans_max_samples):
+    if isinstance(alpha_threshold, bool) or int(alpha_threshold) != alpha_threshold or not 0 <= alpha_threshold <= 256:
+        raise ValueError("alpha_threshold must be an integer in [0, 256]")
+    opts = _native.QuantizationOptions(bool(dither), bool(palette_only), int(color_space), int(kmeans_niter),
+                                       int(kmeans_max_samples), False)
+    palette = np.zeros((max(palette_size, 0), 3), dtype=np.float64, order='F')
+    palette_rgba = np.zeros((max(palette_size, 0), 4), dtype=np.uint8)
+    return int(alpha_threshold), opts, palette, palette_rgba
+
+
+def quantize_rgba(image, palette_size, alpha_threshold=128, dither=True, palette_only=False, color_space=ColorSpace_ICtCp,
+                  tile_size=512, kmeans_niter=32, kmeans_max_samples=512 ** 2, weights=None, want_quantized=True):
+    """Quantise an (H, W, 4) uint8 RGBA image (additive; include/patolette_amd.h: patolette_amd_rgba).  `image` is a numpy array,
+    or a torch CUDA tensor (then the map and the quantized image stay in HBM, as in `quantize_u8`).
+
+    A pixel is transparent iff its alpha < alpha_threshold (an integer in [0, 256]); the others are opaque.
+      * No transparent pixel (always for alpha_threshold=0): bit for bit `quantize_u8` of the RGB bytes; alpha 255 on the used
+        palette rows; transparent_index = -1.
+      * Some: entry 0 is the transparent one (palette row (0, 0, 0), palette_rgba (0, 0, 0, 0)); entries 1 .. palette_size-1 are
+        what `quantize` returns with palette_size-1 colours for the opaque pixels in row-scan order (their weights); the map is 0 on
+        transparent pixels and 1 + the opaque pixel's index otherwise.  The dither walks the whole image's Hilbert curve and skips
+        transparent pixels exactly like positions outside the image (no dithering, the error queue unchanged).
+      * All transparent: success, row 0 the transparent entry, every other row unused, the map all 0.
+    weights: None or width*height values (the opaque pixels' are used).  tile_size > 0 without weights: the saliency weights of
+    the full image's RGB as `quantize_u8` derives them (the RGB hidden under transparent pixels reaches the saliency map too),
+    restricted to the opaque pixels.  palette_size < 2 with opaque and transparent pixels both present fails (exit code -3).
+
+    Returns (success, palette_rgba (K,4) uint8, palette_map (H,W) uint8|uint16|uint32 or None, quantized (H,W,4) uint8 or None
+    (= palette_rgba[palette_map]), palette (K,3) float64, transparent_index (0 or -1), message)."""
+    if hasattr(image, "data_ptr") and getattr(image, "is_cuda", False):
+        return _quantize_rgba_torch(image, palette_size, alpha_threshold, dither, palette_only, color_space, tile_size, kmeans_niter,
+                                    kmeans_max_samples, weights, want_quantized)
+    img = np.ascontiguousarray(image)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 4:
+        raise ValueError("image must be an (H, W, 4) uint8 array")
+    if tile_size < 0:
+        raise ValueError(bad_tile_size)
+    height, width, _ = img.shape
+    n = width * height
+    w = None
+    if weights is not None:
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if w.size != n:
+            raise ValueError("weights must hold width*height values")
+    thr, opts, palette, palette_rgba = _rgba_args(palette_size, alpha_threshold, dither, palette_only, color_space, kmeans_niter,
+                                                  kmeans_max_samples)
+    map_dtype = np.uint8 if palette_size <= 256 else (np.uint16 if palette_size <= 65536 else np.uint32)
+    pmap = None if palette_only else np.zeros((height, width), dtype=map_dtype)
+    quant = np.zeros((height, width, 4), dtype=np.uint8) if (want_quantized and not palette_only) else None
+    code, tidx = C.c_int(0), C.c_int(-1)
+    L = _native.lib()
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size > 0 else None   # noqa: E731
+    L.patolette_amd_rgba(width, height, vp(img), thr, _dp(w), float(tile_size), palette_size, C.byref(opts), _dp(palette),
+                         vp(palette_rgba), vp(pmap), np.dtype(map_dtype).itemsize, vp(quant), C.byref(tidx), C.byref(code))
+    return _rgba_result(L, code.value, palette_rgba, pmap, quant, palette, tidx.value)
+
+
+def _rgba_result(L, code, palette_rgba, pmap, quant, palette, tidx):
+    message = L.get_patolette_exit_code_info_message(code).decode('UTF-8')
+    _raise_saliency(code, message)
+    if code == -1 and _native.last_error().startswith("patolette_amd_rgba:"):
+        raise ValueError(_native.last_error())
+    if code != 0:
+        return (False, None, None, None, None, None, message)
+    return (True, palette_rgba, pmap, quant, palette, tidx, message)
+
+
+def _quantize_rgba_torch(image, palette_size, alpha_threshold, dither, palette_only, color_space, tile_size, kmeans_niter,
+                         kmeans_max_samples, weights, want_quantized):
+    """`quantize_rgba` for a torch CUDA uint8 tensor (H, W, 4) through `patolette_amd_rgba_device`, as `_quantize_u8_torch`: the
+    map (uint8 for K <= 256, else int32) and the quantized image stay in HBM, the palettes come back as numpy arrays."""
+    import torch
+    if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 4:
+        raise ValueError("image must be an (H, W, 4) uint8 tensor")
+    if tile_size < 0:
+        raise ValueError(bad_tile_size)
+    img = image.contiguous()
+    height, width, _ = (int(v) for v in img.shape)
+    n = width * height
+    dev = img.device
+    w = None
+    if weights is not None:
+        w = torch.as_tensor(weights, dtype=torch.float64, device=dev).reshape(-1).contiguous()
+        if w.numel() != n:
+            raise ValueError("weights must hold width*height values")
+    thr, opts, palette, palette_rgba = _rgba_args(palette_size, alpha_threshold, dither, palette_only, color_space, kmeans_niter,
+                                                  kmeans_max_samples)
+    me = 1 if palette_size <= 256 else 4
+    pmap = None if palette_only else torch.zeros((height, width), dtype=torch.uint8 if me == 1 else torch.int32, device=dev)
+    quant = torch.zeros((height, width, 4), dtype=torch.uint8, device=dev) if (want_quantized and not palette_only) else None
+    code, tidx = C.c_int(0), C.c_int(-1)
+    L = _native.lib()
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream().synchronize()          # the library runs on its own stream
+        L.patolette_amd_rgba_device(width, height, C.c_void_p(img.data_ptr()), thr,
+                                    C.c_void_p(w.data_ptr()) if w is not None else None, float(tile_size), palette_size,
+                                    C.byref(opts), _dp(palette), palette_rgba.ctypes.data_as(C.c_void_p) if palette_rgba.size else None,
+                                    C.c_void_p(pmap.data_ptr()) if pmap is not None else None, me,
+                                    C.c_void_p(quant.data_ptr()) if quant is not None else None, C.byref(tidx), C.byref(code))
+    return _rgba_result(L, code.value, palette_rgba, pmap, quant, palette, tidx.value)
+
+
 def quantize_batch(width, height, images, palette_size, weights=None, dither=True, palette_only=False,
                    color_space=ColorSpace_ICtCp, tile_size=512, kmeans_niter=32, kmeans_max_samples=512 ** 2, verbose=False):
     """Quantise a list of independent images of identical size on the current GPU through
@@ -325,6 +428,7 @@ __all__ = [
     "quantize_batch",
     "quantize_u8",
     "quantize_u8_batch",
+    "quantize_rgba",
     "saliency_weights",
     "ColorSpace_sRGB",
     "ColorSpace_CIELuv",

@@ -18,6 +18,8 @@ struct NNWork {                        // scratch of the pruned NN map
     DevBuf<double> dsort;              // lane-per-run dither: the pixels in curve order (3 planes)
     DevBuf<unsigned int> dpos;         // ... their linear pixel numbers (a function of width and height: kept between calls)
     size_t order_w = 0, order_h = 0; int order_dev = -1;
+    DevBuf<unsigned int> dmpos;        // masked dither: the opaque pixels' compact numbers in curve order (made from dpos, which stays as it is)
+    DevBuf<unsigned int> dmcnt;        // ... the compaction's tile counts / offsets and, behind them, the count
     DevBuf<unsigned char> dsmap;       // ... the choices in curve order, and behind them the [S][16] boundary records
     DevBuf<unsigned char> dflag;       // ... [S + 1] which boundaries the last check listed
     size_t dither_segments = 0, dither_repairs = 0, dither_rounds = 0;   // of the last launch_dither
@@ -46,6 +48,15 @@ void launch_nn_map(const double *d_colors, size_t plane_stride, size_t n, const 
 bool dither_lane_layout(size_t width, size_t height, int k);
 void launch_dither(const double *d_img, size_t plane_stride, int which, size_t width, size_t height, const double *d_pal, const double *h_pal, int k,
                    void *d_out, int elem_bytes, NNWork &w, hipStream_t s, int layout = -1);   // layout: 1 lanes, 0 wavefronts, -1 decide here
+
+// The same chain over a width x height image of which only some pixels are visited (the RGBA entry): d_cpos[pixel] = the pixel's
+// number among the m opaque ones (row-scan order), or -1 for a transparent pixel, which the walk skips exactly like a position
+// outside the image.  d_img: the opaque pixels' compact planes (plane_stride >= m), d_out: m choices in compact order.  The layout
+// is decided on m (dither_lane_layout(m, 1, k)) unless the caller passes it.
+void launch_dither_masked(const double *d_img, size_t plane_stride, int which, size_t width, size_t height, const int *d_cpos, size_t m,
+                          const double *d_pal, const double *h_pal, int k, void *d_out, int elem_bytes, NNWork &w, hipStream_t s, int layout = -1);
+// what launch_dither_masked takes of the workspace for an image of npix pixels, reserved before anything is enqueued
+void dither_mask_reserve(NNWork &w, size_t npix);
 
 // test / tuning knob: runs the curve is cut into (0 = chosen from the image size) and in-image pixels of warm-up (< 0 = default)
 void dither_config(int segments, int warm);

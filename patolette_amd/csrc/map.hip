@@ -16,6 +16,7 @@
 // verified at every boundary and repaired where the speculation missed: ~2000 runs of one
 // wavefront each (DitherSeg), or ~130 000 runs of one LANE each on large images (DitherLanes).
 #include "map.h"
+#include "compact.h"
 #include "dither_slots.h"
 
 #include <algorithm>
@@ -1038,10 +1039,15 @@ struct DitherSeg {
 // GT: the palette tables are in global memory (K > 3200).  A template parameter and not a run-time choice of pointer: the chosen
 // colour is read once per pixel ON the serial chain, and through a pointer that may be either space the compiler issues a FLAT load
 // (both address paths, vmcnt and lgkmcnt waited for) where the LDS table needs a ds_read_b64.
-template <typename OutT, int PER, bool GT, int MODE>
+// MASKED (the RGBA entry): the chain visits the mcount opaque pixels whose compact numbers mpos lists in curve order, and skips the
+// transparent ones exactly like positions outside the image.  A "curve position" is then a rank in that table (all of them visited),
+// runs are cut at multiples of 64 ranks, and img / out are the compact planes and map.  The last two arguments come after the others
+// and are read only under MASKED: the unmasked instances are the same code as before they existed.
+template <typename OutT, int PER, bool GT, int MODE, bool MASKED>
 __global__ __launch_bounds__(64) void k_dither(const double *__restrict__ img, size_t plane_stride, unsigned width, unsigned height,
                                                const double *__restrict__ pal /* planar (k,3), linear Rec2020 */, int k,
-                                               OutT *out, DitherWeights wts, double *gtab, DitherSeg sg) {
+                                               OutT *out, DitherWeights wts, double *gtab, DitherSeg sg,
+                                               const unsigned *__restrict__ mpos, unsigned long long mcount) {
     extern __shared__ double lds[];
     constexpr int kRing = 128;                                       // >= 64 + 15 pending pixels
     // the two palette tables live in LDS; a palette too large for that (K > 3200; the reference takes any K,
@@ -1139,21 +1145,26 @@ __global__ __launch_bounds__(64) void k_dither(const double *__restrict__ img, s
     };
 
     // ---- this wavefront's stretch of the curve: [d_begin, d_start) warm-up, [d_start, d_end) its own run ----
-    const unsigned long long total = 1ULL << (2 * L);
-    const unsigned long long npix = (unsigned long long)width * height;
+    const unsigned long long total = MASKED ? mcount : 1ULL << (2 * L);
+    const unsigned long long npix = MASKED ? mcount : (unsigned long long)width * height;
+    // where visited pixel t lies (dither_locate); masked: at rank t, in the block of 64 ranks that starts at t & ~63
+    auto locate = [&](const unsigned long long t, unsigned long long &d, unsigned long long &c) {
+        if constexpr (MASKED) { d = t < mcount ? t & ~63ULL : mcount; c = d; }
+        else dither_locate(L, width, height, t, d, c);
+    };
     const unsigned b = MODE == 0 ? blockIdx.x : blockIdx.x + sg.b0;
     unsigned long long d_begin = 0, d_start = 0, d_end = total;
     unsigned head = 16, count = 16;                                  // ring positions (absolute); head is a multiple of 16
     unsigned *const side = sg.S > 1 ? sg.side + 16u * b : nullptr;
     if (sg.S > 1) {
         unsigned long long c_start = 0, c_begin = 0, cc;
-        if (b > 0) dither_locate(L, width, height, npix * b / sg.S, d_start, c_start);
-        if (b + 1 < sg.S && !(MODE == 1 && sg.through)) dither_locate(L, width, height, npix * (b + 1) / sg.S, d_end, cc);
+        if (b > 0) locate(npix * b / sg.S, d_start, c_start);
+        if (b + 1 < sg.S && !(MODE == 1 && sg.through)) locate(npix * (b + 1) / sg.S, d_end, cc);
         d_begin = d_start;
         if (b > 0) {
             // MODE 0: the warm-up; MODE 1: just the sixteen pixels before the run (their positions end up in the ring)
             const unsigned long long back = MODE == 0 ? sg.warm : 16u;
-            dither_locate(L, width, height, c_start > back ? c_start - back : 0, d_begin, c_begin);
+            locate(c_start > back ? c_start - back : 0, d_begin, c_begin);
             const unsigned cw = (unsigned)(c_start - c_begin);
             if constexpr (MODE == 0) {
                 count = 16u - (cw & 15u);                            // drop cw mod 16 pixels: the warm-up ends with a whole group
@@ -1208,6 +1219,21 @@ __global__ __launch_bounds__(64) void k_dither(const double *__restrict__ img, s
     const bool needs_skip = width < (1u << L) || height < (1u << L);
     // decode the block of 64 positions at d0 and append its in-image pixels to the ring; false = an empty aligned square was skipped
     auto load_block = [&](unsigned long long &d0) -> bool {
+        if constexpr (MASKED) {                                      // 64 ranks of the table: every one below mcount is visited
+            const unsigned long long r = d0 + (unsigned long long)lane;
+            const bool inb = r < mcount;
+            const unsigned long long mask = __ballot(inb);
+            if (inb) {
+                const unsigned p = mpos[r];
+                const unsigned slot = (count + (unsigned)lane) & (kRing - 1);   // (d0 is a multiple of 64: the lanes below are in too)
+                rpx[slot] = pr[p]; rpx[kRing + slot] = pg[p]; rpx[2 * kRing + slot] = pb[p];
+                rpos[slot] = p;
+            }
+            count += (unsigned)__popcll(mask);
+            __builtin_amdgcn_wave_barrier();
+            d0 += 64;
+            return true;
+        }
         if (L >= 3 && needs_skip) {                                  // skip whole out-of-image aligned sub-squares
             for (int j = L; j >= 3; j--) {
                 const unsigned long long span = 1ULL << (2 * j);
@@ -2043,12 +2069,25 @@ static int current_device() { int d = -1; (void)hipGetDevice(&d); return d; }
 static std::atomic<bool> g_dither_order_cache{true};
 void dither_order_cache(bool on) { g_dither_order_cache = on; }
 
+// rank -> pixel number (w.dpos) of a width x height image: a function of the image's dimensions alone, kept between calls on images
+// of one size.  w.dpos must hold width * height entries.
+static void dither_order(NNWork &w, size_t width, size_t height, hipStream_t s) {
+    if (g_dither_order_cache && w.order_w == width && w.order_h == height && w.order_dev == current_device()) return;
+    const size_t npix = width * height;
+    KTIME("k_dither_order", s, 4.0 * npix);
+    const unsigned parts = (unsigned)std::max<size_t>(1, std::min<size_t>(8192, npix / 16384));
+    hipLaunchKernelGGL(k_dither_order, parts, 64, 0, s, (unsigned)width, (unsigned)height, parts, w.dpos.p);
+    w.order_w = width; w.order_h = height; w.order_dev = current_device();
+}
+
 // One lane per run (k_dither_lanes): K in [8, 256], images of 2^16 pixels and more.  h_pal: the palette on the host, planar (k,3).
 // Returns false when the verification stalls (a long flat stretch whose colour is not a palette entry: launch_dither_waves' comment):
 // the caller then takes the wavefront layout, which can walk one run through its successors.
+// mpos: the masked table (mcount opaque pixels, compact numbers in curve order: launch_dither_masked) in place of the cached curve order
 static bool launch_dither_lanes(const double *d_img, size_t plane_stride, int which, size_t width, size_t height, const double *d_pal, const double *h_pal,
-                                int k, void *d_out, int elem_bytes, NNWork &w, const DitherConfig &cfg, const DitherWeights &wts, hipStream_t s) {
-    const size_t npix = width * height;
+                                int k, void *d_out, int elem_bytes, NNWork &w, const DitherConfig &cfg, const DitherWeights &wts, hipStream_t s,
+                                const unsigned *mpos, size_t mcount) {
+    const size_t npix = mpos ? mcount : width * height;
     DitherLanes a{};
     // runs: eight wavefronts of 64 per CU (two per SIMD), none shorter than 256 pixels unless asked for
     size_t S = cfg.segments > 0 ? (size_t)cfg.segments : std::min<size_t>((size_t)num_cus() * 8 * 64, npix / 256);
@@ -2109,8 +2148,10 @@ static bool launch_dither_lanes(const double *d_img, size_t plane_stride, int wh
     w.lut.reserve(((size_t)ncell + ncellw[0] + ncellw[1]) * 32);
     w.clist.reserve((size_t)((ncell + ncellw[0] + ncellw[1]) / 64) * (1 + kCoarseMax) * 2);
     w.dsort.reserve(3 * cells);
-    if (w.dpos.cap < npix) { w.order_w = 0; w.order_h = 0; }
-    w.dpos.reserve(npix);
+    if (!mpos) {
+        if (w.dpos.cap < npix) { w.order_w = 0; w.order_h = 0; }
+        w.dpos.reserve(npix);
+    }
     w.dsmap.reserve(cells + 32 * S + 128);
     w.dside.reserve(S + 16);
     w.dflag.reserve(S + 64);
@@ -2160,16 +2201,10 @@ static bool launch_dither_lanes(const double *d_img, size_t plane_stride, int wh
     HIP_CHECK(hipEventRecord(w.ev_join2, sc));
     double *sx = w.dsort.p, *sy = sx + cells, *sz = sy + cells;
     const dim3 tiles((unsigned)ceil_div((size_t)a.R.Lmax, 64), (unsigned)nw), tiles8((unsigned)ceil_div((size_t)a.R.Lmax, 256), (unsigned)ceil_div(S, 8));
-    if (!(g_dither_order_cache && w.order_w == width && w.order_h == height && w.order_dev == current_device())) {
-        // rank -> pixel number is a function of the image's dimensions alone: kept between calls on images of one size
-        KTIME("k_dither_order", s, 4.0 * npix);
-        const unsigned parts = (unsigned)std::max<size_t>(1, std::min<size_t>(8192, npix / 16384));
-        hipLaunchKernelGGL(k_dither_order, parts, 64, 0, s, (unsigned)width, (unsigned)height, parts, w.dpos.p);
-        w.order_w = width; w.order_h = height; w.order_dev = current_device();
-    }
+    if (!mpos) dither_order(w, width, height, s);
+    const unsigned *sp = mpos ? mpos : (const unsigned *)w.dpos.p;
     {
         KTIME("k_dither_gather", s, 52.0 * npix);
-        const unsigned *sp = (const unsigned *)w.dpos.p;
         switch (which) {
             case PAMD_COPY: hipLaunchKernelGGL(k_dither_streams<PAMD_COPY>, tiles8, 256, 0, s, d_img, plane_stride, sp, a.R, sx, sy, sz); break;
             case PAMD_SRGB_TO_REC2020: hipLaunchKernelGGL(k_dither_streams<PAMD_SRGB_TO_REC2020>, tiles8, 256, 0, s, d_img, plane_stride, sp, a.R, sx, sy, sz); break;
@@ -2229,9 +2264,9 @@ static bool launch_dither_lanes(const double *d_img, size_t plane_stride, int wh
     }
     {
         KTIME("k_dither_unpermute", s, (5.0 + elem_bytes) * npix);
-        if (elem_bytes == 1) hipLaunchKernelGGL(k_dither_unpermute<unsigned char>, tiles, 256, 0, s, (const unsigned char *)a.smap, (const unsigned *)w.dpos.p, a.R, (unsigned char *)d_out);
-        else if (elem_bytes == 4) hipLaunchKernelGGL(k_dither_unpermute<unsigned int>, tiles, 256, 0, s, (const unsigned char *)a.smap, (const unsigned *)w.dpos.p, a.R, (unsigned int *)d_out);
-        else hipLaunchKernelGGL(k_dither_unpermute<unsigned long long>, tiles, 256, 0, s, (const unsigned char *)a.smap, (const unsigned *)w.dpos.p, a.R, (unsigned long long *)d_out);
+        if (elem_bytes == 1) hipLaunchKernelGGL(k_dither_unpermute<unsigned char>, tiles, 256, 0, s, (const unsigned char *)a.smap, sp, a.R, (unsigned char *)d_out);
+        else if (elem_bytes == 4) hipLaunchKernelGGL(k_dither_unpermute<unsigned int>, tiles, 256, 0, s, (const unsigned char *)a.smap, sp, a.R, (unsigned int *)d_out);
+        else hipLaunchKernelGGL(k_dither_unpermute<unsigned long long>, tiles, 256, 0, s, (const unsigned char *)a.smap, sp, a.R, (unsigned long long *)d_out);
     }
     HIP_CHECK(hipGetLastError());
     return true;
@@ -2252,12 +2287,16 @@ __global__ __launch_bounds__(256) void k_dither_convert(const double *__restrict
 
 template <typename OutT>
 static void launch_dither_t(int mode, unsigned blocks, const double *d_img, size_t plane_stride, size_t width, size_t height, const double *d_pal,
-                            int k, OutT *out, const DitherWeights &wts, size_t lds, double *gtab, const DitherSeg &sg, hipStream_t s) {
-#define PAMD_DITHER1(PER, GT, MODE)                                                                                            \
+                            int k, OutT *out, const DitherWeights &wts, size_t lds, double *gtab, const DitherSeg &sg, hipStream_t s,
+                            const unsigned *mpos, size_t mcount) {
+#define PAMD_DITHER2(PER, GT, MODE, MASKED)                                                                                    \
     do {                                                                                                                       \
-        HIP_CHECK(hipFuncSetAttribute((const void *)(k_dither<OutT, PER, GT, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL((k_dither<OutT, PER, GT, MODE>), blocks, 64, lds, s, d_img, plane_stride, (unsigned)width, (unsigned)height, d_pal, k, out, wts, gtab, sg); \
+        HIP_CHECK(hipFuncSetAttribute((const void *)(k_dither<OutT, PER, GT, MODE, MASKED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+        hipLaunchKernelGGL((k_dither<OutT, PER, GT, MODE, MASKED>), blocks, 64, lds, s, d_img, plane_stride, (unsigned)width, (unsigned)height, d_pal, k, \
+                           out, wts, gtab, sg, mpos, (unsigned long long)mcount);                                             \
     } while (0)
+#define PAMD_DITHER1(PER, GT, MODE)                                                                                            \
+    do { if (mpos) PAMD_DITHER2(PER, GT, MODE, true); else PAMD_DITHER2(PER, GT, MODE, false); } while (0)
 #define PAMD_DITHER(PER, GT)                                                                                                   \
     do { if (mode == 0) PAMD_DITHER1(PER, GT, 0); else PAMD_DITHER1(PER, GT, 1); } while (0)
     if (gtab) PAMD_DITHER(0, true);
@@ -2267,6 +2306,7 @@ static void launch_dither_t(int mode, unsigned blocks, const double *d_img, size
     else PAMD_DITHER(0, false);
 #undef PAMD_DITHER
 #undef PAMD_DITHER1
+#undef PAMD_DITHER2
 }
 
 // One lane per run where the pruned search applies (8 <= K <= 256) and the image is large: the lane layout needs ~10^5 runs of a few
@@ -2280,16 +2320,17 @@ bool dither_lane_layout(size_t width, size_t height, int k) {
 }
 
 static void launch_dither_waves(const double *d_img, size_t plane_stride, size_t width, size_t height, const double *d_pal, int k,
-                                void *d_out, int elem_bytes, NNWork &w, hipStream_t s);
+                                void *d_out, int elem_bytes, NNWork &w, hipStream_t s, const unsigned *mpos = nullptr, size_t mcount = 0);
 
-void launch_dither(const double *d_img, size_t plane_stride, int which, size_t width, size_t height, const double *d_pal, const double *h_pal, int k,
-                   void *d_out, int elem_bytes, NNWork &w, hipStream_t s, int layout) {
+static void launch_dither_any(const double *d_img, size_t plane_stride, int which, size_t width, size_t height, const double *d_pal, const double *h_pal,
+                              int k, void *d_out, int elem_bytes, NNWork &w, hipStream_t s, int layout, const unsigned *mpos, size_t mcount) {
     if (width * height >> 32) throw HipError("patolette_amd: the dither kernel numbers pixels with 32 bits");
     if (elem_bytes != 1 && elem_bytes != 4 && elem_bytes != 8) throw HipError("patolette_amd: map element size must be 1, 4 or 8");
+    const size_t npix = mpos ? mcount : width * height;
     {
         const DitherConfig cfg = dither_cfg_snapshot();
         // layout: what the caller decided when it chose the pixels' form (the knobs may change between its look and this one)
-        if (layout >= 0 ? layout != 0 : dither_lane_layout(width, height, k)) {
+        if (layout >= 0 ? layout != 0 : dither_lane_layout(npix, 1, k)) {
             DitherWeights wts;
             const double m = std::exp(std::log(16.0) / (16.0 - 1));
             double v = 1;
@@ -2301,9 +2342,9 @@ void launch_dither(const double *d_img, size_t plane_stride, int which, size_t w
                 HIP_CHECK(hipStreamSynchronize(s));
                 h_pal = hp.data();
             }
-            if (launch_dither_lanes(d_img, plane_stride, which, width, height, d_pal, h_pal, k, d_out, elem_bytes, w, cfg, wts, s)) return;
+            if (launch_dither_lanes(d_img, plane_stride, which, width, height, d_pal, h_pal, k, d_out, elem_bytes, w, cfg, wts, s, mpos, mcount)) return;
             // stalled: the wavefront layout from scratch (it needs the pixels as linear Rec2020 in image order)
-            const size_t n = width * height;
+            const size_t n = npix;
             if (which != PAMD_COPY) {
                 w.dsort.reserve(3 * n);
                 const int gb = stream_blocks(n, 16);
@@ -2316,17 +2357,59 @@ void launch_dither(const double *d_img, size_t plane_stride, int which, size_t w
                 d_img = w.dsort.p; plane_stride = n; which = PAMD_COPY;
             }
             const size_t lane_passes = w.dither_rounds;
-            launch_dither_waves(d_img, plane_stride, width, height, d_pal, k, d_out, elem_bytes, w, s);
+            launch_dither_waves(d_img, plane_stride, width, height, d_pal, k, d_out, elem_bytes, w, s, mpos, mcount);
             w.dither_rounds += lane_passes;
             return;
         }
         if (which != PAMD_COPY) throw HipError("patolette_amd: the wavefront-per-run dither takes linear Rec2020 pixels");
     }
-    launch_dither_waves(d_img, plane_stride, width, height, d_pal, k, d_out, elem_bytes, w, s);
+    launch_dither_waves(d_img, plane_stride, width, height, d_pal, k, d_out, elem_bytes, w, s, mpos, mcount);
 }
 
+void launch_dither(const double *d_img, size_t plane_stride, int which, size_t width, size_t height, const double *d_pal, const double *h_pal, int k,
+                   void *d_out, int elem_bytes, NNWork &w, hipStream_t s, int layout) {
+    launch_dither_any(d_img, plane_stride, which, width, height, d_pal, h_pal, k, d_out, elem_bytes, w, s, layout, nullptr, 0);
+}
+
+// The masked table: which curve ranks hold an opaque pixel (cpos[pixel] >= 0), in curve order, as compact pixel numbers -- one
+// order-preserving compaction over the cached rank -> pixel table, which it reads and leaves as it is.
+namespace {
+struct MaskTableOp {
+    const unsigned *dpos;
+    const int *cpos;
+    unsigned *mpos;
+    using V = int;
+    __device__ V load(size_t r) const { return cpos[dpos[r]]; }
+    __device__ bool keep(V v) const { return v >= 0; }
+    __device__ void put(size_t, V v, bool k, unsigned rank) const { if (k) mpos[rank] = (unsigned)v; }
+};
+}  // namespace
+
+void dither_mask_reserve(NNWork &w, size_t npix) {
+    if (w.dpos.cap < npix) { w.order_w = 0; w.order_h = 0; }
+    w.dpos.reserve(npix);
+    w.dmpos.reserve(npix);
+    w.dmcnt.reserve(compact_tiles(npix) + 1);
+}
+
+void launch_dither_masked(const double *d_img, size_t plane_stride, int which, size_t width, size_t height, const int *d_cpos, size_t m,
+                          const double *d_pal, const double *h_pal, int k, void *d_out, int elem_bytes, NNWork &w, hipStream_t s, int layout) {
+    const size_t npix = width * height;
+    if (npix >> 32) throw HipError("patolette_amd: the dither kernel numbers pixels with 32 bits");
+    if (m == 0 || m > npix) throw HipError("patolette_amd: masked dither with no opaque pixel");
+    dither_mask_reserve(w, npix);
+    dither_order(w, width, height, s);
+    const MaskTableOp op{(const unsigned *)w.dpos.p, d_cpos, w.dmpos.p};
+    unsigned *total = w.dmcnt.p + compact_tiles(npix);
+    launch_compact_count(op, npix, w.dmcnt.p, total, s, "k_dither_mask", 8.0 * npix);
+    launch_compact_write(op, npix, w.dmcnt.p, s, "k_dither_mask", 12.0 * npix + 4.0 * m);
+    HIP_CHECK(hipStreamSynchronize(s));          // (the launchers below size their workspace before they enqueue)
+    launch_dither_any(d_img, plane_stride, which, width, height, d_pal, h_pal, k, d_out, elem_bytes, w, s, layout, w.dmpos.p, m);
+}
+
+// mpos: the masked table (mcount opaque pixels, compact numbers in curve order) or nullptr
 static void launch_dither_waves(const double *d_img, size_t plane_stride, size_t width, size_t height, const double *d_pal, int k,
-                                void *d_out, int elem_bytes, NNWork &w, hipStream_t s) {
+                                void *d_out, int elem_bytes, NNWork &w, hipStream_t s, const unsigned *mpos, size_t mcount) {
     size_t lds = ((size_t)6 * k + 3 * 128) * sizeof(double) + 128 * sizeof(unsigned int);      // palette (raw + weighted) + the ring of pending pixels
     double *gtab = nullptr;
     if (lds > 150 * 1024) {                                      // K > 3200: the tables in global memory (workspace kept with the engine)
@@ -2342,7 +2425,7 @@ static void launch_dither_waves(const double *d_img, size_t plane_stride, size_t
     }
     // Runs: two wavefronts per SIMD fill the issue slots of the chip (one chain alone uses ~2/3 of its SIMD's); never shorter than
     // the warm-up -- below that the speculative steps outnumber the useful ones.
-    const size_t npix = width * height;
+    const size_t npix = mpos ? mcount : width * height;
     const DitherConfig cfg = dither_cfg_snapshot();
     DitherSeg sg{};
     sg.warm = cfg.warm >= 0 ? (unsigned)cfg.warm : 1024u;
@@ -2367,13 +2450,13 @@ static void launch_dither_waves(const double *d_img, size_t plane_stride, size_t
     };
     if (S > 1) reset_counters();
     auto launch = [&](int mode, unsigned blocks) {
-        if (elem_bytes == 1) launch_dither_t<unsigned char>(mode, blocks, d_img, plane_stride, width, height, d_pal, k, (unsigned char *)d_out, wts, lds, gtab, sg, s);
-        else if (elem_bytes == 4) launch_dither_t<unsigned int>(mode, blocks, d_img, plane_stride, width, height, d_pal, k, (unsigned int *)d_out, wts, lds, gtab, sg, s);
-        else launch_dither_t<unsigned long long>(mode, blocks, d_img, plane_stride, width, height, d_pal, k, (unsigned long long *)d_out, wts, lds, gtab, sg, s);
+        if (elem_bytes == 1) launch_dither_t<unsigned char>(mode, blocks, d_img, plane_stride, width, height, d_pal, k, (unsigned char *)d_out, wts, lds, gtab, sg, s, mpos, mcount);
+        else if (elem_bytes == 4) launch_dither_t<unsigned int>(mode, blocks, d_img, plane_stride, width, height, d_pal, k, (unsigned int *)d_out, wts, lds, gtab, sg, s, mpos, mcount);
+        else launch_dither_t<unsigned long long>(mode, blocks, d_img, plane_stride, width, height, d_pal, k, (unsigned long long *)d_out, wts, lds, gtab, sg, s, mpos, mcount);
         HIP_CHECK(hipGetLastError());
     };
     {
-        KTIME("k_dither", s, (24.0 + elem_bytes) * width * height);
+        KTIME("k_dither", s, (24.0 + elem_bytes + (mpos ? 4.0 : 0.0)) * npix);
         launch(0, (unsigned)S);
     }
     if (S == 1 || std::max(width, height) <= 1) return;

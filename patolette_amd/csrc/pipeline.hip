@@ -23,6 +23,8 @@
 #include "map.h"
 #include "saliency.h"
 #include "quant.h"
+#include "rgba.h"
+#include "compact.h"
 
 namespace pamd {
 
@@ -976,6 +978,13 @@ struct Engine {
     DevBuf<unsigned long long> hsize, tileoff;
     DevBuf<unsigned int> hcount, tilecnt;
     DevBuf<unsigned char> lut, dmap, src8, pal8, quant8;
+    // the RGBA entry (run_rgba): tile counts / offsets + the opaque count, each pixel's compact number, the opaque pixels' RGB and
+    // weights, the full index map on its way to the host, the count's pinned landing place
+    DevBuf<unsigned> rgba_cnt;
+    DevBuf<int> rgba_cpos;
+    DevBuf<unsigned char> rgba_rgb, rgba_map;
+    DevBuf<double> rgba_w;
+    PinBuf<unsigned> h_rgba_m;
     DevBuf<ConvertStats> cstats;
     PinBuf<NodeIn> h_stage_in;
     PinBuf<NodeOut> h_stage_out;
@@ -2269,6 +2278,10 @@ static Bounds read_bounds(Engine &E, bool weighted, const std::function<void()> 
 // --------------------------------------------------------------------------------------------
 // the full path, inputs resident in HBM
 // --------------------------------------------------------------------------------------------
+// The RGBA entry's compact image: the pipeline runs on the M opaque pixels as an M x 1 image, and the dither walks the width x height
+// curve over them (launch_dither_masked; cpos[pixel] = compact number or -1)
+struct DitherMask { size_t width, height; const int *cpos; };
+
 struct Pixels {                      // device-resident input image: planar f64 sRGB, or interleaved 8-bit sRGB
     const double *f64 = nullptr;
     const unsigned char *u8 = nullptr;
@@ -2298,7 +2311,7 @@ static ConvertPlan convert_plan(const Engine &E, const patolette__QuantizationOp
 }
 
 static void run_device(Engine &E, size_t width, size_t height, Pixels px, const double *d_weights, size_t K,
-                       const patolette__QuantizationOptions *opt, double *palette, void *d_map, int map_elem) {
+                       const patolette__QuantizationOptions *opt, double *palette, void *d_map, int map_elem, const DitherMask *mask = nullptr) {
     // d_map == nullptr with palette_only unset: the palette takes the same conversions, the map kernels are skipped
     hipStream_t s = E.stream;
     const size_t N = width * height;
@@ -2362,13 +2375,19 @@ static void run_device(Engine &E, size_t width, size_t height, Pixels px, const 
             if (d_map) {
                 HIP_CHECK(hipMemcpyAsync(E.dpal.p, pal.data(), 3 * len * sizeof(double), hipMemcpyHostToDevice, s));
                 HIP_CHECK(hipStreamSynchronize(s));
+                // (masked: this image is the M x 1 list of opaque pixels, and the layout is decided on M as well)
+                auto dither = [&](const double *img, int which, int layout) {
+                    if (mask) launch_dither_masked(img, N, which, mask->width, mask->height, mask->cpos, N, E.dpal.p, pal.data(), (int)len, d_map,
+                                                   map_elem, E.nn, s, layout);
+                    else launch_dither(img, N, which, width, height, E.dpal.p, pal.data(), (int)len, d_map, map_elem, E.nn, s, layout);
+                };
                 if (dither_lane_layout(width, height, (int)len)) {               // decided ONCE: launch_dither is told
                     // the pixels go into curve order anyway: their conversion to linear Rec2020 rides on that pass
-                    launch_dither(E.cvt.p, N, pix, width, height, E.dpal.p, pal.data(), (int)len, d_map, map_elem, E.nn, s, 1);
+                    dither(E.cvt.p, pix, 1);
                 } else {
                     E.aux.reserve(3 * N);
                     launch_convert(pix, E.cvt.p, E.aux.p, N, nullptr, s);      // plane stride of cvt is N for x,y,z
-                    launch_dither(E.aux.p, N, PAMD_COPY, width, height, E.dpal.p, pal.data(), (int)len, d_map, map_elem, E.nn, s, 0);
+                    dither(E.aux.p, PAMD_COPY, 0);
                 }
                 E.stats.dither_segments = E.nn.dither_segments; E.stats.dither_repairs = E.nn.dither_repairs; E.stats.dither_rounds = E.nn.dither_rounds; E.stats.dither_through = E.nn.dither_through;
     E.stats.dither_jumps = E.nn.dither_jumps; E.stats.dither_solo = E.nn.dither_solo;
@@ -2599,6 +2618,39 @@ static void palette_to_u8(const double *palette, size_t K, unsigned char *out) {
         }
 }
 
+// Host 8-bit image up into E.src8 (reserved), as run_host does it: a large image goes up in four pieces of whole pixels, each converted
+// (second stream) while the next is on the link.  weight_plane: the call will have weights (E.cvt gets their plane now: run_device
+// must not move what is converted here).  Returns whether E.cvt / E.cstats hold the converted image; nothing is waited for.
+static bool upload_u8(Engine &E, const unsigned char *pixels, int channels, size_t N, bool weight_plane, const patolette__QuantizationOptions *opt) {
+    hipStream_t s = E.stream;
+    const size_t chunk_min = getenv("PAMD_UPLOAD_CHUNK_MIN") ? (size_t)atoll(getenv("PAMD_UPLOAD_CHUNK_MIN")) : ((size_t)1 << 21);
+    if (!(N >= chunk_min && !E.shard)) {
+        HIP_CHECK(hipMemcpyAsync(E.src8.p, pixels, N * (size_t)channels, hipMemcpyHostToDevice, s));
+        return false;
+    }
+    if (!E.stream2) {
+        HIP_CHECK(hipStreamCreateWithFlags(&E.stream2, hipStreamNonBlocking));
+        for (hipEvent_t *e : {&E.ev_up[0], &E.ev_up[1], &E.ev_join}) HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    }
+    const ConvertPlan cp = convert_plan(E, opt, N);
+    E.cvt.reserve((weight_plane ? 4 : 3) * N);
+    E.cstats.reserve(1);
+    HIP_CHECK(hipEventRecord(E.ev_join, E.stream));
+    HIP_CHECK(hipStreamWaitEvent(E.stream2, E.ev_join, 0));
+    const size_t nch = 4, per = ((N + nch - 1) / nch + 255) & ~(size_t)255;
+    size_t c = 0;
+    for (size_t lo = 0; lo < N; lo += per, c++) {
+        const size_t cnt = std::min(per, N - lo);
+        HIP_CHECK(hipMemcpyAsync(E.src8.p + lo * (size_t)channels, pixels + lo * (size_t)channels, cnt * (size_t)channels, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipEventRecord(E.ev_up[c & 1], s));
+        HIP_CHECK(hipStreamWaitEvent(E.stream2, E.ev_up[c & 1], 0));
+        launch_convert_u8(cp.which, E.src8.p, channels, E.cvt.p, N, E.cstats.p, E.stream2, cp.sumk, cp.momk, lo, lo + cnt, c == 0);
+    }
+    HIP_CHECK(hipEventRecord(E.ev_join, E.stream2));
+    HIP_CHECK(hipStreamWaitEvent(s, E.ev_join, 0));
+    return true;
+}
+
 // 8-bit adaptor around the path: interleaved u8 in; f64 palette, u8 palette, index map and
 // reconstructed u8 image out.  `pixels`, `d_map_out`, `d_quant_out` are device pointers when `on_device`.
 static void run_u8(Engine &E, size_t width, size_t height, const unsigned char *pixels, int channels, const double *weights,
@@ -2617,34 +2669,7 @@ static void run_u8(Engine &E, size_t width, size_t height, const unsigned char *
         E.src8.reserve(N * (size_t)channels);
         if (weights) E.wsrc.reserve(N);
         d_px = E.src8.p;
-        // as run_host: a large image goes up in four pieces of whole pixels, each converted (second stream) while the next is on the link
-        const size_t chunk_min = getenv("PAMD_UPLOAD_CHUNK_MIN") ? (size_t)atoll(getenv("PAMD_UPLOAD_CHUNK_MIN")) : ((size_t)1 << 21);
-        const bool derive = !weights && tile_size > 0.0;             // the saliency stage reads the 8-bit image itself (it stays where it is)
-        if (N >= chunk_min && !E.shard) {
-            if (!E.stream2) {
-                HIP_CHECK(hipStreamCreateWithFlags(&E.stream2, hipStreamNonBlocking));
-                for (hipEvent_t *e : {&E.ev_up[0], &E.ev_up[1], &E.ev_join}) HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-            }
-            const ConvertPlan cp = convert_plan(E, opt, N);
-            E.cvt.reserve(((weights || derive) ? 4 : 3) * N);        // (the derived weights' plane: run_device must not move what is converted here)
-            E.cstats.reserve(1);
-            HIP_CHECK(hipEventRecord(E.ev_join, E.stream));
-            HIP_CHECK(hipStreamWaitEvent(E.stream2, E.ev_join, 0));
-            const size_t nch = 4, per = ((N + nch - 1) / nch + 255) & ~(size_t)255;
-            size_t c = 0;
-            for (size_t lo = 0; lo < N; lo += per, c++) {
-                const size_t cnt = std::min(per, N - lo);
-                HIP_CHECK(hipMemcpyAsync(E.src8.p + lo * (size_t)channels, pixels + lo * (size_t)channels, cnt * (size_t)channels, hipMemcpyHostToDevice, s));
-                HIP_CHECK(hipEventRecord(E.ev_up[c & 1], s));
-                HIP_CHECK(hipStreamWaitEvent(E.stream2, E.ev_up[c & 1], 0));
-                launch_convert_u8(cp.which, E.src8.p, channels, E.cvt.p, N, E.cstats.p, E.stream2, cp.sumk, cp.momk, lo, lo + cnt, c == 0);
-            }
-            HIP_CHECK(hipEventRecord(E.ev_join, E.stream2));
-            HIP_CHECK(hipStreamWaitEvent(s, E.ev_join, 0));
-            converted = true;
-        } else {
-            HIP_CHECK(hipMemcpyAsync(E.src8.p, pixels, N * (size_t)channels, hipMemcpyHostToDevice, s));
-        }
+        converted = upload_u8(E, pixels, channels, N, weights || (!weights && tile_size > 0.0), opt);
         if (weights) {
             E.wsrc.reserve(N);
             HIP_CHECK(hipMemcpyAsync(E.wsrc.p, weights, N * sizeof(double), hipMemcpyHostToDevice, s));
@@ -2702,6 +2727,126 @@ static void run_u8(Engine &E, size_t width, size_t height, const unsigned char *
             }
         }
         E.sync();
+    }
+    E.stats.ms_upload = up;
+    E.stats.ms_download = now_ms() - t0;
+    E.stats.ms_total += up + E.stats.ms_download;
+}
+
+// The RGBA entry (include/patolette_amd.h, patolette_amd_rgba): the opaque pixels (alpha >= thr) are compacted in row-scan order and
+// the path runs on them as an M x 1 image with one palette row less (row 0 is the transparent entry); the dither walks the full image's
+// curve over them (DitherMask).  Every pixel opaque: the path runs on the image itself with the full palette, exactly as run_u8 does.
+// One kernel then writes the full index map and the RGBA image.  `pixels`, `map_out`, `quant_out` are device pointers when `on_device`.
+static void run_rgba(Engine &E, size_t width, size_t height, const unsigned char *pixels, int thr, const double *weights, double tile_size,
+                     size_t K, const patolette__QuantizationOptions *opt, double *palette, unsigned char *palette_rgba, void *map_out,
+                     int map_elem_out, unsigned char *quant_out, int *transparent_index, bool on_device) {
+    const size_t N = width * height;
+    hipStream_t s = E.stream;
+    double t0 = now_ms();
+    WsGuard wg(&E.stream, &E.stream2);
+    const bool derive = !weights && tile_size > 0.0;
+    const bool weighted = weights || derive;
+    const bool want_map = !opt->palette_only && (map_out || quant_out);
+    const int me = map_elem_for(K);                                  // the compact map (choices < K - 1 when masked)
+    auto aligned = [](const void *p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; };
+    if (on_device && ((map_out && !aligned(map_out, (size_t)map_elem_out)) || (quant_out && !aligned(quant_out, 4))))
+        throw HipError("patolette_amd_rgba_device: palette_map and quantized must be aligned to their element size");
+    const bool stage_px = !on_device || !aligned(pixels, 4);         // the kernels read one 32-bit word per pixel
+    // everything the call can take of the workspace, before anything is enqueued (run_device's own preparation at M <= N pixels
+    // is then a no-op, save for what it reserves behind a synchronisation)
+    if (derive) { E.wsal.reserve(N); saliency_reserve(E.sal, width, height); }
+    ws_prepare(E, N, K, weighted, opt->verbose);
+    E.cvt.reserve((weighted ? 4 : 3) * N); E.cstats.reserve(1);
+    E.rgba_cnt.reserve(compact_tiles(N) + 1); E.h_rgba_m.reserve(1);
+    E.rgba_cpos.reserve(N); E.rgba_rgb.reserve(3 * N);
+    if (weighted) E.rgba_w.reserve(N);
+    E.pal8.reserve(4 * K);
+    if (want_map) {
+        E.dmap.reserve(N * (size_t)me);
+        if (opt->dither) { E.aux.reserve(3 * N); dither_mask_reserve(E.nn, N); }
+        else if (opt->color_space == patolette__CIELuv) E.aux.reserve(3 * N);
+        if (!on_device && map_out) E.rgba_map.reserve(N * (size_t)map_elem_out);
+        if (!on_device && quant_out) E.quant8.reserve(4 * N);
+    }
+    if (stage_px) E.src8.reserve(4 * N);
+    if (weights && !on_device) E.wsrc.reserve(N);
+
+    // upload (host images: converted behind the upload, as run_u8 -- kept if every pixel turns out opaque)
+    const unsigned char *d_px = pixels;
+    const double *d_w = weights;
+    bool converted = false;
+    if (!on_device) converted = upload_u8(E, pixels, 4, N, weighted, opt);
+    else if (stage_px) HIP_CHECK(hipMemcpyAsync(E.src8.p, pixels, 4 * N, hipMemcpyDeviceToDevice, s));
+    if (stage_px) d_px = E.src8.p;
+    if (weights && !on_device) {
+        HIP_CHECK(hipMemcpyAsync(E.wsrc.p, weights, N * sizeof(double), hipMemcpyHostToDevice, s));
+        d_w = E.wsrc.p;
+    }
+    // count the opaque pixels (one small synchronisation)
+    unsigned *d_m = E.rgba_cnt.p + compact_tiles(N);
+    launch_alpha_count(d_px, N, thr, E.rgba_cnt.p, d_m, s);
+    HIP_CHECK(hipMemcpyAsync(E.h_rgba_m.p, d_m, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    const size_t M = E.h_rgba_m.p[0];
+    const double up = now_ms() - t0;
+    const bool masked = M < N;
+    if (masked && M > 0 && K < 2) throw CodeError(-3, "Palette size should be greater than 0.");
+    if (transparent_index) *transparent_index = masked ? 0 : -1;
+
+    E.ms_saliency = 0.0;
+    const size_t Kq = masked ? K - 1 : K;                            // rows the path makes
+    std::vector<double> pal(3 * std::max<size_t>(Kq, 1), -1.0);
+    size_t len = 0;
+    void *d_cmap = want_map ? (void *)E.dmap.p : nullptr;
+    // weights the binding derives (tile_size > 0): over the full image's RGB, as run_u8 -- then restricted to the opaque pixels
+    if (M > 0 && derive) d_w = derive_weights(E, nullptr, d_px, 4, width, height, tile_size);
+    if (masked) {
+        launch_alpha_compact(d_px, N, M, thr, E.rgba_cnt.p, d_w, E.rgba_cpos.p, E.rgba_rgb.p, d_w ? E.rgba_w.p : nullptr, s);
+        HIP_CHECK(hipStreamSynchronize(s));                           // (run_device sizes its workspace before it enqueues)
+    }
+    if (M > 0) {
+        if (!masked) {
+            Pixels px8{nullptr, d_px, 4};
+            px8.converted = converted;
+            run_device(E, width, height, px8, d_w, K, opt, pal.data(), d_cmap, me);
+        } else {
+            const DitherMask mask{width, height, E.rgba_cpos.p};
+            Pixels px8{nullptr, E.rgba_rgb.p, 3};
+            run_device(E, M, 1, px8, d_w ? E.rgba_w.p : nullptr, Kq, opt, pal.data(), d_cmap, me, &mask);
+        }
+        len = E.stats.n_clusters;
+    } else {
+        E.stats = patolette_amd__Stats{};
+    }
+    E.stats.ms_saliency = E.ms_saliency;
+    E.stats.ms_total += E.ms_saliency;
+    t0 = now_ms();
+
+    // palettes: row 0 the transparent entry when masked; unused rows -1 / (0, 0, 0, 0)
+    const size_t off = masked ? 1 : 0;
+    std::vector<unsigned char> p8(3 * std::max<size_t>(Kq, 1)), prgba(4 * K, 0);
+    if (Kq > 0) palette_to_u8(pal.data(), Kq, p8.data());
+    for (size_t i = 0; i < len; i++) {
+        for (int c = 0; c < 3; c++) prgba[4 * (off + i) + c] = p8[3 * i + c];
+        prgba[4 * (off + i) + 3] = 255;
+    }
+    if (palette) {
+        for (size_t j = 0; j < 3 * K; j++) palette[j] = -1.0;
+        if (masked) for (int c = 0; c < 3; c++) palette[K * (size_t)c] = 0.0;
+        for (int c = 0; c < 3; c++) for (size_t i = 0; i < Kq; i++) palette[K * (size_t)c + off + i] = pal[Kq * (size_t)c + i];
+    }
+    if (palette_rgba) std::memcpy(palette_rgba, prgba.data(), 4 * K);
+
+    if (want_map) {
+        if (!masked && opt->dither && std::max(width, height) <= 1)
+            HIP_CHECK(hipMemsetAsync(E.dmap.p, 0, N * (size_t)me, s));        // 1x1 dither visits nothing (riemersma.c:452-456): entry 0
+        HIP_CHECK(hipMemcpyAsync(E.pal8.p, prgba.data(), 4 * K, hipMemcpyHostToDevice, s));
+        void *d_map = map_out ? (on_device ? map_out : (void *)E.rgba_map.p) : nullptr;
+        unsigned char *d_q = quant_out ? (on_device ? quant_out : E.quant8.p) : nullptr;
+        launch_rgba_expand(d_cmap, me, masked ? E.rgba_cpos.p : nullptr, N, M, (unsigned)off, E.pal8.p, (int)K, d_map, map_elem_out, d_q, s);
+        if (!on_device && map_out) HIP_CHECK(hipMemcpyAsync(map_out, d_map, N * (size_t)map_elem_out, hipMemcpyDeviceToHost, s));
+        if (!on_device && quant_out) HIP_CHECK(hipMemcpyAsync(quant_out, d_q, 4 * N, hipMemcpyDeviceToHost, s));
+        E.sync();                                                     // (prgba is a local: the copy must have left the host)
     }
     E.stats.ms_upload = up;
     E.stats.ms_download = now_ms() - t0;
@@ -3004,6 +3149,53 @@ static void u8_entry(bool on_device, size_t width, size_t height, const unsigned
         fprintf(stderr, "patolette: %s\n", ex.what());
         *exit_code = -1;
     }
+}
+
+static void rgba_entry(bool on_device, size_t width, size_t height, const unsigned char *pixels, int alpha_threshold, const double *weights,
+                       double tile_size, size_t palette_size, const patolette__QuantizationOptions *options, double *palette,
+                       unsigned char *palette_rgba, void *palette_map, int map_elem_bytes, unsigned char *quantized, int *transparent_index,
+                       int *exit_code) {
+    *exit_code = validate(width, height, palette_size);
+    if (*exit_code != 0) return;
+    const char *bad = nullptr;
+    if (alpha_threshold < 0 || alpha_threshold > 256) bad = "patolette_amd_rgba: alpha_threshold must lie in [0, 256]";
+    else if (validate_u8(palette_size, 4, palette_map, map_elem_bytes) != 0)
+        bad = "patolette_amd_rgba: map_elem_bytes must be 1, 2, 4 or 8 and able to hold palette_size - 1";
+    if (bad) {
+        try { engine().last_error = bad; } catch (...) {}
+        fprintf(stderr, "%s\n", bad);
+        *exit_code = -1;
+        return;
+    }
+    try {
+        Engine &E = engine();
+        E.init();
+        run_rgba(E, width, height, pixels, alpha_threshold, weights, tile_size, palette_size, options, palette, palette_rgba, palette_map,
+                 map_elem_bytes, quantized, transparent_index, on_device);
+        *exit_code = 0;
+    } catch (const CodeError &ex) {
+        engine().last_error = ex.what();
+        *exit_code = ex.code;
+    } catch (const std::exception &ex) {
+        engine().last_error = ex.what();
+        fprintf(stderr, "patolette: %s\n", ex.what());
+        *exit_code = -1;
+    }
+}
+
+void patolette_amd_rgba(size_t width, size_t height, const unsigned char *pixels, int alpha_threshold, const double *weights, double tile_size,
+                        size_t palette_size, const patolette__QuantizationOptions *options, double *palette, unsigned char *palette_rgba,
+                        void *palette_map, int map_elem_bytes, unsigned char *quantized, int *transparent_index, int *exit_code) {
+    rgba_entry(false, width, height, pixels, alpha_threshold, weights, tile_size, palette_size, options, palette, palette_rgba, palette_map,
+               map_elem_bytes, quantized, transparent_index, exit_code);
+}
+
+void patolette_amd_rgba_device(size_t width, size_t height, const unsigned char *d_pixels, int alpha_threshold, const double *d_weights,
+                               double tile_size, size_t palette_size, const patolette__QuantizationOptions *options, double *palette,
+                               unsigned char *palette_rgba, void *d_palette_map, int map_elem_bytes, unsigned char *d_quantized,
+                               int *transparent_index, int *exit_code) {
+    rgba_entry(true, width, height, d_pixels, alpha_threshold, d_weights, tile_size, palette_size, options, palette, palette_rgba,
+               d_palette_map, map_elem_bytes, d_quantized, transparent_index, exit_code);
 }
 
 void patolette_amd_u8(size_t width, size_t height, const unsigned char *pixels, int channels, const double *weights,
