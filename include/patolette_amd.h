@@ -105,6 +105,40 @@ void patolette_amd_u8_device(size_t width, size_t height, const unsigned char *d
                              unsigned char *palette_u8, void *d_palette_map, int map_elem_bytes,
                              unsigned char *d_quantized, int *exit_code);
 
+/* ---- an animation: frames of one size, ONE palette, every frame dithered on its own ----------------
+ * pixels: `frames` images of width x height, interleaved 8-bit sRGB with `channels` (3 or 4; a 4th byte is ignored) bytes per pixel,
+ * one after another (the (frames, height, width, channels) array of numpy).  n = width*height, N = frames*n.  Options as patolette_amd_u8().
+ *   Weights.  weights non-NULL: N values in frame order, used as they are.  Else tile_size > 0: frame f's weights are what
+ *       patolette_amd_u8() derives for frame f as an image of its own (saliency per frame, that frame's rows x cols in the formula).
+ *       Else unweighted.
+ *   Palette.  What patolette() computes up to and including the KMeans refinement (patolette.c:201-264) for the N pixels of the frames
+ *       laid one after another in frame order, with the weights above in the same order.  The quantisers and the KMeans subsample see a
+ *       list of N colours (geometry does not enter); kmeans_max_samples applies to N.
+ *   Maps.  For each frame separately, patolette()'s map stage (patolette.c:266-324) with that palette on the frame's n pixels: without
+ *       dithering the nearest entry (for CIELuv after the reference's detour to ICtCp, palette and pixels alike); with dithering
+ *       patolette__DITHER_riemersma over that frame's own width x height curve, starting from an empty error queue.  No state passes
+ *       from one frame to the next.
+ *   Outputs, each optional (NULL): palette (palette_size,3) column-major f64, unused rows -1, and palette_u8 as patolette_amd_u8()
+ *       makes them (the palette takes the conversions of the branch that was run, dither or nearest); palette_map: N elements of
+ *       map_elem_bytes (1, 2, 4 or 8; able to hold palette_size-1), frame after frame; quantized = N x 3 interleaved =
+ *       palette_u8[palette_map].  palette_only: no maps.
+ * Hence, bit for bit: frames == 1 is patolette_amd_u8() on that image, every output.  Without dithering every output equals
+ * patolette_amd_u8() on the frames stacked into one width x (frames*height) image (explicit or no weights).  With dithering the
+ * palette equals that stacked call's; the maps in general do not (the stacked call walks ONE curve through all frames).
+ * Exit codes as patolette_amd_u8(); frames == 0 is -2 like an empty image; N above 2^31 pixels fails with -4 (the dither numbers the
+ * pixels and their places in its run layout with 32 bits; patolette_amd_last_error says so), bad channels / map_elem_bytes with -1.
+ * Statistics (patolette_amd_last_stats): dither_segments is the number of runs over all frames -- the same number in every frame, so
+ * no run straddles a frame start; dither_repairs / rounds / jumps / solo count over all frames.
+ * The *_device flavour takes device pointers for pixels / weights / palette_map / quantized (map_elem_bytes 1 when palette_size <= 256,
+ * else 4); palette and palette_u8 stay host memory. */
+void patolette_amd_frames_u8(size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels, const double *weights,
+                             double tile_size, size_t palette_size, const patolette__QuantizationOptions *options, double *palette,
+                             unsigned char *palette_u8, void *palette_map, int map_elem_bytes, unsigned char *quantized, int *exit_code);
+void patolette_amd_frames_u8_device(size_t frames, size_t width, size_t height, const unsigned char *d_pixels, int channels,
+                                    const double *d_weights, double tile_size, size_t palette_size,
+                                    const patolette__QuantizationOptions *options, double *palette, unsigned char *palette_u8,
+                                    void *d_palette_map, int map_elem_bytes, unsigned char *d_quantized, int *exit_code);
+
 /* ---- RGBA images: a transparent palette slot, an alpha-aware dither ---------------------------
  * pixels: width*height interleaved 8-bit RGBA.  Pixel i is TRANSPARENT iff alpha_i < alpha_threshold (an integer in [0, 256]);
  * every other pixel is OPAQUE.  M = number of opaque pixels, N = width*height.

@@ -10,7 +10,8 @@ constants.  The work behind it runs in hand-written HIP kernels on gfx950 throug
 (patolette.pyx:203-313).  Additive (not in the reference): the `weights=` keyword (explicit
 per-pixel weights instead of the saliency-derived ones), `saliency_weights`, `quantize_batch`, the 8-bit adaptor `quantize_u8` and its
 batch form `quantize_u8_batch`, and `quantize_rgba` for RGBA images: a palette built from the visible pixels only, one reserved
-transparent index, and a dither that walks past transparent pixels as the reference's walks past positions outside the image.
+transparent index, and a dither that walks past transparent pixels as the reference's walks past positions outside the image;
+and `quantize_frames` for an animation: frames of one size that share one palette, each frame dithered along its own curve.
 """
 import ctypes as C
 
@@ -212,6 +213,100 @@ def _quantize_u8_torch(image, palette_size, dither, palette_only, color_space, t
     if code.value != 0:
         return (False, None, None, None, None, message)
     return (True, palette_u8, pmap, quant, palette, message)
+
+
+def quantize_frames(frames, palette_size, dither=True, palette_only=False, color_space=ColorSpace_ICtCp, tile_size=512,
+                    kmeans_niter=32, kmeans_max_samples=512 ** 2, weights=None, want_quantized=True):
+    """Quantise an animation (additive; include/patolette_amd.h: patolette_amd_frames_u8): `frames` is an (F, H, W, 3|4) uint8 sRGB
+    array, or a torch CUDA tensor of that shape (then the maps and the quantized frames stay in HBM, as in `quantize_u8`).  All
+    frames share ONE palette; every frame gets its own index map.
+
+      * Palette: what `quantize` computes (up to and including the KMeans refinement) for the F*H*W pixels of the frames laid one
+        after another; `kmeans_max_samples` applies to all of them.
+      * Maps: each frame mapped on its own with that palette -- the nearest entry, or with `dither` the reference's Riemersma walk
+        over that frame's own W x H curve from an empty error queue.  No state passes between frames.
+      * weights: None or F*H*W values in frame order.  tile_size > 0 without weights: every frame gets the saliency weights
+        `quantize_u8` derives for it as an image of its own.
+    F == 1 is `quantize_u8` of that image; without dithering the result equals `quantize_u8` of the frames stacked into one
+    (F*H, W) image; with dithering the palette equals that call's, the maps do not (one curve would run through all frames).
+
+    Returns (success, palette_u8 (K,3) uint8, maps (F,H,W) uint8|uint16|uint32 or None, quantized (F,H,W,3) uint8 or None
+    (= palette_u8[maps]), palette (K,3) float64 as `quantize` returns it, message)."""
+    if hasattr(frames, "data_ptr") and getattr(frames, "is_cuda", False):
+        return _quantize_frames_torch(frames, palette_size, dither, palette_only, color_space, tile_size, kmeans_niter,
+                                      kmeans_max_samples, weights, want_quantized)
+    if not isinstance(frames, np.ndarray):
+        frames = np.asarray(frames)
+    if frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[3] not in (3, 4):
+        raise ValueError("frames must be an (F, H, W, 3|4) uint8 array")
+    if tile_size < 0:
+        raise ValueError(bad_tile_size)
+    img = np.ascontiguousarray(frames)
+    count, height, width, channels = img.shape
+    n = count * width * height
+    w = None
+    if weights is not None:
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if w.size != n:
+            raise ValueError("weights must hold frames*width*height values")
+    opts = _native.QuantizationOptions(bool(dither), bool(palette_only), int(color_space), int(kmeans_niter),
+                                       int(kmeans_max_samples), False)
+    palette = np.zeros((max(palette_size, 0), 3), dtype=np.float64, order='F')
+    palette_u8 = np.zeros((max(palette_size, 0), 3), dtype=np.uint8)
+    map_dtype = np.uint8 if palette_size <= 256 else (np.uint16 if palette_size <= 65536 else np.uint32)
+    maps = None if palette_only else np.zeros((count, height, width), dtype=map_dtype)
+    quant = np.zeros((count, height, width, 3), dtype=np.uint8) if (want_quantized and not palette_only) else None
+    code = C.c_int(0)
+    L = _native.lib()
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size > 0 else None   # noqa: E731
+    L.patolette_amd_frames_u8(count, width, height, vp(img), channels, _dp(w), float(tile_size), palette_size, C.byref(opts),
+                              _dp(palette), vp(palette_u8), vp(maps), np.dtype(map_dtype).itemsize, vp(quant), C.byref(code))
+    message = L.get_patolette_exit_code_info_message(code.value).decode('UTF-8')
+    _raise_saliency(code.value, message)
+    if code.value != 0:
+        return (False, None, None, None, None, message)
+    return (True, palette_u8, maps, quant, palette, message)
+
+
+def _quantize_frames_torch(frames, palette_size, dither, palette_only, color_space, tile_size, kmeans_niter, kmeans_max_samples,
+                           weights, want_quantized):
+    """`quantize_frames` for a torch CUDA uint8 tensor (F, H, W, 3|4) through `patolette_amd_frames_u8_device`, as
+    `_quantize_u8_torch`: the maps (uint8 for K <= 256, else int32) and the quantized frames stay in HBM."""
+    import torch
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] not in (3, 4):
+        raise ValueError("frames must be an (F, H, W, 3|4) uint8 tensor")
+    if tile_size < 0:
+        raise ValueError(bad_tile_size)
+    img = frames.contiguous()
+    count, height, width, channels = (int(v) for v in img.shape)
+    n = count * width * height
+    dev = img.device
+    w = None
+    if weights is not None:
+        w = torch.as_tensor(weights, dtype=torch.float64, device=dev).reshape(-1).contiguous()
+        if w.numel() != n:
+            raise ValueError("weights must hold frames*width*height values")
+    opts = _native.QuantizationOptions(bool(dither), bool(palette_only), int(color_space), int(kmeans_niter),
+                                       int(kmeans_max_samples), False)
+    palette = np.zeros((max(palette_size, 0), 3), dtype=np.float64, order='F')
+    palette_u8 = np.zeros((max(palette_size, 0), 3), dtype=np.uint8)
+    me = 1 if palette_size <= 256 else 4
+    maps = None if palette_only else torch.zeros((count, height, width), dtype=torch.uint8 if me == 1 else torch.int32, device=dev)
+    quant = torch.zeros((count, height, width, 3), dtype=torch.uint8, device=dev) if (want_quantized and not palette_only) else None
+    code = C.c_int(0)
+    L = _native.lib()
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream().synchronize()          # the library runs on its own stream
+        L.patolette_amd_frames_u8_device(count, width, height, C.c_void_p(img.data_ptr()) if n else None, channels,
+                                         C.c_void_p(w.data_ptr()) if w is not None else None, float(tile_size), palette_size,
+                                         C.byref(opts), _dp(palette), palette_u8.ctypes.data_as(C.c_void_p) if palette_u8.size else None,
+                                         C.c_void_p(maps.data_ptr()) if maps is not None and n else None, me,
+                                         C.c_void_p(quant.data_ptr()) if quant is not None and n else None, C.byref(code))
+    message = L.get_patolette_exit_code_info_message(code.value).decode('UTF-8')
+    _raise_saliency(code.value, message)
+    if code.value != 0:
+        return (False, None, None, None, None, message)
+    return (True, palette_u8, maps, quant, palette, message)
 
 
 def _rgba_args(palette_size, alpha_threshold, dither, palette_only, color_space, kmeans_niter, kmeans_max_samples):
@@ -429,6 +524,7 @@ __all__ = [
     "quantize_u8",
     "quantize_u8_batch",
     "quantize_rgba",
+    "quantize_frames",
     "saliency_weights",
     "ColorSpace_sRGB",
     "ColorSpace_CIELuv",

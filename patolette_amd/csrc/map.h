@@ -49,6 +49,15 @@ bool dither_lane_layout(size_t width, size_t height, int k);
 void launch_dither(const double *d_img, size_t plane_stride, int which, size_t width, size_t height, const double *d_pal, const double *h_pal, int k,
                    void *d_out, int elem_bytes, NNWork &w, hipStream_t s, int layout = -1);   // layout: 1 lanes, 0 wavefronts, -1 decide here
 
+// `frames` images of width x height one after another (frame f's pixels at offset f * width * height of every plane and of d_out), one
+// palette: every frame is dithered along its own curve from the empty error queue, exactly as launch_dither would dither it alone.
+// Where dither_frames_lane_layout holds, all frames are walked side by side in one set of launches; otherwise frame after frame
+// through the wavefront layout, which takes linear Rec2020 pixels (which == PAMD_COPY).  At most kDitherFramesMaxPixels in all.
+constexpr size_t kDitherFramesMaxPixels = (size_t)1 << 31;
+bool dither_frames_lane_layout(size_t frames, size_t width, size_t height, int k);
+void launch_dither_frames(const double *d_img, size_t plane_stride, int which, size_t frames, size_t width, size_t height, const double *d_pal,
+                          const double *h_pal, int k, void *d_out, int elem_bytes, NNWork &w, hipStream_t s, int layout = -1);
+
 // The same chain over a width x height image of which only some pixels are visited (the RGBA entry): d_cpos[pixel] = the pixel's
 // number among the m opaque ones (row-scan order), or -1 for a transparent pixel, which the walk skips exactly like a position
 // outside the image.  d_img: the opaque pixels' compact planes (plane_stride >= m), d_out: m choices in compact order.  The layout

@@ -1389,9 +1389,12 @@ __global__ __launch_bounds__(64) void k_dither_order(unsigned width, unsigned he
 // pixels).  Write side: eight consecutive runs = 64 bytes.
 // WHICH: the conversion into linear Rec2020 the pixels still need (patolette.c:268-299; PAMD_COPY = none), done on the way -- the
 // same device routine k_convert applies, so the same bits, without a pass of its own over the image
-template <int WHICH>
-__global__ __launch_bounds__(256) void k_dither_streams(const double *__restrict__ img, size_t plane_stride, const unsigned *__restrict__ spos, DitherRuns R,
-                                                       double *__restrict__ sx, double *__restrict__ sy, double *__restrict__ sz) {
+// FRAMES (launch_dither_frames): the image is a stack of frames of n pixels each, `fruns` runs per frame, and spos is the table of
+// ONE frame: run b lies in frame b / fruns, whose ranks start at t(b / fruns * fruns) = frame * n, which is also where its pixels start
+// (a body shared by two kernels, not a flag on one: k_dither_streams keeps its argument list, so its code is what it was)
+template <int WHICH, bool FRAMES>
+__device__ __forceinline__ void dither_streams_tile(const double *__restrict__ img, size_t plane_stride, const unsigned *__restrict__ spos, const DitherRuns R,
+                                                    double *__restrict__ sx, double *__restrict__ sy, double *__restrict__ sz, unsigned fruns) {
     __shared__ unsigned long long t0[9];
     __shared__ double tile[3][8][257];
     const unsigned w = blockIdx.y, p0 = blockIdx.x * 256u, tid = threadIdx.x;
@@ -1403,7 +1406,10 @@ __global__ __launch_bounds__(256) void k_dither_streams(const double *__restrict
     for (int i = 0; i < 8; i++) {                                    // run i of the tile: consecutive threads = consecutive ranks
         const unsigned p = p0 + tid;
         const bool ok = 8u * w + i < R.S && t0[i] + p < t0[i + 1];
-        pix[i] = ok ? spos[t0[i] + p] : 0xFFFFFFFFu;
+        if constexpr (FRAMES) {
+            const unsigned long long f0 = R.t((8u * w + i) / fruns * fruns);
+            pix[i] = ok ? (unsigned)f0 + spos[t0[i] + p - f0] : 0xFFFFFFFFu;
+        } else pix[i] = ok ? spos[t0[i] + p] : 0xFFFFFFFFu;
     }
     double v[8][3];
 #pragma unroll
@@ -1428,10 +1434,22 @@ __global__ __launch_bounds__(256) void k_dither_streams(const double *__restrict
         }
     }
 }
+template <int WHICH>
+__global__ __launch_bounds__(256) void k_dither_streams(const double *__restrict__ img, size_t plane_stride, const unsigned *__restrict__ spos, DitherRuns R,
+                                                       double *__restrict__ sx, double *__restrict__ sy, double *__restrict__ sz) {
+    dither_streams_tile<WHICH, false>(img, plane_stride, spos, R, sx, sy, sz, 0u);
+}
+template <int WHICH>
+__global__ __launch_bounds__(256) void k_dither_streams_frames(const double *__restrict__ img, size_t plane_stride, const unsigned *__restrict__ spos, DitherRuns R,
+                                                              double *__restrict__ sx, double *__restrict__ sy, double *__restrict__ sz, unsigned fruns) {
+    dither_streams_tile<WHICH, true>(img, plane_stride, spos, R, sx, sy, sz, fruns);
+}
 
 // tile (pt, w): runs 64 w .. 64 w + 63, positions 64 pt .. 64 pt + 63 of the choices, back to the image's pixel order
-template <typename OutT>
-__global__ __launch_bounds__(256) void k_dither_unpermute(const unsigned char *__restrict__ smap, const unsigned *__restrict__ spos, DitherRuns R, OutT *__restrict__ out) {
+// FRAMES: `fruns` runs per frame, spos the table of one frame (as dither_streams_tile)
+template <typename OutT, bool FRAMES>
+__device__ __forceinline__ void dither_unpermute_tile(const unsigned char *__restrict__ smap, const unsigned *__restrict__ spos, const DitherRuns R,
+                                                      OutT *__restrict__ out, unsigned fruns) {
     __shared__ unsigned long long t0[65];
     __shared__ unsigned char sm[64][65];
     const unsigned w = blockIdx.y, p0 = blockIdx.x * 64u, tid = threadIdx.x;
@@ -1445,8 +1463,22 @@ __global__ __launch_bounds__(256) void k_dither_unpermute(const unsigned char *_
 #pragma unroll
     for (int i = 0; i < 16; i++) {                                   // consecutive threads: consecutive ranks of one run
         const unsigned e = tid + 256u * i, l = e >> 6, p = p0 + (e & 63u);
-        if (64u * w + l < R.S && t0[l] + p < t0[l + 1]) out[spos[t0[l] + p]] = (OutT)sm[l][e & 63u];
+        if (64u * w + l < R.S && t0[l] + p < t0[l + 1]) {
+            if constexpr (FRAMES) {
+                const unsigned long long f0 = R.t((64u * w + l) / fruns * fruns);
+                out[f0 + spos[t0[l] + p - f0]] = (OutT)sm[l][e & 63u];
+            } else out[spos[t0[l] + p]] = (OutT)sm[l][e & 63u];
+        }
     }
+}
+template <typename OutT>
+__global__ __launch_bounds__(256) void k_dither_unpermute(const unsigned char *__restrict__ smap, const unsigned *__restrict__ spos, DitherRuns R, OutT *__restrict__ out) {
+    dither_unpermute_tile<OutT, false>(smap, spos, R, out, 0u);
+}
+template <typename OutT>
+__global__ __launch_bounds__(256) void k_dither_unpermute_frames(const unsigned char *__restrict__ smap, const unsigned *__restrict__ spos, DitherRuns R,
+                                                                OutT *__restrict__ out, unsigned fruns) {
+    dither_unpermute_tile<OutT, true>(smap, spos, R, out, fruns);
 }
 
 struct DitherLanes {
@@ -1466,11 +1498,18 @@ struct DitherLanes {
     struct Wider { NNGrid g; double hi[3]; const unsigned char *lut, *lut2; } wide[2];
     float amb;                           // f32 first pass: first and second must differ by more than this
     float amb_p, amb_x;                  // ... for a query outside the grid: amb_p + amb_x |x - lo|^2
+    // frame-batched walk (the kernels' FRAMES instantiations; the others never read it; it sits in the struct's tail padding): runs per
+    // frame.  Run b with b % fruns == 0 begins a frame: it starts from the empty queue, which is the chain's own state there, takes no
+    // warm-up, has no boundary to check, and no repair walk continues into it.
+    unsigned fruns;
 };
+static_assert(sizeof(DitherLanes) == 456, "DitherLanes: fruns must not move the kernels' other arguments");
 
+template <bool FRAMES>
 __global__ __launch_bounds__(256) void k_dither_lane_check(DitherLanes a) {
     const unsigned b = blockIdx.x * blockDim.x + threadIdx.x + 1u;
     if (b >= a.R.S) return;
+    if constexpr (FRAMES) { if (b % a.fruns == 0) return; }          // a frame's first run: exact by construction (flag[b] stays 0)
     const unsigned lp = (unsigned)(a.R.t(b) - a.R.t(b - 1));        // length of run b - 1
     bool same = true;
     for (unsigned i = 0; i < 16; i++) same = same && a.side[16ull * b + i] == (unsigned short)a.smap[a.R.idx(b - 1, lp - 16 + i)];
@@ -1530,6 +1569,7 @@ __device__ __attribute__((noinline)) int dither_nearest_all(const double x, cons
     return best;
 }
 
+template <bool FRAMES>
 __global__ __launch_bounds__(256) void k_dither_lanes(DitherLanes a, const double *__restrict__ pal /* planar (k,3), linear Rec2020 */, int k, DitherWeights wts) {
     extern __shared__ double lds[];
     double *praw = lds, *pwt = lds + 3 * k;                        // [3][k] raw palette; [3][k] scaled by the (float)-cast weights (riemersma.c:419-425)
@@ -1547,10 +1587,11 @@ __global__ __launch_bounds__(256) void k_dither_lanes(DitherLanes a, const doubl
     const unsigned len = (unsigned)(a.R.t(b + 1) - a.R.t(b));       // this run
     const unsigned lp = b > 0 ? (unsigned)(a.R.t(b) - a.R.t(b - 1)) : 0u;   // the one before it
     // steps [0, wu) read the end of run b - 1 (the neighbouring column), steps [wu, wu + len) this run
-    const unsigned wu = b > 0 ? a.warm : 0u;
+    // (a run that starts a chain -- run 0, FRAMES: a frame's first -- has the empty queue and no warm-up)
+    const unsigned wu = FRAMES ? (b % a.fruns != 0 ? a.warm : 0u) : (b > 0 ? a.warm : 0u);
     const size_t own = a.R.idx(b, 0);
     size_t at = wu ? a.R.idx(b - 1, lp - wu) : own;                // where step 0 reads
-    if (active && b > 0 && wu < 16) {                               // a warm-up of fewer than sixteen steps leaves no record to pass the check
+    if (active && (FRAMES ? b % a.fruns != 0 : b > 0) && wu < 16) {                              // a warm-up of fewer than sixteen steps leaves no record to pass the check
         for (int i = 0; i < 16; i++) a.side[16ull * b + i] = 0xFFFFu;
     }
 #define PAMD_DL_EACH(M) M(0) M(1) M(2) M(3) M(4) M(5) M(6) M(7) M(8) M(9) M(10) M(11) M(12) M(13) M(14) M(15)
@@ -1749,7 +1790,7 @@ __global__ __launch_bounds__(256) void k_dither_lanes(DitherLanes a, const doubl
 // wavefront of its own takes k_dither's step (the palette search across the 64 lanes, no table: ~0.45 us).  Pixels and choices
 // in the transposed layout (one cache line per lane and load: a few thousand runs, it does not matter here); the queue rebuilt
 // from the sixteen choices before the run as k_dither<.., 1> does; stops when a whole group of sixteen equals what is there.
-template <int PER>
+template <int PER, bool FRAMES>
 __global__ __launch_bounds__(64) void k_dither_lane_repair(DitherLanes a, const double *__restrict__ pal /* planar (k,3), linear Rec2020 */, int k, DitherWeights wts) {
     extern __shared__ double lds[];
     constexpr int kRing = 128;                                       // >= 64 + 15 pending pixels
@@ -1949,6 +1990,7 @@ __global__ __launch_bounds__(64) void k_dither_lane_repair(DitherLanes a, const 
             // the end of run r: the rules of the walk below
             const unsigned nr = r + 1;
             if (nr >= a.R.S) { halt = true; break; }
+            if constexpr (FRAMES) { if (nr % a.fruns == 0) { halt = true; break; } }   // the next frame: another chain
             const bool listed = a.flag[nr] != 0;
             if (listed && !in_row && !solo) { halt = true; break; }
             if (!listed) in_row = false;
@@ -2032,6 +2074,7 @@ __global__ __launch_bounds__(64) void k_dither_lane_repair(DitherLanes a, const 
         // run r is final for this pass.  On into the next one?
         const unsigned nr = r + 1;
         if (nr >= a.R.S) break;
+        if constexpr (FRAMES) { if (nr % a.fruns == 0) break; }     // the next frame: another chain
         const bool listed = a.flag[nr] != 0;
         if (done) {
             // met what was there: the rest of run r stands.  If the next boundary stands too (or another row starts there), finished;
@@ -2084,14 +2127,23 @@ static void dither_order(NNWork &w, size_t width, size_t height, hipStream_t s) 
 // Returns false when the verification stalls (a long flat stretch whose colour is not a palette entry: launch_dither_waves' comment):
 // the caller then takes the wavefront layout, which can walk one run through its successors.
 // mpos: the masked table (mcount opaque pixels, compact numbers in curve order: launch_dither_masked) in place of the cached curve order
+// frames > 1 (launch_dither_frames; no mask): d_img / d_out hold that many width x height frames one after another, each walked along
+// its own curve from the empty queue -- one cut with the same number of runs in every frame, so that run boundaries fall on the
+// frame starts (t(f S / frames) = f width height exactly), one table of width * height ranks, one set of launches
 static bool launch_dither_lanes(const double *d_img, size_t plane_stride, int which, size_t width, size_t height, const double *d_pal, const double *h_pal,
                                 int k, void *d_out, int elem_bytes, NNWork &w, const DitherConfig &cfg, const DitherWeights &wts, hipStream_t s,
-                                const unsigned *mpos, size_t mcount) {
-    const size_t npix = mpos ? mcount : width * height;
+                                const unsigned *mpos, size_t mcount, size_t frames = 1) {
+    const size_t nframe = width * height;
+    const size_t npix = mpos ? mcount : frames * nframe;
     DitherLanes a{};
     // runs: eight wavefronts of 64 per CU (two per SIMD), none shorter than 256 pixels unless asked for
     size_t S = cfg.segments > 0 ? (size_t)cfg.segments : std::min<size_t>((size_t)num_cus() * 8 * 64, npix / 256);
     S = std::max<size_t>(1, std::min(std::min(S, npix / 64), (size_t)8 * 65535));    // (a tile row per 8 runs: grid.y)
+    if (frames > 1) {                                               // the same limits, per frame (dither_frames_lane_layout: they leave one run at least)
+        const size_t per = cfg.segments > 0 ? ceil_div((size_t)cfg.segments, frames) : std::min<size_t>((size_t)num_cus() * 8 * 64, npix / 256) / frames;
+        a.fruns = (unsigned)std::max<size_t>(1, std::min(std::min(per, nframe / 64), (size_t)8 * 65535 / frames));
+        S = frames * a.fruns;
+    }
     a.R.N = npix; a.R.S = (unsigned)S; a.R.Lmax = (unsigned)ceil_div(npix, S);
     // warm-up: 256 pixels.  With a repair pass that costs a tenth of a millisecond (one wavefront per listed run) the 2-6 % of the
     // boundaries that 256 steps do not settle are cheaper than 256 more steps for every run (8192^2: noise 3.65 -> 3.28 ms,
@@ -2149,8 +2201,8 @@ static bool launch_dither_lanes(const double *d_img, size_t plane_stride, int wh
     w.clist.reserve((size_t)((ncell + ncellw[0] + ncellw[1]) / 64) * (1 + kCoarseMax) * 2);
     w.dsort.reserve(3 * cells);
     if (!mpos) {
-        if (w.dpos.cap < npix) { w.order_w = 0; w.order_h = 0; }
-        w.dpos.reserve(npix);
+        if (w.dpos.cap < nframe) { w.order_w = 0; w.order_h = 0; }
+        w.dpos.reserve(nframe);
     }
     w.dsmap.reserve(cells + 32 * S + 128);
     w.dside.reserve(S + 16);
@@ -2205,13 +2257,19 @@ static bool launch_dither_lanes(const double *d_img, size_t plane_stride, int wh
     const unsigned *sp = mpos ? mpos : (const unsigned *)w.dpos.p;
     {
         KTIME("k_dither_gather", s, 52.0 * npix);
+#define PAMD_DITHER_STREAMS(WHICH)                                                                                              \
+        do {                                                                                                                   \
+            if (a.fruns) hipLaunchKernelGGL(k_dither_streams_frames<WHICH>, tiles8, 256, 0, s, d_img, plane_stride, sp, a.R, sx, sy, sz, a.fruns); \
+            else hipLaunchKernelGGL(k_dither_streams<WHICH>, tiles8, 256, 0, s, d_img, plane_stride, sp, a.R, sx, sy, sz); \
+        } while (0)
         switch (which) {
-            case PAMD_COPY: hipLaunchKernelGGL(k_dither_streams<PAMD_COPY>, tiles8, 256, 0, s, d_img, plane_stride, sp, a.R, sx, sy, sz); break;
-            case PAMD_SRGB_TO_REC2020: hipLaunchKernelGGL(k_dither_streams<PAMD_SRGB_TO_REC2020>, tiles8, 256, 0, s, d_img, plane_stride, sp, a.R, sx, sy, sz); break;
-            case PAMD_CIELUV_TO_REC2020: hipLaunchKernelGGL(k_dither_streams<PAMD_CIELUV_TO_REC2020>, tiles8, 256, 0, s, d_img, plane_stride, sp, a.R, sx, sy, sz); break;
-            case PAMD_ICTCP_TO_REC2020: hipLaunchKernelGGL(k_dither_streams<PAMD_ICTCP_TO_REC2020>, tiles8, 256, 0, s, d_img, plane_stride, sp, a.R, sx, sy, sz); break;
+            case PAMD_COPY: PAMD_DITHER_STREAMS(PAMD_COPY); break;
+            case PAMD_SRGB_TO_REC2020: PAMD_DITHER_STREAMS(PAMD_SRGB_TO_REC2020); break;
+            case PAMD_CIELUV_TO_REC2020: PAMD_DITHER_STREAMS(PAMD_CIELUV_TO_REC2020); break;
+            case PAMD_ICTCP_TO_REC2020: PAMD_DITHER_STREAMS(PAMD_ICTCP_TO_REC2020); break;
             default: throw HipError("patolette_amd: the dither takes its pixels as linear Rec2020, sRGB, CIELuv or ICtCp");
         }
+#undef PAMD_DITHER_STREAMS
     }
     HIP_CHECK(hipStreamWaitEvent(s, w.ev_join, 0));
     HIP_CHECK(hipStreamWaitEvent(s, w.ev_join2, 0));
@@ -2223,7 +2281,8 @@ static bool launch_dither_lanes(const double *d_img, size_t plane_stride, int wh
     const size_t lds = (size_t)6 * k * sizeof(double) + (size_t)k * sizeof(float4);
     {
         KTIME("k_dither", s, 25.0 * npix);
-        hipLaunchKernelGGL(k_dither_lanes, (unsigned)ceil_div(S, 256), 256, lds, s, a, d_pal, k, wts);
+        if (a.fruns) hipLaunchKernelGGL(k_dither_lanes<true>, (unsigned)ceil_div(S, 256), 256, lds, s, a, d_pal, k, wts);
+        else hipLaunchKernelGGL(k_dither_lanes<false>, (unsigned)ceil_div(S, 256), 256, lds, s, a, d_pal, k, wts);
     }
     HIP_CHECK(hipGetLastError());
     w.dither_segments = S; w.dither_repairs = 0; w.dither_rounds = 0; w.dither_through = 0; w.dither_jumps = 0; w.dither_solo = 0;
@@ -2234,7 +2293,8 @@ static bool launch_dither_lanes(const double *d_img, size_t plane_stride, int wh
         HIP_CHECK(hipMemsetAsync(w.dside.p + 1, 0, sizeof(unsigned), s));
         {
             KTIME("k_dither_fix", s, 0.0);
-            hipLaunchKernelGGL(k_dither_lane_check, (unsigned)ceil_div(S - 1, 256), 256, 0, s, a);
+            if (a.fruns) hipLaunchKernelGGL(k_dither_lane_check<true>, (unsigned)ceil_div(S - 1, 256), 256, 0, s, a);
+            else hipLaunchKernelGGL(k_dither_lane_check<false>, (unsigned)ceil_div(S - 1, 256), 256, 0, s, a);
         }
         HIP_CHECK(hipMemcpyAsync(w.hrep.p, w.dside.p, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
@@ -2257,16 +2317,28 @@ static bool launch_dither_lanes(const double *d_img, size_t plane_stride, int wh
         KTIME("k_dither_fix", s, 0.0);
         const size_t lds_r = (size_t)6 * k * sizeof(double) + 3 * 128 * sizeof(double) + 128 * sizeof(unsigned) + 2048;   // + the history of choices
         const unsigned nblk = solo ? 1u : nf;
-        if (k <= 64) hipLaunchKernelGGL(k_dither_lane_repair<1>, nblk, 64, lds_r, s, a, d_pal, k, wts);
-        else if (k <= 128) hipLaunchKernelGGL(k_dither_lane_repair<2>, nblk, 64, lds_r, s, a, d_pal, k, wts);
-        else hipLaunchKernelGGL(k_dither_lane_repair<4>, nblk, 64, lds_r, s, a, d_pal, k, wts);
+#define PAMD_DITHER_REPAIR(PER)                                                                                                 \
+        do {                                                                                                                   \
+            if (a.fruns) hipLaunchKernelGGL((k_dither_lane_repair<PER, true>), nblk, 64, lds_r, s, a, d_pal, k, wts);          \
+            else hipLaunchKernelGGL((k_dither_lane_repair<PER, false>), nblk, 64, lds_r, s, a, d_pal, k, wts);                 \
+        } while (0)
+        if (k <= 64) PAMD_DITHER_REPAIR(1);
+        else if (k <= 128) PAMD_DITHER_REPAIR(2);
+        else PAMD_DITHER_REPAIR(4);
+#undef PAMD_DITHER_REPAIR
         HIP_CHECK(hipGetLastError());
     }
     {
         KTIME("k_dither_unpermute", s, (5.0 + elem_bytes) * npix);
-        if (elem_bytes == 1) hipLaunchKernelGGL(k_dither_unpermute<unsigned char>, tiles, 256, 0, s, (const unsigned char *)a.smap, sp, a.R, (unsigned char *)d_out);
-        else if (elem_bytes == 4) hipLaunchKernelGGL(k_dither_unpermute<unsigned int>, tiles, 256, 0, s, (const unsigned char *)a.smap, sp, a.R, (unsigned int *)d_out);
-        else hipLaunchKernelGGL(k_dither_unpermute<unsigned long long>, tiles, 256, 0, s, (const unsigned char *)a.smap, sp, a.R, (unsigned long long *)d_out);
+#define PAMD_DITHER_UNPERMUTE(T)                                                                                                \
+        do {                                                                                                                   \
+            if (a.fruns) hipLaunchKernelGGL(k_dither_unpermute_frames<T>, tiles, 256, 0, s, (const unsigned char *)a.smap, sp, a.R, (T *)d_out, a.fruns); \
+            else hipLaunchKernelGGL(k_dither_unpermute<T>, tiles, 256, 0, s, (const unsigned char *)a.smap, sp, a.R, (T *)d_out); \
+        } while (0)
+        if (elem_bytes == 1) PAMD_DITHER_UNPERMUTE(unsigned char);
+        else if (elem_bytes == 4) PAMD_DITHER_UNPERMUTE(unsigned int);
+        else PAMD_DITHER_UNPERMUTE(unsigned long long);
+#undef PAMD_DITHER_UNPERMUTE
     }
     HIP_CHECK(hipGetLastError());
     return true;
@@ -2369,6 +2441,66 @@ static void launch_dither_any(const double *d_img, size_t plane_stride, int whic
 void launch_dither(const double *d_img, size_t plane_stride, int which, size_t width, size_t height, const double *d_pal, const double *h_pal, int k,
                    void *d_out, int elem_bytes, NNWork &w, hipStream_t s, int layout) {
     launch_dither_any(d_img, plane_stride, which, width, height, d_pal, h_pal, k, d_out, elem_bytes, w, s, layout, nullptr, 0);
+}
+
+// ---- frames of one size, one palette (patolette_amd_frames_u8) ----
+// What the frame-batched lane walk needs besides dither_lane_layout on all the pixels: a run of 64 pixels at least in every frame,
+// and one tile row per 8 runs (grid.y)
+bool dither_frames_lane_layout(size_t frames, size_t width, size_t height, int k) {
+    const size_t n = width * height;
+    return frames > 0 && n >= 64 && frames <= (size_t)8 * 65535 && dither_lane_layout(frames * n, 1, k);
+}
+
+// Every frame dithered along its own curve from the empty queue.  The lane layout walks all frames side by side (launch_dither_lanes
+// with frames > 1).  Frame after frame through the single-image wavefront layout: whatever the lane layout does not take (a palette
+// outside 8 .. 256 rows, too few pixels, a knob that asks for wavefronts), and a batched walk whose verification stalled for good.
+void launch_dither_frames(const double *d_img, size_t plane_stride, int which, size_t frames, size_t width, size_t height, const double *d_pal,
+                          const double *h_pal, int k, void *d_out, int elem_bytes, NNWork &w, hipStream_t s, int layout) {
+    const size_t n = width * height, N = frames * n;
+    if (frames == 0 || n == 0 || N / n != frames || N > kDitherFramesMaxPixels) throw HipError("patolette_amd: the frame-batched dither takes up to 2^31 pixels in all");
+    if (elem_bytes != 1 && elem_bytes != 4 && elem_bytes != 8) throw HipError("patolette_amd: map element size must be 1, 4 or 8");
+    if (frames == 1) { launch_dither(d_img, plane_stride, which, width, height, d_pal, h_pal, k, d_out, elem_bytes, w, s, layout); return; }
+    size_t lane_passes = 0;
+    if (layout >= 0 ? layout != 0 : dither_frames_lane_layout(frames, width, height, k)) {
+        // (layout: what the caller decided when it chose the pixels' form; the knobs may have changed since, the hard limits have not)
+        if (!(n >= 64 && frames <= (size_t)8 * 65535 && k >= 8 && k <= 256)) throw HipError("patolette_amd: these frames cannot take the lane layout");
+        const DitherConfig cfg = dither_cfg_snapshot();
+        DitherWeights wts;
+        const double m = std::exp(std::log(16.0) / (16.0 - 1));
+        double v = 1;
+        for (int i = 0; i < 16; i++) { wts.w[i] = v / 16.0; v *= m; }
+        std::vector<double> hp;
+        if (!h_pal) {
+            hp.resize(3 * (size_t)k);
+            HIP_CHECK(hipMemcpyAsync(hp.data(), d_pal, hp.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+            h_pal = hp.data();
+        }
+        if (launch_dither_lanes(d_img, plane_stride, which, width, height, d_pal, h_pal, k, d_out, elem_bytes, w, cfg, wts, s, nullptr, 0, frames)) return;
+        // stalled: the wavefront layout from scratch, frame by frame (it needs the pixels as linear Rec2020 in image order; w.dsort
+        // holds more than 3 N already)
+        if (which != PAMD_COPY) {
+            w.dsort.reserve(3 * N);
+            const int gb = stream_blocks(N, 16);
+            switch (which) {
+                case PAMD_SRGB_TO_REC2020: hipLaunchKernelGGL(k_dither_convert<PAMD_SRGB_TO_REC2020>, gb, 256, 0, s, d_img, plane_stride, N, w.dsort.p); break;
+                case PAMD_CIELUV_TO_REC2020: hipLaunchKernelGGL(k_dither_convert<PAMD_CIELUV_TO_REC2020>, gb, 256, 0, s, d_img, plane_stride, N, w.dsort.p); break;
+                default: hipLaunchKernelGGL(k_dither_convert<PAMD_ICTCP_TO_REC2020>, gb, 256, 0, s, d_img, plane_stride, N, w.dsort.p); break;
+            }
+            HIP_CHECK(hipGetLastError());
+            d_img = w.dsort.p; plane_stride = N; which = PAMD_COPY;
+        }
+        lane_passes = w.dither_rounds;
+    }
+    if (which != PAMD_COPY) throw HipError("patolette_amd: the wavefront-per-run dither takes linear Rec2020 pixels");
+    size_t segments = 0, repairs = 0, rounds = lane_passes, through = 0, jumps = 0, solo = 0;
+    for (size_t f = 0; f < frames; f++) {
+        launch_dither_waves(d_img + f * n, plane_stride, width, height, d_pal, k, (unsigned char *)d_out + f * n * (size_t)elem_bytes, elem_bytes, w, s);
+        segments += w.dither_segments; repairs += w.dither_repairs; rounds += w.dither_rounds; through += w.dither_through;
+        jumps += w.dither_jumps; solo += w.dither_solo;
+    }
+    w.dither_segments = segments; w.dither_repairs = repairs; w.dither_rounds = rounds; w.dither_through = through;
+    w.dither_jumps = jumps; w.dither_solo = solo;
 }
 
 // The masked table: which curve ranks hold an opaque pixel (cpos[pixel] >= 0), in curve order, as compact pixel numbers -- one

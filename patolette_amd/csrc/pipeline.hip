@@ -2281,6 +2281,10 @@ static Bounds read_bounds(Engine &E, bool weighted, const std::function<void()> 
 // The RGBA entry's compact image: the pipeline runs on the M opaque pixels as an M x 1 image, and the dither walks the width x height
 // curve over them (launch_dither_masked; cpos[pixel] = compact number or -1)
 struct DitherMask { size_t width, height; const int *cpos; };
+// The frames entry's stack: the pipeline runs on count * width * height pixels as ONE image of width x (count * height) -- the palette
+// stage sees a list of colours, the nearest map is position-independent -- and only the dither knows the frames: each is walked along
+// its own width x height curve from the empty queue (launch_dither_frames)
+struct Frames { size_t count, width, height; };
 
 struct Pixels {                      // device-resident input image: planar f64 sRGB, or interleaved 8-bit sRGB
     const double *f64 = nullptr;
@@ -2311,7 +2315,8 @@ static ConvertPlan convert_plan(const Engine &E, const patolette__QuantizationOp
 }
 
 static void run_device(Engine &E, size_t width, size_t height, Pixels px, const double *d_weights, size_t K,
-                       const patolette__QuantizationOptions *opt, double *palette, void *d_map, int map_elem, const DitherMask *mask = nullptr) {
+                       const patolette__QuantizationOptions *opt, double *palette, void *d_map, int map_elem, const DitherMask *mask = nullptr,
+                       const Frames *frames = nullptr) {
     // d_map == nullptr with palette_only unset: the palette takes the same conversions, the map kernels are skipped
     hipStream_t s = E.stream;
     const size_t N = width * height;
@@ -2379,9 +2384,12 @@ static void run_device(Engine &E, size_t width, size_t height, Pixels px, const 
                 auto dither = [&](const double *img, int which, int layout) {
                     if (mask) launch_dither_masked(img, N, which, mask->width, mask->height, mask->cpos, N, E.dpal.p, pal.data(), (int)len, d_map,
                                                    map_elem, E.nn, s, layout);
+                    else if (frames) launch_dither_frames(img, N, which, frames->count, frames->width, frames->height, E.dpal.p, pal.data(), (int)len,
+                                                          d_map, map_elem, E.nn, s, layout);
                     else launch_dither(img, N, which, width, height, E.dpal.p, pal.data(), (int)len, d_map, map_elem, E.nn, s, layout);
                 };
-                if (dither_lane_layout(width, height, (int)len)) {               // decided ONCE: launch_dither is told
+                if (frames ? dither_frames_lane_layout(frames->count, frames->width, frames->height, (int)len)
+                           : dither_lane_layout(width, height, (int)len)) {      // decided ONCE: launch_dither is told
                     // the pixels go into curve order anyway: their conversion to linear Rec2020 rides on that pass
                     dither(E.cvt.p, pix, 1);
                 } else {
@@ -2436,11 +2444,16 @@ struct CodeError : std::runtime_error {        // failure with a dedicated exit 
 };
 
 // weights the Python binding derives when tile_size > 0 (patolette.pyx:407-414), left on the device
+// frames > 1 (8-bit input only): that many width x height images one after another, each weighted as an image of its own
 static const double *derive_weights(Engine &E, const double *d_f64, const unsigned char *d_u8, int channels, size_t width,
-                                    size_t height, double tile_size) {
-    E.wsal.reserve(width * height);
+                                    size_t height, double tile_size, size_t frames = 1) {
+    const size_t n = width * height;
+    E.wsal.reserve(frames * n);
     const double t0 = now_ms();
-    const int rc = saliency_weights(E.sal, d_f64, d_u8, channels, width, height, tile_size, E.wsal.p, E.stream);
+    int rc = kSalOk;
+    for (size_t f = 0; f < frames && rc == kSalOk; f++)
+        rc = saliency_weights(E.sal, d_f64, d_u8 ? d_u8 + f * n * (size_t)channels : nullptr, channels, width, height, tile_size, E.wsal.p + f * n,
+                              E.stream);
     if (ktimer().enabled) ktimer().collect();
     E.ms_saliency = now_ms() - t0;
     if (rc == kSalBadShape) throw CodeError(-5, "saliency weights: image shape not supported");
@@ -2655,13 +2668,22 @@ static bool upload_u8(Engine &E, const unsigned char *pixels, int channels, size
 // reconstructed u8 image out.  `pixels`, `d_map_out`, `d_quant_out` are device pointers when `on_device`.
 static void run_u8(Engine &E, size_t width, size_t height, const unsigned char *pixels, int channels, const double *weights,
                    double tile_size, size_t K, const patolette__QuantizationOptions *opt, double *palette, unsigned char *palette_u8,
-                   void *map_out, int map_elem_out, unsigned char *quant_out, bool on_device, bool map_on_device = false) {
+                   void *map_out, int map_elem_out, unsigned char *quant_out, bool on_device, bool map_on_device = false,
+                   const Frames *frames = nullptr) {
+    // frames: the image is that stack (width x height = frames->width x frames->count * frames->height); weights, upload, map
+    // download and reconstruction serve it as they serve one image
     const size_t N = width * height;
     hipStream_t s = E.stream;
     double t0 = now_ms();
     WsGuard wg(&E.stream, &E.stream2);
-    if (!weights && tile_size > 0.0) { E.wsal.reserve(N); saliency_reserve(E.sal, width, height); }
+    if (!weights && tile_size > 0.0) { E.wsal.reserve(N); saliency_reserve(E.sal, width, frames ? frames->height : height); }
     ws_prepare(E, N, K, weights || tile_size > 0.0, opt->verbose);   // (as run_host)
+    {   // what the stages below take of the workspace, before anything is enqueued (their own reservations are then no-ops)
+        const bool wmap = !opt->palette_only && (map_out || quant_out);
+        E.cvt.reserve(((weights || tile_size > 0.0) ? 4 : 3) * N); E.cstats.reserve(1);
+        if (wmap && !((on_device || map_on_device) && map_out && map_elem_out == map_elem_for(K))) E.dmap.reserve(N * (size_t)map_elem_for(K));
+        if (wmap && quant_out) { E.pal8.reserve(3 * K); if (!on_device) E.quant8.reserve(3 * N); }
+    }
     const unsigned char *d_px = pixels;
     const double *d_w = weights;
     bool converted = false;
@@ -2679,7 +2701,10 @@ static void run_u8(Engine &E, size_t width, size_t height, const unsigned char *
     }
     const double up = now_ms() - t0;
     E.ms_saliency = 0.0;
-    if (!weights && tile_size > 0.0) d_w = derive_weights(E, nullptr, d_px, channels, width, height, tile_size);
+    if (!weights && tile_size > 0.0) {
+        if (frames) d_w = derive_weights(E, nullptr, d_px, channels, frames->width, frames->height, tile_size, frames->count);
+        else d_w = derive_weights(E, nullptr, d_px, channels, width, height, tile_size);
+    }
     const int me = map_elem_for(K);
     const bool want_map = !opt->palette_only && (map_out || quant_out);
     void *d_map = nullptr;                  // stays null when no map-derived output is wanted: the map kernels are skipped
@@ -2690,7 +2715,7 @@ static void run_u8(Engine &E, size_t width, size_t height, const unsigned char *
     std::vector<double> pal(3 * K);
     Pixels px8{nullptr, d_px, channels};
     px8.converted = converted;
-    run_device(E, width, height, px8, d_w, K, opt, pal.data(), d_map, me);
+    run_device(E, width, height, px8, d_w, K, opt, pal.data(), d_map, me, nullptr, frames);
     E.stats.ms_saliency = E.ms_saliency;
     E.stats.ms_total += E.ms_saliency;
     t0 = now_ms();
@@ -2698,7 +2723,7 @@ static void run_u8(Engine &E, size_t width, size_t height, const unsigned char *
     palette_to_u8(pal.data(), K, p8.data());
     if (palette) std::memcpy(palette, pal.data(), 3 * K * sizeof(double));
     if (palette_u8) std::memcpy(palette_u8, p8.data(), 3 * K);
-    const bool touched = !(opt->dither && std::max(width, height) <= 1);       // 1x1 dither visits nothing
+    const bool touched = !(opt->dither && std::max(width, frames ? frames->height : height) <= 1);       // 1x1 dither visits nothing
     if (want_map && touched) {
         if (quant_out) {
             E.pal8.reserve(3 * K);
@@ -3151,6 +3176,45 @@ static void u8_entry(bool on_device, size_t width, size_t height, const unsigned
     }
 }
 
+// F frames of one size, one palette (include/patolette_amd.h): the path on the stack of frames, the dither frame by frame
+static void frames_entry(bool on_device, size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels,
+                         const double *weights, double tile_size, size_t palette_size, const patolette__QuantizationOptions *options,
+                         double *palette, unsigned char *palette_u8, void *palette_map, int map_elem_bytes, unsigned char *quantized,
+                         int *exit_code) {
+    *exit_code = frames == 0 ? -2 : validate(width, height, palette_size);
+    if (*exit_code != 0) return;
+    const size_t n = width * height;
+    if (frames > kDitherFramesMaxPixels / n) {                      // (n <= 1.6e9: no overflow before this)
+        const char *msg = "patolette_amd_frames: frames * width * height exceeds 2^31 pixels";
+        try { engine().last_error = msg; } catch (...) {}
+        fprintf(stderr, "%s\n", msg);
+        *exit_code = -4;
+        return;
+    }
+    if (validate_u8(palette_size, channels, palette_map, map_elem_bytes) != 0) {
+        const char *msg = "patolette_amd_frames: bad channels / map_elem_bytes";
+        try { engine().last_error = msg; } catch (...) {}
+        fprintf(stderr, "%s\n", msg);
+        *exit_code = -1;
+        return;
+    }
+    try {
+        Engine &E = engine();
+        E.init();
+        const Frames fr{frames, width, height};
+        run_u8(E, width, frames * height, pixels, channels, weights, tile_size, palette_size, options, palette, palette_u8, palette_map,
+               map_elem_bytes, quantized, on_device, false, frames > 1 ? &fr : nullptr);      // (one frame: the image entry itself)
+        *exit_code = 0;
+    } catch (const CodeError &ex) {
+        engine().last_error = ex.what();
+        *exit_code = ex.code;
+    } catch (const std::exception &ex) {
+        engine().last_error = ex.what();
+        fprintf(stderr, "patolette: %s\n", ex.what());
+        *exit_code = -1;
+    }
+}
+
 static void rgba_entry(bool on_device, size_t width, size_t height, const unsigned char *pixels, int alpha_threshold, const double *weights,
                        double tile_size, size_t palette_size, const patolette__QuantizationOptions *options, double *palette,
                        unsigned char *palette_rgba, void *palette_map, int map_elem_bytes, unsigned char *quantized, int *transparent_index,
@@ -3196,6 +3260,21 @@ void patolette_amd_rgba_device(size_t width, size_t height, const unsigned char 
                                int *transparent_index, int *exit_code) {
     rgba_entry(true, width, height, d_pixels, alpha_threshold, d_weights, tile_size, palette_size, options, palette, palette_rgba,
                d_palette_map, map_elem_bytes, d_quantized, transparent_index, exit_code);
+}
+
+void patolette_amd_frames_u8(size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels, const double *weights,
+                             double tile_size, size_t palette_size, const patolette__QuantizationOptions *options, double *palette,
+                             unsigned char *palette_u8, void *palette_map, int map_elem_bytes, unsigned char *quantized, int *exit_code) {
+    frames_entry(false, frames, width, height, pixels, channels, weights, tile_size, palette_size, options, palette, palette_u8, palette_map,
+                 map_elem_bytes, quantized, exit_code);
+}
+
+void patolette_amd_frames_u8_device(size_t frames, size_t width, size_t height, const unsigned char *d_pixels, int channels,
+                                    const double *d_weights, double tile_size, size_t palette_size,
+                                    const patolette__QuantizationOptions *options, double *palette, unsigned char *palette_u8,
+                                    void *d_palette_map, int map_elem_bytes, unsigned char *d_quantized, int *exit_code) {
+    frames_entry(true, frames, width, height, d_pixels, channels, d_weights, tile_size, palette_size, options, palette, palette_u8,
+                 d_palette_map, map_elem_bytes, d_quantized, exit_code);
 }
 
 void patolette_amd_u8(size_t width, size_t height, const unsigned char *pixels, int channels, const double *weights,
