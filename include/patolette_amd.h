@@ -139,6 +139,55 @@ void patolette_amd_frames_u8_device(size_t frames, size_t width, size_t height, 
                                     const patolette__QuantizationOptions *options, double *palette, unsigned char *palette_u8,
                                     void *d_palette_map, int map_elem_bytes, unsigned char *d_quantized, int *exit_code);
 
+/* ---- remap: 8-bit images and frames onto a palette the CALLER gives --------------------------------
+ * No palette is made: the index map of the pixels on the given palette, as patolette()'s map stage takes it for colour space sRGB.
+ *   Pixels.  `frames` images of width x height, interleaved 8-bit sRGB with `channels` (3 or 4; a 4th byte is ignored) bytes per pixel, one
+ *       after another, exactly as patolette_amd_frames_u8() takes them; frames == 1 is the single image.  Pixel value = v / 255.0.
+ *       n = width*height, N = frames*n.
+ *   Palette.  Exactly one of
+ *       palette_u8: palette_rows x 3 interleaved bytes; entry value = v / 255.0, the expression the pixels take;
+ *       palette:    (palette_rows, 3) column-major f64 sRGB as patolette() and the entries above return it.  Trailing rows equal to
+ *                   (-1, -1, -1) (the fill of unused rows) are dropped; what remains must be at least one row and all finite.  Values
+ *                   outside [0, 1] are taken as they are (the conversions are defined for them as the reference's are).
+ *       Map indices are row numbers of the palette as given.  Rows: what the map kernels take (no limit of this entry's own).
+ *   Maps, frame by frame, no state passing from one frame to the next:
+ *       dither == 0: palette and pixels go sRGB -> ICtCp (patolette__COLOR_sRGB_Matrix_to_ICtCp_Matrix), then
+ *           patolette__PALETTE_fill_palette_map_nearest -- the space in which the reference takes its nearest map for both of its
+ *           perceptual colour spaces (patolette.c:300-324).  Ties: the lowest index.
+ *       dither != 0: palette and pixels go sRGB -> linear Rec2020 (patolette__COLOR_sRGB_Matrix_to_Linear_Rec2020_Matrix), then
+ *           patolette__DITHER_riemersma over that frame's own width x height curve from an empty error queue (patolette.c:268-299 for
+ *           colour space sRGB).
+ *   Outputs, each optional (NULL): palette_map, N elements of map_elem_bytes (1, 2, 4 or 8; able to hold palette_rows-1), frame after
+ *       frame; quantized = N x 3 interleaved = pal8[palette_map], where pal8 is palette_u8 as given, or for an f64 palette
+ *       clip(palette * 255, 0, 255) truncated to bytes (what patolette_amd_u8() returns as palette_u8; dropped rows 0).
+ *   Exit codes: 0; -2 an empty image or frames == 0; -4 more than 2^31 pixels in all with dithering (more than 40000^2 without); -1 bad
+ *       channels / map_elem_bytes, both or neither palette given, no usable or a non-finite palette row (patolette_amd_last_error says
+ *       which).  A failed call leaves the thread's engine usable.
+ *   Statistics (patolette_amd_last_stats): ms_upload, ms_map, ms_download, ms_total and the dither counters (as
+ *       patolette_amd_frames_u8() counts them); every quantiser field is 0.  patolette_amd_last_map_palette: the palette in the map's space.
+ * Hence: a pixel whose bytes equal a palette_u8 entry's takes the same conversion of the same value -- in the reference's arithmetic it is
+ * at distance exactly 0 from that entry (here the pixels are converted on the device and the palette on the host, which agree to the
+ * 0.51 ulp of patolette_amd_pow: far below what separates two distinct byte rows); remapping the quantized image of an 8-bit call onto
+ * that call's palette_u8 (distinct rows) returns that call's map and image, dither on or off.
+ * NOT promised: that a remap with the F64 palette some earlier call returned is bit for bit that call's own map.  The returned palette
+ * has been through the map space -> sRGB conversion, and the way back costs an ulp or two: on the CPU reference this moved 0 of
+ * 60 000 nearest choices but 44 of 12 288 dithered ones on one of three synthetic scenes (a dither chain that meets a near-tie
+ * diverges from there on).  With the 8-bit palette of that call the difference is large (about 30 % of the map): the bytes are a
+ * different palette.
+ * The *_device flavour takes device pointers for pixels / palette_map / quantized (map_elem_bytes 1 for up to 256 palette rows, else
+ * 4); both palettes stay host memory. */
+void patolette_amd_remap_u8(size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels, const double *palette,
+                            const unsigned char *palette_u8, size_t palette_rows, int dither, void *palette_map, int map_elem_bytes,
+                            unsigned char *quantized, int *exit_code);
+void patolette_amd_remap_u8_device(size_t frames, size_t width, size_t height, const unsigned char *d_pixels, int channels,
+                                   const double *palette, const unsigned char *palette_u8, size_t palette_rows, int dither,
+                                   void *d_palette_map, int map_elem_bytes, unsigned char *d_quantized, int *exit_code);
+/* TESTS ONLY: by default a remap converts its pixels inside the map kernels where those exist -- the nearest map from 2^22 pixels on
+ * with 8 .. 256 palette rows, the dither where it runs one lane per run (patolette_amd_dither_layout_in_use) -- so that no f64 image is
+ * written; 1 makes every remap convert the image into f64 planes first (the route every other case takes), 0 restores the default.
+ * Same map either way.  Process-wide; returns the previous setting. */
+int patolette_amd_debug_remap_two_pass(int on);
+
 /* ---- RGBA images: a transparent palette slot, an alpha-aware dither ---------------------------
  * pixels: width*height interleaved 8-bit RGBA.  Pixel i is TRANSPARENT iff alpha_i < alpha_threshold (an integer in [0, 256]);
  * every other pixel is OPAQUE.  M = number of opaque pixels, N = width*height.

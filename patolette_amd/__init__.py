@@ -11,7 +11,8 @@ constants.  The work behind it runs in hand-written HIP kernels on gfx950 throug
 per-pixel weights instead of the saliency-derived ones), `saliency_weights`, `quantize_batch`, the 8-bit adaptor `quantize_u8` and its
 batch form `quantize_u8_batch`, and `quantize_rgba` for RGBA images: a palette built from the visible pixels only, one reserved
 transparent index, and a dither that walks past transparent pixels as the reference's walks past positions outside the image;
-and `quantize_frames` for an animation: frames of one size that share one palette, each frame dithered along its own curve.
+and `quantize_frames` for an animation: frames of one size that share one palette, each frame dithered along its own curve;
+and `remap`, which makes no palette: it maps 8-bit images or frames onto a palette the caller gives (a fixed one, an earlier call's).
 """
 import ctypes as C
 
@@ -309,6 +310,95 @@ def _quantize_frames_torch(frames, palette_size, dither, palette_only, color_spa
     return (True, palette_u8, maps, quant, palette, message)
 
 
+def _remap_palette(palette):
+    """(K, 3) uint8 -> (bytes array, None); (K, 3) float -> (None, column-major float64)."""
+    pal = np.asarray(palette)
+    if pal.ndim != 2 or pal.shape[1] != 3 or pal.shape[0] < 1:
+        raise ValueError("palette must be a (K, 3) uint8 or float array with at least one row")
+    if pal.dtype == np.uint8:
+        return np.ascontiguousarray(pal), None
+    if pal.dtype.kind != "f":                                  # (other integers would be read as sRGB values far outside [0, 1])
+        raise ValueError("palette must be a (K, 3) uint8 or float array with at least one row")
+    return None, np.asfortranarray(pal, dtype=np.float64)
+
+
+def _remap_result(L, code, pmap, quant):
+    if code == -1 and _native.last_error().startswith("patolette_amd_remap:"):
+        raise ValueError(_native.last_error())
+    message = L.get_patolette_exit_code_info_message(code).decode('UTF-8')
+    if code != 0:
+        return (False, None, None, message)
+    return (True, pmap, quant, message)
+
+
+def remap(image, palette, dither=True, want_quantized=True):
+    """Map an 8-bit image, or frames of one size, onto a palette the caller gives (additive; include/patolette_amd.h:
+    patolette_amd_remap_u8).  No palette is made.
+
+      * image: (H, W, 3|4) or (F, H, W, 3|4) uint8 sRGB, a numpy array or a torch CUDA tensor (then the map and the quantized
+        image stay in HBM, as in `quantize_u8`).  A 4th channel is ignored.
+      * palette: (K, 3) uint8 (entry = v / 255, as the pixels), or (K, 3) float sRGB in any layout -- so both `palette_u8` and
+        `palette` of every return tuple of this module can be passed straight in.  Trailing (-1, -1, -1) rows of a float palette
+        (unused rows) are dropped; indices are row numbers of the palette as given.
+      * dither=False: the nearest entry in ICtCp; dither=True: the reference's Riemersma walk in linear Rec2020 over each frame's own
+        W x H curve from an empty error queue.  No state passes between frames: remap(frames, p)[1][i] == remap(frames[i], p)[1].
+    Remapping a call's quantized image onto that call's `palette_u8` gives back its map.  Remapping the ORIGINAL image onto the float
+    palette a `quantize*` call returned is close to, not bit for bit, that call's map (the header says why).
+
+    Returns (success, palette_map (H,W) or (F,H,W) uint8|uint16|uint32 by K, quantized (..., 3) uint8 = pal8[palette_map] or None,
+    message)."""
+    if hasattr(image, "data_ptr") and getattr(image, "is_cuda", False):
+        return _remap_torch(image, palette, dither, want_quantized)
+    if not isinstance(image, np.ndarray):
+        image = np.asarray(image)
+    if image.dtype != np.uint8 or image.ndim not in (3, 4) or image.shape[-1] not in (3, 4):
+        raise ValueError("image must be an (H, W, 3|4) or (F, H, W, 3|4) uint8 array")
+    pal8, palf = _remap_palette(palette)
+    img = np.ascontiguousarray(image)
+    shape = img.shape[:-1]
+    count, (height, width), channels = (shape[0] if img.ndim == 4 else 1), shape[-2:], img.shape[-1]
+    rows = (pal8 if pal8 is not None else palf).shape[0]
+    map_dtype = np.uint8 if rows <= 256 else (np.uint16 if rows <= 65536 else np.uint32)
+    pmap = np.zeros(shape, dtype=map_dtype)
+    quant = np.zeros(shape + (3,), dtype=np.uint8) if want_quantized else None
+    code = C.c_int(0)
+    L = _native.lib()
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size > 0 else None   # noqa: E731
+    L.patolette_amd_remap_u8(count, width, height, vp(img), channels, _dp(palf), vp(pal8), rows, 1 if dither else 0, vp(pmap),
+                             np.dtype(map_dtype).itemsize, vp(quant), C.byref(code))
+    return _remap_result(L, code.value, pmap, quant)
+
+
+def _remap_torch(image, palette, dither, want_quantized):
+    """`remap` for a torch CUDA uint8 tensor (H, W, 3|4) or (F, H, W, 3|4) through `patolette_amd_remap_u8_device`, as
+    `_quantize_u8_torch`: the map (uint8 for K <= 256, else int32) and the quantized image stay in HBM; the palette is host memory.
+    Import torch BEFORE patolette_amd in such a process (see `_quantize_u8_torch`)."""
+    import torch
+    if image.dtype != torch.uint8 or image.dim() not in (3, 4) or image.shape[-1] not in (3, 4):
+        raise ValueError("image must be an (H, W, 3|4) or (F, H, W, 3|4) uint8 tensor")
+    if hasattr(palette, "detach"):
+        palette = palette.detach().cpu().numpy()
+    pal8, palf = _remap_palette(palette)
+    img = image.contiguous()
+    shape = tuple(int(v) for v in img.shape[:-1])
+    count, (height, width), channels = (shape[0] if img.dim() == 4 else 1), shape[-2:], int(img.shape[-1])
+    n = count * width * height
+    dev = img.device
+    rows = (pal8 if pal8 is not None else palf).shape[0]
+    me = 1 if rows <= 256 else 4
+    pmap = torch.zeros(shape, dtype=torch.uint8 if me == 1 else torch.int32, device=dev)
+    quant = torch.zeros(shape + (3,), dtype=torch.uint8, device=dev) if want_quantized else None
+    code = C.c_int(0)
+    L = _native.lib()
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream().synchronize()          # the library runs on its own stream
+        L.patolette_amd_remap_u8_device(count, width, height, C.c_void_p(img.data_ptr()) if n else None, channels, _dp(palf),
+                                        pal8.ctypes.data_as(C.c_void_p) if pal8 is not None else None, rows, 1 if dither else 0,
+                                        C.c_void_p(pmap.data_ptr()) if n else None, me,
+                                        C.c_void_p(quant.data_ptr()) if quant is not None and n else None, C.byref(code))
+    return _remap_result(L, code.value, pmap, quant)
+
+
 def _rgba_args(palette_size, alpha_threshold, dither, palette_only, color_space, kmeans_niter, kmeans_max_samples):
     if isinstance(alpha_threshold, bool) or int(alpha_threshold) != alpha_threshold or not 0 <= alpha_threshold <= 256:
         raise ValueError("alpha_threshold must be an integer in [0, 256]")
@@ -525,6 +615,7 @@ __all__ = [
     "quantize_u8_batch",
     "quantize_rgba",
     "quantize_frames",
+    "remap",
     "saliency_weights",
     "ColorSpace_sRGB",
     "ColorSpace_CIELuv",

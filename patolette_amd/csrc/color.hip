@@ -31,7 +31,7 @@ __global__ __launch_bounds__(256) void k_convert(SRC src, double *__restrict__ d
     // centred covariance without another sweep (pipeline.hip quantize_clusters)
     const bool do_mom = do_sum && momk.M0 != 0.0;
     double acc2[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    constexpr bool kLut = std::is_same<SRC, SrcU8>::value && (WHICH == PAMD_SRGB_TO_ICTCP || WHICH == PAMD_SRGB_TO_CIELUV);
+    constexpr bool kLut = std::is_same<SRC, SrcU8>::value && (WHICH == PAMD_SRGB_TO_ICTCP || WHICH == PAMD_SRGB_TO_CIELUV || WHICH == PAMD_SRGB_TO_REC2020);
     __shared__ double glut[kLut ? 256 : 1];                // companding of the 256 possible 8-bit values (sRGB.c:70-89)
     pow_tables_to_lds();
     __syncthreads();
@@ -191,6 +191,7 @@ void launch_convert_u8(int which, const unsigned char *pixels, int channels, dou
     switch (which) {
         case PAMD_SRGB_TO_ICTCP: hipLaunchKernelGGL((k_convert<PAMD_SRGB_TO_ICTCP, SrcU8>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end); break;
         case PAMD_SRGB_TO_CIELUV: hipLaunchKernelGGL((k_convert<PAMD_SRGB_TO_CIELUV, SrcU8>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end); break;
+        case PAMD_SRGB_TO_REC2020: hipLaunchKernelGGL((k_convert<PAMD_SRGB_TO_REC2020, SrcU8>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end); break;   // the remap entry's dither
         case PAMD_COPY: hipLaunchKernelGGL((k_convert<PAMD_COPY, SrcU8>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end); break;
         default: throw HipError("patolette_amd: unknown conversion");
     }

@@ -238,6 +238,10 @@ __device__ __forceinline__ void dev_convert_linear(double c[3]) {
         dc::rec2020_to_ictcp(c);
     } else if constexpr (WHICH == PAMD_SRGB_TO_CIELUV) {
         dc::linear_to_cieluv(c);
+    } else if constexpr (WHICH == PAMD_SRGB_TO_REC2020) {
+        double x, y, z;
+        dc::linear_to_xyz(c[0], c[1], c[2], x, y, z);
+        dc::xyz_to_rec2020(x, y, z, c);
     }
 }
 

@@ -43,6 +43,11 @@ struct NNWork {                        // scratch of the pruned NN map
 // lo/hi: exact per-plane min/max of the colours if known (else nullptr: computed with one more pass)
 void launch_nn_map(const double *d_colors, size_t plane_stride, size_t n, const double *d_pal, int k,
                    void *d_out, int elem_bytes, const double *lo, const double *hi, NNWork &w, hipStream_t s);
+// The same map straight from interleaved 8-bit sRGB pixels (`channels` 3 or 4 bytes each; palette in ICtCp): the LDS-table kernel with
+// a byte source that converts in registers, no f64 image.  Only where nn_map_u8_applies (the sizes and palettes that kernel takes);
+// elements of 1 or 4 bytes.
+bool nn_map_u8_applies(size_t n, int k);
+void launch_nn_map_u8(const unsigned char *d_px, int channels, size_t n, const double *d_pal, int k, void *d_out, int elem_bytes, NNWork &w, hipStream_t s);
 // which: the conversion the pixels still need on their way into linear Rec2020 (PAMD_COPY: none) -- only the lane-per-run layout
 // (dither_lane_layout) converts on the fly; h_pal: the same palette on the host if the caller has it (else it is read back)
 bool dither_lane_layout(size_t width, size_t height, int k);
@@ -57,6 +62,13 @@ constexpr size_t kDitherFramesMaxPixels = (size_t)1 << 31;
 bool dither_frames_lane_layout(size_t frames, size_t width, size_t height, int k);
 void launch_dither_frames(const double *d_img, size_t plane_stride, int which, size_t frames, size_t width, size_t height, const double *d_pal,
                           const double *h_pal, int k, void *d_out, int elem_bytes, NNWork &w, hipStream_t s, int layout = -1);
+
+// The lane layout straight from interleaved 8-bit sRGB pixels (the remap entry): `frames` images of width x height, `channels` (3 or 4)
+// bytes per pixel, palette in linear Rec2020; the conversion rides on the gather and no f64 image exists.  Only where the lane layout
+// applies (dither_lane_layout, resp. dither_frames_lane_layout for frames > 1).  Returns false when the walk's verification stalled
+// for good: the caller then converts the image and calls launch_dither / launch_dither_frames.
+bool launch_dither_u8(const unsigned char *d_px, int channels, size_t frames, size_t width, size_t height, const double *d_pal, const double *h_pal,
+                      int k, void *d_out, int elem_bytes, NNWork &w, hipStream_t s);
 
 // The same chain over a width x height image of which only some pixels are visited (the RGBA entry): d_cpos[pixel] = the pixel's
 // number among the m opaque ones (row-scan order), or -1 for a transparent pixel, which the walk skips exactly like a position

@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
+#include <mutex>
 #include <type_traits>
 
 #define PAMD_POW_TABLES_IN_LDS
@@ -488,8 +489,15 @@ struct PalSoA { const double *x, *y, *z; };
 
 // LDS of k_nn_map_mid: table, f32 records, f64 palette, and what is left of the CU's 160 KB for the wavefronts' overflow queues
 constexpr size_t kMidLdsFixed = 131072 + 256 * 16 + 3 * 256 * 8;
-constexpr int mid_queue(const int waves) { const int q = (int)((163840 - kMidLdsFixed) / ((size_t)waves * 28)); return q > 64 ? 64 : (q & ~3); }   // parked pixels per wavefront (28 B each)
-constexpr size_t mid_lds(const int waves) { return kMidLdsFixed + (size_t)waves * mid_queue(waves) * 28; }
+// extra: what a pixel source adds to the fixed part (NNSrcU8: its decode table in the dynamic part + the 4 KB of pow tables, static)
+constexpr int mid_queue(const int waves, const size_t extra = 0) { const int q = (int)((163840 - kMidLdsFixed - extra) / ((size_t)waves * 28)); return q > 64 ? 64 : (q & ~3); }   // parked pixels per wavefront (28 B each)
+constexpr size_t mid_lds(const int waves, const size_t extra = 0, const size_t dyn_extra = 0) { return kMidLdsFixed + dyn_extra + (size_t)waves * mid_queue(waves, extra) * 28; }
+
+// Where k_nn_map_mid takes its pixels from.  NNSrcPlanes: planar f64 in the map's space (plane stride N).  NNSrcU8 (the remap entry):
+// interleaved 8-bit sRGB, ch bytes per pixel, converted to ICtCp in registers -- the companding from the table of its 256 possible
+// arguments, then dev_convert_linear, exactly as k_convert<PAMD_SRGB_TO_ICTCP, SrcU8> does it: the same bits, no f64 image.
+struct NNSrcPlanes { const double *c; size_t N; static constexpr bool kBytes = false; static constexpr size_t kLdsDyn = 0, kLdsStatic = 0; };
+struct NNSrcU8 { const unsigned char *p; size_t ch; static constexpr bool kBytes = true; static constexpr size_t kLdsDyn = 256 * 8, kLdsStatic = (128 * 3 + 64 * 2) * 8; };
 
 // One parked pixel through its record of the G^3 table: the first eight entries unconditionally in two groups of four (a record is
 // padded with its last entry, and re-evaluating an entry cannot change a strict-'<' arg-min), the second group only when some lane
@@ -543,8 +551,8 @@ __device__ unsigned long long g_dl_wave[4096][4];  // ... and per wavefront of t
 __device__ unsigned long long g_dl_stats[8];      // k_dither_lanes (PAMD_NN_STATS): lane-steps, outside the grid, long-list cells, ambiguous; wavefront-steps, with an exact pass, with a full scan, candidate-loop trips
 __device__ unsigned g_nn_flags;                             // timing experiments (wrong maps): 1 = drains evaluate nothing, 2 = nothing is parked
 #endif
-template <typename OutT, int P, int WAVES>
-__global__ __launch_bounds__(64 * WAVES) void k_nn_map_mid(const double *__restrict__ c, size_t N, size_t n, const double *__restrict__ pal, int k,
+template <typename OutT, int P, int WAVES, class SRC = NNSrcPlanes>
+__global__ __launch_bounds__(64 * WAVES) void k_nn_map_mid(const SRC src, size_t n, const double *__restrict__ pal, int k,
                                                      NNGrid g, const unsigned int *__restrict__ mid, const float4 *__restrict__ rec32,
                                                      const unsigned char *__restrict__ lut, const unsigned char *__restrict__ lut2, OutT *__restrict__ out) {
     extern __shared__ unsigned char smem_mid[];
@@ -558,15 +566,28 @@ __global__ __launch_bounds__(64 * WAVES) void k_nn_map_mid(const double *__restr
     double *spx = (double *)(R + 256), *spy = spx + 256, *spz = spy + 256;       // the f64 palette (the exact loop of the parked pixels)
     const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     // this wavefront's overflow queue: coordinates and pixel index of up to kMidQueue pixels
-    constexpr int kMidQueue = mid_queue(WAVES);
-    double *qx = spz + 256 + wid * 3 * kMidQueue, *qy = qx + kMidQueue, *qz = qy + kMidQueue;
-    unsigned int *qi = (unsigned int *)(spz + 256 + WAVES * 3 * kMidQueue) + wid * kMidQueue;
+    constexpr int kMidQueue = mid_queue(WAVES, SRC::kLdsDyn + SRC::kLdsStatic);
+    double *glut = spz + 256;                                                    // NNSrcU8: the companding of the 256 possible bytes
+    double *qx = spz + 256 + SRC::kLdsDyn / 8 + wid * 3 * kMidQueue, *qy = qx + kMidQueue, *qz = qy + kMidQueue;
+    unsigned int *qi = (unsigned int *)(spz + 256 + SRC::kLdsDyn / 8 + WAVES * 3 * kMidQueue) + wid * kMidQueue;
     const PalSoA sp{spx, spy, spz};
 
     constexpr size_t tile = (size_t)64 * P;
     const size_t step = (size_t)gridDim.x * WAVES * tile;
-    double nx[P], ny[P], nz[P];
+    double nx[SRC::kBytes ? 1 : P], ny[SRC::kBytes ? 1 : P], nz[SRC::kBytes ? 1 : P];
+    unsigned nb[SRC::kBytes ? P : 1];                                             // NNSrcU8: the next tile's pixels as packed bytes
     auto fetch = [&](const size_t base) {                                         // wave-uniform base
+        if constexpr (SRC::kBytes) {
+            const unsigned last = (unsigned)(n - base - 1);
+#pragma unroll
+            for (int p = 0; p < P; p++) {
+                const unsigned t = min(128u * (unsigned)(p >> 1) + 2u * (unsigned)lane + (unsigned)(p & 1), last);
+                const unsigned char *q = src.p + (base + t) * src.ch;
+                nb[p] = (unsigned)q[0] | ((unsigned)q[1] << 8) | ((unsigned)q[2] << 16);
+            }
+        } else {
+        const double *c = src.c;
+        const size_t N = src.N;
         const double *cb = c + base;
         if (base + tile <= n && ((N | base) & 1) == 0) {                          // 16-byte aligned pairs in every plane
 #pragma unroll
@@ -584,9 +605,15 @@ __global__ __launch_bounds__(64 * WAVES) void k_nn_map_mid(const double *__restr
 #pragma unroll
             for (int p = 0; p < P; p++) { const unsigned t = min(128u * (unsigned)(p >> 1) + 2u * (unsigned)lane + (unsigned)(p & 1), last); nx[p] = cb[t]; ny[p] = cb[N + t]; nz[p] = cb[2 * N + t]; }
         }
+        }
     };
     size_t base = ((size_t)blockIdx.x * WAVES + wid) * tile;
     if (base < n) fetch(base);                                                    // in flight while the table is copied in
+    if constexpr (SRC::kBytes) {
+        pow_tables_to_lds();
+        __syncthreads();
+        for (int b = threadIdx.x; b < 256; b += 64 * WAVES) glut[b] = dc::gamma_decode((double)b / 255.0);
+    }
     for (int i = threadIdx.x; i < ncell / 4; i += 64 * WAVES) ((uint4 *)T)[i] = ((const uint4 *)mid)[i];
     for (int j = threadIdx.x; j < 256; j += 64 * WAVES) {
         const bool in = j < k;
@@ -604,10 +631,24 @@ __global__ __launch_bounds__(64 * WAVES) void k_nn_map_mid(const double *__restr
     const bool out_even = (reinterpret_cast<size_t>(out) & 1) == 0;               // packed two-byte stores need an even address
     for (; base < n; base += step) {
         double x[P], y[P], z[P];
+        unsigned cur[SRC::kBytes ? P : 1];
+        if constexpr (SRC::kBytes) {
 #pragma unroll
-        for (int p = 0; p < P; p++) { x[p] = nx[p]; y[p] = ny[p]; z[p] = nz[p]; }
+            for (int p = 0; p < P; p++) cur[p] = nb[p];
+        } else {
+#pragma unroll
+            for (int p = 0; p < P; p++) { x[p] = nx[p]; y[p] = ny[p]; z[p] = nz[p]; }
+        }
         const bool lasttile = base + step >= n;
         if (!lasttile) fetch(base + step);                                        // the next tile's pixels are in flight during this one
+        if constexpr (SRC::kBytes) {
+#pragma unroll
+            for (int p = 0; p < P; p++) {
+                double cc[3] = {glut[cur[p] & 0xffu], glut[(cur[p] >> 8) & 0xffu], glut[(cur[p] >> 16) & 0xffu]};
+                dev_convert_linear<PAMD_SRGB_TO_ICTCP>(cc);
+                x[p] = cc[0]; y[p] = cc[1]; z[p] = cc[2];
+            }
+        }
         const unsigned left = (unsigned)min((size_t)tile, n - base);
         OutT *ob = out + base;
         unsigned e[P];
@@ -771,7 +812,7 @@ static void launch_nn_lut(const double *d_colors, size_t plane_stride, size_t n,
             if (attr_mid.first()) HIP_CHECK(hipFuncSetAttribute((const void *)(k_nn_map_mid<OutT, P, WAVES>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mid_lds(WAVES)));
             const int blocks = (int)std::min<size_t>((size_t)num_cus(), ceil_div(n, (size_t)64 * WAVES * P));
             KTIME("k_nn_map", s, (24.0 + sizeof(OutT)) * n);
-            hipLaunchKernelGGL((k_nn_map_mid<OutT, P, WAVES>), blocks, 64 * WAVES, mid_lds(WAVES), s, d_colors, plane_stride, n, d_pal, k, g, (const unsigned int *)w.mid.p,
+            hipLaunchKernelGGL((k_nn_map_mid<OutT, P, WAVES>), blocks, 64 * WAVES, mid_lds(WAVES), s, NNSrcPlanes{d_colors, plane_stride}, n, d_pal, k, g, (const unsigned int *)w.mid.p,
                                (const float4 *)(w.mid.p + ncell / 8), (const unsigned char *)l1, (const unsigned char *)l2, out);
             return;
         }
@@ -794,6 +835,103 @@ static void launch_nn_lut(const double *d_colors, size_t plane_stride, size_t n,
         KTIME("k_nn_map", s, (24.0 + sizeof(OutT)) * n);
         hipLaunchKernelGGL((k_nn_map_lut<OutT, unsigned short>), stream_blocks(n, 8), 256, lds, s, d_colors, plane_stride, n, d_pal, k, g, (const unsigned short *)l16, (const unsigned short *)l16b, out);
     }
+}
+
+// min / max per ICtCp plane over ALL 2^24 8-bit sRGB colours, converted exactly as NNSrcU8 converts a pixel: bounds that enclose
+// whatever an 8-bit image holds, under the device's own rounding (Ct and Cp are not monotone in the bytes: the cube's corners do not do)
+__global__ __launch_bounds__(256) void k_srgb8_ictcp_bounds(unsigned long long *keys /* min[3], max[3] */) {
+    __shared__ double glut[256];
+    pow_tables_to_lds();
+    __syncthreads();
+    glut[threadIdx.x] = dc::gamma_decode((double)threadIdx.x / 255.0);
+    __syncthreads();
+    double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < (1u << 24); i += gridDim.x * 256u) {
+        double c[3] = {glut[i & 0xffu], glut[(i >> 8) & 0xffu], glut[i >> 16]};
+        dev_convert_linear<PAMD_SRGB_TO_ICTCP>(c);
+#pragma unroll
+        for (int a = 0; a < 3; a++) { mn[a] = fmin(mn[a], c[a]); mx[a] = fmax(mx[a], c[a]); }
+    }
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        double lo = mn[a], hi = mx[a];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { lo = fmin(lo, __shfl_down(lo, o, 64)); hi = fmax(hi, __shfl_down(hi, o, 64)); }
+        if ((threadIdx.x & 63) == 0 && lo <= hi) { atomicMin(&keys[a], f64_key(lo)); atomicMax(&keys[3 + a], f64_key(hi)); }
+    }
+}
+
+// ... made once per device (0.4 ms) and kept
+static void srgb8_ictcp_bounds(NNWork &w, hipStream_t s, double lo[3], double hi[3]) {
+    struct Box { bool have = false; double lo[3], hi[3]; };
+    static std::mutex mu;
+    static Box boxes[64];
+    int dev = -1;
+    HIP_CHECK(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(mu);
+    Box local, &b = (dev >= 0 && dev < 64) ? boxes[dev] : local;
+    if (!b.have) {
+        w.keys.reserve(6);
+        unsigned long long init[6] = {~0ULL, ~0ULL, ~0ULL, 0ULL, 0ULL, 0ULL}, got[6];
+        HIP_CHECK(hipMemcpyAsync(w.keys.p, init, sizeof init, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_srgb8_ictcp_bounds, 2048, 256, 0, s, w.keys.p);
+        HIP_CHECK(hipMemcpyAsync(got, w.keys.p, sizeof got, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        for (int a = 0; a < 3; a++) { b.lo[a] = key_f64(got[a]); b.hi[a] = key_f64(got[3 + a]); }
+        b.have = true;
+    }
+    for (int a = 0; a < 3; a++) { lo[a] = b.lo[a]; hi[a] = b.hi[a]; }
+}
+
+static NNGrid nn_grid(const double blo[3], const double bhi[3], int G) {
+    NNGrid g;
+    g.G = G;
+    for (int a = 0; a < 3; a++) {
+        double r = bhi[a] - blo[a];
+        if (!(r > 0) || !std::isfinite(r)) r = 0;
+        g.lo[a] = blo[a];
+        g.cw[a] = r / g.G;
+        g.inv[a] = r > 0 ? g.G / r : 0.0;
+    }
+    return g;
+}
+
+// The nearest map straight from interleaved 8-bit sRGB pixels (the remap entry; palette in ICtCp): k_nn_map_mid with the byte source.
+// The grid spans the image of the whole 8-bit sRGB cube (the kernel takes a pixel's cell without a clamp: the box must enclose every
+// pixel, and exact bounds of THIS image would cost its conversion a second time).
+bool nn_map_u8_applies(size_t n, int k) { return n >= ((size_t)1 << 22) && !(n >> 32) && k >= 8 && k <= 256; }
+template <typename OutT>
+static void launch_nn_mid_u8(const unsigned char *d_px, int channels, size_t n, const double *d_pal, int k, OutT *out, NNWork &w, hipStream_t s) {
+    double blo[3], bhi[3];
+    srgb8_ictcp_bounds(w, s, blo, bhi);
+    const NNGrid g = nn_grid(blo, bhi, 64);
+    const int ncell = g.G * g.G * g.G, ncoarse = ncell / 64;
+    w.lut.reserve((size_t)ncell * 32);
+    unsigned char *l1 = w.lut.p, *l2 = w.lut.p + (size_t)ncell * 16;
+    w.mid.reserve((size_t)(ncell / 8) + 257 * 4);
+    w.clist.reserve((size_t)ncoarse * (1 + kCoarseMax) * 2);
+    {
+        KTIME("k_nn_lut_build", s, 32.0 * ncell);
+        hipLaunchKernelGGL(k_nn_lut_coarse<unsigned char>, ncoarse, 64, 0, s, d_pal, k, g, w.clist.p, (float4 *)(w.mid.p + ncell / 8));
+        hipLaunchKernelGGL(k_nn_lut_build<unsigned char>, ncoarse, 64, 0, s, d_pal, k, g, l1, l2, (const unsigned char *)w.clist.p, w.mid.p);
+    }
+    constexpr int P = sizeof(OutT) == 1 ? 4 : 2, WAVES = 16;
+    constexpr size_t lds = mid_lds(WAVES, NNSrcU8::kLdsDyn + NNSrcU8::kLdsStatic, NNSrcU8::kLdsDyn);
+    static_assert(lds + NNSrcU8::kLdsStatic <= 163840, "the CU's LDS");
+    static PerDeviceOnce attr_mid;
+    if (attr_mid.first()) HIP_CHECK(hipFuncSetAttribute((const void *)(k_nn_map_mid<OutT, P, WAVES, NNSrcU8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int blocks = (int)std::min<size_t>((size_t)num_cus(), ceil_div(n, (size_t)64 * WAVES * P));
+    KTIME("k_nn_map_u8", s, ((double)channels + sizeof(OutT)) * n);
+    hipLaunchKernelGGL((k_nn_map_mid<OutT, P, WAVES, NNSrcU8>), blocks, 64 * WAVES, lds, s, NNSrcU8{d_px, (size_t)channels}, n, d_pal, k, g, (const unsigned int *)w.mid.p,
+                       (const float4 *)(w.mid.p + ncell / 8), (const unsigned char *)l1, (const unsigned char *)l2, out);
+}
+void launch_nn_map_u8(const unsigned char *d_px, int channels, size_t n, const double *d_pal, int k, void *d_out, int elem_bytes, NNWork &w, hipStream_t s) {
+    if (!nn_map_u8_applies(n, k)) throw HipError("patolette_amd: the byte-source map kernel takes 2^22 .. 2^32 pixels and 8 .. 256 palette rows");
+    if (channels != 3 && channels != 4) throw HipError("patolette_amd: 8-bit pixels have 3 or 4 channels");
+    if (elem_bytes == 1) launch_nn_mid_u8<unsigned char>(d_px, channels, n, d_pal, k, (unsigned char *)d_out, w, s);
+    else if (elem_bytes == 4) launch_nn_mid_u8<unsigned int>(d_px, channels, n, d_pal, k, (unsigned int *)d_out, w, s);
+    else throw HipError("patolette_amd: the byte-source map kernel writes 1- or 4-byte elements");
+    HIP_CHECK(hipGetLastError());
 }
 
 // lo/hi: per-plane bounds of the colours (exact min/max), or nullptr to have them computed here
@@ -819,15 +957,7 @@ void launch_nn_map(const double *d_colors, size_t plane_stride, size_t n, const 
         HIP_CHECK(hipStreamSynchronize(s));
         for (int a = 0; a < 3; a++) { blo[a] = key_f64(got[a]); bhi[a] = key_f64(got[3 + a]); }
     }
-    NNGrid g;
-    g.G = n >= ((size_t)1 << 22) ? 64 : 32;
-    for (int a = 0; a < 3; a++) {
-        double r = bhi[a] - blo[a];
-        if (!(r > 0) || !std::isfinite(r)) r = 0;
-        g.lo[a] = blo[a];
-        g.cw[a] = r / g.G;
-        g.inv[a] = r > 0 ? g.G / r : 0.0;
-    }
+    const NNGrid g = nn_grid(blo, bhi, n >= ((size_t)1 << 22) ? 64 : 32);
     if (elem_bytes == 1) launch_nn_lut<unsigned char>(d_colors, plane_stride, n, d_pal, k, (unsigned char *)d_out, g, w, s);
     else if (elem_bytes == 4) launch_nn_lut<unsigned int>(d_colors, plane_stride, n, d_pal, k, (unsigned int *)d_out, g, w, s);
     else launch_nn_lut<unsigned long long>(d_colors, plane_stride, n, d_pal, k, (unsigned long long *)d_out, g, w, s);
@@ -1392,15 +1522,27 @@ __global__ __launch_bounds__(64) void k_dither_order(unsigned width, unsigned he
 // FRAMES (launch_dither_frames): the image is a stack of frames of n pixels each, `fruns` runs per frame, and spos is the table of
 // ONE frame: run b lies in frame b / fruns, whose ranks start at t(b / fruns * fruns) = frame * n, which is also where its pixels start
 // (a body shared by two kernels, not a flag on one: k_dither_streams keeps its argument list, so its code is what it was)
-template <int WHICH, bool FRAMES>
+// U8 (the remap entry): the pixels are interleaved 8-bit sRGB (px8, ch bytes each) instead of f64 planes, WHICH is
+// PAMD_SRGB_TO_REC2020, and the companding comes from the table of its 256 possible arguments b / 255.0 (as k_convert builds it for
+// 8-bit input: the same function of the same argument, hence the bits a conversion of the f64 value gives) -- no pow per pixel
+template <int WHICH, bool FRAMES, bool U8 = false>
 __device__ __forceinline__ void dither_streams_tile(const double *__restrict__ img, size_t plane_stride, const unsigned *__restrict__ spos, const DitherRuns R,
-                                                    double *__restrict__ sx, double *__restrict__ sy, double *__restrict__ sz, unsigned fruns) {
+                                                    double *__restrict__ sx, double *__restrict__ sy, double *__restrict__ sz, unsigned fruns,
+                                                    const unsigned char *__restrict__ px8 = nullptr, int ch = 3) {
     __shared__ unsigned long long t0[9];
     __shared__ double tile[3][8][257];
     const unsigned w = blockIdx.y, p0 = blockIdx.x * 256u, tid = threadIdx.x;
     if (tid < 9) { const unsigned b = 8u * w + tid; t0[tid] = b <= R.S ? R.t(b) : R.N; }
     if constexpr (WHICH != PAMD_COPY) pow_tables_to_lds();
     __syncthreads();
+    const double *glut = nullptr;
+    if constexpr (U8) {
+        static_assert(WHICH == PAMD_SRGB_TO_REC2020, "8-bit pixels are sRGB");
+        __shared__ double s_glut[256];
+        s_glut[tid] = dc::gamma_decode((double)tid / 255.0);             // (256 threads)
+        __syncthreads();
+        glut = s_glut;
+    }
     unsigned pix[8];
 #pragma unroll
     for (int i = 0; i < 8; i++) {                                    // run i of the tile: consecutive threads = consecutive ranks
@@ -1412,13 +1554,24 @@ __device__ __forceinline__ void dither_streams_tile(const double *__restrict__ i
         } else pix[i] = ok ? spos[t0[i] + p] : 0xFFFFFFFFu;
     }
     double v[8][3];
+    if constexpr (U8) {
 #pragma unroll
-    for (int i = 0; i < 8; i++)
+        for (int i = 0; i < 8; i++) {
+            unsigned b[3] = {0u, 0u, 0u};
+            if (pix[i] != 0xFFFFFFFFu) { const unsigned char *q = px8 + (size_t)pix[i] * (size_t)ch; b[0] = q[0]; b[1] = q[1]; b[2] = q[2]; }
+            v[i][0] = glut[b[0]]; v[i][1] = glut[b[1]]; v[i][2] = glut[b[2]];
+            dev_convert_linear<PAMD_SRGB_TO_REC2020>(v[i]);                  // rec2020.c:104-126 behind the companding
+            if (pix[i] == 0xFFFFFFFFu) { v[i][0] = 0.0; v[i][1] = 0.0; v[i][2] = 0.0; }
+        }
+    } else {
 #pragma unroll
-        for (int c = 0; c < 3; c++) v[i][c] = pix[i] != 0xFFFFFFFFu ? img[(size_t)c * plane_stride + pix[i]] : 0.0;
-    if constexpr (WHICH != PAMD_COPY) {
+        for (int i = 0; i < 8; i++)
 #pragma unroll
-        for (int i = 0; i < 8; i++) if (pix[i] != 0xFFFFFFFFu) dev_convert<WHICH>(v[i]);
+            for (int c = 0; c < 3; c++) v[i][c] = pix[i] != 0xFFFFFFFFu ? img[(size_t)c * plane_stride + pix[i]] : 0.0;
+        if constexpr (WHICH != PAMD_COPY) {
+#pragma unroll
+            for (int i = 0; i < 8; i++) if (pix[i] != 0xFFFFFFFFu) dev_convert<WHICH>(v[i]);
+        }
     }
 #pragma unroll
     for (int i = 0; i < 8; i++)
@@ -1443,6 +1596,16 @@ template <int WHICH>
 __global__ __launch_bounds__(256) void k_dither_streams_frames(const double *__restrict__ img, size_t plane_stride, const unsigned *__restrict__ spos, DitherRuns R,
                                                               double *__restrict__ sx, double *__restrict__ sy, double *__restrict__ sz, unsigned fruns) {
     dither_streams_tile<WHICH, true>(img, plane_stride, spos, R, sx, sy, sz, fruns);
+}
+
+// the same from interleaved 8-bit sRGB pixels (launch_dither_u8)
+__global__ __launch_bounds__(256) void k_dither_streams_u8(const unsigned char *__restrict__ px8, int ch, const unsigned *__restrict__ spos, DitherRuns R,
+                                                          double *__restrict__ sx, double *__restrict__ sy, double *__restrict__ sz) {
+    dither_streams_tile<PAMD_SRGB_TO_REC2020, false, true>(nullptr, 0, spos, R, sx, sy, sz, 0u, px8, ch);
+}
+__global__ __launch_bounds__(256) void k_dither_streams_frames_u8(const unsigned char *__restrict__ px8, int ch, const unsigned *__restrict__ spos, DitherRuns R,
+                                                                 double *__restrict__ sx, double *__restrict__ sy, double *__restrict__ sz, unsigned fruns) {
+    dither_streams_tile<PAMD_SRGB_TO_REC2020, true, true>(nullptr, 0, spos, R, sx, sy, sz, fruns, px8, ch);
 }
 
 // tile (pt, w): runs 64 w .. 64 w + 63, positions 64 pt .. 64 pt + 63 of the choices, back to the image's pixel order
@@ -2108,6 +2271,18 @@ int dither_solo_cap(int cap) { return g_dither_solo_cap.exchange(cap < 0 ? 4096 
 static std::atomic<int> g_dither_stall_passes{2};                    // passes without progress before one wavefront goes alone (tests: 0 = at once)
 int dither_stall_passes(int n) { return g_dither_stall_passes.exchange(n < 0 ? 2 : n); }
 
+// the sixteen weights of the error queue (riemersma.c: a geometric ramp from 1/16 to 1)
+static DitherWeights dither_weights() {
+    DitherWeights wts;
+    const double m = std::exp(std::log(16.0) / (16.0 - 1));
+    double v = 1;
+    for (int i = 0; i < 16; i++) { wts.w[i] = v / 16.0; v *= m; }
+    return wts;
+}
+// what the lane walk itself can take, whatever the knobs say: a run of 64 pixels in every frame, one tile row per 8 runs (grid.y),
+// the pruned search's palette sizes
+static bool dither_lanes_possible(size_t frames, size_t n, int k) { return frames > 0 && n >= 64 && frames <= (size_t)8 * 65535 && k >= 8 && k <= 256; }
+
 static int current_device() { int d = -1; (void)hipGetDevice(&d); return d; }
 static std::atomic<bool> g_dither_order_cache{true};
 void dither_order_cache(bool on) { g_dither_order_cache = on; }
@@ -2132,7 +2307,8 @@ static void dither_order(NNWork &w, size_t width, size_t height, hipStream_t s) 
 // frame starts (t(f S / frames) = f width height exactly), one table of width * height ranks, one set of launches
 static bool launch_dither_lanes(const double *d_img, size_t plane_stride, int which, size_t width, size_t height, const double *d_pal, const double *h_pal,
                                 int k, void *d_out, int elem_bytes, NNWork &w, const DitherConfig &cfg, const DitherWeights &wts, hipStream_t s,
-                                const unsigned *mpos, size_t mcount, size_t frames = 1) {
+                                const unsigned *mpos, size_t mcount, size_t frames = 1, const unsigned char *src8 = nullptr, int channels = 3) {
+    // src8 (launch_dither_u8; no mask): the pixels as interleaved 8-bit sRGB, `channels` bytes each, in place of d_img / which
     const size_t nframe = width * height;
     const size_t npix = mpos ? mcount : frames * nframe;
     DitherLanes a{};
@@ -2255,7 +2431,11 @@ static bool launch_dither_lanes(const double *d_img, size_t plane_stride, int wh
     const dim3 tiles((unsigned)ceil_div((size_t)a.R.Lmax, 64), (unsigned)nw), tiles8((unsigned)ceil_div((size_t)a.R.Lmax, 256), (unsigned)ceil_div(S, 8));
     if (!mpos) dither_order(w, width, height, s);
     const unsigned *sp = mpos ? mpos : (const unsigned *)w.dpos.p;
-    {
+    if (src8) {
+        KTIME("k_dither_gather_u8", s, (28.0 + channels) * npix);
+        if (a.fruns) hipLaunchKernelGGL(k_dither_streams_frames_u8, tiles8, 256, 0, s, src8, channels, sp, a.R, sx, sy, sz, a.fruns);
+        else hipLaunchKernelGGL(k_dither_streams_u8, tiles8, 256, 0, s, src8, channels, sp, a.R, sx, sy, sz);
+    } else {
         KTIME("k_dither_gather", s, 52.0 * npix);
 #define PAMD_DITHER_STREAMS(WHICH)                                                                                              \
         do {                                                                                                                   \
@@ -2403,10 +2583,7 @@ static void launch_dither_any(const double *d_img, size_t plane_stride, int whic
         const DitherConfig cfg = dither_cfg_snapshot();
         // layout: what the caller decided when it chose the pixels' form (the knobs may change between its look and this one)
         if (layout >= 0 ? layout != 0 : dither_lane_layout(npix, 1, k)) {
-            DitherWeights wts;
-            const double m = std::exp(std::log(16.0) / (16.0 - 1));
-            double v = 1;
-            for (int i = 0; i < 16; i++) { wts.w[i] = v / 16.0; v *= m; }
+            const DitherWeights wts = dither_weights();
             std::vector<double> hp;
             if (!h_pal) {
                 hp.resize(3 * (size_t)k);
@@ -2443,12 +2620,28 @@ void launch_dither(const double *d_img, size_t plane_stride, int which, size_t w
     launch_dither_any(d_img, plane_stride, which, width, height, d_pal, h_pal, k, d_out, elem_bytes, w, s, layout, nullptr, 0);
 }
 
+// The remap entry's dither from 8-bit sRGB pixels (frames images of width x height, channels bytes per pixel; palette in linear
+// Rec2020): the lane layout with the conversion on the gather, no f64 image.  The caller has checked that the lane layout applies
+// (dither_lane_layout / dither_frames_lane_layout).  false: the verification stalled for good (launch_dither_lanes) and nothing
+// usable was written -- the caller converts the image and takes launch_dither / launch_dither_frames.
+bool launch_dither_u8(const unsigned char *d_px, int channels, size_t frames, size_t width, size_t height, const double *d_pal, const double *h_pal,
+                      int k, void *d_out, int elem_bytes, NNWork &w, hipStream_t s) {
+    const size_t n = width * height, N = frames * n;
+    if (frames == 0 || n == 0 || N / n != frames || N > kDitherFramesMaxPixels) throw HipError("patolette_amd: the dither takes up to 2^31 pixels in all");
+    if (elem_bytes != 1 && elem_bytes != 4 && elem_bytes != 8) throw HipError("patolette_amd: map element size must be 1, 4 or 8");
+    if (channels != 3 && channels != 4) throw HipError("patolette_amd: 8-bit pixels have 3 or 4 channels");
+    if (!dither_lanes_possible(frames, n, k)) throw HipError("patolette_amd: this image cannot take the lane layout");
+    const DitherConfig cfg = dither_cfg_snapshot();
+    const DitherWeights wts = dither_weights();
+    return launch_dither_lanes(nullptr, 0, PAMD_SRGB_TO_REC2020, width, height, d_pal, h_pal, k, d_out, elem_bytes, w, cfg, wts, s, nullptr, 0, frames, d_px, channels);
+}
+
 // ---- frames of one size, one palette (patolette_amd_frames_u8) ----
 // What the frame-batched lane walk needs besides dither_lane_layout on all the pixels: a run of 64 pixels at least in every frame,
 // and one tile row per 8 runs (grid.y)
 bool dither_frames_lane_layout(size_t frames, size_t width, size_t height, int k) {
     const size_t n = width * height;
-    return frames > 0 && n >= 64 && frames <= (size_t)8 * 65535 && dither_lane_layout(frames * n, 1, k);
+    return dither_lanes_possible(frames, n, k) && dither_lane_layout(frames * n, 1, k);
 }
 
 // Every frame dithered along its own curve from the empty queue.  The lane layout walks all frames side by side (launch_dither_lanes
@@ -2463,12 +2656,9 @@ void launch_dither_frames(const double *d_img, size_t plane_stride, int which, s
     size_t lane_passes = 0;
     if (layout >= 0 ? layout != 0 : dither_frames_lane_layout(frames, width, height, k)) {
         // (layout: what the caller decided when it chose the pixels' form; the knobs may have changed since, the hard limits have not)
-        if (!(n >= 64 && frames <= (size_t)8 * 65535 && k >= 8 && k <= 256)) throw HipError("patolette_amd: these frames cannot take the lane layout");
+        if (!dither_lanes_possible(frames, n, k)) throw HipError("patolette_amd: these frames cannot take the lane layout");
         const DitherConfig cfg = dither_cfg_snapshot();
-        DitherWeights wts;
-        const double m = std::exp(std::log(16.0) / (16.0 - 1));
-        double v = 1;
-        for (int i = 0; i < 16; i++) { wts.w[i] = v / 16.0; v *= m; }
+        const DitherWeights wts = dither_weights();
         std::vector<double> hp;
         if (!h_pal) {
             hp.resize(3 * (size_t)k);
@@ -2549,12 +2739,7 @@ static void launch_dither_waves(const double *d_img, size_t plane_stride, size_t
         gtab = w.dtab.p;
         lds = (size_t)3 * 128 * sizeof(double) + 128 * sizeof(unsigned int);
     }
-    DitherWeights wts;
-    {
-        const double m = std::exp(std::log(16.0) / (16.0 - 1));
-        double v = 1;
-        for (int i = 0; i < 16; i++) { wts.w[i] = v / 16.0; v *= m; }
-    }
+    const DitherWeights wts = dither_weights();
     // Runs: two wavefronts per SIMD fill the issue slots of the chip (one chain alone uses ~2/3 of its SIMD's); never shorter than
     // the warm-up -- below that the speculative steps outnumber the useful ones.
     const size_t npix = mpos ? mcount : width * height;

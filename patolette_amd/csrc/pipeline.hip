@@ -2664,6 +2664,22 @@ static bool upload_u8(Engine &E, const unsigned char *pixels, int channels, size
     return true;
 }
 
+// the device's index map (elements of me: 1 or 4 bytes) into a host buffer with elements of map_elem_out (1, 2, 4 or 8)
+static void download_map(const void *d_map, int me, size_t N, void *map_out, int map_elem_out) {
+    if (map_elem_out == me) { HIP_CHECK(hipMemcpy(map_out, d_map, N * (size_t)me, hipMemcpyDeviceToHost)); return; }
+    std::vector<unsigned char> tmp(N * (size_t)me);
+    HIP_CHECK(hipMemcpy(tmp.data(), d_map, tmp.size(), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < N; i++) {
+        const size_t v = me == 1 ? (size_t)tmp[i] : (size_t)reinterpret_cast<unsigned int *>(tmp.data())[i];
+        switch (map_elem_out) {
+            case 1: ((unsigned char *)map_out)[i] = (unsigned char)v; break;
+            case 2: ((unsigned short *)map_out)[i] = (unsigned short)v; break;
+            case 4: ((unsigned int *)map_out)[i] = (unsigned int)v; break;
+            default: ((size_t *)map_out)[i] = v; break;
+        }
+    }
+}
+
 // 8-bit adaptor around the path: interleaved u8 in; f64 palette, u8 palette, index map and
 // reconstructed u8 image out.  `pixels`, `d_map_out`, `d_quant_out` are device pointers when `on_device`.
 static void run_u8(Engine &E, size_t width, size_t height, const unsigned char *pixels, int channels, const double *weights,
@@ -2736,26 +2752,107 @@ static void run_u8(Engine &E, size_t width, size_t height, const unsigned char *
         }
         if (map_out && d_map != map_out) {
             if (on_device || map_on_device) throw HipError("patolette_amd: device map_elem_bytes must be 1 for K <= 256, else 4");
-            if (map_elem_out == me) HIP_CHECK(hipMemcpy(map_out, d_map, N * (size_t)me, hipMemcpyDeviceToHost));
-            else {
-                std::vector<unsigned char> tmp(N * (size_t)me);
-                HIP_CHECK(hipMemcpy(tmp.data(), d_map, tmp.size(), hipMemcpyDeviceToHost));
-                for (size_t i = 0; i < N; i++) {
-                    const size_t v = me == 1 ? (size_t)tmp[i] : (size_t)reinterpret_cast<unsigned int *>(tmp.data())[i];
-                    switch (map_elem_out) {
-                        case 1: ((unsigned char *)map_out)[i] = (unsigned char)v; break;
-                        case 2: ((unsigned short *)map_out)[i] = (unsigned short)v; break;
-                        case 4: ((unsigned int *)map_out)[i] = (unsigned int)v; break;
-                        default: ((size_t *)map_out)[i] = v; break;
-                    }
-                }
-            }
+            download_map(d_map, me, N, map_out, map_elem_out);
         }
         E.sync();
     }
     E.stats.ms_upload = up;
     E.stats.ms_download = now_ms() - t0;
     E.stats.ms_total += up + E.stats.ms_download;
+}
+
+// --------------------------------------------------------------------------------------------
+// remap: 8-bit pixels onto a palette the caller gives (include/patolette_amd.h, patolette_amd_remap_u8)
+// --------------------------------------------------------------------------------------------
+// TESTS ONLY (patolette_amd_debug_remap_two_pass): every remap converts the image into f64 planes first
+static std::atomic<int> g_remap_two_pass{0};
+
+// pal: the palette's k rows, planar (k,3) f64 sRGB; p8: the bytes `quantized` is made of, me-indexed rows (K8 >= k of them: the palette as
+// given, dropped rows included).  `pixels`, `map_out`, `quant_out` are device pointers when `on_device`.
+// Nearest, two-pass: pixels -> ICtCp planes (k_convert_u8, whose statistics bound the grid) -> launch_nn_map.  Nearest, fused (where the
+// LDS-table kernel runs): launch_nn_map_u8 converts in registers.  Dither, two-pass: pixels -> linear
+// Rec2020 planes -> launch_dither / launch_dither_frames.  Dither, fused (where the lane layout runs): launch_dither_u8 gathers the
+// bytes along the curve and converts them there; no f64 image is written.
+static void run_remap(Engine &E, size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels, std::vector<double> pal,
+                      size_t k, const std::vector<unsigned char> &p8, size_t K8, bool dither, void *map_out, int map_elem_out,
+                      unsigned char *quant_out, bool on_device) {
+    const size_t n = width * height, N = frames * n;
+    hipStream_t s = E.stream;
+    const double t_start = now_ms();
+    WsGuard wg(&E.stream, &E.stream2);
+    E.stats = patolette_amd__Stats{};
+    const int me = map_elem_for(K8);
+    const bool want = map_out || quant_out;
+    const bool lanes = dither && (frames > 1 ? dither_frames_lane_layout(frames, width, height, (int)k) : dither_lane_layout(width, height, (int)k));
+    const bool fused = !g_remap_two_pass.load(std::memory_order_relaxed) && (dither ? lanes : nn_map_u8_applies(N, (int)k));
+    // the workspace, before anything is enqueued
+    if (!on_device) E.src8.reserve(N * (size_t)channels);
+    E.dpal.reserve(3 * k); E.h_pal.reserve(3 * k);
+    if (want && !fused) { E.cvt.reserve(3 * N); E.cstats.reserve(1); E.h_cstats.reserve(1); }
+    void *d_map = nullptr;
+    if (want) {
+        if (on_device && map_out && map_elem_out == me) d_map = map_out;
+        else { E.dmap.reserve(N * (size_t)me); d_map = E.dmap.p; }
+        if (quant_out) { E.pal8.reserve(3 * K8); if (!on_device) E.quant8.reserve(3 * N); }
+    }
+    if (on_device && map_out && d_map != map_out) throw HipError("patolette_amd: device map_elem_bytes must be 1 for up to 256 palette rows, else 4");
+    const unsigned char *d_px = pixels;
+    if (!on_device) {
+        HIP_CHECK(hipMemcpyAsync(E.src8.p, pixels, N * (size_t)channels, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        d_px = E.src8.p;
+    }
+    E.stats.ms_upload = now_ms() - t_start;
+    // the palette into the space its map compares in (patolette.c:268-299 for colour space sRGB, resp. :300-324)
+    double t0 = now_ms();
+    palette_rows(pal, k, dither ? hm::color::srgb_to_rec2020 : hm::color::srgb_to_ictcp);
+    E.map_palette = pal;
+    const bool touched = !(dither && std::max(width, height) <= 1);                   // 1x1 dither visits nothing (riemersma.c:452-456)
+    if (want) {
+        std::memcpy(E.h_pal.p, pal.data(), 3 * k * sizeof(double));
+        HIP_CHECK(hipMemcpyAsync(E.dpal.p, E.h_pal.p, 3 * k * sizeof(double), hipMemcpyHostToDevice, s));
+        if (!dither && fused) {
+            HIP_CHECK(hipStreamSynchronize(s));                                       // (the map kernels' tables are reserved on an idle stream)
+            launch_nn_map_u8(d_px, channels, N, E.dpal.p, (int)k, d_map, me, E.nn, s);
+        } else if (!dither) {
+            launch_convert_u8(PAMD_SRGB_TO_ICTCP, d_px, channels, E.cvt.p, N, E.cstats.p, s);
+            const Bounds b = read_bounds(E, false);                                   // (waits: the map kernels' tables are reserved on an idle stream)
+            launch_nn_map(E.cvt.p, N, N, E.dpal.p, (int)k, d_map, me, b.lo, b.hi, E.nn, s);
+        } else {
+            bool done = false;
+            if (fused) {
+                HIP_CHECK(hipStreamSynchronize(s));
+                done = launch_dither_u8(d_px, channels, frames, width, height, E.dpal.p, pal.data(), (int)k, d_map, me, E.nn, s);
+                // the lane walk's verification stalled beyond patolette_amd_debug_dither_solo_cap: the planes after all, for the wavefront layout
+                if (!done) { HIP_CHECK(hipStreamSynchronize(s)); E.cvt.reserve(3 * N); }
+            }
+            if (!done) {
+                const int layout = (lanes && !fused) ? 1 : 0;                         // (after a stalled lane walk: not the same walk again)
+                launch_convert_u8(PAMD_SRGB_TO_REC2020, d_px, channels, E.cvt.p, N, nullptr, s);
+                HIP_CHECK(hipStreamSynchronize(s));
+                if (frames > 1) launch_dither_frames(E.cvt.p, N, PAMD_COPY, frames, width, height, E.dpal.p, pal.data(), (int)k, d_map, me, E.nn, s, layout);
+                else launch_dither(E.cvt.p, N, PAMD_COPY, width, height, E.dpal.p, pal.data(), (int)k, d_map, me, E.nn, s, layout);
+            }
+            E.stats.dither_segments = E.nn.dither_segments; E.stats.dither_repairs = E.nn.dither_repairs; E.stats.dither_rounds = E.nn.dither_rounds;
+            E.stats.dither_through = E.nn.dither_through; E.stats.dither_jumps = E.nn.dither_jumps; E.stats.dither_solo = E.nn.dither_solo;
+        }
+        E.sync();
+    }
+    E.stats.ms_map = now_ms() - t0;
+    t0 = now_ms();
+    if (want && touched) {
+        if (quant_out) {
+            HIP_CHECK(hipMemcpyAsync(E.pal8.p, p8.data(), 3 * K8, hipMemcpyHostToDevice, s));
+            unsigned char *d_q = on_device ? quant_out : E.quant8.p;
+            launch_reconstruct(d_map, me, N, E.pal8.p, (int)K8, d_q, s);
+            if (!on_device) HIP_CHECK(hipMemcpyAsync(quant_out, d_q, 3 * N, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+        }
+        if (map_out && d_map != map_out) download_map(d_map, me, N, map_out, map_elem_out);
+        E.sync();
+    }
+    E.stats.ms_download = now_ms() - t0;
+    E.stats.ms_total = now_ms() - t_start;
 }
 
 // The RGBA entry (include/patolette_amd.h, patolette_amd_rgba): the opaque pixels (alpha >= thr) are compacted in row-scan order and
@@ -3215,6 +3312,59 @@ static void frames_entry(bool on_device, size_t frames, size_t width, size_t hei
     }
 }
 
+// 8-bit pixels onto the caller's palette (include/patolette_amd.h): the arguments, then run_remap
+static void remap_entry(bool on_device, size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels, const double *palette,
+                        const unsigned char *palette_u8, size_t palette_rows, int dither, void *palette_map, int map_elem_bytes,
+                        unsigned char *quantized, int *exit_code) {
+    auto fail = [&](int code, const char *msg) {
+        try { engine().last_error = msg; } catch (...) {}
+        fprintf(stderr, "%s\n", msg);
+        *exit_code = code;
+    };
+    *exit_code = frames == 0 ? -2 : validate(width, height, 1);
+    if (*exit_code != 0) return;
+    const size_t n = width * height;
+    if (frames > (dither ? kDitherFramesMaxPixels : (size_t)40000 * 40000) / n)
+        return fail(-4, dither ? "patolette_amd_remap: frames * width * height exceeds 2^31 pixels (the dither numbers pixels with 32 bits)"
+                               : "patolette_amd_remap: frames * width * height is too big");
+    if ((palette != nullptr) == (palette_u8 != nullptr)) return fail(-1, "patolette_amd_remap: pass exactly one of palette and palette_u8");
+    if (palette_rows < 1 || palette_rows > ((size_t)1 << 31)) return fail(-1, "patolette_amd_remap: the palette needs at least one row");
+    if (validate_u8(palette_rows, channels, palette_map, map_elem_bytes) != 0)
+        return fail(-1, "patolette_amd_remap: bad channels / map_elem_bytes (1, 2, 4 or 8, able to hold palette_rows - 1)");
+    if (!pixels) return fail(-1, "patolette_amd_remap: no pixels");
+    // the rows, planar (k,3) f64 sRGB, and the bytes `quantized` is made of
+    size_t k = palette_rows;
+    std::vector<double> pal;
+    std::vector<unsigned char> p8(3 * palette_rows);
+    if (palette_u8) {
+        pal.resize(3 * k);
+        for (size_t i = 0; i < k; i++) for (int c = 0; c < 3; c++) pal[(size_t)c * k + i] = (double)palette_u8[3 * i + c] / 255.0;
+        std::memcpy(p8.data(), palette_u8, 3 * palette_rows);
+    } else {
+        auto row_is = [&](size_t i, double v) { return palette[i] == v && palette[palette_rows + i] == v && palette[2 * palette_rows + i] == v; };
+        while (k > 0 && row_is(k - 1, -1.0)) k--;                          // the reference's fill of unused rows (patolette.c:327-336)
+        if (k == 0) return fail(-1, "patolette_amd_remap: every palette row is the unused-row fill (-1, -1, -1)");
+        pal.resize(3 * k);
+        for (size_t i = 0; i < k; i++) for (int c = 0; c < 3; c++) {
+            const double v = palette[palette_rows * (size_t)c + i];
+            if (!std::isfinite(v)) return fail(-1, "patolette_amd_remap: the palette holds a value that is not finite");
+            pal[(size_t)c * k + i] = v;
+        }
+        palette_to_u8(palette, palette_rows, p8.data());
+    }
+    try {
+        Engine &E = engine();
+        E.init();
+        run_remap(E, frames, width, height, pixels, channels, std::move(pal), k, p8, palette_rows, dither != 0, palette_map, map_elem_bytes, quantized,
+                  on_device);
+        *exit_code = 0;
+    } catch (const std::exception &ex) {
+        engine().last_error = ex.what();
+        fprintf(stderr, "patolette: %s\n", ex.what());
+        *exit_code = -1;
+    }
+}
+
 static void rgba_entry(bool on_device, size_t width, size_t height, const unsigned char *pixels, int alpha_threshold, const double *weights,
                        double tile_size, size_t palette_size, const patolette__QuantizationOptions *options, double *palette,
                        unsigned char *palette_rgba, void *palette_map, int map_elem_bytes, unsigned char *quantized, int *transparent_index,
@@ -3261,6 +3411,22 @@ void patolette_amd_rgba_device(size_t width, size_t height, const unsigned char 
     rgba_entry(true, width, height, d_pixels, alpha_threshold, d_weights, tile_size, palette_size, options, palette, palette_rgba,
                d_palette_map, map_elem_bytes, d_quantized, transparent_index, exit_code);
 }
+
+void patolette_amd_remap_u8(size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels, const double *palette,
+                            const unsigned char *palette_u8, size_t palette_rows, int dither, void *palette_map, int map_elem_bytes,
+                            unsigned char *quantized, int *exit_code) {
+    remap_entry(false, frames, width, height, pixels, channels, palette, palette_u8, palette_rows, dither, palette_map, map_elem_bytes, quantized,
+                exit_code);
+}
+
+void patolette_amd_remap_u8_device(size_t frames, size_t width, size_t height, const unsigned char *d_pixels, int channels, const double *palette,
+                                   const unsigned char *palette_u8, size_t palette_rows, int dither, void *d_palette_map, int map_elem_bytes,
+                                   unsigned char *d_quantized, int *exit_code) {
+    remap_entry(true, frames, width, height, d_pixels, channels, palette, palette_u8, palette_rows, dither, d_palette_map, map_elem_bytes,
+                d_quantized, exit_code);
+}
+
+int patolette_amd_debug_remap_two_pass(int on) { return g_remap_two_pass.exchange(on ? 1 : 0); }
 
 void patolette_amd_frames_u8(size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels, const double *weights,
                              double tile_size, size_t palette_size, const patolette__QuantizationOptions *options, double *palette,
