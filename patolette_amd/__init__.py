@@ -133,6 +133,115 @@ def saliency_weights(width, height, colors, tile_size=512):
     return out
 
 
+# ---- the 8-bit entries: each serves numpy arrays (host entry) and torch CUDA tensors (the `_device` entry: the image, the index map and
+# the quantized image stay in HBM, the palettes are numpy arrays either way).  torch is only used to allocate those outputs and to
+# order the call after the producer of the image.  Import torch BEFORE patolette_amd in such a process: both link a HIP runtime with
+# the same SONAME and torch does not initialise on the one this library would otherwise load first.
+
+def _is_cuda(a):
+    return hasattr(a, "data_ptr") and getattr(a, "is_cuda", False)
+
+
+def _u8_pixels(a, ndims, channels, wanted):
+    """`a` as contiguous uint8 pixels -> (pixels, shape as ints, torch device or None for a numpy array); a ValueError asking for
+    `wanted` (%s: "array" or "tensor") unless it is uint8 with len(shape) in ndims and shape[-1] in channels."""
+    dev = a.device if _is_cuda(a) else None
+    if dev is not None:
+        import torch
+        px, is_u8 = a.contiguous(), a.dtype == torch.uint8
+    else:
+        px = np.ascontiguousarray(a)
+        is_u8 = px.dtype == np.uint8
+    shape = tuple(int(v) for v in px.shape)
+    if not is_u8 or len(shape) not in ndims or shape[-1] not in channels:
+        raise ValueError(wanted % ("tensor" if dev is not None else "array"))
+    return px, shape, dev
+
+
+def _weights(weights, n, dev, what="width*height"):
+    """None, or the weights as n contiguous float64 values where the pixels are (dev: see _u8_pixels)."""
+    if weights is None:
+        return None
+    if dev is not None:
+        import torch
+        w = torch.as_tensor(weights, dtype=torch.float64, device=dev).reshape(-1).contiguous()
+    else:
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+    if len(w) != n:
+        raise ValueError("weights must hold %s values" % what)
+    return w
+
+
+def _options(dither, palette_only, color_space, kmeans_niter, kmeans_max_samples):
+    return _native.QuantizationOptions(bool(dither), bool(palette_only), int(color_space), int(kmeans_niter), int(kmeans_max_samples),
+                                       False)
+
+
+def _map_dtype(rows):
+    return np.uint8 if rows <= 256 else (np.uint16 if rows <= 65536 else np.uint32)
+
+
+def _outputs(shape, rows, channels, dev, want_map=True, want_quantized=True):
+    """Zeroed (index map of `shape`, bytes per map element, quantized image of shape + (channels,)) next to the pixels; None for
+    what is not wanted.  The map's elements: numpy uint8 / uint16 / uint32 by the palette's rows; torch uint8 / int32, as the
+    kernels write them (the device entries convert no map)."""
+    if dev is None:
+        pmap = np.zeros(shape, dtype=_map_dtype(rows)) if want_map else None
+        quant = np.zeros(shape + (channels,), dtype=np.uint8) if want_quantized else None
+        return pmap, np.dtype(_map_dtype(rows)).itemsize, quant
+    import torch
+    pmap = torch.zeros(shape, dtype=torch.uint8 if rows <= 256 else torch.int32, device=dev) if want_map else None
+    quant = torch.zeros(shape + (channels,), dtype=torch.uint8, device=dev) if want_quantized else None
+    return pmap, 1 if rows <= 256 else 4, quant
+
+
+def _vp(a):
+    """The address of a numpy array or a torch tensor as the C ABI types it (double* for float64 arrays, else void*); None for
+    None and for empty ones."""
+    if a is None:
+        return None
+    if hasattr(a, "data_ptr"):
+        return C.c_void_p(a.data_ptr()) if a.numel() > 0 else None
+    if a.dtype == np.float64:
+        return _dp(a)
+    return a.ctypes.data_as(C.c_void_p) if a.size > 0 else None
+
+
+def _call(name, dev, *args):
+    """The C entry `name` for host arrays; `name`_device for a torch device, selected and with its current stream drained first
+    (the library runs on its own stream)."""
+    L = _native.lib()
+    if dev is None:
+        return getattr(L, name)(*args)
+    import torch
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream().synchronize()
+        return getattr(L, name + "_device")(*args)
+
+
+def _message(code):
+    return _native.lib().get_patolette_exit_code_info_message(code).decode('UTF-8')
+
+
+def _u8_result(code, palette_u8, pmap, quant, palette):
+    message = _message(code)
+    _raise_saliency(code, message)
+    if code != 0:
+        return (False, None, None, None, None, message)
+    return (True, palette_u8, pmap, quant, palette, message)
+
+
+def _quantize_stack(name, lead, px, shape, dev, w, tile_size, palette_size, opts, palette, want_quantized):
+    """patolette_amd_u8 (lead = ()) and patolette_amd_frames_u8 (lead = (frames,)) on pixels of `shape` = (..., H, W, channels)."""
+    height, width, channels = shape[-3:]
+    palette_u8 = np.zeros((max(palette_size, 0), 3), dtype=np.uint8)
+    pmap, map_elem, quant = _outputs(shape[:-1], palette_size, 3, dev, not opts.palette_only, want_quantized and not opts.palette_only)
+    code = C.c_int(0)
+    _call(name, dev, *lead, width, height, _vp(px), channels, _vp(w), float(tile_size), palette_size, C.byref(opts), _vp(palette),
+          _vp(palette_u8), _vp(pmap), map_elem, _vp(quant), C.byref(code))
+    return _u8_result(code.value, palette_u8, pmap, quant, palette)
+
+
 def quantize_u8(image, palette_size, dither=True, palette_only=False, color_space=ColorSpace_ICtCp, tile_size=512,
                 kmeans_niter=32, kmeans_max_samples=512 ** 2, weights=None, want_quantized=True):
     """8-bit adaptor (additive): `image` is an (H, W, 3|4) uint8 sRGB array as an image
@@ -142,78 +251,12 @@ def quantize_u8(image, palette_size, dither=True, palette_only=False, color_spac
 
     Returns (success, palette_u8 (K,3) uint8, palette_map (H,W) uint8|uint16|uint32 or None,
     quantized (H,W,3) uint8 or None, palette (K,3) float64 as `quantize` returns it, message)."""
-    if hasattr(image, "data_ptr") and getattr(image, "is_cuda", False):
-        return _quantize_u8_torch(image, palette_size, dither, palette_only, color_space, tile_size, kmeans_niter,
-                                  kmeans_max_samples, weights, want_quantized)
-    img = np.ascontiguousarray(image)
-    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] not in (3, 4):
-        raise ValueError("image must be an (H, W, 3|4) uint8 array")
-    height, width, channels = img.shape
-    n = width * height
-    w = None
-    if weights is not None:
-        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
-        if w.size != n:
-            raise ValueError("weights must hold width*height values")
-    opts = _native.QuantizationOptions(bool(dither), bool(palette_only), int(color_space), int(kmeans_niter),
-                                       int(kmeans_max_samples), False)
+    px, shape, dev = _u8_pixels(image, (3,), (3, 4), "image must be an (H, W, 3|4) uint8 %s")
+    # (unlike its siblings: no tile_size < 0 check -- a negative one derives no weights -- and the palette's rows are not clamped)
+    w = _weights(weights, shape[0] * shape[1], dev)
     palette = np.zeros((palette_size, 3), dtype=np.float64, order='F')
-    palette_u8 = np.zeros((max(palette_size, 0), 3), dtype=np.uint8)
-    map_dtype = np.uint8 if palette_size <= 256 else (np.uint16 if palette_size <= 65536 else np.uint32)
-    pmap = None if palette_only else np.zeros((height, width), dtype=map_dtype)
-    quant = np.zeros((height, width, 3), dtype=np.uint8) if (want_quantized and not palette_only) else None
-    code = C.c_int(0)
-    L = _native.lib()
-    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size > 0 else None   # noqa: E731
-    L.patolette_amd_u8(width, height, vp(img), channels, _dp(w), float(tile_size), palette_size, C.byref(opts), _dp(palette),
-                       vp(palette_u8), vp(pmap), np.dtype(map_dtype).itemsize, vp(quant), C.byref(code))
-    message = L.get_patolette_exit_code_info_message(code.value).decode('UTF-8')
-    _raise_saliency(code.value, message)
-    if code.value != 0:
-        return (False, None, None, None, None, message)
-    return (True, palette_u8, pmap, quant, palette, message)
-
-
-def _quantize_u8_torch(image, palette_size, dither, palette_only, color_space, tile_size, kmeans_niter, kmeans_max_samples,
-                       weights, want_quantized):
-    """`quantize_u8` for a torch CUDA uint8 tensor (H, W, 3|4): the image, the index map (uint8 for K <= 256, else int32)
-    and the reconstructed image stay in HBM (`patolette_amd_u8_device`); the palettes come back as numpy arrays.
-    torch is only used to allocate the outputs and to order this call after the producer of `image`.
-    Import torch BEFORE patolette_amd in such a process: both link a HIP runtime with the same SONAME and torch does not
-    initialise on the one this library would otherwise load first."""
-    import torch
-    if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] not in (3, 4):
-        raise ValueError("image must be an (H, W, 3|4) uint8 tensor")
-    img = image.contiguous()
-    height, width, channels = (int(v) for v in img.shape)
-    n = width * height
-    dev = img.device
-    w = None
-    if weights is not None:
-        w = torch.as_tensor(weights, dtype=torch.float64, device=dev).reshape(-1).contiguous()
-        if w.numel() != n:
-            raise ValueError("weights must hold width*height values")
-    opts = _native.QuantizationOptions(bool(dither), bool(palette_only), int(color_space), int(kmeans_niter),
-                                       int(kmeans_max_samples), False)
-    palette = np.zeros((palette_size, 3), dtype=np.float64, order='F')
-    palette_u8 = np.zeros((max(palette_size, 0), 3), dtype=np.uint8)
-    me = 1 if palette_size <= 256 else 4
-    pmap = None if palette_only else torch.zeros((height, width), dtype=torch.uint8 if me == 1 else torch.int32, device=dev)
-    quant = torch.zeros((height, width, 3), dtype=torch.uint8, device=dev) if (want_quantized and not palette_only) else None
-    code = C.c_int(0)
-    L = _native.lib()
-    with torch.cuda.device(dev):
-        torch.cuda.current_stream().synchronize()          # the library runs on its own stream
-        L.patolette_amd_u8_device(width, height, C.c_void_p(img.data_ptr()), channels,
-                                  C.c_void_p(w.data_ptr()) if w is not None else None, float(tile_size), palette_size,
-                                  C.byref(opts), _dp(palette), palette_u8.ctypes.data_as(C.c_void_p),
-                                  C.c_void_p(pmap.data_ptr()) if pmap is not None else None, me,
-                                  C.c_void_p(quant.data_ptr()) if quant is not None else None, C.byref(code))
-    message = L.get_patolette_exit_code_info_message(code.value).decode('UTF-8')
-    _raise_saliency(code.value, message)
-    if code.value != 0:
-        return (False, None, None, None, None, message)
-    return (True, palette_u8, pmap, quant, palette, message)
+    return _quantize_stack("patolette_amd_u8", (), px, shape, dev, w, tile_size, palette_size,
+                           _options(dither, palette_only, color_space, kmeans_niter, kmeans_max_samples), palette, want_quantized)
 
 
 def quantize_frames(frames, palette_size, dither=True, palette_only=False, color_space=ColorSpace_ICtCp, tile_size=512,
@@ -233,81 +276,13 @@ def quantize_frames(frames, palette_size, dither=True, palette_only=False, color
 
     Returns (success, palette_u8 (K,3) uint8, maps (F,H,W) uint8|uint16|uint32 or None, quantized (F,H,W,3) uint8 or None
     (= palette_u8[maps]), palette (K,3) float64 as `quantize` returns it, message)."""
-    if hasattr(frames, "data_ptr") and getattr(frames, "is_cuda", False):
-        return _quantize_frames_torch(frames, palette_size, dither, palette_only, color_space, tile_size, kmeans_niter,
-                                      kmeans_max_samples, weights, want_quantized)
-    if not isinstance(frames, np.ndarray):
-        frames = np.asarray(frames)
-    if frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[3] not in (3, 4):
-        raise ValueError("frames must be an (F, H, W, 3|4) uint8 array")
+    px, shape, dev = _u8_pixels(frames, (4,), (3, 4), "frames must be an (F, H, W, 3|4) uint8 %s")
     if tile_size < 0:
         raise ValueError(bad_tile_size)
-    img = np.ascontiguousarray(frames)
-    count, height, width, channels = img.shape
-    n = count * width * height
-    w = None
-    if weights is not None:
-        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
-        if w.size != n:
-            raise ValueError("weights must hold frames*width*height values")
-    opts = _native.QuantizationOptions(bool(dither), bool(palette_only), int(color_space), int(kmeans_niter),
-                                       int(kmeans_max_samples), False)
+    w = _weights(weights, shape[0] * shape[1] * shape[2], dev, "frames*width*height")
     palette = np.zeros((max(palette_size, 0), 3), dtype=np.float64, order='F')
-    palette_u8 = np.zeros((max(palette_size, 0), 3), dtype=np.uint8)
-    map_dtype = np.uint8 if palette_size <= 256 else (np.uint16 if palette_size <= 65536 else np.uint32)
-    maps = None if palette_only else np.zeros((count, height, width), dtype=map_dtype)
-    quant = np.zeros((count, height, width, 3), dtype=np.uint8) if (want_quantized and not palette_only) else None
-    code = C.c_int(0)
-    L = _native.lib()
-    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size > 0 else None   # noqa: E731
-    L.patolette_amd_frames_u8(count, width, height, vp(img), channels, _dp(w), float(tile_size), palette_size, C.byref(opts),
-                              _dp(palette), vp(palette_u8), vp(maps), np.dtype(map_dtype).itemsize, vp(quant), C.byref(code))
-    message = L.get_patolette_exit_code_info_message(code.value).decode('UTF-8')
-    _raise_saliency(code.value, message)
-    if code.value != 0:
-        return (False, None, None, None, None, message)
-    return (True, palette_u8, maps, quant, palette, message)
-
-
-def _quantize_frames_torch(frames, palette_size, dither, palette_only, color_space, tile_size, kmeans_niter, kmeans_max_samples,
-                           weights, want_quantized):
-    """`quantize_frames` for a torch CUDA uint8 tensor (F, H, W, 3|4) through `patolette_amd_frames_u8_device`, as
-    `_quantize_u8_torch`: the maps (uint8 for K <= 256, else int32) and the quantized frames stay in HBM."""
-    import torch
-    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] not in (3, 4):
-        raise ValueError("frames must be an (F, H, W, 3|4) uint8 tensor")
-    if tile_size < 0:
-        raise ValueError(bad_tile_size)
-    img = frames.contiguous()
-    count, height, width, channels = (int(v) for v in img.shape)
-    n = count * width * height
-    dev = img.device
-    w = None
-    if weights is not None:
-        w = torch.as_tensor(weights, dtype=torch.float64, device=dev).reshape(-1).contiguous()
-        if w.numel() != n:
-            raise ValueError("weights must hold frames*width*height values")
-    opts = _native.QuantizationOptions(bool(dither), bool(palette_only), int(color_space), int(kmeans_niter),
-                                       int(kmeans_max_samples), False)
-    palette = np.zeros((max(palette_size, 0), 3), dtype=np.float64, order='F')
-    palette_u8 = np.zeros((max(palette_size, 0), 3), dtype=np.uint8)
-    me = 1 if palette_size <= 256 else 4
-    maps = None if palette_only else torch.zeros((count, height, width), dtype=torch.uint8 if me == 1 else torch.int32, device=dev)
-    quant = torch.zeros((count, height, width, 3), dtype=torch.uint8, device=dev) if (want_quantized and not palette_only) else None
-    code = C.c_int(0)
-    L = _native.lib()
-    with torch.cuda.device(dev):
-        torch.cuda.current_stream().synchronize()          # the library runs on its own stream
-        L.patolette_amd_frames_u8_device(count, width, height, C.c_void_p(img.data_ptr()) if n else None, channels,
-                                         C.c_void_p(w.data_ptr()) if w is not None else None, float(tile_size), palette_size,
-                                         C.byref(opts), _dp(palette), palette_u8.ctypes.data_as(C.c_void_p) if palette_u8.size else None,
-                                         C.c_void_p(maps.data_ptr()) if maps is not None and n else None, me,
-                                         C.c_void_p(quant.data_ptr()) if quant is not None and n else None, C.byref(code))
-    message = L.get_patolette_exit_code_info_message(code.value).decode('UTF-8')
-    _raise_saliency(code.value, message)
-    if code.value != 0:
-        return (False, None, None, None, None, message)
-    return (True, palette_u8, maps, quant, palette, message)
+    return _quantize_stack("patolette_amd_frames_u8", shape[:1], px, shape, dev, w, tile_size, palette_size,
+                           _options(dither, palette_only, color_space, kmeans_niter, kmeans_max_samples), palette, want_quantized)
 
 
 def _remap_palette(palette):
@@ -320,15 +295,6 @@ def _remap_palette(palette):
     if pal.dtype.kind != "f":                                  # (other integers would be read as sRGB values far outside [0, 1])
         raise ValueError("palette must be a (K, 3) uint8 or float array with at least one row")
     return None, np.asfortranarray(pal, dtype=np.float64)
-
-
-def _remap_result(L, code, pmap, quant):
-    if code == -1 and _native.last_error().startswith("patolette_amd_remap:"):
-        raise ValueError(_native.last_error())
-    message = L.get_patolette_exit_code_info_message(code).decode('UTF-8')
-    if code != 0:
-        return (False, None, None, message)
-    return (True, pmap, quant, message)
 
 
 def remap(image, palette, dither=True, want_quantized=True):
@@ -347,66 +313,22 @@ def remap(image, palette, dither=True, want_quantized=True):
 
     Returns (success, palette_map (H,W) or (F,H,W) uint8|uint16|uint32 by K, quantized (..., 3) uint8 = pal8[palette_map] or None,
     message)."""
-    if hasattr(image, "data_ptr") and getattr(image, "is_cuda", False):
-        return _remap_torch(image, palette, dither, want_quantized)
-    if not isinstance(image, np.ndarray):
-        image = np.asarray(image)
-    if image.dtype != np.uint8 or image.ndim not in (3, 4) or image.shape[-1] not in (3, 4):
-        raise ValueError("image must be an (H, W, 3|4) or (F, H, W, 3|4) uint8 array")
-    pal8, palf = _remap_palette(palette)
-    img = np.ascontiguousarray(image)
-    shape = img.shape[:-1]
-    count, (height, width), channels = (shape[0] if img.ndim == 4 else 1), shape[-2:], img.shape[-1]
-    rows = (pal8 if pal8 is not None else palf).shape[0]
-    map_dtype = np.uint8 if rows <= 256 else (np.uint16 if rows <= 65536 else np.uint32)
-    pmap = np.zeros(shape, dtype=map_dtype)
-    quant = np.zeros(shape + (3,), dtype=np.uint8) if want_quantized else None
-    code = C.c_int(0)
-    L = _native.lib()
-    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size > 0 else None   # noqa: E731
-    L.patolette_amd_remap_u8(count, width, height, vp(img), channels, _dp(palf), vp(pal8), rows, 1 if dither else 0, vp(pmap),
-                             np.dtype(map_dtype).itemsize, vp(quant), C.byref(code))
-    return _remap_result(L, code.value, pmap, quant)
-
-
-def _remap_torch(image, palette, dither, want_quantized):
-    """`remap` for a torch CUDA uint8 tensor (H, W, 3|4) or (F, H, W, 3|4) through `patolette_amd_remap_u8_device`, as
-    `_quantize_u8_torch`: the map (uint8 for K <= 256, else int32) and the quantized image stay in HBM; the palette is host memory.
-    Import torch BEFORE patolette_amd in such a process (see `_quantize_u8_torch`)."""
-    import torch
-    if image.dtype != torch.uint8 or image.dim() not in (3, 4) or image.shape[-1] not in (3, 4):
-        raise ValueError("image must be an (H, W, 3|4) or (F, H, W, 3|4) uint8 tensor")
-    if hasattr(palette, "detach"):
+    px, shape, dev = _u8_pixels(image, (3, 4), (3, 4), "image must be an (H, W, 3|4) or (F, H, W, 3|4) uint8 %s")
+    if dev is not None and hasattr(palette, "detach"):            # (a tensor image may come with a tensor palette: that one is host data)
         palette = palette.detach().cpu().numpy()
     pal8, palf = _remap_palette(palette)
-    img = image.contiguous()
-    shape = tuple(int(v) for v in img.shape[:-1])
-    count, (height, width), channels = (shape[0] if img.dim() == 4 else 1), shape[-2:], int(img.shape[-1])
-    n = count * width * height
-    dev = img.device
+    count, (height, width), channels = (shape[0] if len(shape) == 4 else 1), shape[-3:-1], shape[-1]
     rows = (pal8 if pal8 is not None else palf).shape[0]
-    me = 1 if rows <= 256 else 4
-    pmap = torch.zeros(shape, dtype=torch.uint8 if me == 1 else torch.int32, device=dev)
-    quant = torch.zeros(shape + (3,), dtype=torch.uint8, device=dev) if want_quantized else None
+    pmap, map_elem, quant = _outputs(shape[:-1], rows, 3, dev, True, want_quantized)
     code = C.c_int(0)
-    L = _native.lib()
-    with torch.cuda.device(dev):
-        torch.cuda.current_stream().synchronize()          # the library runs on its own stream
-        L.patolette_amd_remap_u8_device(count, width, height, C.c_void_p(img.data_ptr()) if n else None, channels, _dp(palf),
-                                        pal8.ctypes.data_as(C.c_void_p) if pal8 is not None else None, rows, 1 if dither else 0,
-                                        C.c_void_p(pmap.data_ptr()) if n else None, me,
-                                        C.c_void_p(quant.data_ptr()) if quant is not None and n else None, C.byref(code))
-    return _remap_result(L, code.value, pmap, quant)
-
-
-def _rgba_args(palette_size, alpha_threshold, dither, palette_only, color_space, kmeans_niter, kmeans_max_samples):
-    if isinstance(alpha_threshold, bool) or int(alpha_threshold) != alpha_threshold or not 0 <= alpha_threshold <= 256:
-        raise ValueError("alpha_threshold must be an integer in [0, 256]")
-    opts = _native.QuantizationOptions(bool(dither), bool(palette_only), int(color_space), int(kmeans_niter),
-                                       int(kmeans_max_samples), False)
-    palette = np.zeros((max(palette_size, 0), 3), dtype=np.float64, order='F')
-    palette_rgba = np.zeros((max(palette_size, 0), 4), dtype=np.uint8)
-    return int(alpha_threshold), opts, palette, palette_rgba
+    _call("patolette_amd_remap_u8", dev, count, width, height, _vp(px), channels, _vp(palf), _vp(pal8), rows, 1 if dither else 0,
+          _vp(pmap), map_elem, _vp(quant), C.byref(code))
+    if code.value == -1 and _native.last_error().startswith("patolette_amd_remap:"):
+        raise ValueError(_native.last_error())
+    message = _message(code.value)
+    if code.value != 0:
+        return (False, None, None, message)
+    return (True, pmap, quant, message)
 
 
 def quantize_rgba(image, palette_size, alpha_threshold=128, dither=True, palette_only=False, color_space=ColorSpace_ICtCp,
@@ -428,77 +350,27 @@ def quantize_rgba(image, palette_size, alpha_threshold=128, dither=True, palette
 
     Returns (success, palette_rgba (K,4) uint8, palette_map (H,W) uint8|uint16|uint32 or None, quantized (H,W,4) uint8 or None
     (= palette_rgba[palette_map]), palette (K,3) float64, transparent_index (0 or -1), message)."""
-    if hasattr(image, "data_ptr") and getattr(image, "is_cuda", False):
-        return _quantize_rgba_torch(image, palette_size, alpha_threshold, dither, palette_only, color_space, tile_size, kmeans_niter,
-                                    kmeans_max_samples, weights, want_quantized)
-    img = np.ascontiguousarray(image)
-    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 4:
-        raise ValueError("image must be an (H, W, 4) uint8 array")
+    px, shape, dev = _u8_pixels(image, (3,), (4,), "image must be an (H, W, 4) uint8 %s")
     if tile_size < 0:
         raise ValueError(bad_tile_size)
-    height, width, _ = img.shape
-    n = width * height
-    w = None
-    if weights is not None:
-        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
-        if w.size != n:
-            raise ValueError("weights must hold width*height values")
-    thr, opts, palette, palette_rgba = _rgba_args(palette_size, alpha_threshold, dither, palette_only, color_space, kmeans_niter,
-                                                  kmeans_max_samples)
-    map_dtype = np.uint8 if palette_size <= 256 else (np.uint16 if palette_size <= 65536 else np.uint32)
-    pmap = None if palette_only else np.zeros((height, width), dtype=map_dtype)
-    quant = np.zeros((height, width, 4), dtype=np.uint8) if (want_quantized and not palette_only) else None
+    height, width = shape[:2]
+    w = _weights(weights, width * height, dev)
+    if isinstance(alpha_threshold, bool) or int(alpha_threshold) != alpha_threshold or not 0 <= alpha_threshold <= 256:
+        raise ValueError("alpha_threshold must be an integer in [0, 256]")
+    opts = _options(dither, palette_only, color_space, kmeans_niter, kmeans_max_samples)
+    palette = np.zeros((max(palette_size, 0), 3), dtype=np.float64, order='F')
+    palette_rgba = np.zeros((max(palette_size, 0), 4), dtype=np.uint8)
+    pmap, map_elem, quant = _outputs(shape[:2], palette_size, 4, dev, not palette_only, want_quantized and not palette_only)
     code, tidx = C.c_int(0), C.c_int(-1)
-    L = _native.lib()
-    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size > 0 else None   # noqa: E731
-    L.patolette_amd_rgba(width, height, vp(img), thr, _dp(w), float(tile_size), palette_size, C.byref(opts), _dp(palette),
-                         vp(palette_rgba), vp(pmap), np.dtype(map_dtype).itemsize, vp(quant), C.byref(tidx), C.byref(code))
-    return _rgba_result(L, code.value, palette_rgba, pmap, quant, palette, tidx.value)
-
-
-def _rgba_result(L, code, palette_rgba, pmap, quant, palette, tidx):
-    message = L.get_patolette_exit_code_info_message(code).decode('UTF-8')
-    _raise_saliency(code, message)
-    if code == -1 and _native.last_error().startswith("patolette_amd_rgba:"):
+    _call("patolette_amd_rgba", dev, width, height, _vp(px), int(alpha_threshold), _vp(w), float(tile_size), palette_size, C.byref(opts),
+          _vp(palette), _vp(palette_rgba), _vp(pmap), map_elem, _vp(quant), C.byref(tidx), C.byref(code))
+    message = _message(code.value)
+    _raise_saliency(code.value, message)
+    if code.value == -1 and _native.last_error().startswith("patolette_amd_rgba:"):
         raise ValueError(_native.last_error())
-    if code != 0:
+    if code.value != 0:
         return (False, None, None, None, None, None, message)
-    return (True, palette_rgba, pmap, quant, palette, tidx, message)
-
-
-def _quantize_rgba_torch(image, palette_size, alpha_threshold, dither, palette_only, color_space, tile_size, kmeans_niter,
-                         kmeans_max_samples, weights, want_quantized):
-    """`quantize_rgba` for a torch CUDA uint8 tensor (H, W, 4) through `patolette_amd_rgba_device`, as `_quantize_u8_torch`: the
-    map (uint8 for K <= 256, else int32) and the quantized image stay in HBM, the palettes come back as numpy arrays."""
-    import torch
-    if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 4:
-        raise ValueError("image must be an (H, W, 4) uint8 tensor")
-    if tile_size < 0:
-        raise ValueError(bad_tile_size)
-    img = image.contiguous()
-    height, width, _ = (int(v) for v in img.shape)
-    n = width * height
-    dev = img.device
-    w = None
-    if weights is not None:
-        w = torch.as_tensor(weights, dtype=torch.float64, device=dev).reshape(-1).contiguous()
-        if w.numel() != n:
-            raise ValueError("weights must hold width*height values")
-    thr, opts, palette, palette_rgba = _rgba_args(palette_size, alpha_threshold, dither, palette_only, color_space, kmeans_niter,
-                                                  kmeans_max_samples)
-    me = 1 if palette_size <= 256 else 4
-    pmap = None if palette_only else torch.zeros((height, width), dtype=torch.uint8 if me == 1 else torch.int32, device=dev)
-    quant = torch.zeros((height, width, 4), dtype=torch.uint8, device=dev) if (want_quantized and not palette_only) else None
-    code, tidx = C.c_int(0), C.c_int(-1)
-    L = _native.lib()
-    with torch.cuda.device(dev):
-        torch.cuda.current_stream().synchronize()          # the library runs on its own stream
-        L.patolette_amd_rgba_device(width, height, C.c_void_p(img.data_ptr()), thr,
-                                    C.c_void_p(w.data_ptr()) if w is not None else None, float(tile_size), palette_size,
-                                    C.byref(opts), _dp(palette), palette_rgba.ctypes.data_as(C.c_void_p) if palette_rgba.size else None,
-                                    C.c_void_p(pmap.data_ptr()) if pmap is not None else None, me,
-                                    C.c_void_p(quant.data_ptr()) if quant is not None else None, C.byref(tidx), C.byref(code))
-    return _rgba_result(L, code.value, palette_rgba, pmap, quant, palette, tidx.value)
+    return (True, palette_rgba, pmap, quant, palette, tidx.value, message)
 
 
 def quantize_batch(width, height, images, palette_size, weights=None, dither=True, palette_only=False,
@@ -574,18 +446,13 @@ def quantize_u8_batch(images, palette_size, weights=None, dither=True, palette_o
     n = width * height
     if weights is not None and len(weights) != count:
         raise ValueError("weights must hold one entry (array or None) per image")
-    ws = [None] * count if weights is None else [None if w is None else np.ascontiguousarray(w, dtype=np.float64).reshape(-1) for w in weights]
-    for w in ws:
-        if w is not None and w.size != n:
-            raise ValueError("weights must hold width*height values")
-    opts = _native.QuantizationOptions(bool(dither), bool(palette_only), int(color_space), int(kmeans_niter),
-                                       int(kmeans_max_samples), False)
-    map_dtype = np.uint8 if palette_size <= 256 else (np.uint16 if palette_size <= 65536 else np.uint32)
+    ws = [_weights(w, n, None) for w in (weights if weights is not None else [None] * count)]
+    opts = _options(dither, palette_only, color_space, kmeans_niter, kmeans_max_samples)
     pals = [np.zeros((palette_size, 3), dtype=np.float64, order='F') for _ in range(count)]
     pal8 = [np.zeros((max(palette_size, 0), 3), dtype=np.uint8) for _ in range(count)]
-    maps = [None if palette_only else np.zeros((height, width), dtype=map_dtype) for _ in range(count)]
-    quants = [np.zeros((height, width, 3), dtype=np.uint8) if (want_quantized and not palette_only) else None for _ in range(count)]
-    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size > 0 else C.c_void_p()   # noqa: E731
+    maps, map_elems, quants = zip(*[_outputs((height, width), palette_size, 3, None, not palette_only, want_quantized and not palette_only)
+                                    for _ in range(count)])
+    vp = lambda a: _vp(a) or C.c_void_p()   # noqa: E731  (an array of pointers wants a null pointer, not None)
     PV = C.c_void_p * count
     PD = _native.dp * count
     codes = (C.c_int * count)()
@@ -593,17 +460,9 @@ def quantize_u8_batch(images, palette_size, weights=None, dither=True, palette_o
     L.patolette_amd_batch_u8(count, width, height, PV(*[vp(im) for im in imgs]), channels,
                              None if weights is None else PD(*[_dp(w) if w is not None else _native.dp() for w in ws]),
                              float(tile_size), palette_size, C.byref(opts), PD(*[_dp(p) for p in pals]), PV(*[vp(p) for p in pal8]),
-                             None if palette_only else PV(*[vp(m) for m in maps]), np.dtype(map_dtype).itemsize,
+                             None if palette_only else PV(*[vp(m) for m in maps]), map_elems[0],
                              PV(*[vp(q) for q in quants]) if (want_quantized and not palette_only) else None, codes)
-    out = []
-    for i in range(count):
-        msg = L.get_patolette_exit_code_info_message(codes[i]).decode('UTF-8')
-        _raise_saliency(codes[i], msg)
-        if codes[i] != 0:
-            out.append((False, None, None, None, None, msg))
-        else:
-            out.append((True, pal8[i], maps[i], quants[i], pals[i], msg))
-    return out
+    return [_u8_result(codes[i], pal8[i], maps[i], quants[i], pals[i]) for i in range(count)]
 
 
 __all__ = [

@@ -2291,10 +2291,10 @@ struct Pixels {                      // device-resident input image: planar f64 
     const unsigned char *u8 = nullptr;
     int channels = 3;
     bool rows = false;               // f64 as (N,3) row-major instead of planar
-    bool converted = false;          // E.cvt already holds the converted image and E.cstats its statistics (run_host: chunk by chunk behind the upload)
+    bool converted = false;          // E.cvt already holds the converted image and E.cstats its statistics (upload_image: chunk by chunk behind the upload)
 };
 
-// What stage S1 launches: the conversion and the sums that ride with it (run_device; run_host when it converts behind the upload)
+// What stage S1 launches: the conversion and the sums that ride with it (run_device; upload_image when it converts behind the upload)
 struct ConvertPlan { int which; BinK sumk, momk; };
 static ConvertPlan convert_plan(const Engine &E, const patolette__QuantizationOptions *opt, size_t N) {
     ConvertPlan p{PAMD_COPY, BinK{0.0, 0.0}, BinK{0.0, 0.0}};
@@ -2313,6 +2313,14 @@ static ConvertPlan convert_plan(const Engine &E, const patolette__QuantizationOp
     }
     return p;
 }
+
+// the dither launchers' counters of their last walk, into the call's statistics
+static void copy_dither_stats(Engine &E) {
+    E.stats.dither_segments = E.nn.dither_segments; E.stats.dither_repairs = E.nn.dither_repairs; E.stats.dither_rounds = E.nn.dither_rounds;
+    E.stats.dither_through = E.nn.dither_through; E.stats.dither_jumps = E.nn.dither_jumps; E.stats.dither_solo = E.nn.dither_solo;
+}
+// whether the map stage writes the map at all: a 1x1 dither visits nothing (riemersma.c:452-456)
+static bool map_touched(bool dither, size_t width, size_t height) { return !(dither && std::max(width, height) <= 1); }
 
 static void run_device(Engine &E, size_t width, size_t height, Pixels px, const double *d_weights, size_t K,
                        const patolette__QuantizationOptions *opt, double *palette, void *d_map, int map_elem, const DitherMask *mask = nullptr,
@@ -2336,7 +2344,7 @@ static void run_device(Engine &E, size_t width, size_t height, Pixels px, const 
     const ConvertPlan cp = convert_plan(E, opt, N);
     const int which = cp.which;
     const BinK sumk = cp.sumk, momk = cp.momk;
-    if (px.converted) { /* run_host has converted the image chunk by chunk behind its upload */ }
+    if (px.converted) { /* upload_image has converted the image chunk by chunk behind its upload */ }
     else if (px.u8) launch_convert_u8(which, px.u8, px.channels, E.cvt.p, N, E.cstats.p, s, sumk, momk);
     else if (px.rows) launch_convert_rows(which, px.f64, E.cvt.p, N, E.cstats.p, s, sumk, momk);
     else launch_convert(which, px.f64, E.cvt.p, N, E.cstats.p, s, sumk, momk);
@@ -2397,8 +2405,7 @@ static void run_device(Engine &E, size_t width, size_t height, Pixels px, const 
                     launch_convert(pix, E.cvt.p, E.aux.p, N, nullptr, s);      // plane stride of cvt is N for x,y,z
                     dither(E.aux.p, PAMD_COPY, 0);
                 }
-                E.stats.dither_segments = E.nn.dither_segments; E.stats.dither_repairs = E.nn.dither_repairs; E.stats.dither_rounds = E.nn.dither_rounds; E.stats.dither_through = E.nn.dither_through;
-    E.stats.dither_jumps = E.nn.dither_jumps; E.stats.dither_solo = E.nn.dither_solo;
+                copy_dither_stats(E);
             }
             palette_rows(pal, len, hm::color::rec2020_to_srgb);
         } else {                                                               // patolette.c:300-324
@@ -2533,6 +2540,54 @@ static void download_map_widened(Engine &E, const void *d_map, int me, size_t N,
     for (auto &th : pool) th.join();
 }
 
+// A host image up into E.src (f64: planar, or (N,3) row-major when `rows`) or E.src8 (interleaved 8-bit pixels of 3 or 4 channels), which
+// the caller has reserved; `host` describes it as Pixels describes a device image.  Nothing is waited for.
+// Large images go up in pieces and what a piece completes is converted (on a second stream) while the next one is on the link:
+// the conversion (0.5 ms of a 4096^2 image's 7 ms upload) disappears behind the copy.  Its statistics are exact sums and keyed
+// extrema, so the chunking changes no bit.  With derived weights too: the saliency stage reads the sRGB source, which stays where it is.
+// weight_plane: the call will have weights (E.cvt gets their plane now: run_device must not move what is converted here).
+// Returns whether E.cvt / E.cstats hold the converted image.
+static bool upload_image(Engine &E, const Pixels &host, size_t N, bool weight_plane, const patolette__QuantizationOptions *opt) {
+    hipStream_t s = E.stream;
+    unsigned char *dst = host.u8 ? E.src8.p : (unsigned char *)E.src.p;
+    const unsigned char *from = host.u8 ? host.u8 : (const unsigned char *)host.f64;
+    const size_t px_bytes = host.u8 ? (size_t)host.channels : 3 * sizeof(double);
+    const size_t chunk_min = getenv("PAMD_UPLOAD_CHUNK_MIN") ? (size_t)atoll(getenv("PAMD_UPLOAD_CHUNK_MIN")) : ((size_t)1 << 21);   // (read per call: tests lower it)
+    if (!(N >= chunk_min && !E.shard)) {
+        HIP_CHECK(hipMemcpyAsync(dst, from, N * px_bytes, hipMemcpyHostToDevice, s));
+        return false;
+    }
+    if (!E.stream2) {
+        HIP_CHECK(hipStreamCreateWithFlags(&E.stream2, hipStreamNonBlocking));
+        for (hipEvent_t *e : {&E.ev_up[0], &E.ev_up[1], &E.ev_join}) HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    }
+    const ConvertPlan cp = convert_plan(E, opt, N);
+    E.cvt.reserve((weight_plane ? 4 : 3) * N);
+    E.cstats.reserve(1);
+    HIP_CHECK(hipEventRecord(E.ev_join, s));                     // whatever the engine's stream still holds comes first
+    HIP_CHECK(hipStreamWaitEvent(E.stream2, E.ev_join, 0));
+    // planar source: the first two planes go up whole (every copy call has a fixed cost: 24 pieces made the upload 0.44 ms
+    // longer than one), the third in four pieces with the conversion of the pixels it completes behind each; row-major
+    // and 8-bit sources: four pieces of whole pixels
+    const bool planar = host.f64 && !host.rows;
+    const size_t head = planar ? 2 * N * sizeof(double) : 0, step = planar ? sizeof(double) : px_bytes;   // bytes ahead of the pieces; per pixel of a piece
+    if (planar) HIP_CHECK(hipMemcpyAsync(dst, from, head, hipMemcpyHostToDevice, s));
+    const size_t nch = 4, per = ((N + nch - 1) / nch + 255) & ~(size_t)255;
+    size_t c = 0;
+    for (size_t lo = 0; lo < N; lo += per, c++) {
+        const size_t cnt = std::min(per, N - lo);
+        HIP_CHECK(hipMemcpyAsync(dst + head + lo * step, from + head + lo * step, cnt * step, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipEventRecord(E.ev_up[c & 1], s));
+        HIP_CHECK(hipStreamWaitEvent(E.stream2, E.ev_up[c & 1], 0));
+        if (host.u8) launch_convert_u8(cp.which, E.src8.p, host.channels, E.cvt.p, N, E.cstats.p, E.stream2, cp.sumk, cp.momk, lo, lo + cnt, c == 0);
+        else if (host.rows) launch_convert_rows(cp.which, E.src.p, E.cvt.p, N, E.cstats.p, E.stream2, cp.sumk, cp.momk, lo, lo + cnt, c == 0);
+        else launch_convert(cp.which, E.src.p, E.cvt.p, N, E.cstats.p, E.stream2, cp.sumk, cp.momk, lo, lo + cnt, c == 0);
+    }
+    HIP_CHECK(hipEventRecord(E.ev_join, E.stream2));
+    HIP_CHECK(hipStreamWaitEvent(s, E.ev_join, 0));
+    return true;
+}
+
 // host-buffer entry: upload, run, download + widen
 static void run_host(Engine &E, size_t width, size_t height, const double *data, const double *weights, double tile_size,
                      size_t K, const patolette__QuantizationOptions *opt, double *palette, size_t *palette_map, bool rows = false,
@@ -2541,60 +2596,14 @@ static void run_host(Engine &E, size_t width, size_t height, const double *data,
     const size_t N = width * height;
     double t0 = now_ms();
     WsGuard wg(&E.stream, &E.stream2);
+    const bool derive = !weights && tile_size > 0.0, weighted = weights || derive;
     E.src.reserve(3 * N);
     if (weights) E.wsrc.reserve(N);
-    else if (tile_size > 0.0) { E.wsal.reserve(N); saliency_reserve(E.sal, width, height); }
-    ws_prepare(E, N, K, weights || tile_size > 0.0, opt->verbose);   // (the workspace as run_device will want it: nothing is queued yet)
-    // Large images go up in pieces and what a piece completes is converted (on a second stream) while the next one is on the link:
-    // the conversion (0.5 ms of a 4096^2 image's 7 ms upload) disappears behind the copy.  Its statistics are exact sums and keyed
-    // extrema, so the chunking changes no bit.  With derived weights too: the saliency stage reads the sRGB source, which stays where it is.
-    const size_t chunk_min = getenv("PAMD_UPLOAD_CHUNK_MIN") ? (size_t)atoll(getenv("PAMD_UPLOAD_CHUNK_MIN")) : ((size_t)1 << 21);   // (read per call: tests lower it)
-    const bool derive = !weights && tile_size > 0.0;
-    const bool chunked = N >= chunk_min && !E.shard;
-    bool converted = false;
-    if (chunked) {
-        const bool overlap = true;
-        // planar source: the first two planes go up whole (every copy call has a fixed cost: 24 pieces made the upload 0.44 ms
-        // longer than one), the third in four pieces with the conversion of the pixels it completes behind each; row-major
-        // source: four pieces of whole pixels
-        const size_t nch = 4, per = ((N + nch - 1) / nch + 255) & ~(size_t)255;
-        ConvertPlan cp{};
-        if (overlap) {
-            if (!E.stream2) {
-                HIP_CHECK(hipStreamCreateWithFlags(&E.stream2, hipStreamNonBlocking));
-                for (hipEvent_t *e : {&E.ev_up[0], &E.ev_up[1], &E.ev_join}) HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-            }
-            cp = convert_plan(E, opt, N);
-            E.cvt.reserve(((weights || derive) ? 4 : 3) * N);        // (the derived weights' plane: run_device must not move what is converted here)
-            E.cstats.reserve(1);
-            HIP_CHECK(hipEventRecord(E.ev_join, E.stream));          // whatever the engine's stream still holds comes first
-            HIP_CHECK(hipStreamWaitEvent(E.stream2, E.ev_join, 0));
-        }
-        if (!rows) HIP_CHECK(hipMemcpyAsync(E.src.p, data, 2 * N * sizeof(double), hipMemcpyHostToDevice, E.stream));
-        size_t c = 0;
-        for (size_t lo = 0; lo < N; lo += per, c++) {
-            const size_t cnt = std::min(per, N - lo);
-            if (rows) HIP_CHECK(hipMemcpyAsync(E.src.p + 3 * lo, data + 3 * lo, 3 * cnt * sizeof(double), hipMemcpyHostToDevice, E.stream));
-            else HIP_CHECK(hipMemcpyAsync(E.src.p + 2 * N + lo, data + 2 * N + lo, cnt * sizeof(double), hipMemcpyHostToDevice, E.stream));
-            if (overlap) {
-                HIP_CHECK(hipEventRecord(E.ev_up[c & 1], E.stream));
-                HIP_CHECK(hipStreamWaitEvent(E.stream2, E.ev_up[c & 1], 0));
-                if (rows) launch_convert_rows(cp.which, E.src.p, E.cvt.p, N, E.cstats.p, E.stream2, cp.sumk, cp.momk, lo, lo + cnt, c == 0);
-                else launch_convert(cp.which, E.src.p, E.cvt.p, N, E.cstats.p, E.stream2, cp.sumk, cp.momk, lo, lo + cnt, c == 0);
-            }
-        }
-        if (overlap) {
-            HIP_CHECK(hipEventRecord(E.ev_join, E.stream2));
-            HIP_CHECK(hipStreamWaitEvent(E.stream, E.ev_join, 0));
-            converted = true;
-        }
-    } else {
-        HIP_CHECK(hipMemcpyAsync(E.src.p, data, 3 * N * sizeof(double), hipMemcpyHostToDevice, E.stream));
-    }
-    if (weights) {
-        E.wsrc.reserve(N);
-        HIP_CHECK(hipMemcpyAsync(E.wsrc.p, weights, N * sizeof(double), hipMemcpyHostToDevice, E.stream));
-    }
+    else if (derive) { E.wsal.reserve(N); saliency_reserve(E.sal, width, height); }
+    ws_prepare(E, N, K, weighted, opt->verbose);   // (the workspace as run_device will want it: nothing is queued yet)
+    Pixels px{E.src.p, nullptr, 3, rows};
+    px.converted = upload_image(E, Pixels{data, nullptr, 3, rows}, N, weighted, opt);
+    if (weights) HIP_CHECK(hipMemcpyAsync(E.wsrc.p, weights, N * sizeof(double), hipMemcpyHostToDevice, E.stream));
     HIP_CHECK(hipStreamSynchronize(E.stream));
     const double up = now_ms() - t0;
     const double *d_w = weights ? E.wsrc.p : nullptr;
@@ -2603,18 +2612,11 @@ static void run_host(Engine &E, size_t width, size_t height, const double *data,
     const int me = map_elem_for(K);
     if (!opt->palette_only && !d_map_out) E.dmap.reserve(N * (size_t)me);
     std::vector<double> pal(3 * K);
-    Pixels px{E.src.p, nullptr, 3, rows};
-    px.converted = converted;
     run_device(E, width, height, px, d_w, K, opt, pal.data(), d_map_out ? d_map_out : (void *)E.dmap.p, me);
     E.stats.ms_saliency = E.ms_saliency;
     E.stats.ms_total += E.ms_saliency;
     t0 = now_ms();
-    if (!opt->palette_only && !d_map_out) {
-        const bool touched = !(opt->dither && std::max(width, height) <= 1);   // 1x1 dither visits nothing (riemersma.c:452-456)
-        if (touched) {
-            download_map_widened(E, E.dmap.p, me, N, palette_map);
-        }
-    }
+    if (!opt->palette_only && !d_map_out && map_touched(opt->dither, width, height)) download_map_widened(E, E.dmap.p, me, N, palette_map);
     std::memcpy(palette, pal.data(), 3 * K * sizeof(double));
     E.stats.ms_upload = up;
     E.stats.ms_download = now_ms() - t0;
@@ -2629,39 +2631,6 @@ static void palette_to_u8(const double *palette, size_t K, unsigned char *out) {
             v = v < 0.0 ? 0.0 : (v > 255.0 ? 255.0 : v);
             out[3 * i + c] = (unsigned char)v;
         }
-}
-
-// Host 8-bit image up into E.src8 (reserved), as run_host does it: a large image goes up in four pieces of whole pixels, each converted
-// (second stream) while the next is on the link.  weight_plane: the call will have weights (E.cvt gets their plane now: run_device
-// must not move what is converted here).  Returns whether E.cvt / E.cstats hold the converted image; nothing is waited for.
-static bool upload_u8(Engine &E, const unsigned char *pixels, int channels, size_t N, bool weight_plane, const patolette__QuantizationOptions *opt) {
-    hipStream_t s = E.stream;
-    const size_t chunk_min = getenv("PAMD_UPLOAD_CHUNK_MIN") ? (size_t)atoll(getenv("PAMD_UPLOAD_CHUNK_MIN")) : ((size_t)1 << 21);
-    if (!(N >= chunk_min && !E.shard)) {
-        HIP_CHECK(hipMemcpyAsync(E.src8.p, pixels, N * (size_t)channels, hipMemcpyHostToDevice, s));
-        return false;
-    }
-    if (!E.stream2) {
-        HIP_CHECK(hipStreamCreateWithFlags(&E.stream2, hipStreamNonBlocking));
-        for (hipEvent_t *e : {&E.ev_up[0], &E.ev_up[1], &E.ev_join}) HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    }
-    const ConvertPlan cp = convert_plan(E, opt, N);
-    E.cvt.reserve((weight_plane ? 4 : 3) * N);
-    E.cstats.reserve(1);
-    HIP_CHECK(hipEventRecord(E.ev_join, E.stream));
-    HIP_CHECK(hipStreamWaitEvent(E.stream2, E.ev_join, 0));
-    const size_t nch = 4, per = ((N + nch - 1) / nch + 255) & ~(size_t)255;
-    size_t c = 0;
-    for (size_t lo = 0; lo < N; lo += per, c++) {
-        const size_t cnt = std::min(per, N - lo);
-        HIP_CHECK(hipMemcpyAsync(E.src8.p + lo * (size_t)channels, pixels + lo * (size_t)channels, cnt * (size_t)channels, hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipEventRecord(E.ev_up[c & 1], s));
-        HIP_CHECK(hipStreamWaitEvent(E.stream2, E.ev_up[c & 1], 0));
-        launch_convert_u8(cp.which, E.src8.p, channels, E.cvt.p, N, E.cstats.p, E.stream2, cp.sumk, cp.momk, lo, lo + cnt, c == 0);
-    }
-    HIP_CHECK(hipEventRecord(E.ev_join, E.stream2));
-    HIP_CHECK(hipStreamWaitEvent(s, E.ev_join, 0));
-    return true;
 }
 
 // the device's index map (elements of me: 1 or 4 bytes) into a host buffer with elements of map_elem_out (1, 2, 4 or 8)
@@ -2680,6 +2649,38 @@ static void download_map(const void *d_map, int me, size_t N, void *map_out, int
     }
 }
 
+// Where the 8-bit entries' index map (elements of map_elem_for(K8) bytes) lands: in the caller's buffer when that is device memory, else
+// in E.dmap; null when no map-derived output is wanted (the map kernels are then skipped).  Reserves that place and what u8_outputs
+// takes of the workspace: the caller does this before it enqueues anything.
+static void *u8_map_place(Engine &E, size_t N, size_t K8, bool want, void *map_out, int map_elem_out, bool map_on_device,
+                          const unsigned char *quant_out, bool quant_on_device) {
+    if (!want) return nullptr;
+    if (quant_out) { E.pal8.reserve(3 * K8); if (!quant_on_device) E.quant8.reserve(3 * N); }
+    if (map_out && map_on_device) {
+        if (map_elem_out != map_elem_for(K8)) throw HipError("patolette_amd: device map_elem_bytes must be 1 for K <= 256, else 4");
+        return map_out;
+    }
+    E.dmap.reserve(N * (size_t)map_elem_for(K8));
+    return E.dmap.p;
+}
+
+// The 8-bit entries' output stage, from the map at d_map (u8_map_place) and the K8 palette rows' bytes p8: quantized = p8[map] made on the
+// device and copied out unless `on_device`; the map downloaded, and widened or narrowed to map_elem_out, where it is not in place already
+static void u8_outputs(Engine &E, const void *d_map, size_t N, const unsigned char *p8, size_t K8, void *map_out, int map_elem_out,
+                       unsigned char *quant_out, bool on_device) {
+    hipStream_t s = E.stream;
+    const int me = map_elem_for(K8);
+    if (quant_out) {
+        HIP_CHECK(hipMemcpyAsync(E.pal8.p, p8, 3 * K8, hipMemcpyHostToDevice, s));
+        unsigned char *d_q = on_device ? quant_out : E.quant8.p;
+        launch_reconstruct(d_map, me, N, E.pal8.p, (int)K8, d_q, s);
+        if (!on_device) HIP_CHECK(hipMemcpyAsync(quant_out, d_q, 3 * N, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+    }
+    if (map_out && d_map != map_out) download_map(d_map, me, N, map_out, map_elem_out);
+    E.sync();
+}
+
 // 8-bit adaptor around the path: interleaved u8 in; f64 palette, u8 palette, index map and
 // reconstructed u8 image out.  `pixels`, `d_map_out`, `d_quant_out` are device pointers when `on_device`.
 static void run_u8(Engine &E, size_t width, size_t height, const unsigned char *pixels, int channels, const double *weights,
@@ -2689,17 +2690,17 @@ static void run_u8(Engine &E, size_t width, size_t height, const unsigned char *
     // frames: the image is that stack (width x height = frames->width x frames->count * frames->height); weights, upload, map
     // download and reconstruction serve it as they serve one image
     const size_t N = width * height;
+    const size_t fcount = frames ? frames->count : 1, fheight = frames ? frames->height : height;   // one image: a stack of one
     hipStream_t s = E.stream;
     double t0 = now_ms();
     WsGuard wg(&E.stream, &E.stream2);
-    if (!weights && tile_size > 0.0) { E.wsal.reserve(N); saliency_reserve(E.sal, width, frames ? frames->height : height); }
-    ws_prepare(E, N, K, weights || tile_size > 0.0, opt->verbose);   // (as run_host)
-    {   // what the stages below take of the workspace, before anything is enqueued (their own reservations are then no-ops)
-        const bool wmap = !opt->palette_only && (map_out || quant_out);
-        E.cvt.reserve(((weights || tile_size > 0.0) ? 4 : 3) * N); E.cstats.reserve(1);
-        if (wmap && !((on_device || map_on_device) && map_out && map_elem_out == map_elem_for(K))) E.dmap.reserve(N * (size_t)map_elem_for(K));
-        if (wmap && quant_out) { E.pal8.reserve(3 * K); if (!on_device) E.quant8.reserve(3 * N); }
-    }
+    const bool derive = !weights && tile_size > 0.0, weighted = weights || derive;
+    if (derive) { E.wsal.reserve(N); saliency_reserve(E.sal, width, fheight); }
+    ws_prepare(E, N, K, weighted, opt->verbose);   // (as run_host)
+    // what the stages below take of the workspace, before anything is enqueued (their own reservations are then no-ops)
+    E.cvt.reserve((weighted ? 4 : 3) * N); E.cstats.reserve(1);
+    void *d_map = u8_map_place(E, N, K, !opt->palette_only && (map_out || quant_out), map_out, map_elem_out, on_device || map_on_device,
+                               quant_out, on_device);
     const unsigned char *d_px = pixels;
     const double *d_w = weights;
     bool converted = false;
@@ -2707,9 +2708,8 @@ static void run_u8(Engine &E, size_t width, size_t height, const unsigned char *
         E.src8.reserve(N * (size_t)channels);
         if (weights) E.wsrc.reserve(N);
         d_px = E.src8.p;
-        converted = upload_u8(E, pixels, channels, N, weights || (!weights && tile_size > 0.0), opt);
+        converted = upload_image(E, Pixels{nullptr, pixels, channels}, N, weighted, opt);
         if (weights) {
-            E.wsrc.reserve(N);
             HIP_CHECK(hipMemcpyAsync(E.wsrc.p, weights, N * sizeof(double), hipMemcpyHostToDevice, s));
             d_w = E.wsrc.p;
         }
@@ -2717,21 +2717,11 @@ static void run_u8(Engine &E, size_t width, size_t height, const unsigned char *
     }
     const double up = now_ms() - t0;
     E.ms_saliency = 0.0;
-    if (!weights && tile_size > 0.0) {
-        if (frames) d_w = derive_weights(E, nullptr, d_px, channels, frames->width, frames->height, tile_size, frames->count);
-        else d_w = derive_weights(E, nullptr, d_px, channels, width, height, tile_size);
-    }
-    const int me = map_elem_for(K);
-    const bool want_map = !opt->palette_only && (map_out || quant_out);
-    void *d_map = nullptr;                  // stays null when no map-derived output is wanted: the map kernels are skipped
-    if (want_map) {
-        if ((on_device || map_on_device) && map_out && map_elem_out == me) d_map = map_out;
-        else { E.dmap.reserve(N * (size_t)me); d_map = E.dmap.p; }
-    }
+    if (derive) d_w = derive_weights(E, nullptr, d_px, channels, width, fheight, tile_size, fcount);   // (each frame as an image of its own)
     std::vector<double> pal(3 * K);
     Pixels px8{nullptr, d_px, channels};
     px8.converted = converted;
-    run_device(E, width, height, px8, d_w, K, opt, pal.data(), d_map, me, nullptr, frames);
+    run_device(E, width, height, px8, d_w, K, opt, pal.data(), d_map, map_elem_for(K), nullptr, frames);
     E.stats.ms_saliency = E.ms_saliency;
     E.stats.ms_total += E.ms_saliency;
     t0 = now_ms();
@@ -2739,23 +2729,7 @@ static void run_u8(Engine &E, size_t width, size_t height, const unsigned char *
     palette_to_u8(pal.data(), K, p8.data());
     if (palette) std::memcpy(palette, pal.data(), 3 * K * sizeof(double));
     if (palette_u8) std::memcpy(palette_u8, p8.data(), 3 * K);
-    const bool touched = !(opt->dither && std::max(width, frames ? frames->height : height) <= 1);       // 1x1 dither visits nothing
-    if (want_map && touched) {
-        if (quant_out) {
-            E.pal8.reserve(3 * K);
-            HIP_CHECK(hipMemcpyAsync(E.pal8.p, p8.data(), 3 * K, hipMemcpyHostToDevice, s));
-            unsigned char *d_q = quant_out;
-            if (!on_device) { E.quant8.reserve(3 * N); d_q = E.quant8.p; }
-            launch_reconstruct(d_map, me, N, E.pal8.p, (int)K, d_q, s);
-            if (!on_device) HIP_CHECK(hipMemcpyAsync(quant_out, d_q, 3 * N, hipMemcpyDeviceToHost, s));
-            HIP_CHECK(hipStreamSynchronize(s));
-        }
-        if (map_out && d_map != map_out) {
-            if (on_device || map_on_device) throw HipError("patolette_amd: device map_elem_bytes must be 1 for K <= 256, else 4");
-            download_map(d_map, me, N, map_out, map_elem_out);
-        }
-        E.sync();
-    }
+    if (d_map && map_touched(opt->dither, width, fheight)) u8_outputs(E, d_map, N, p8.data(), K, map_out, map_elem_out, quant_out, on_device);
     E.stats.ms_upload = up;
     E.stats.ms_download = now_ms() - t0;
     E.stats.ms_total += up + E.stats.ms_download;
@@ -2782,20 +2756,14 @@ static void run_remap(Engine &E, size_t frames, size_t width, size_t height, con
     WsGuard wg(&E.stream, &E.stream2);
     E.stats = patolette_amd__Stats{};
     const int me = map_elem_for(K8);
-    const bool want = map_out || quant_out;
     const bool lanes = dither && (frames > 1 ? dither_frames_lane_layout(frames, width, height, (int)k) : dither_lane_layout(width, height, (int)k));
     const bool fused = !g_remap_two_pass.load(std::memory_order_relaxed) && (dither ? lanes : nn_map_u8_applies(N, (int)k));
     // the workspace, before anything is enqueued
     if (!on_device) E.src8.reserve(N * (size_t)channels);
     E.dpal.reserve(3 * k); E.h_pal.reserve(3 * k);
+    void *d_map = u8_map_place(E, N, K8, map_out || quant_out, map_out, map_elem_out, on_device, quant_out, on_device);
+    const bool want = d_map != nullptr;
     if (want && !fused) { E.cvt.reserve(3 * N); E.cstats.reserve(1); E.h_cstats.reserve(1); }
-    void *d_map = nullptr;
-    if (want) {
-        if (on_device && map_out && map_elem_out == me) d_map = map_out;
-        else { E.dmap.reserve(N * (size_t)me); d_map = E.dmap.p; }
-        if (quant_out) { E.pal8.reserve(3 * K8); if (!on_device) E.quant8.reserve(3 * N); }
-    }
-    if (on_device && map_out && d_map != map_out) throw HipError("patolette_amd: device map_elem_bytes must be 1 for up to 256 palette rows, else 4");
     const unsigned char *d_px = pixels;
     if (!on_device) {
         HIP_CHECK(hipMemcpyAsync(E.src8.p, pixels, N * (size_t)channels, hipMemcpyHostToDevice, s));
@@ -2807,7 +2775,6 @@ static void run_remap(Engine &E, size_t frames, size_t width, size_t height, con
     double t0 = now_ms();
     palette_rows(pal, k, dither ? hm::color::srgb_to_rec2020 : hm::color::srgb_to_ictcp);
     E.map_palette = pal;
-    const bool touched = !(dither && std::max(width, height) <= 1);                   // 1x1 dither visits nothing (riemersma.c:452-456)
     if (want) {
         std::memcpy(E.h_pal.p, pal.data(), 3 * k * sizeof(double));
         HIP_CHECK(hipMemcpyAsync(E.dpal.p, E.h_pal.p, 3 * k * sizeof(double), hipMemcpyHostToDevice, s));
@@ -2833,24 +2800,13 @@ static void run_remap(Engine &E, size_t frames, size_t width, size_t height, con
                 if (frames > 1) launch_dither_frames(E.cvt.p, N, PAMD_COPY, frames, width, height, E.dpal.p, pal.data(), (int)k, d_map, me, E.nn, s, layout);
                 else launch_dither(E.cvt.p, N, PAMD_COPY, width, height, E.dpal.p, pal.data(), (int)k, d_map, me, E.nn, s, layout);
             }
-            E.stats.dither_segments = E.nn.dither_segments; E.stats.dither_repairs = E.nn.dither_repairs; E.stats.dither_rounds = E.nn.dither_rounds;
-            E.stats.dither_through = E.nn.dither_through; E.stats.dither_jumps = E.nn.dither_jumps; E.stats.dither_solo = E.nn.dither_solo;
+            copy_dither_stats(E);
         }
         E.sync();
     }
     E.stats.ms_map = now_ms() - t0;
     t0 = now_ms();
-    if (want && touched) {
-        if (quant_out) {
-            HIP_CHECK(hipMemcpyAsync(E.pal8.p, p8.data(), 3 * K8, hipMemcpyHostToDevice, s));
-            unsigned char *d_q = on_device ? quant_out : E.quant8.p;
-            launch_reconstruct(d_map, me, N, E.pal8.p, (int)K8, d_q, s);
-            if (!on_device) HIP_CHECK(hipMemcpyAsync(quant_out, d_q, 3 * N, hipMemcpyDeviceToHost, s));
-            HIP_CHECK(hipStreamSynchronize(s));
-        }
-        if (map_out && d_map != map_out) download_map(d_map, me, N, map_out, map_elem_out);
-        E.sync();
-    }
+    if (want && map_touched(dither, width, height)) u8_outputs(E, d_map, N, p8.data(), K8, map_out, map_elem_out, quant_out, on_device);
     E.stats.ms_download = now_ms() - t0;
     E.stats.ms_total = now_ms() - t_start;
 }
@@ -2897,7 +2853,7 @@ static void run_rgba(Engine &E, size_t width, size_t height, const unsigned char
     const unsigned char *d_px = pixels;
     const double *d_w = weights;
     bool converted = false;
-    if (!on_device) converted = upload_u8(E, pixels, 4, N, weighted, opt);
+    if (!on_device) converted = upload_image(E, Pixels{nullptr, pixels, 4}, N, weighted, opt);
     else if (stage_px) HIP_CHECK(hipMemcpyAsync(E.src8.p, pixels, 4 * N, hipMemcpyDeviceToDevice, s));
     if (stage_px) d_px = E.src8.p;
     if (weights && !on_device) {
@@ -2960,8 +2916,8 @@ static void run_rgba(Engine &E, size_t width, size_t height, const unsigned char
     if (palette_rgba) std::memcpy(palette_rgba, prgba.data(), 4 * K);
 
     if (want_map) {
-        if (!masked && opt->dither && std::max(width, height) <= 1)
-            HIP_CHECK(hipMemsetAsync(E.dmap.p, 0, N * (size_t)me, s));        // 1x1 dither visits nothing (riemersma.c:452-456): entry 0
+        if (!masked && !map_touched(opt->dither, width, height))
+            HIP_CHECK(hipMemsetAsync(E.dmap.p, 0, N * (size_t)me, s));        // (a 1x1 dither wrote nothing: entry 0)
         HIP_CHECK(hipMemcpyAsync(E.pal8.p, prgba.data(), 4 * K, hipMemcpyHostToDevice, s));
         void *d_map = map_out ? (on_device ? map_out : (void *)E.rgba_map.p) : nullptr;
         unsigned char *d_q = quant_out ? (on_device ? quant_out : E.quant8.p) : nullptr;
@@ -3015,6 +2971,31 @@ static int slice_args_ok(size_t total_pixels, size_t slice_begin, size_t slice_p
     return slice_pixels > 0 && slice_begin <= total_pixels && slice_pixels <= total_pixels - slice_begin && slice_data &&
            (options->palette_only || slice_map);
 }
+// Runs body(E) on the calling thread's engine, initialised.  Returns 0; a CodeError's own code (its message recorded, nothing printed);
+// or -1 for any other failure (its message recorded for patolette_amd_last_error, and printed)
+template <typename F>
+static int guarded(F body) {
+    try {
+        Engine &E = engine();
+        E.init();
+        body(E);
+        return 0;
+    } catch (const CodeError &ex) {
+        engine().last_error = ex.what();
+        return ex.code;
+    } catch (const std::exception &ex) {
+        engine().last_error = ex.what();
+        fprintf(stderr, "patolette: %s\n", ex.what());
+        return -1;
+    }
+}
+// An unusable argument, found before any engine is initialised (no device is needed to be told so): recorded, printed, the code set
+static void fail_args(int *exit_code, int code, const char *msg) {
+    try { engine().last_error = msg; } catch (...) {}
+    fprintf(stderr, "%s\n", msg);
+    *exit_code = code;
+}
+
 // runs `body` on the calling thread's engine with the slice description attached
 // args_ok: this rank's arguments passed slice_args_ok.  A rank that returned early on bad arguments would leave its peers
 // waiting in the first collective for ever, so the verdicts are summed over the group first and every rank fails together.
@@ -3023,24 +3004,16 @@ static void slice_entry(size_t total_pixels, size_t slice_begin, const patolette
     Shard sh;
     sh.total = total_pixels; sh.begin = slice_begin; sh.comm = *comm;
     Engine *Ep = nullptr;
-    try {
-        Engine &E = engine();
+    *exit_code = guarded([&](Engine &E) {
         Ep = &E;
-        E.init();
         E.shard = &sh;
         int bad = args_ok ? 0 : 1;
         comm_sum_host(E, &bad, 1, 2);
         if (bad) throw HipError(args_ok ? "patolette_amd_slice: another rank of the group passed unusable arguments"
                                         : "patolette_amd_slice: unusable arguments (empty slice, slice outside the image, missing buffer)");
         body(E);
-        E.shard = nullptr;
-        *exit_code = 0;
-    } catch (const std::exception &ex) {
-        if (Ep) Ep->shard = nullptr;
-        engine().last_error = ex.what();
-        fprintf(stderr, "patolette: %s\n", ex.what());
-        *exit_code = -1;
-    }
+    });
+    if (Ep) Ep->shard = nullptr;
 }
 
 extern "C" {
@@ -3049,16 +3022,7 @@ void patolette(size_t width, size_t height, const double *data, const double *we
                const patolette__QuantizationOptions *options, double *palette, size_t *palette_map, int *exit_code) {
     *exit_code = validate(width, height, palette_size);
     if (*exit_code != 0) return;
-    try {
-        Engine &E = engine();
-        E.init();
-        run_host(E, width, height, data, weights, 0.0, palette_size, options, palette, palette_map);
-        *exit_code = 0;
-    } catch (const std::exception &ex) {
-        engine().last_error = ex.what();
-        fprintf(stderr, "patolette: %s\n", ex.what());
-        *exit_code = -1;
-    }
+    *exit_code = guarded([&](Engine &E) { run_host(E, width, height, data, weights, 0.0, palette_size, options, palette, palette_map); });
 }
 
 void patolette_amd_quantize(size_t width, size_t height, const double *data, const double *weights, double tile_size,
@@ -3066,19 +3030,7 @@ void patolette_amd_quantize(size_t width, size_t height, const double *data, con
                             size_t *palette_map, int *exit_code) {
     *exit_code = validate(width, height, palette_size);
     if (*exit_code != 0) return;
-    try {
-        Engine &E = engine();
-        E.init();
-        run_host(E, width, height, data, weights, tile_size, palette_size, options, palette, palette_map);
-        *exit_code = 0;
-    } catch (const CodeError &ex) {
-        engine().last_error = ex.what();
-        *exit_code = ex.code;
-    } catch (const std::exception &ex) {
-        engine().last_error = ex.what();
-        fprintf(stderr, "patolette: %s\n", ex.what());
-        *exit_code = -1;
-    }
+    *exit_code = guarded([&](Engine &E) { run_host(E, width, height, data, weights, tile_size, palette_size, options, palette, palette_map); });
 }
 
 void patolette_amd_quantize_rows(size_t width, size_t height, const double *rows, const double *weights, double tile_size,
@@ -3086,19 +3038,7 @@ void patolette_amd_quantize_rows(size_t width, size_t height, const double *rows
                                  size_t *palette_map, int *exit_code) {
     *exit_code = validate(width, height, palette_size);
     if (*exit_code != 0) return;
-    try {
-        Engine &E = engine();
-        E.init();
-        run_host(E, width, height, rows, weights, tile_size, palette_size, options, palette, palette_map, true);
-        *exit_code = 0;
-    } catch (const CodeError &ex) {
-        engine().last_error = ex.what();
-        *exit_code = ex.code;
-    } catch (const std::exception &ex) {
-        engine().last_error = ex.what();
-        fprintf(stderr, "patolette: %s\n", ex.what());
-        *exit_code = -1;
-    }
+    *exit_code = guarded([&](Engine &E) { run_host(E, width, height, rows, weights, tile_size, palette_size, options, palette, palette_map, true); });
 }
 
 void patolette_amd_slice(size_t total_pixels, size_t slice_begin, size_t slice_pixels, const double *slice_data,
@@ -3232,106 +3172,50 @@ void patolette_amd_device(size_t width, size_t height, const double *d_data, con
                           int map_elem_bytes, int *exit_code) {
     *exit_code = validate(width, height, palette_size);
     if (*exit_code != 0) return;
-    try {
-        Engine &E = engine();
-        E.init();
+    *exit_code = guarded([&](Engine &E) {
         std::vector<double> pal(3 * palette_size);
         run_device(E, width, height, Pixels{d_data, nullptr, 3}, d_weights, palette_size, options, pal.data(), d_palette_map,
                    map_elem_bytes);
         std::memcpy(palette, pal.data(), 3 * palette_size * sizeof(double));
-        *exit_code = 0;
-    } catch (const std::exception &ex) {
-        engine().last_error = ex.what();
-        fprintf(stderr, "patolette: %s\n", ex.what());
-        *exit_code = -1;
-    }
+    });
 }
 
-static void u8_entry(bool on_device, size_t width, size_t height, const unsigned char *pixels, int channels,
-                     const double *weights, double tile_size, size_t palette_size, const patolette__QuantizationOptions *options, double *palette,
-                     unsigned char *palette_u8, void *palette_map, int map_elem_bytes, unsigned char *quantized, int *exit_code) {
-    *exit_code = validate(width, height, palette_size);
-    if (*exit_code != 0) return;
-    if (validate_u8(palette_size, channels, palette_map, map_elem_bytes) != 0) {
-        fprintf(stderr, "patolette_amd: bad channels / map_elem_bytes for the u8 entry point\n");
-        *exit_code = -1;
-        return;
-    }
-    try {
-        Engine &E = engine();
-        E.init();
-        run_u8(E, width, height, pixels, channels, weights, tile_size, palette_size, options, palette, palette_u8, palette_map,
-               map_elem_bytes, quantized, on_device);
-        *exit_code = 0;
-    } catch (const CodeError &ex) {
-        engine().last_error = ex.what();
-        *exit_code = ex.code;
-    } catch (const std::exception &ex) {
-        engine().last_error = ex.what();
-        fprintf(stderr, "patolette: %s\n", ex.what());
-        *exit_code = -1;
-    }
-}
-
-// F frames of one size, one palette (include/patolette_amd.h): the path on the stack of frames, the dither frame by frame
+// F frames of one size, one palette (include/patolette_amd.h): the path on the stack of frames, the dither frame by frame.  The image
+// entries (patolette_amd_u8*) are the case of one frame; bad_u8_args: the caller's text for what validate_u8 rejects
 static void frames_entry(bool on_device, size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels,
                          const double *weights, double tile_size, size_t palette_size, const patolette__QuantizationOptions *options,
                          double *palette, unsigned char *palette_u8, void *palette_map, int map_elem_bytes, unsigned char *quantized,
-                         int *exit_code) {
+                         const char *bad_u8_args, int *exit_code) {
     *exit_code = frames == 0 ? -2 : validate(width, height, palette_size);
     if (*exit_code != 0) return;
     const size_t n = width * height;
-    if (frames > kDitherFramesMaxPixels / n) {                      // (n <= 1.6e9: no overflow before this)
-        const char *msg = "patolette_amd_frames: frames * width * height exceeds 2^31 pixels";
-        try { engine().last_error = msg; } catch (...) {}
-        fprintf(stderr, "%s\n", msg);
-        *exit_code = -4;
-        return;
-    }
-    if (validate_u8(palette_size, channels, palette_map, map_elem_bytes) != 0) {
-        const char *msg = "patolette_amd_frames: bad channels / map_elem_bytes";
-        try { engine().last_error = msg; } catch (...) {}
-        fprintf(stderr, "%s\n", msg);
-        *exit_code = -1;
-        return;
-    }
-    try {
-        Engine &E = engine();
-        E.init();
+    if (frames > kDitherFramesMaxPixels / n)                        // (n <= 1.6e9: no overflow before this, and never with one frame)
+        return fail_args(exit_code, -4, "patolette_amd_frames: frames * width * height exceeds 2^31 pixels");
+    if (validate_u8(palette_size, channels, palette_map, map_elem_bytes) != 0) return fail_args(exit_code, -1, bad_u8_args);
+    *exit_code = guarded([&](Engine &E) {
         const Frames fr{frames, width, height};
         run_u8(E, width, frames * height, pixels, channels, weights, tile_size, palette_size, options, palette, palette_u8, palette_map,
-               map_elem_bytes, quantized, on_device, false, frames > 1 ? &fr : nullptr);      // (one frame: the image entry itself)
-        *exit_code = 0;
-    } catch (const CodeError &ex) {
-        engine().last_error = ex.what();
-        *exit_code = ex.code;
-    } catch (const std::exception &ex) {
-        engine().last_error = ex.what();
-        fprintf(stderr, "patolette: %s\n", ex.what());
-        *exit_code = -1;
-    }
+               map_elem_bytes, quantized, on_device, false, frames > 1 ? &fr : nullptr);      // (one frame: the image itself)
+    });
 }
+static const char *const kBadFramesArgs = "patolette_amd_frames: bad channels / map_elem_bytes";
+static const char *const kBadU8Args = "patolette_amd: bad channels / map_elem_bytes for the u8 entry point";
 
 // 8-bit pixels onto the caller's palette (include/patolette_amd.h): the arguments, then run_remap
 static void remap_entry(bool on_device, size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels, const double *palette,
                         const unsigned char *palette_u8, size_t palette_rows, int dither, void *palette_map, int map_elem_bytes,
                         unsigned char *quantized, int *exit_code) {
-    auto fail = [&](int code, const char *msg) {
-        try { engine().last_error = msg; } catch (...) {}
-        fprintf(stderr, "%s\n", msg);
-        *exit_code = code;
-    };
     *exit_code = frames == 0 ? -2 : validate(width, height, 1);
     if (*exit_code != 0) return;
     const size_t n = width * height;
     if (frames > (dither ? kDitherFramesMaxPixels : (size_t)40000 * 40000) / n)
-        return fail(-4, dither ? "patolette_amd_remap: frames * width * height exceeds 2^31 pixels (the dither numbers pixels with 32 bits)"
+        return fail_args(exit_code, -4, dither ? "patolette_amd_remap: frames * width * height exceeds 2^31 pixels (the dither numbers pixels with 32 bits)"
                                : "patolette_amd_remap: frames * width * height is too big");
-    if ((palette != nullptr) == (palette_u8 != nullptr)) return fail(-1, "patolette_amd_remap: pass exactly one of palette and palette_u8");
-    if (palette_rows < 1 || palette_rows > ((size_t)1 << 31)) return fail(-1, "patolette_amd_remap: the palette needs at least one row");
+    if ((palette != nullptr) == (palette_u8 != nullptr)) return fail_args(exit_code, -1, "patolette_amd_remap: pass exactly one of palette and palette_u8");
+    if (palette_rows < 1 || palette_rows > ((size_t)1 << 31)) return fail_args(exit_code, -1, "patolette_amd_remap: the palette needs at least one row");
     if (validate_u8(palette_rows, channels, palette_map, map_elem_bytes) != 0)
-        return fail(-1, "patolette_amd_remap: bad channels / map_elem_bytes (1, 2, 4 or 8, able to hold palette_rows - 1)");
-    if (!pixels) return fail(-1, "patolette_amd_remap: no pixels");
+        return fail_args(exit_code, -1, "patolette_amd_remap: bad channels / map_elem_bytes (1, 2, 4 or 8, able to hold palette_rows - 1)");
+    if (!pixels) return fail_args(exit_code, -1, "patolette_amd_remap: no pixels");
     // the rows, planar (k,3) f64 sRGB, and the bytes `quantized` is made of
     size_t k = palette_rows;
     std::vector<double> pal;
@@ -3343,26 +3227,19 @@ static void remap_entry(bool on_device, size_t frames, size_t width, size_t heig
     } else {
         auto row_is = [&](size_t i, double v) { return palette[i] == v && palette[palette_rows + i] == v && palette[2 * palette_rows + i] == v; };
         while (k > 0 && row_is(k - 1, -1.0)) k--;                          // the reference's fill of unused rows (patolette.c:327-336)
-        if (k == 0) return fail(-1, "patolette_amd_remap: every palette row is the unused-row fill (-1, -1, -1)");
+        if (k == 0) return fail_args(exit_code, -1, "patolette_amd_remap: every palette row is the unused-row fill (-1, -1, -1)");
         pal.resize(3 * k);
         for (size_t i = 0; i < k; i++) for (int c = 0; c < 3; c++) {
             const double v = palette[palette_rows * (size_t)c + i];
-            if (!std::isfinite(v)) return fail(-1, "patolette_amd_remap: the palette holds a value that is not finite");
+            if (!std::isfinite(v)) return fail_args(exit_code, -1, "patolette_amd_remap: the palette holds a value that is not finite");
             pal[(size_t)c * k + i] = v;
         }
         palette_to_u8(palette, palette_rows, p8.data());
     }
-    try {
-        Engine &E = engine();
-        E.init();
+    *exit_code = guarded([&](Engine &E) {
         run_remap(E, frames, width, height, pixels, channels, std::move(pal), k, p8, palette_rows, dither != 0, palette_map, map_elem_bytes, quantized,
                   on_device);
-        *exit_code = 0;
-    } catch (const std::exception &ex) {
-        engine().last_error = ex.what();
-        fprintf(stderr, "patolette: %s\n", ex.what());
-        *exit_code = -1;
-    }
+    });
 }
 
 static void rgba_entry(bool on_device, size_t width, size_t height, const unsigned char *pixels, int alpha_threshold, const double *weights,
@@ -3371,30 +3248,13 @@ static void rgba_entry(bool on_device, size_t width, size_t height, const unsign
                        int *exit_code) {
     *exit_code = validate(width, height, palette_size);
     if (*exit_code != 0) return;
-    const char *bad = nullptr;
-    if (alpha_threshold < 0 || alpha_threshold > 256) bad = "patolette_amd_rgba: alpha_threshold must lie in [0, 256]";
-    else if (validate_u8(palette_size, 4, palette_map, map_elem_bytes) != 0)
-        bad = "patolette_amd_rgba: map_elem_bytes must be 1, 2, 4 or 8 and able to hold palette_size - 1";
-    if (bad) {
-        try { engine().last_error = bad; } catch (...) {}
-        fprintf(stderr, "%s\n", bad);
-        *exit_code = -1;
-        return;
-    }
-    try {
-        Engine &E = engine();
-        E.init();
+    if (alpha_threshold < 0 || alpha_threshold > 256) return fail_args(exit_code, -1, "patolette_amd_rgba: alpha_threshold must lie in [0, 256]");
+    if (validate_u8(palette_size, 4, palette_map, map_elem_bytes) != 0)
+        return fail_args(exit_code, -1, "patolette_amd_rgba: map_elem_bytes must be 1, 2, 4 or 8 and able to hold palette_size - 1");
+    *exit_code = guarded([&](Engine &E) {
         run_rgba(E, width, height, pixels, alpha_threshold, weights, tile_size, palette_size, options, palette, palette_rgba, palette_map,
                  map_elem_bytes, quantized, transparent_index, on_device);
-        *exit_code = 0;
-    } catch (const CodeError &ex) {
-        engine().last_error = ex.what();
-        *exit_code = ex.code;
-    } catch (const std::exception &ex) {
-        engine().last_error = ex.what();
-        fprintf(stderr, "patolette: %s\n", ex.what());
-        *exit_code = -1;
-    }
+    });
 }
 
 void patolette_amd_rgba(size_t width, size_t height, const unsigned char *pixels, int alpha_threshold, const double *weights, double tile_size,
@@ -3432,7 +3292,7 @@ void patolette_amd_frames_u8(size_t frames, size_t width, size_t height, const u
                              double tile_size, size_t palette_size, const patolette__QuantizationOptions *options, double *palette,
                              unsigned char *palette_u8, void *palette_map, int map_elem_bytes, unsigned char *quantized, int *exit_code) {
     frames_entry(false, frames, width, height, pixels, channels, weights, tile_size, palette_size, options, palette, palette_u8, palette_map,
-                 map_elem_bytes, quantized, exit_code);
+                 map_elem_bytes, quantized, kBadFramesArgs, exit_code);
 }
 
 void patolette_amd_frames_u8_device(size_t frames, size_t width, size_t height, const unsigned char *d_pixels, int channels,
@@ -3440,22 +3300,22 @@ void patolette_amd_frames_u8_device(size_t frames, size_t width, size_t height, 
                                     const patolette__QuantizationOptions *options, double *palette, unsigned char *palette_u8,
                                     void *d_palette_map, int map_elem_bytes, unsigned char *d_quantized, int *exit_code) {
     frames_entry(true, frames, width, height, d_pixels, channels, d_weights, tile_size, palette_size, options, palette, palette_u8,
-                 d_palette_map, map_elem_bytes, d_quantized, exit_code);
+                 d_palette_map, map_elem_bytes, d_quantized, kBadFramesArgs, exit_code);
 }
 
 void patolette_amd_u8(size_t width, size_t height, const unsigned char *pixels, int channels, const double *weights,
                       double tile_size, size_t palette_size, const patolette__QuantizationOptions *options, double *palette,
                       unsigned char *palette_u8, void *palette_map, int map_elem_bytes, unsigned char *quantized, int *exit_code) {
-    u8_entry(false, width, height, pixels, channels, weights, tile_size, palette_size, options, palette, palette_u8, palette_map,
-             map_elem_bytes, quantized, exit_code);
+    frames_entry(false, 1, width, height, pixels, channels, weights, tile_size, palette_size, options, palette, palette_u8, palette_map,
+                 map_elem_bytes, quantized, kBadU8Args, exit_code);
 }
 
 void patolette_amd_u8_device(size_t width, size_t height, const unsigned char *d_pixels, int channels, const double *d_weights,
                              double tile_size, size_t palette_size, const patolette__QuantizationOptions *options, double *palette,
                              unsigned char *palette_u8, void *d_palette_map, int map_elem_bytes, unsigned char *d_quantized,
                              int *exit_code) {
-    u8_entry(true, width, height, d_pixels, channels, d_weights, tile_size, palette_size, options, palette, palette_u8, d_palette_map,
-             map_elem_bytes, d_quantized, exit_code);
+    frames_entry(true, 1, width, height, d_pixels, channels, d_weights, tile_size, palette_size, options, palette, palette_u8,
+                 d_palette_map, map_elem_bytes, d_quantized, kBadU8Args, exit_code);
 }
 
 // Independent images: up to six are in flight at once, each on its own engine (HIP stream + workspace) driven by
@@ -3537,10 +3397,8 @@ void patolette_amd_batch_u8(size_t count, size_t width, size_t height, const uns
                             const patolette__QuantizationOptions *options, double *const *palettes, unsigned char *const *palettes_u8,
                             void *const *palette_maps, int map_elem_bytes, unsigned char *const *quantized, int *exit_codes) {
     int v = validate(width, height, palette_size);
-    if (v == 0 && validate_u8(palette_size, channels, palette_maps ? (const void *)palette_maps : nullptr, map_elem_bytes) != 0) {
-        fprintf(stderr, "patolette_amd: bad channels / map_elem_bytes for the u8 entry point\n");
-        v = -1;
-    }
+    if (v == 0 && validate_u8(palette_size, channels, palette_maps ? (const void *)palette_maps : nullptr, map_elem_bytes) != 0)
+        fail_args(&v, -1, kBadU8Args);
     if (v != 0) { for (size_t i = 0; i < count; i++) exit_codes[i] = v; return; }
     batch_run(count, width, height, options, exit_codes, [&](Engine &E, size_t i) {
         run_u8(E, width, height, pixels[i], channels, weights ? weights[i] : nullptr, tile_size, palette_size, options, palettes[i],
@@ -3703,10 +3561,9 @@ int patolette_amd_dither(const double *colors, size_t width, size_t height, cons
     HIP_CHECK(hipMemcpy(E.src.p, colors, 3 * n * sizeof(double), hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(E.dpal.p, palette, 3 * k * sizeof(double), hipMemcpyHostToDevice));
     launch_dither(E.src.p, n, PAMD_COPY, width, height, E.dpal.p, palette, (int)k, E.dmap.p, 4, E.nn, E.stream);
-    E.stats.dither_segments = E.nn.dither_segments; E.stats.dither_repairs = E.nn.dither_repairs; E.stats.dither_rounds = E.nn.dither_rounds; E.stats.dither_through = E.nn.dither_through;
-    E.stats.dither_jumps = E.nn.dither_jumps; E.stats.dither_solo = E.nn.dither_solo;
+    copy_dither_stats(E);
     E.sync();
-    if (std::max(width, height) > 1) {
+    if (map_touched(true, width, height)) {
         std::vector<unsigned int> tmp(n);
         HIP_CHECK(hipMemcpy(tmp.data(), E.dmap.p, n * 4, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < n; i++) map[i] = tmp[i];

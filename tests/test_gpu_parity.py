@@ -631,7 +631,7 @@ def test_chunked_upload_with_overlapped_conversion(gpu, ob, monkeypatch, rows_ma
 
 @pytest.mark.parametrize("channels,weighted,hw", [(3, False, (61, 83)), (4, True, (97, 45)), (3, True, (33, 129))])
 def test_u8_entry_chunked_upload_with_overlapped_conversion(gpu, ob, monkeypatch, channels, weighted, hw):
-    """patolette_amd_u8 uploads large 8-bit images in chunks and converts each behind the next one's copy (run_u8: second stream,
+    """patolette_amd_u8 uploads large 8-bit images in chunks and converts each behind the next one's copy (upload_image: second stream,
     the statistics started by chunk 0 only); forced here onto small images of odd sizes, 3 and 4 bytes per pixel, with and without
     explicit weights: identical to the single-copy path and equal to the oracle fed with the by-hand conversion (README.md:156-158)."""
     import patolette_amd as p
