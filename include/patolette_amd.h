@@ -24,7 +24,8 @@ extern "C" {
 /* ---- device management ------------------------------------------------------------------ */
 int  patolette_amd_device_count(void);                 /* 0 if no usable HIP device */
 int  patolette_amd_set_device(int ordinal);            /* 0 ok */
-const char *patolette_amd_last_error(void);            /* message of the last failure on this thread */
+const char *patolette_amd_last_error(void);            /* message of the last failure on this thread (kept with the thread's engine:
+                                                          "" after patolette_amd_release_workspace or a change of device) */
 void *patolette_amd_malloc(size_t bytes);              /* hipMalloc; NULL on failure */
 void patolette_amd_free(void *dptr);
 int  patolette_amd_memcpy_h2d(void *dst, const void *src, size_t bytes);
@@ -475,7 +476,8 @@ int patolette_amd_debug_workspace(int flags);
 /* late growths counted since the library loaded (bit 1 of patolette_amd_debug_workspace) */
 unsigned long long patolette_amd_debug_late_growths(void);
 
-/* ---- per-kernel timing with HIP events on the launch stream ------------------------------ */
+/* ---- per-kernel timing with HIP events on the launch stream ------------------------------
+ * The timer is the calling thread's own: these calls switch, select and read the timing of launches made on this thread only. */
 void patolette_amd_profile_enable(int on);   /* also resets the accumulated numbers */
 /* restrict the timing to the kernel of this name (NULL or "" = every kernel): two event records per launch
  * cost ~7 us, so a throughput measurement times only the kernel it reports the roofline of */

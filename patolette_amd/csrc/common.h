@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -170,15 +171,21 @@ struct PinBuf {
 
 inline size_t ceil_div(size_t a, size_t b) { return (a + b - 1) / b; }
 
-// hipFuncSetAttribute applies to the current device: a once-flag per device (one process may drive several GPUs)
+// hipFuncSetAttribute applies to the current device: a once-step per device (one process may drive several GPUs).  Caller
+// threads arrive here together (one engine each), so the step runs under the lock and the device counts as done only after
+// the step has returned: a thread that finds `done` set may launch at once, one that does not waits for the step's end, and a
+// step that throws (HIP_CHECK) leaves the device not done for the next caller.  Warm path: one acquire load.
 struct PerDeviceOnce {
-    bool done[64] = {};
-    bool first() {
+    std::mutex mu;
+    std::atomic<bool> done[64] = {};
+    template <class F> void once(F &&step) {
         int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return true;
-        if (done[dev]) return false;
-        done[dev] = true;
-        return true;
+        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { step(); return; }
+        if (done[dev].load(std::memory_order_acquire)) return;
+        std::lock_guard<std::mutex> lk(mu);
+        if (done[dev].load(std::memory_order_relaxed)) return;
+        step();
+        done[dev].store(true, std::memory_order_release);
     }
 };
 

@@ -2160,12 +2160,12 @@ void kmeans_iterate(KMeansWork &w, size_t nx, int k, bool weighted, int niter, h
         HIP_CHECK(hipMemsetAsync(w.fsum.p, 0, 4 * (size_t)k * sizeof(unsigned long long), s));
         ablocks = (int)std::min<size_t>(std::max<size_t>(ceil_div(nx, (size_t)4096), 1), 2048);
         static PerDeviceOnce attr5;
-        if (attr5.first()) {
+        attr5.once([&] {
             HIP_CHECK(hipFuncSetAttribute((const void *)k_km_accum<true, int>, hipFuncAttributeMaxDynamicSharedMemorySize, 32 * kKMeansMaxK));
             HIP_CHECK(hipFuncSetAttribute((const void *)k_km_accum<false, int>, hipFuncAttributeMaxDynamicSharedMemorySize, 32 * kKMeansMaxK));
             HIP_CHECK(hipFuncSetAttribute((const void *)k_km_accum<true, unsigned char>, hipFuncAttributeMaxDynamicSharedMemorySize, 32 * kKMeansMaxK));
             HIP_CHECK(hipFuncSetAttribute((const void *)k_km_accum<false, unsigned char>, hipFuncAttributeMaxDynamicSharedMemorySize, 32 * kKMeansMaxK));
-        }
+        });
     }
     // the order-free update after any of the assignment kernels below (a8: one byte per sample, else an int)
     auto update_sums = [&](const bool a8) {
@@ -2194,7 +2194,7 @@ void kmeans_iterate(KMeansWork &w, size_t nx, int k, bool weighted, int niter, h
     const size_t lds_sct = (size_t)5 * k * sizeof(unsigned int);
     const size_t lds_sct_pair = (size_t)9 * k * sizeof(unsigned int) + (size_t)4 * (k + 64) * sizeof(float4);
     static PerDeviceOnce attr;
-    if (attr.first()) {
+    attr.once([&] {
         HIP_CHECK(hipFuncSetAttribute((const void *)k_km_assign_count<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * kKMeansMaxK * 4));
         HIP_CHECK(hipFuncSetAttribute((const void *)k_km_scatter<true, int>, hipFuncAttributeMaxDynamicSharedMemorySize, 5 * kKMeansMaxK * 4));
         HIP_CHECK(hipFuncSetAttribute((const void *)k_km_scatter<false, int>, hipFuncAttributeMaxDynamicSharedMemorySize, 5 * kKMeansMaxK * 4));
@@ -2202,7 +2202,7 @@ void kmeans_iterate(KMeansWork &w, size_t nx, int k, bool weighted, int niter, h
         HIP_CHECK(hipFuncSetAttribute((const void *)k_km_scatter<false, unsigned char>, hipFuncAttributeMaxDynamicSharedMemorySize, 5 * kKMeansMaxK * 4));
         HIP_CHECK(hipFuncSetAttribute((const void *)k_km_update<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 4096 * 4));
         HIP_CHECK(hipFuncSetAttribute((const void *)k_km_update<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 4096 * 4));
-    }
+    });
     if (!w.mt_seeded) { hipLaunchKernelGGL(k_km_mt_seed, 1, 1, 0, s, w.mt.p); w.mt_seeded = true; }   // the start of std::mt19937(1234), kept
     { KTIME("k_km_prep", s, 28.0 * k); hipLaunchKernelGGL(k_km_prep, (std::max(k, kKmFlagWords) + 255) / 256, 256, 0, s, w.cent.p, k, w.c4.p, w.flags.p); }
     // many samples: exact candidate pruning (the grid is rebuilt per iteration, ~0.1 ms, against ~1 ms of full scans per
@@ -2213,9 +2213,9 @@ void kmeans_iterate(KMeansWork &w, size_t nx, int k, bool weighted, int niter, h
     const int G = nx >= g64_min ? 64 : 32;
     if (use_lut) {
         static PerDeviceOnce attr2;
-        if (attr2.first()) {
+        attr2.once([&] {
             HIP_CHECK(hipFuncSetAttribute((const void *)k_km_assign_lut, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * kKMeansMaxK * 4));
-        }
+        });
         w.lut.reserve((size_t)G * G * G * 16); w.bkeys.reserve(kKmSlots * 6); w.grid.reserve(64 + sizeof(double));
         w.clist.reserve((size_t)(G * G * G / 64) * (2 + kKmCoarseMax));
         hipLaunchKernelGGL(k_km_bounds_init, 1, 256, 0, s, w.bkeys.p);
@@ -2235,10 +2235,10 @@ void kmeans_iterate(KMeansWork &w, size_t nx, int k, bool weighted, int niter, h
         // assignment), so the first iteration's `old` only has to be a valid byte: zeroed here rather than left as found.
         HIP_CHECK(hipMemsetAsync(w.assign.p, 0, nx, s));
         static PerDeviceOnce attr4;
-        if (attr4.first()) {
+        attr4.once([&] {
             HIP_CHECK(hipFuncSetAttribute((const void *)k_km_update_lists<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kKmDirectCap * 20));
             HIP_CHECK(hipFuncSetAttribute((const void *)k_km_update_lists<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kKmDirectCap * 20));
-        }
+        });
     }
     const bool use_mid = use_lut && G == 64 && k % 8 == 0;    // four-candidate table in LDS
     if (use_mid) w.mid.reserve(32 * 32 * 32);
@@ -2277,9 +2277,9 @@ void kmeans_iterate(KMeansWork &w, size_t nx, int k, bool weighted, int niter, h
                 const int nmid = 32 * 32 * 32;
                 const size_t lds_mid = ((size_t)nmid + 4 * 256 + 16 * 256) * 4 + (size_t)16 * kKmQueue * 16;
                 static PerDeviceOnce attr3;
-                if (attr3.first()) {
+                attr3.once([&] {
                     HIP_CHECK(hipFuncSetAttribute((const void *)k_km_assign_mid, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mid));
-                }
+                });
                 const int mblocks = std::min(num_cus(), (nchunks + 15) / 16);
                 KTIME("k_km_assign", s, 16.0 * nx);
                 hipLaunchKernelGGL(k_km_assign_mid, mblocks, 1024, lds_mid, s, ks, nx, w.c4.p, k, chunk_len, nchunks, (unsigned char *)w.assign.p, w.table.p,
@@ -2313,10 +2313,10 @@ void kmeans_iterate(KMeansWork &w, size_t nx, int k, bool weighted, int niter, h
                 const size_t lds_up = coop_on ? (size_t)4 * 4096 * sizeof(float) : 0;
                 const unsigned long long lm = coop_on ? long_min : ~0ULL;
                 static PerDeviceOnce attr6;
-                if (attr6.first()) {
+                attr6.once([&] {
                     HIP_CHECK(hipFuncSetAttribute((const void *)k_km_update<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 4096 * 4));
                     HIP_CHECK(hipFuncSetAttribute((const void *)k_km_update<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 4096 * 4));
-                }
+                });
                 if (weighted) hipLaunchKernelGGL((k_km_update<true, true>), k, 256, lds_up, s, w.sorted.p, w.rowtot.p, k, (unsigned long long)nx, w.cent.p, w.hassign.p, w.c4.p, w.ticket.p, w.mt.p, lm, w.hs.p);
                 else hipLaunchKernelGGL((k_km_update<false, true>), k, 256, lds_up, s, w.sorted.p, w.rowtot.p, k, (unsigned long long)nx, w.cent.p, w.hassign.p, w.c4.p, w.ticket.p, w.mt.p, lm, w.hs.p);
             }
@@ -2329,18 +2329,18 @@ void kmeans_iterate(KMeansWork &w, size_t nx, int k, bool weighted, int niter, h
             if (use_mid && chunk_len >= 4096 && k <= 256) {
                 constexpr size_t lds_ls = (size_t)(512 + 1024 + 4096 / 4 + 4 * 4096) * sizeof(unsigned int);
                 static PerDeviceOnce attr5;
-                if (attr5.first()) {
+                attr5.once([&] {
                     HIP_CHECK(hipFuncSetAttribute((const void *)k_km_scatter_lds<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ls));
                     HIP_CHECK(hipFuncSetAttribute((const void *)k_km_scatter_lds<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ls));
-                }
+                });
                 if (weighted) hipLaunchKernelGGL(k_km_scatter_lds<true>, nchunks, 256, lds_ls, s, ks, a8, nx, k, chunk_len, nchunks, w.table.p, w.rowtot.p, w.sorted.p);
                 else hipLaunchKernelGGL(k_km_scatter_lds<false>, nchunks, 256, lds_ls, s, ks, a8, nx, k, chunk_len, nchunks, w.table.p, w.rowtot.p, w.sorted.p);
             } else if (use_mid && chunk_len >= 2 * k) {
                 static PerDeviceOnce attr3;
-                if (attr3.first()) {
+                attr3.once([&] {
                     HIP_CHECK(hipFuncSetAttribute((const void *)k_km_scatter<true, unsigned char, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 9 * 256 * 4 + 4 * (256 + 64) * 16));
                     HIP_CHECK(hipFuncSetAttribute((const void *)k_km_scatter<false, unsigned char, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 9 * 256 * 4 + 4 * (256 + 64) * 16));
-                }
+                });
                 if (weighted) hipLaunchKernelGGL((k_km_scatter<true, unsigned char, true>), cblocks, 256, lds_sct_pair, s, ks, a8, nx, k, nbits, chunk_len, nchunks, w.table.p, w.rowtot.p, w.sorted.p);
                 else hipLaunchKernelGGL((k_km_scatter<false, unsigned char, true>), cblocks, 256, lds_sct_pair, s, ks, a8, nx, k, nbits, chunk_len, nchunks, w.table.p, w.rowtot.p, w.sorted.p);
             } else if (use_mid) {

@@ -809,7 +809,7 @@ static void launch_nn_lut(const double *d_colors, size_t plane_stride, size_t n,
             // CIELuv one, interleaved launches).  (Four pixels per lane with 4- or 8-byte map elements spill.)
             constexpr int P = sizeof(OutT) == 1 ? 4 : 2, WAVES = 16;
             static PerDeviceOnce attr_mid;
-            if (attr_mid.first()) HIP_CHECK(hipFuncSetAttribute((const void *)(k_nn_map_mid<OutT, P, WAVES>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mid_lds(WAVES)));
+            attr_mid.once([&] { HIP_CHECK(hipFuncSetAttribute((const void *)(k_nn_map_mid<OutT, P, WAVES>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mid_lds(WAVES))); });
             const int blocks = (int)std::min<size_t>((size_t)num_cus(), ceil_div(n, (size_t)64 * WAVES * P));
             KTIME("k_nn_map", s, (24.0 + sizeof(OutT)) * n);
             hipLaunchKernelGGL((k_nn_map_mid<OutT, P, WAVES>), blocks, 64 * WAVES, mid_lds(WAVES), s, NNSrcPlanes{d_colors, plane_stride}, n, d_pal, k, g, (const unsigned int *)w.mid.p,
@@ -829,9 +829,9 @@ static void launch_nn_lut(const double *d_colors, size_t plane_stride, size_t n,
             hipLaunchKernelGGL(k_nn_lut_build<unsigned short>, ncoarse, 64, 0, s, d_pal, k, g, l16, l16b, (const unsigned short *)w.clist.p, (unsigned int *)nullptr);
         }
         static PerDeviceOnce attr;
-        if (attr.first()) {
+        attr.once([&] {
             HIP_CHECK(hipFuncSetAttribute((const void *)(k_nn_map_lut<OutT, unsigned short>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 4096 * 8));
-        }
+        });
         KTIME("k_nn_map", s, (24.0 + sizeof(OutT)) * n);
         hipLaunchKernelGGL((k_nn_map_lut<OutT, unsigned short>), stream_blocks(n, 8), 256, lds, s, d_colors, plane_stride, n, d_pal, k, g, (const unsigned short *)l16, (const unsigned short *)l16b, out);
     }
@@ -919,7 +919,7 @@ static void launch_nn_mid_u8(const unsigned char *d_px, int channels, size_t n, 
     constexpr size_t lds = mid_lds(WAVES, NNSrcU8::kLdsDyn + NNSrcU8::kLdsStatic, NNSrcU8::kLdsDyn);
     static_assert(lds + NNSrcU8::kLdsStatic <= 163840, "the CU's LDS");
     static PerDeviceOnce attr_mid;
-    if (attr_mid.first()) HIP_CHECK(hipFuncSetAttribute((const void *)(k_nn_map_mid<OutT, P, WAVES, NNSrcU8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    attr_mid.once([&] { HIP_CHECK(hipFuncSetAttribute((const void *)(k_nn_map_mid<OutT, P, WAVES, NNSrcU8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); });
     const int blocks = (int)std::min<size_t>((size_t)num_cus(), ceil_div(n, (size_t)64 * WAVES * P));
     KTIME("k_nn_map_u8", s, ((double)channels + sizeof(OutT)) * n);
     hipLaunchKernelGGL((k_nn_map_mid<OutT, P, WAVES, NNSrcU8>), blocks, 64 * WAVES, lds, s, NNSrcU8{d_px, (size_t)channels}, n, d_pal, k, g, (const unsigned int *)w.mid.p,

@@ -2585,6 +2585,10 @@ static bool upload_image(Engine &E, const Pixels &host, size_t N, bool weight_pl
     }
     HIP_CHECK(hipEventRecord(E.ev_join, E.stream2));
     HIP_CHECK(hipStreamWaitEvent(s, E.ev_join, 0));
+    // A stream whose LAST operation is a wait on an event keeps answering hipErrorNotReady to hipStreamQuery, even after
+    // hipStreamSynchronize on it has returned; a record behind the wait makes the stream's state readable again (the late-growth
+    // count of patolette_amd_debug_workspace asks exactly that question).  Both pieces' waits on ev_up[0] are enqueued by now.
+    HIP_CHECK(hipEventRecord(E.ev_up[0], s));
     return true;
 }
 

@@ -1083,7 +1083,7 @@ static void launch_hist_fix(const QuantBuffers &qb, const Tile *d_tiles, int nti
     constexpr int NQ = W ? 14 : 10;
     const size_t lds = (size_t)NQ * kBuckets * sizeof(unsigned long long) + kBuckets * (sizeof(unsigned int) + sizeof(unsigned long long));
     static PerDeviceOnce attr_set;
-    if (attr_set.first()) HIP_CHECK(hipFuncSetAttribute((const void *)k_hist_fix<W, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    attr_set.once([&] { HIP_CHECK(hipFuncSetAttribute((const void *)k_hist_fix<W, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); });
     KTIME("k_hist_gq", s, (W ? 34.0 : 26.0) * px);
     const int g = std::min(ntiles, 256 * (W ? 2 : 3));       // resident blocks per CU by LDS footprint (46 / 63 KB)
     hipLaunchKernelGGL((k_hist_fix<W, true>), g, 512, lds, s, qb, d_tiles, ntiles, d_nodes, d_hist, d_hsize, d_hcount, from_end ? 1 : 0);
@@ -1097,7 +1097,7 @@ static void launch_hist_t(const QuantBuffers &qb, const Tile *d_tiles, int ntile
     constexpr int NQ = GQ ? (W ? 14 : 10) : (W ? 4 : 3);
     size_t lds = (size_t)NQ * 2 * kBuckets * sizeof(double) + kBuckets * (sizeof(unsigned int) + sizeof(unsigned long long));
     static PerDeviceOnce attr_set;
-    if (attr_set.first()) HIP_CHECK(hipFuncSetAttribute((const void *)k_hist<W, GQ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    attr_set.once([&] { HIP_CHECK(hipFuncSetAttribute((const void *)k_hist<W, GQ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); });
     KTIME_DYN(GQ ? "k_hist_gq" : "k_hist_lq", s, (W ? 34.0 : 26.0), px, px_src);
     // resident blocks per CU by LDS footprint (4 for the local quantiser's 29 KB, 1 for the global quantiser's 82+ KB);
     // each block walks its run of tiles and flushes once per node run
