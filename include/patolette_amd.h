@@ -61,7 +61,9 @@ void patolette_amd_device(size_t width, size_t height, const double *d_data, con
  * unweighted.  Extra exit codes (messages via get_patolette_exit_code_info_message): -5 the image
  * shape cannot be processed (the reference raises for it too: a side <= 3 pixels, fewer than 100
  * pixels, or a border band of floor(0.1*sqrt(w*h)) pixels that does not fit), -6 a border band has
- * a singular colour covariance (numpy raises LinAlgError in the reference). */
+ * a singular colour covariance (numpy raises LinAlgError in the reference), -7 the saliency map is
+ * degenerate: one of the maxima it is normalised by is 0 or not finite (an image whose channel mean
+ * is constant has barrier distance 0 everywhere), for which the reference's weights are all NaN. */
 void patolette_amd_quantize(size_t width, size_t height, const double *data, const double *weights,
                             double tile_size, size_t palette_size,
                             const patolette__QuantizationOptions *options, double *palette,
@@ -74,7 +76,7 @@ void patolette_amd_quantize_rows(size_t width, size_t height, const double *rows
                                  const patolette__QuantizationOptions *options, double *palette,
                                  size_t *palette_map, int *exit_code);
 /* the stage alone, host buffers: data as for patolette(); weights_out[width*height].  Returns 0,
- * -1 (HIP error), -2 (shape), -3 (singular covariance). */
+ * -1 (HIP error), -2 (shape), -3 (singular covariance), -4 (degenerate map: what -7 stands for above). */
 int patolette_amd_saliency_weights(size_t width, size_t height, const double *data, double tile_size,
                                    double *weights_out);
 

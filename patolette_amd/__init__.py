@@ -37,8 +37,9 @@ bad_tile_size = 'tile_size parameter expected to be in the range [0, inf]'
 
 def _raise_saliency(code, message):
     """Exit codes of the saliency stage: the reference raises Python exceptions in the same situations
-    (patolette.pyx:157-158 / :228-232 shape, numpy LinAlgError for a singular border covariance)."""
-    if code == -5:
+    (patolette.pyx:157-158 / :228-232 shape, numpy LinAlgError for a singular border covariance).  -7, the degenerate map, is the
+    one case where the reference raises nothing: it goes on with all-NaN weights (0 / 0 at patolette.pyx:291)."""
+    if code == -5 or code == -7:
         raise ValueError(message)
     if code == -6:
         raise np.linalg.LinAlgError("Singular matrix (%s)" % message)
@@ -128,6 +129,8 @@ def saliency_weights(width, height, colors, tile_size=512):
         _raise_saliency(-5, L.get_patolette_exit_code_info_message(-5).decode('UTF-8'))
     if rc == -3:
         _raise_saliency(-6, L.get_patolette_exit_code_info_message(-6).decode('UTF-8'))
+    if rc == -4:
+        _raise_saliency(-7, L.get_patolette_exit_code_info_message(-7).decode('UTF-8'))
     if rc != 0:
         raise RuntimeError(_native.last_error())
     return out

@@ -112,6 +112,10 @@ template <> struct WsPoison<float> {
     static void dev(float *p, size_t a, size_t b) { ws_poison_dev(p + a, (b - a) * sizeof(float)); }
     static void host(float *, size_t, size_t) {}
 };
+template <> struct WsPoison<float4> {            // the saliency stage's barrier state: its skewed copy has cells no kernel writes
+    static void dev(float4 *p, size_t a, size_t b) { ws_poison_dev(p + a, (b - a) * sizeof(float4)); }
+    static void host(float4 *, size_t, size_t) {}
+};
 
 // ---- simple device buffer with capacity reuse ----
 template <typename T>

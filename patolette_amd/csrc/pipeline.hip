@@ -2465,6 +2465,7 @@ static const double *derive_weights(Engine &E, const double *d_f64, const unsign
     E.ms_saliency = now_ms() - t0;
     if (rc == kSalBadShape) throw CodeError(-5, "saliency weights: image shape not supported");
     if (rc == kSalSingular) throw CodeError(-6, "saliency weights: singular border covariance");
+    if (rc == kSalDegenerate) throw CodeError(-7, "saliency weights: degenerate saliency map");
     return E.wsal.p;
 }
 
@@ -2952,12 +2953,15 @@ static int validate_u8(size_t K, int channels, const void *map_out, int map_elem
 // ============================================================================================
 using namespace pamd;
 
-static const char *kMessages[8] = {                                        // patolette.c:32-38, then the additive codes
+static const char *kMessages[9] = {                                        // patolette.c:32-38, then the additive codes
     "Quantization successful.", "Internal quantization error.", "Image dimensions should be greater than 0.",
     "Palette size should be greater than 0.", "Image dimensions are too big.",
     "Saliency weights: image shape not supported (needs more than 3 pixels per side, at least 100 pixels, and a "
     "border band that fits).",
-    "Saliency weights: a border band has a singular colour covariance.", nullptr};
+    "Saliency weights: a border band has a singular colour covariance.",
+    "Saliency weights: the saliency map is degenerate (one of its normalising maxima is 0 or not finite, as for a constant "
+    "channel mean); the reference's weights are NaN for this image.",
+    nullptr};
 
 #define PAMD_GUARD_BEGIN try { Engine &E = engine(); E.init(); (void)E;
 #define PAMD_GUARD_END(ret_fail)                                             \
@@ -3105,7 +3109,7 @@ int patolette_amd_saliency_weights(size_t width, size_t height, const double *da
         return 0;
     } catch (const CodeError &ex) {
         engine().last_error = ex.what();
-        return ex.code == -5 ? kSalBadShape : kSalSingular;
+        return ex.code == -5 ? kSalBadShape : ex.code == -6 ? kSalSingular : kSalDegenerate;
     } catch (const std::exception &ex) {
         engine().last_error = ex.what();
         fprintf(stderr, "patolette: %s\n", ex.what());
@@ -3122,7 +3126,7 @@ int patolette_amd_mbd(size_t rows, size_t cols, const float *img, int iters, flo
 }
 
 const char *get_patolette_exit_code_info_message(int exit_code) {
-    if (exit_code > 0 || exit_code < -6) return nullptr;
+    if (exit_code > 0 || exit_code < -7) return nullptr;
     return kMessages[-1 * exit_code];
 }
 

@@ -17,6 +17,7 @@ struct SalDev {                      // device-resident scalars of one saliency 
     unsigned long long maxkey[kSalMax][kStatSlots];
     double mx[kSalMax];              // folded maxima (rounded through f32 where the reference holds a `cdef float`)
     int singular;                    // a border band has a singular covariance (numpy raises LinAlgError)
+    int degenerate;                  // a folded maximum -- a normaliser of the map -- is 0 or not finite (the reference's weights are NaN)
 };
 
 struct SalWork {
@@ -31,12 +32,14 @@ struct SalWork {
 };
 
 // error codes of the stage
-constexpr int kSalOk = 0, kSalBadShape = -2, kSalSingular = -3;
+constexpr int kSalOk = 0, kSalBadShape = -2, kSalSingular = -3, kSalDegenerate = -4;
 
 // the stage's workspace for an image of this size, reserved before the caller enqueues anything (no regrowth behind queued work)
 void saliency_reserve(SalWork &w, size_t width, size_t height);
 // Returns kSalBadShape without touching the device when the reference's get_weights cannot process the
 // shape.  On success d_weights (width*height f64, device) holds 1 + sal^2 * N / tile_size^2.
+// kSalSingular: a border band's covariance has no inverse.  kSalDegenerate: one of the maxima the map is divided by is 0 or not
+// finite (a constant channel mean: barrier distance 0 everywhere, 0 / 0), so the reference's weights are NaN; d_weights is then garbage.
 // d_f64 planar (channels >= 0) or (N,3) row-major (channels < 0); d_u8 interleaved with `channels` bytes per pixel
 int saliency_weights(SalWork &w, const double *d_f64, const unsigned char *d_u8, int channels, size_t width, size_t height,
                      double tile_size, double *d_weights, hipStream_t s);

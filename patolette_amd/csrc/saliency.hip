@@ -98,7 +98,7 @@ __global__ void k_sal_init(SalDev *d) {
     for (int i = t; i < kStatSlots * 4 * 3 * 2; i += blockDim.x) (&d->sum[0][0][0][0])[i] = 0.0;
     for (int i = t; i < kStatSlots * 4 * 6 * 2; i += blockDim.x) (&d->cov[0][0][0][0])[i] = 0.0;
     for (int i = t; i < kSalMax * kStatSlots; i += blockDim.x) (&d->maxkey[0][0])[i] = f64_key(-INFINITY);
-    if (t == 0) d->singular = 0;
+    if (t == 0) { d->singular = 0; d->degenerate = 0; }
 }
 
 // sums of Lab over the four border bands (np.mean(..., axis=(0,1)), patolette.pyx:221-224); blockIdx.y = band
@@ -234,6 +234,9 @@ __global__ void k_sal_fold(SalDev *d, int first, int count, int as_f32) {
     double m = key_f64(best);
     if (as_f32) m = (double)(float)m;
     d->mx[first + k] = m;
+    // every folded maximum is a divisor of the next pass: 0 (a constant channel mean leaves the barrier distance 0 everywhere) or a
+    // non-finite one (fmax drops the NaNs of 0 / 0, the maximum stays -inf) makes the reference's weights NaN
+    if (m == 0.0 || !isfinite(m)) atomicExch(&d->degenerate, 1);
 }
 
 // pass A: maxima of the four contrasts (patolette.pyx:272-275) and of the barrier distance (:289)
@@ -655,6 +658,7 @@ int saliency_weights(SalWork &w, const double *d_f64, const unsigned char *d_u8,
     HIP_CHECK(hipStreamSynchronize(s));
     if (stalled) throw HipError("patolette_amd: the raster scan gave up waiting for a strip (device oversubscribed?)");
     if (w.host.p->singular) return kSalSingular;
+    if (w.host.p->degenerate) return kSalDegenerate;
     return kSalOk;
 }
 

@@ -177,7 +177,7 @@ def quantize_batch_sharded(width, height, images, palette_size, dist=None, quant
     if quantize_fn is None:
         from . import _native
         L = _native.lib()
-        for c in range(-6, 1):
+        for c in range(-7, 1):
             m = L.get_patolette_exit_code_info_message(c)
             if m:
                 messages[c] = m.decode("UTF-8")
@@ -204,7 +204,7 @@ def quantize_batch_sharded(width, height, images, palette_size, dist=None, quant
 
         def fail(j, e):
             # Nothing an image (or its loader) raises may leave this rank before the gathers: the others would wait for ever.
-            # Only what the SALIENCY STAGE raises keeps its own exit code -- the binding turns codes -5 / -6 into a ValueError /
+            # Only what the SALIENCY STAGE raises keeps its own exit code -- the binding turns codes -5 / -7 / -6 into a ValueError /
             # LinAlgError carrying the library's message for that code (patolette_amd._raise_saliency); a ValueError from a loader,
             # a shape check or an unknown keyword is the reference's "internal error" (-1) with its text, as on the RCCL path.
             text = str(e)
@@ -213,6 +213,8 @@ def quantize_batch_sharded(width, height, images, palette_size, dist=None, quant
                 code = -6
             elif isinstance(e, ValueError) and messages.get(-5) and text == messages[-5]:
                 code = -5
+            elif isinstance(e, ValueError) and messages.get(-7) and text == messages[-7]:
+                code = -7
             errors[idx[j]] = text if code != -1 else "%s: %s" % (type(e).__name__, e)
             put(j, (False, None, None, text), code)
 
@@ -279,7 +281,7 @@ def quantize_batch_sharded(width, height, images, palette_size, dist=None, quant
             msg = messages.get(code, MESSAGES[-1])
             if code != 0:
                 why = bytes(g_txt[r][j]).rstrip(b"\0").decode("UTF-8", "replace")
-                msg = why if why and code in (-5, -6) else (msg + " (" + why + ")" if why else msg)
+                msg = why if why and code in (-5, -6, -7) else (msg + " (" + why + ")" if why else msg)
                 out.append((False, None, None, msg))
             else:
                 m = None

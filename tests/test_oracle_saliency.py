@@ -6,7 +6,7 @@ cross-formulation checks, not a pinning against the reference's own output (orac
 import numpy as np
 import pytest
 
-from tests.util import scene
+from tests.util import constant_mean_image, posterised_noise, scene, tie_images
 
 
 def test_rgb2lab_known_answers():
@@ -59,6 +59,32 @@ def test_mbd_c_matches_python_definition(ob, rows, cols):
         got = ob.mbd(img, iters)
         assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
     assert ob.mbd(np.zeros((3, 9), dtype=np.float32)) is None
+
+
+@pytest.mark.parametrize("rows,cols", [(4, 4), (5, 9), (17, 23), (40, 37)])
+def test_mbd_c_matches_python_definition_on_ties(ob, rows, cols):
+    """The checker itself where the visit's tie rules decide (`d <= b1 and d <= b2`, `b1 <= b2`): posterised noise, a flat image,
+    integer ramps, a checkerboard, one bright pixel, a step edge.  Tie-free noise (above) cannot tell `<=` from `<`.
+    iters = 0 is included: orc_mbd takes it and returns the initial state (0 on the frame, +inf inside)."""
+    contents = dict(tie_images(rows, cols), posterised=posterised_noise(rows, cols, rows * 100 + cols))
+    for name, img in contents.items():
+        for iters in (0, 1, 2, 3, 4):
+            want = _mbd_python(img, iters)
+            got = ob.mbd(img, iters)
+            assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (name, iters)
+
+
+def test_get_weights_is_nan_for_a_constant_channel_mean():
+    """What the product's exit code -7 (degenerate saliency map) stands for: colours that vary -- the border covariances are
+    well conditioned -- while their channel mean is one constant.  The barrier distance is then 0 everywhere, `sal / sal_max` is
+    0 / 0, and every weight the reference's get_weights returns is NaN."""
+    from oracle import saliency
+    for rows, cols in ((40, 40), (67, 130)):
+        img = constant_mean_image(rows, cols, rows + cols)
+        assert np.array_equal(np.unique(np.mean(img, axis=2).astype(np.float32)), [np.float32(0.5)])
+        with np.errstate(all="ignore"):
+            w = saliency.get_weights(img, 20.0)
+        assert w.shape == (rows * cols,) and np.all(np.isnan(w))
 
 
 def test_get_weights_properties():

@@ -52,3 +52,33 @@ def scene(rows, cols, seed):
         inside = ((yy - cy) / ry) ** 2 + ((xx - cx) / rx) ** 2 < 1.0
         img[inside] = rng.uniform(0.0, 1.0, size=3)
     return np.clip(img + rng.normal(0.0, 0.02, img.shape), 0.0, 1.0)
+
+
+def posterised_noise(rows, cols, seed, levels=8):
+    """(rows, cols) float32 noise on `levels` evenly spaced values in [0,1]: almost every comparison a raster scan makes is a tie."""
+    rng = np.random.default_rng(seed)
+    return (rng.integers(0, levels, size=(rows, cols)) / (levels - 1)).astype(np.float32)
+
+
+def tie_images(rows, cols):
+    """name -> (rows, cols) float32 images whose minimum-barrier scans are decided by exact ties almost everywhere."""
+    yy, xx = np.mgrid[0:rows, 0:cols]
+    bright = np.full((rows, cols), 0.25, dtype=np.float32)
+    bright[rows // 2, cols // 2] = 1.0
+    return {
+        "flat": np.full((rows, cols), 0.5, dtype=np.float32),
+        "hramp": xx.astype(np.float32),
+        "vramp": yy.astype(np.float32),
+        "diag": (xx + yy).astype(np.float32),
+        "checker": ((xx + yy) & 1).astype(np.float32),
+        "bright": bright,
+        "step": (xx >= cols // 2).astype(np.float32),
+    }
+
+
+def constant_mean_image(rows, cols, seed, values=(0.25, 0.5, 0.75)):
+    """(rows, cols, 3) float64: every pixel a random permutation of `values`, so the channel mean is one constant while the
+    colours -- and the border bands' covariances -- are well spread."""
+    rng = np.random.default_rng(seed)
+    order = np.argsort(rng.random((rows, cols, 3)), axis=2)
+    return np.asarray(values, dtype=np.float64)[order]
