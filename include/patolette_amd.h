@@ -170,7 +170,7 @@ void patolette_amd_frames_u8_device(size_t frames, size_t width, size_t height, 
  *       patolette_amd_frames_u8() counts them); every quantiser field is 0.  patolette_amd_last_map_palette: the palette in the map's space.
  * Hence: a pixel whose bytes equal a palette_u8 entry's takes the same conversion of the same value -- in the reference's arithmetic it is
  * at distance exactly 0 from that entry (here the pixels are converted on the device and the palette on the host, which agree to the
- * 0.51 ulp of patolette_amd_pow: far below what separates two distinct byte rows); remapping the quantized image of an 8-bit call onto
+ * 0.52 ulp of patolette_amd_pow: far below what separates two distinct byte rows); remapping the quantized image of an 8-bit call onto
  * that call's palette_u8 (distinct rows) returns that call's map and image, dither on or off.
  * NOT promised: that a remap with the F64 palette some earlier call returned is bit for bit that call's own map.  The returned palette
  * has been through the map space -> sRGB conversion, and the way back costs an ulp or two: on the CPU reference this moved 0 of
@@ -349,7 +349,7 @@ int patolette_amd_principal_axis(const double cov6[6], double axis[3]);
 /* the same solver as the DEVICE runs it inside the split loop's control kernel (one problem per lane): `count` column-major 3x3
  * matrices in, w (3 per problem), z (9 per problem) and LAPACK's info out; host buffers.  Returns 0, or -1 on a HIP error. */
 int patolette_amd_eigen_sym3_device(const double *a_colmajor, size_t count, double *w, double *z, int *info);
-/* out[i] = pow(x[i], y) as the colour conversions evaluate it on the device (x >= 0; <= 0.51 ulp) */
+/* out[i] = pow(x[i], y) as the colour conversions evaluate it on the device (x >= 0; <= 0.52 ulp) */
 int patolette_amd_pow(const double *x, double y, double *out, size_t n);
 
 enum {

@@ -19,10 +19,11 @@ struct ConvertStats {                // filled by k_convert / k_weight_stats (or
     unsigned int nonfinite_f32;      // some converted value is NaN / Inf once cast to float (faiss Clustering.cpp:295-304 scans for that)
 };
 
-// pow(x, y) for the conversions: x >= 0 (anything else returns what libm returns: NaN for x < 0 with a non-integer y),
-// any finite y.  The conversions spend nine pow() per pixel (ICtCp) and the library routine costs ~250 instructions;
+// pow(x, y) for the conversions: x >= 0 (anything else returns what libm returns: NaN for x < 0 with a non-integer y, the signed
+// power of |x| with an integer one; only pow(-0, odd y) is +0 where libm has -0, and no conversion can ask for it), any finite y.
+// The conversions spend nine pow() per pixel (ICtCp) and the library routine costs ~250 instructions;
 // this one ~70: log2 by a 128-entry table + degree-8 series, the product y*log2(x) and the argument of exp2 carried
-// as double-double, exp2 by a 64-entry table + degree-7 series (tables: tools/gen_pow_tables.py).  Error <= 0.51 ulp:
+// as double-double, exp2 by a 64-entry table + degree-7 series (tables: tools/gen_pow_tables.py).  Error <= 0.52 ulp:
 // 99.8 % of results are bit-identical to glibc's correctly rounded pow, the rest are its neighbours.
 // The two tables (4 KB) are read at data-dependent places in the middle of every pow: from global memory that is an L1 round
 // trip on the critical path, nine times in a row per ICtCp pixel.  A translation unit that defines PAMD_POW_TABLES_IN_LDS before
@@ -50,8 +51,14 @@ __device__ __forceinline__ double horner_sc(const double z, const double acc, co
 }
 __device__ __forceinline__ double pamd_pow(double x, double y) {
     using namespace powtab;
-    if (!(x > 0.0)) return x == 0.0 ? (y > 0 ? 0.0 : (y == 0 ? 1.0 : INFINITY)) : NAN;
-    if (isinf(x)) return y > 0 ? INFINITY : (y == 0 ? 1.0 : 0.0);
+    bool neg = false;                                                        // the result is -pow(-x, y): x < 0 and y an odd integer
+    if (!(x > 0.0)) {
+        if (x == 0.0) return y > 0 ? 0.0 : (y == 0 ? 1.0 : INFINITY);
+        if (!(x < 0.0 && y == __builtin_rint(y))) return NAN;                // (a non-integer constant y folds all of this to NAN)
+        neg = 0.5 * y != __builtin_rint(0.5 * y);
+        x = -x;
+    }
+    if (isinf(x)) { const double r = y > 0 ? INFINITY : (y == 0 ? 1.0 : 0.0); return neg ? -r : r; }
     const double m = __builtin_amdgcn_frexp_mant(x) * 2.0;                 // [1, 2)
     const int e = __builtin_amdgcn_frexp_exp(x) - 1;
     const int i = (int)((m - 1.0) * 128.0) & 127;                           // (already in 0..127: the mask tells the compiler, whose full
@@ -66,15 +73,16 @@ __device__ __forceinline__ double pamd_pow(double x, double y) {
     const double poly = (z * z) * horner_sc(z, horner_sc(z, horner_sc(z, horner_sc(z, horner_sc(z, horner_sc(z, kL8, kL7), kL6), kL5), kL4), kL3), kL2);
     const double Ll = ((((err + ae) + zh * kInvLn2Lo) + zl * kInvLn2Hi) + Tlo) + (poly + (2 * kL2) * (zh * zl));
     const double Ph = y * Lh, Pl = __builtin_fma(y, Lh, -Ph) + y * Ll;       // y * log2(x) = Ph + Pl
-    if (Ph > 1100.0) return INFINITY;
-    if (Ph < -1200.0) return 0.0;
+    if (Ph > 1100.0) return neg ? -INFINITY : INFINITY;
+    if (Ph < -1200.0) return neg ? -0.0 : 0.0;
     const double kd = __builtin_rint(Ph * 64.0);
     const double f = (Ph - kd * 0.015625) + Pl;                              // the subtraction is exact
     const int k = (int)kd;                                                   // |kd| <= 1200 * 64: one conversion (a 64-bit one costs six)
     const int j = k & 63, n = k >> 6;
     const double q = f * horner_sc(f, horner_sc(f, horner_sc(f, horner_sc(f, horner_sc(f, horner_sc(f, kE7, kE6), kE5), kE4), kE3), kE2), kE1);
     const double Th = PAMD_POW_EXP[j][0], Tl = PAMD_POW_EXP[j][1];
-    return ldexp(Th + __builtin_fma(Th, q, Tl), n);
+    const double res = ldexp(Th + __builtin_fma(Th, q, Tl), n);
+    return neg ? -res : res;
 }
 
 namespace dc {
@@ -85,10 +93,10 @@ __device__ constexpr double c1 = 0.8359375, c2 = 18.8515625, c3 = 18.6875;
 // a / D for a constant D, correctly rounded in three instructions instead of the ~20 of the generic IEEE sequence:
 // y = RN(1/D) (folded at compile time), q = RN(a y), r = a - q D (exact, one FMA), result RN(q + r y) = RN(a / D)
 // (Markstein's theorem; checked against exact rational arithmetic for these divisors).  The residual must not underflow, so
-// operands below 1e-200 take the generic division.
+// operands below 1e-200 take the generic division; so do infinities (the residual of an infinite quotient is NaN) and NaN.
 __device__ __forceinline__ double div_const(const double a, const double D) {
     const double y = 1.0 / D;
-    if (__builtin_expect(fabs(a) < 1e-200 && a != 0.0, 0)) return a / D;
+    if (__builtin_expect(!(fabs(a) >= 1e-200 && fabs(a) < INFINITY) && a != 0.0, 0)) return a / D;
     const double q = a * y;
     const double r = __builtin_fma(-q, D, a);
     return __builtin_fma(r, y, q);
