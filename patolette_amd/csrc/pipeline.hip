@@ -25,6 +25,7 @@
 #include "quant.h"
 #include "rgba.h"
 #include "compact.h"
+#include "split_frontier.h"
 
 namespace pamd {
 
@@ -229,11 +230,7 @@ constexpr int kLqNodeCap = 16 * kLqDevMaxK + 256;     // candidate-tree nodes; b
 constexpr int kLqRoundCap = 512;                      // nodes evaluated per round (more candidates wait for the next one)
 constexpr int kLqMaxRounds = 96;
 
-struct LqRec {
-    double val;                                       // the split's benefit once known, else the bound `ub`
-    int left;                                         // left child (right = +1) once the node is in a round, else -1
-    int kn;                                           // known: never splits (one member, solver failed) or its split is evaluated
-};
+// (LqRec, the record the device leaves per node for the replay: split_frontier.h)
 struct LqCen { double mean[3]; double gn; };          // what PALETTE_create needs of a node (create.c:11-33) + its member count
 struct LqHead {                                       // copied to the host at every check
     int done, error, rounds, nnodes, neval, pad;
@@ -555,7 +552,6 @@ __global__ __launch_bounds__(256) void k_lq_export(const LqCtl *c, LqHead *head,
 
 // the split trace's records of a device-driven call, made when somebody asks for them (patolette_amd_last_split_trace): one thread
 // per commit of the replay
-struct LqCommit { int row, node, new_row, left; };
 __global__ void k_lq_trace(const NodeDev *nodes, const LqCommit *commits, int n, patolette_amd__SplitRecord *out) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
@@ -989,8 +985,7 @@ struct Engine {
     PinBuf<NodeIn> h_stage_in;
     PinBuf<NodeOut> h_stage_out;
     PinBuf<int> h_ids, h_ids_get;
-    PinBuf<Tile> h_tilesA, h_tilesP;
-    PinBuf<int> h_round, h_tile0;
+    PinBuf<int> h_round;
     PinBuf<double> h_dbl;
     PinBuf<unsigned char> h_bytes, h_packet, h_mapstage;
     DevBuf<unsigned char> packet;
@@ -1183,24 +1178,6 @@ struct HNode {
     double ub = 0;
 };
 
-static void build_tiles(const std::vector<int> &round, const std::vector<HNode> &hn, int tile, std::vector<Tile> &out,
-                        std::vector<int> *tile0) {
-    out.clear();
-    if (tile0) tile0->clear();
-    for (size_t r = 0; r < round.size(); r++) {
-        const HNode &nd = hn[round[r]];
-        if (tile0) tile0->push_back((int)out.size());
-        for (unsigned long long o = 0; o < nd.n; o += (unsigned long long)tile) {
-            Tile t;
-            t.start = nd.begin + o;
-            t.count = (unsigned)std::min<unsigned long long>((unsigned long long)tile, nd.n - o);
-            t.node = (unsigned)round[r];
-            out.push_back(t);
-        }
-    }
-    if (tile0) tile0->push_back((int)out.size());
-}
-
 static NodeIn make_nodedev(const HNode &h, const Bounds &b) {
     NodeIn d;
     std::memset(&d, 0, sizeof d);
@@ -1216,21 +1193,6 @@ static NodeIn make_nodedev(const HNode &h, const Bounds &b) {
 
 // Host staging buffers are pinned and one per purpose; every round ends with a stream sync (get_nodes), so a
 // buffer is never rewritten while an earlier async copy from it is still in flight.
-static void upload_tiles(Engine &E, const std::vector<Tile> &t, DevBuf<Tile> &dst, PinBuf<Tile> &stage) {
-    if (t.empty()) return;
-    dst.reserve(t.size());
-    stage.reserve(t.size());
-    std::memcpy(stage.p, t.data(), t.size() * sizeof(Tile));
-    HIP_CHECK(hipMemcpyAsync(dst.p, stage.p, t.size() * sizeof(Tile), hipMemcpyHostToDevice, E.stream));
-}
-static void upload_ints(Engine &E, const std::vector<int> &v, DevBuf<int> &dst, PinBuf<int> &stage) {
-    if (v.empty()) return;
-    dst.reserve(v.size());
-    stage.reserve(v.size());
-    std::memcpy(stage.p, v.data(), v.size() * sizeof(int));
-    HIP_CHECK(hipMemcpyAsync(dst.p, stage.p, v.size() * sizeof(int), hipMemcpyHostToDevice, E.stream));
-}
-
 static void put_nodes(Engine &E, const std::vector<int> &ids, const std::vector<NodeIn> &recs) {
     const int n = (int)ids.size();
     if (!n) return;
@@ -1313,6 +1275,30 @@ static void leaf_bound(HNode &h) {
     if (b == b && b < h.ub) h.ub = b;                              // NaN / larger: keep the distortion
 }
 
+// The element counts of the quantisers' tables, from three inputs: the pixels on this GPU, the plane count and the nodes a round may
+// hold -- 1 for the root, nr for a round of the host-driven split loop, kLqRoundCap for the device-driven one.  A round of several
+// nodes has up to one partial tile per node on top of the image's own.
+struct QuantSizes {
+    size_t bufA, bufB, bkt, tilesA, tilesP, tilecnt, tileoff, hist, hsize, hcount, lut;
+    QuantSizes(size_t pixels, size_t planes, size_t nodes) {
+        const size_t slack = nodes > 1 ? nodes : 0;
+        bufA = bufB = planes * pixels + 64;                      // + the slack k_scatter_bin's pixel-less lanes store to
+        bkt = pixels;
+        tilesA = ceil_div(pixels, (size_t)kTileA) + slack; tilesP = ceil_div(pixels, (size_t)kTileP) + slack;
+        tilecnt = tileoff = tilesP * kMaxChildren;
+        hist = std::max(hist_slot_doubles(), (size_t)kNQ_LQ * 2 * kBuckets * nodes);
+        hsize = hcount = lut = nodes * kBuckets;
+    }
+};
+// DevBuf::reserve frees the old allocation: call this only where the stream holds no queued work, or where an earlier call has
+// reserved as much already (a no-op then)
+static void reserve_quant_tables(Engine &E, const QuantSizes &z, const char *file = __builtin_FILE(), int line = __builtin_LINE()) {
+    E.bufA.reserve(z.bufA, file, line); E.bufB.reserve(z.bufB, file, line); E.bkt.reserve(z.bkt, file, line);
+    E.tilesA.reserve(z.tilesA, file, line); E.tilesP.reserve(z.tilesP, file, line);
+    E.tilecnt.reserve(z.tilecnt, file, line); E.tileoff.reserve(z.tileoff, file, line);
+    E.hist.reserve(z.hist, file, line); E.hsize.reserve(z.hsize, file, line); E.hcount.reserve(z.hcount, file, line); E.lut.reserve(z.lut, file, line);
+}
+
 // --------------------------------------------------------------------------------------------
 // GQ + LQ + PALETTE_create on the converted image in E.cvt (planar, stride N, optional w plane)
 // returns centres planar (len,3)
@@ -1323,14 +1309,12 @@ static void leaf_bound(HNode &h) {
 static void gq_prepare(Engine &E, size_t N, bool weighted) {
     hipStream_t s = E.stream;
     const size_t planes = weighted ? 4 : 3;
-    E.bufA.reserve(planes * N + 64); E.bufB.reserve(planes * N + 64); E.bkt.reserve(N);   // + the slack k_scatter_bin's pixel-less lanes store to
-    const int ntA = (int)ceil_div(N, (size_t)kTileA), ntP = (int)ceil_div(N, (size_t)kTileP);
-    E.tilesA.reserve(ntA); E.tilesP.reserve(ntP);
+    const QuantSizes z(N, planes, 1);
+    reserve_quant_tables(E, z);
+    const int ntA = (int)z.tilesA, ntP = (int)z.tilesP;
     E.h_round.reserve(kBuckets);                                // (receives the bucket counts later: sized once, before any copy uses it)
     E.round_nodes.reserve(1); E.node_tile0.reserve(2);
-    E.tilecnt.reserve((size_t)ntP * kMaxChildren); E.tileoff.reserve((size_t)ntP * kMaxChildren);
     const size_t hs = hist_slot_doubles();
-    E.hist.reserve(hs); E.hsize.reserve(kBuckets); E.hcount.reserve(kBuckets); E.lut.reserve(kBuckets);
     hipLaunchKernelGGL(k_gq_prepare, 64, 256, 0, s, E.tilesA.p, ntA, E.tilesP.p, ntP, (unsigned long long)N, E.round_nodes.p, E.node_tile0.p,
                        E.hist.p, (unsigned long long)hs, E.hsize.p, E.hcount.p);
     HIP_CHECK(hipGetLastError());
@@ -1338,105 +1322,6 @@ static void gq_prepare(Engine &E, size_t N, bool weighted) {
 }
 
 
-
-// The greedy loop of local.c:347-390 over the evaluated candidate tree (rec: per node the split's benefit once known, else the bound;
-// the left child; known).  Exactly the host-driven loop's steps (quantize_clusters_run below), except that nothing is left to
-// evaluate: false if a step is blocked by an undecided node all the same (the device's selection rule forbids it).
-struct LqReplay { std::vector<int> result; std::vector<LqCommit> commits; bool stopped_early = false; };
-// the same loop over the whole frontier at every step (the reference's shape): what PAMD_LQ_REPLAY_CHECK=1 holds the blocked form below to
-static bool lq_replay_plain(const LqRec *rec, int kbase, int first_base, size_t K, LqReplay &out) {
-    std::vector<int> &result = out.result;
-    result.assign(K, -1);
-    for (int j = 0; j < kbase; j++) result[j] = first_base + j;
-    size_t count = (size_t)kbase;
-    std::vector<double> fval(K, 0.0);
-    std::vector<char> fkn(K, 0);
-    for (size_t j = 0; j < count; j++) { fval[j] = rec[result[j]].val; fkn[j] = (char)rec[result[j]].kn; }
-    const int fault = g_debug_fault.load(std::memory_order_relaxed);
-    while (count < K) {
-        int best = -1; double bv = 0, mu = -1;
-        for (size_t j = 0; j < count; j++) {
-            if (fkn[j]) { if (best < 0 || fval[j] > bv) { bv = fval[j]; best = (int)j; } }      // first maximum (vector.c:26-46)
-            else if (fval[j] > mu) mu = fval[j];
-        }
-        if (mu < 0 || (best >= 0 && bv > mu)) {
-            if (fault == 2) {                                      // tests only: a WRONG greedy step (the second best known one)
-                int second = -1; double sv = -1;
-                for (size_t j = 0; j < count; j++) if ((int)j != best && fkn[j] && fval[j] > sv) { sv = fval[j]; second = (int)j; }
-                if (second >= 0 && sv >= kDelta && sv < bv) { best = second; bv = sv; }
-            }
-            if (!(bv >= kDelta)) { out.stopped_early = true; break; }          // benefit < DELTA: stop (local.c:365-370)
-            const int id = result[best], l = rec[id].left;
-            out.commits.push_back(LqCommit{best, id, (int)count, l});
-            result[count] = l; result[best] = l + 1;               // local.c:375-376: palette ORDER
-            fval[count] = rec[l].val; fkn[count] = (char)rec[l].kn;
-            fval[best] = rec[l + 1].val; fkn[best] = (char)rec[l + 1].kn;
-            count++;
-            continue;
-        }
-        if (std::max(best >= 0 ? bv : 0.0, mu) < kDelta) { out.stopped_early = true; break; }
-        return false;
-    }
-    result.resize(count);
-    return true;
-}
-
-static bool lq_replay(const LqRec *rec, int kbase, int first_base, size_t K, LqReplay &out) {
-    std::vector<int> &result = out.result;
-    result.assign(K, -1);
-    for (int j = 0; j < kbase; j++) result[j] = first_base + j;
-    size_t count = (size_t)kbase;
-    // The frontier in blocks of sixteen rows, each with its first maximum among the known rows and the maximum among the unknown
-    // ones: a step changes two rows, so it rescans two blocks and the blocks' summaries instead of the whole frontier (254 steps over
-    // up to 256 rows: 50 us of a 1920x1080 call's 1.6 ms before)
-    constexpr size_t B = 16;
-    const size_t nb = (K + B - 1) / B;
-    std::vector<double> fval(nb * B, 0.0);
-    std::vector<char> fkn(nb * B, 0);
-    std::vector<double> bbv(nb, 0.0), bmu(nb, -1.0);
-    std::vector<int> bbest(nb, -1);
-    auto rescan = [&](const size_t b) {
-        int best = -1; double bv = 0, mu = -1;
-        const size_t lo = b * B, hi = std::min(count, lo + B);
-        for (size_t j = lo; j < hi; j++) {
-            if (fkn[j]) { if (best < 0 || fval[j] > bv) { bv = fval[j]; best = (int)j; } }      // first maximum (vector.c:26-46)
-            else if (fval[j] > mu) mu = fval[j];
-        }
-        bbest[b] = best; bbv[b] = bv; bmu[b] = mu;
-    };
-    for (size_t j = 0; j < count; j++) { fval[j] = rec[result[j]].val; fkn[j] = (char)rec[result[j]].kn; }
-    for (size_t b = 0; b < nb; b++) rescan(b);
-    const int fault = g_debug_fault.load(std::memory_order_relaxed);
-    while (count < K) {
-        int best = -1; double bv = 0, mu = -1;
-        const size_t nbu = (count + B - 1) / B;
-        for (size_t b = 0; b < nbu; b++) {                       // ascending blocks, strict '>': the first maximum of all rows
-            if (bbest[b] >= 0 && (best < 0 || bbv[b] > bv)) { bv = bbv[b]; best = bbest[b]; }
-            if (bmu[b] > mu) mu = bmu[b];
-        }
-        if (mu < 0 || (best >= 0 && bv > mu)) {
-            if (fault == 2) {                                      // tests only: a WRONG greedy step (the second best known one)
-                int second = -1; double sv = -1;
-                for (size_t j = 0; j < count; j++) if ((int)j != best && fkn[j] && fval[j] > sv) { sv = fval[j]; second = (int)j; }
-                if (second >= 0 && sv >= kDelta && sv < bv) { best = second; bv = sv; }
-            }
-            if (!(bv >= kDelta)) { out.stopped_early = true; break; }          // benefit < DELTA: stop (local.c:365-370)
-            const int id = result[best], l = rec[id].left;
-            out.commits.push_back(LqCommit{best, id, (int)count, l});
-            result[count] = l; result[best] = l + 1;               // local.c:375-376: palette ORDER
-            fval[count] = rec[l].val; fkn[count] = (char)rec[l].kn;
-            fval[best] = rec[l + 1].val; fkn[best] = (char)rec[l + 1].kn;
-            count++;
-            rescan((size_t)best / B);
-            if ((count - 1) / B != (size_t)best / B) rescan((count - 1) / B);
-            continue;
-        }
-        if (std::max(best >= 0 ? bv : 0.0, mu) < kDelta) { out.stopped_early = true; break; }
-        return false;
-    }
-    result.resize(count);
-    return true;
-}
 
 // patolette_amd_set_split_loop: 2 (default) the device-driven loop for images below kLqDeviceAutoPixels, 1 wherever it applies,
 // 0 the host-driven one everywhere.  Measured, round 6 (profiles/r06_split_loop_ab.txt), per call, device against host-driven:
@@ -1456,19 +1341,13 @@ static bool lq_device_eligible(const Engine &E, size_t N, size_t K, bool verbose
 // What the quantisers of a call on an image of N pixels will reserve -- gq_prepare's tables, the node table and, when the call may
 // take the device-driven split loop, that loop's tables at their caps (lq_device_loop) -- reserved before the call enqueues
 // anything.  DevBuf::reserve frees the old allocation: never while queued work may still use it (the host-driven loop grows its
-// staging only after a synchronisation, see upload_tiles).  A no-op on every later call at this size.
+// tables only after a synchronisation, see lq_host_round).  A no-op on every later call at this size.
 static void ws_prepare(Engine &E, size_t N, size_t K, bool weighted, bool verbose) {
     const size_t planes = weighted ? 4 : 3;
     const bool lq_dev = lq_device_eligible(E, N, K, verbose, true);
-    const size_t slack = lq_dev ? (size_t)kLqRoundCap : 0, ntA = ceil_div(N, (size_t)kTileA) + slack, ntP = ceil_div(N, (size_t)kTileP) + slack;
-    const size_t tables = lq_dev ? (size_t)kLqRoundCap * kBuckets : (size_t)kBuckets;
     E.cvt.reserve(planes * N); E.cstats.reserve(1);
-    E.bufA.reserve(planes * N + 64); E.bufB.reserve(planes * N + 64); E.bkt.reserve(N);
-    E.tilesA.reserve(ntA); E.tilesP.reserve(ntP);
-    E.tilecnt.reserve(ntP * kMaxChildren); E.tileoff.reserve(ntP * kMaxChildren);
+    reserve_quant_tables(E, QuantSizes(N, planes, lq_dev ? (size_t)kLqRoundCap : 1));
     E.round_nodes.reserve(1); E.node_tile0.reserve(2); E.h_round.reserve(kBuckets);
-    E.hist.reserve(std::max(hist_slot_doubles(), lq_dev ? (size_t)kNQ_LQ * 2 * kBuckets * kLqRoundCap : 0));
-    E.hsize.reserve(tables); E.hcount.reserve(tables); E.lut.reserve(tables);
     E.nodes.reserve(std::max<size_t>(4 * K + 64, lq_dev ? (size_t)kLqNodeCap : 0));
     E.h_dbl.reserve(16 * kBuckets * 2 + 64);
     E.gq.reserve(1); E.gqout.reserve(1); E.h_gqout.reserve(1); E.h_gq.reserve(1);
@@ -1487,12 +1366,10 @@ static int lq_device_loop(Engine &E, size_t N, size_t K, bool weighted, bool inv
                           int first_base, int nnodes, std::vector<double> &centers, size_t &len, unsigned long long *max_members) {
     hipStream_t s = E.stream;
     const size_t lqs = (size_t)kNQ_LQ * 2 * kBuckets;
-    const int ntA_ub = (int)ceil_div(N, (size_t)kTileA) + kLqRoundCap, ntP_ub = (int)ceil_div(N, (size_t)kTileP) + kLqRoundCap;
+    const QuantSizes z(N, weighted ? 4 : 3, kLqRoundCap);          // (ws_prepare reserved as much: the stream holds queued work here)
+    const int ntA_ub = (int)z.tilesA, ntP_ub = (int)z.tilesP;      // the image's tiles + one partial tile per node of a round
     E.lqctl.reserve(1); E.h_lqhead.reserve(1); E.h_lqrec.reserve(kLqNodeCap); E.h_lqcen.reserve(kLqNodeCap);
-    E.hist.reserve(std::max(hist_slot_doubles(), lqs * kLqRoundCap)); E.hsize.reserve((size_t)kLqRoundCap * kBuckets);
-    E.hcount.reserve((size_t)kLqRoundCap * kBuckets); E.lut.reserve((size_t)kLqRoundCap * kBuckets);
-    E.tilesA.reserve(ntA_ub); E.tilesP.reserve(ntP_ub);
-    E.tilecnt.reserve((size_t)ntP_ub * kMaxChildren); E.tileoff.reserve((size_t)ntP_ub * kMaxChildren);
+    reserve_quant_tables(E, z);
     LqCtl *c = E.lqctl.p;
     LqHead *head = E.h_lqhead.p;
     for (int r = 0; r < kLqMaxRounds; r++) { head->round_px[r] = 0.0; head->round_nr[r] = 0.0; }
@@ -1558,12 +1435,13 @@ static int lq_device_loop(Engine &E, size_t N, size_t K, bool weighted, bool inv
     // 254 steps); one sequential copy brings them in (18-28 us)
     E.lq_rec_local.resize((size_t)head->nnodes);
     std::memcpy(E.lq_rec_local.data(), E.h_lqrec.p, (size_t)head->nnodes * sizeof(LqRec));
-    const bool replay_ok = lq_replay(E.lq_rec_local.data(), kbase, first_base, K, rp);
+    const int fault = g_debug_fault.load(std::memory_order_relaxed);
+    const bool replay_ok = lq_replay(E.lq_rec_local.data(), kbase, first_base, K, kDelta, fault, rp);
     const double t_rp1 = now_ms();
     static const bool replay_check = getenv("PAMD_LQ_REPLAY_CHECK") != nullptr;
     if (replay_check || !replay_ok) {
         LqReplay ref;
-        const bool ref_ok = lq_replay_plain(E.lq_rec_local.data(), kbase, first_base, K, ref);
+        const bool ref_ok = lq_replay_plain(E.lq_rec_local.data(), kbase, first_base, K, kDelta, fault, ref);
         if (ref_ok != replay_ok || ref.result != rp.result || ref.stopped_early != rp.stopped_early)
             fprintf(stderr, "patolette_amd: split loop: the two replays DISAGREE (plain %d, %zu rows; blocked %d, %zu rows), kbase %d, K %zu, nodes %d, rounds %d\n",
                     (int)ref_ok, ref.result.size(), (int)replay_ok, rp.result.size(), kbase, K, head->nnodes, head->rounds);
@@ -1616,25 +1494,33 @@ static void materialise_trace(Engine &E) {
     HIP_CHECK(hipStreamSynchronize(E.stream));
 }
 
-static int quantize_clusters_run(Engine &E, size_t N, size_t K, bool weighted, const Bounds &bnd,
-                                 std::vector<double> &centers, size_t &len, bool verbose, unsigned long long *max_members, bool allow_device) {
-    hipStream_t s = E.stream;
-    const size_t planes = weighted ? 4 : 3;
-    const Shard *sh = E.shard;                                  // the image is dealt out over a group of GPUs: N is this GPU's part
-    const size_t Nt = sh ? sh->total : N;                       // pixels of the whole image
-    const bool inv_sums = sh || E.invariant;
-    if (E.prep_N != N || E.prep_planes != planes) gq_prepare(E, N, weighted);   // (the stage-level entry points come here unprepared)
-    E.prep_N = 0;
-    // PAMD_LQ_DEVICE=0: the host-driven split loop everywhere (A/B, and what sliced images, K > 256 and verbose calls always take)
-    const bool dev_eligible = lq_device_eligible(E, N, K, verbose, allow_device);
-    E.nodes.reserve(std::max<size_t>(4 * K + 64, dev_eligible ? (size_t)kLqNodeCap : 0));
-    std::vector<HNode> hn;
-    hn.reserve(4 * K + 64);
-    double t0 = now_ms();
+// One quantize_clusters_run call: what its stages (below, in their order) share
+struct QuantCall {
+    Engine &E;
+    const size_t N, Nt, K;                                      // pixels on this GPU (a sliced image: this GPU's part), of the whole image; palette size
+    const bool weighted, inv_sums, verbose, dev_eligible;
+    const Shard *sh;                                            // the image is dealt out over a group of GPUs
+    const Bounds &bnd;
+    std::vector<double> &centers; size_t &len; unsigned long long *max_members;
+    const QuantBuffers qroot, qlq;
+    const int ntA0, ntP0;                                       // the root's tilings (gq_prepare)
+    const size_t hs;                                            // doubles of the global quantiser's histogram
+    double t0;                                                  // start of the running stage (stats.ms_gq, ms_lq)
+    std::vector<HNode> hn;                                      // id 0: the root
+    bool mom_path = false;                                      // the root's covariance came with the conversion pass: one sweep less
+    double axis[3] = {0, 0, 0};                                 // the root's principal axis
+    int kbase = 0;
+    std::vector<int> base_ids;
+    std::vector<NodeOut> got;
+};
 
-    // ---------------- global quantiser (global.c:388-443) ----------------
-    // unweighted PCA of all pixels: mean, centred covariance, dsyev
-    HNode root; root.begin = 0; root.n = N; root.gn = Nt; root.buf = 0; root.sw = (double)Nt;
+// ---------------- global quantiser (global.c:388-443) ----------------
+// unweighted PCA of all pixels: mean, centred covariance, dsyev
+static void gq_root_mean(QuantCall &C) {
+    Engine &E = C.E;
+    const size_t Nt = C.Nt;
+    const Bounds &bnd = C.bnd;
+    HNode root; root.begin = 0; root.n = C.N; root.gn = Nt; root.buf = 0; root.sw = (double)Nt;
     E.h_dbl.reserve(16 * kBuckets * 2 + 64);
     if (bnd.have_sum) {
         const double inv = 1 / (double)Nt;                      // matrix2D.c:229; the sums came with the conversion pass
@@ -1642,9 +1528,9 @@ static int quantize_clusters_run(Engine &E, size_t N, size_t K, bool weighted, c
     } else {
         int rootP = 1; while ((1ULL << rootP) < (Nt > 1 ? Nt : 2)) rootP++;
         E.sum6.reserve(kSum3Slots * 6);
-        launch_sum3(E.cvt.p, N, make_bink(bnd.e_lin, rootP), E.sum6.p, s);
-        if (sh) comm_sum_dev(E, E.sum6.p, kSum3Slots * 6, 0);
-        HIP_CHECK(hipMemcpyAsync(E.h_dbl.p, E.sum6.p, kSum3Slots * 6 * sizeof(double), hipMemcpyDeviceToHost, s));
+        launch_sum3(E.cvt.p, C.N, make_bink(bnd.e_lin, rootP), E.sum6.p, E.stream);
+        if (C.sh) comm_sum_dev(E, E.sum6.p, kSum3Slots * 6, 0);
+        HIP_CHECK(hipMemcpyAsync(E.h_dbl.p, E.sum6.p, kSum3Slots * 6 * sizeof(double), hipMemcpyDeviceToHost, E.stream));
         E.sync();
         const double inv = 1 / (double)Nt;                      // matrix2D.c:229
         for (int j = 0; j < 3; j++) {
@@ -1653,23 +1539,24 @@ static int quantize_clusters_run(Engine &E, size_t N, size_t K, bool weighted, c
             root.mean[j] = (p0 + p1) * inv;
         }
     }
-    hn.push_back(root);                                         // id 0
-    QuantBuffers qroot{{E.cvt.p, E.bufA.p}, E.bkt.p, N, weighted};
-    QuantBuffers qlq{{E.bufB.p, E.bufA.p}, E.bkt.p, N, weighted};
-    std::vector<int> round = {0};
-    const int ntA0 = (int)ceil_div(N, (size_t)kTileA), ntP0 = (int)ceil_div(N, (size_t)kTileP);   // the root's tilings (gq_prepare)
-    // every sweep over the pixels starts where the previous one stopped (see the split rounds below): the conversion wrote the
-    // image front to back, so the root's moments are taken back to front, the extrema front to back, ...
-    std::vector<NodeOut> got;
-    bool mom_path = bnd.have_mom && !sh;                        // one sweep less: the directions of the following ones flip
-    if (mom_path) {
+    C.hn.push_back(root);                                       // id 0
+}
+
+// every sweep over the pixels starts where the previous one stopped (see the split rounds below): the conversion wrote the
+// image front to back, so the root's moments are taken back to front, the extrema front to back, ...
+static void gq_root_covariance(QuantCall &C) {
+    Engine &E = C.E;
+    const Bounds &bnd = C.bnd;
+    std::vector<HNode> &hn = C.hn;
+    C.mom_path = bnd.have_mom && !C.sh;                         // one sweep less: the directions of the following ones flip
+    if (C.mom_path) {
         // The conversion pass took the column sums S1 and the raw second moments S2 as exact pairs: the centred sums
         // S2_jk - S1_j S1_k / n (pca.c:62-101 about the mean, matrix2D.c:200-233) follow in extended precision, then ONE rounding
         // to double -- instead of a sweep over the image and a round trip.  What the shortcut cannot undo: every product x_j x_k was
         // rounded to double before it was binned (relative 2^-53, systematic for a flat image), so the difference is good to
         // ~1e-16 of S2 and no better: an image whose spread is tiny against its mean -- trace(cov) below 1e-6 of trace(S2), i.e.
         // fewer than ~10 digits left --, or a difference that came out negative, takes the centred sweep below instead.
-        const long double nn = (long double)Nt;
+        const long double nn = (long double)C.Nt;
         long double s1[3], c6[6], s2d[3] = {0, 0, 0};
         for (int j = 0; j < 3; j++) s1[j] = (long double)bnd.sum2[j][0] + (long double)bnd.sum2[j][1];
         static const int ja[6] = {0, 1, 2, 1, 2, 2}, jb[6] = {0, 0, 0, 1, 1, 2};       // xx, yx, zx, yy, zy, zz
@@ -1679,92 +1566,122 @@ static int quantize_clusters_run(Engine &E, size_t N, size_t K, bool weighted, c
             c6[q] = s2 - s1[ja[q]] * s1[jb[q]] / nn;
         }
         const long double tr = c6[0] + c6[3] + c6[5], tr2 = s2d[0] + s2d[1] + s2d[2];
-        if (!(tr > 1e-6L * tr2) || c6[0] < 0 || c6[3] < 0 || c6[5] < 0) mom_path = false;
+        if (!(tr > 1e-6L * tr2) || c6[0] < 0 || c6[3] < 0 || c6[5] < 0) C.mom_path = false;
         else {
             for (int q = 0; q < 6; q++) hn[0].cov6[q] = (double)c6[q];
             hn[0].dist = (double)tr;
         }
     }
-    if (!mom_path) {
+    if (!C.mom_path) {
         NodeIn d = make_nodedev(hn[0], bnd);
         put_nodes(E, {0}, {d});
-        launch_cov_nodes(qroot, E.cvt.p, E.tilesA.p, ntA0, N, E.nodes.p, s, true);
-        if (sh) shard_exchange_acc(E, shard_upload_ids(E, {0}), 1);
-        get_nodes(E, {0}, got);
-        absorb_moments(hn[0], got[0]);
+        launch_cov_nodes(C.qroot, E.cvt.p, E.tilesA.p, C.ntA0, C.N, E.nodes.p, E.stream, true);
+        if (C.sh) shard_exchange_acc(E, shard_upload_ids(E, {0}), 1);
+        get_nodes(E, {0}, C.got);
+        absorb_moments(hn[0], C.got[0]);
     }
-    double axis[3];
-    if (!node_axis(hn[0], axis)) return -1;
+}
+
+// the root's axis, the head of the split trace, then projection, 512 buckets, cell moments (sort.c, cells.c:53-139).
+// false: the eigen-solve failed
+static bool gq_root_histogram(QuantCall &C) {
+    Engine &E = C.E;
+    hipStream_t s = E.stream;
+    const HNode &root = C.hn[0];
+    if (!node_axis(root, C.axis)) return false;
     E.trace.clear();
     E.trace_pending = false;
     E.trace_hdr = patolette_amd__SplitTrace{};
-    for (int j = 0; j < 3; j++) E.trace_hdr.gq_axis[j] = axis[j];
-    for (int q = 0; q < 6; q++) E.trace_hdr.gq_cov6[q] = hn[0].cov6[q] / hn[0].sw;
-
-    // projection, 512 buckets, cell moments (sort.c, cells.c:53-139)
+    for (int j = 0; j < 3; j++) E.trace_hdr.gq_axis[j] = C.axis[j];
+    for (int q = 0; q < 6; q++) E.trace_hdr.gq_cov6[q] = root.cov6[q] / root.sw;
     {
-        NodeIn d = make_nodedev(hn[0], bnd);
-        for (int j = 0; j < 3; j++) d.axis[j] = axis[j];
+        NodeIn d = make_nodedev(root, C.bnd);
+        for (int j = 0; j < 3; j++) d.axis[j] = C.axis[j];
         d.slot = 0;
         put_nodes(E, {0}, {d});
     }
-    const size_t hs = hist_slot_doubles();
-    launch_minmax(qroot, E.tilesA.p, ntA0, N, E.nodes.p, s, mom_path);
-    if (sh) shard_exchange_keys(E, shard_upload_ids(E, {0}), 1);
-    launch_hist(qroot, true, E.tilesA.p, ntA0, N, E.nodes.p, E.hist.p, E.hsize.p, E.hcount.p, s, !mom_path, Nt >= ((size_t)1 << 18));
-    if (sh) { comm_sum_dev(E, E.hist.p, hs, 0); comm_sum_dev(E, E.hcount.p, kBuckets, 2); }
-    // The quantiser's decisions (global.c:189-298) on the device, the partition behind them without the host looking (k_gq_control):
-    // one GPU, palettes of more than twelve colours (so that base clusters < K whatever the image), not verbose.  PAMD_GQ_DEVICE=0:
-    // the host's turn everywhere (A/B; what sliced images, small palettes and verbose calls always take)
-    const bool gq_dev = g_gq_device.load(std::memory_order_relaxed) != 0 && !sh && !verbose && K > (size_t)kGqMaxK;
-    int kbase = 0;
-    std::vector<int> base_ids;
-    if (gq_dev) {
-        E.gq.reserve(1); E.gqout.reserve(1); E.h_gqout.reserve(1);
-        *E.h_gqout.p = GqOut{};
-        {
-            KTIME("k_gq_control", s, (double)hs * 8);
-            hipLaunchKernelGGL(k_gq_control, 1, 1024, 0, s, (const double *)E.hist.p, (const unsigned int *)E.hcount.p, E.gq.p, (int)std::min<size_t>(K, (size_t)1 << 30),
-                               weighted ? 1 : 0, E.nodes.p, 1, E.lut.p, E.gqout.p, E.h_gqout.p);
-            HIP_CHECK(hipGetLastError());
-        }
-        launch_partition(qroot, E.tilesP.p, ntP0, N, E.round_nodes.p, E.node_tile0.p, 1, E.nodes.p, E.lut.p, E.tilecnt.p, E.tileoff.p, true, s, inv_sums,
-                         mom_path, nullptr, nullptr, true);
-        launch_cov_children(qroot, E.tilesA.p, ntA0, N, E.nodes.p, s, !mom_path, true);
-        auto trace_header = [&]() {                              // (after a synchronisation)
-            const GqOut &o = *E.h_gqout.p;
-            E.trace_hdr.n_base = o.kbase;
-            for (int j = 0; j <= o.kbase && j < 14; j++) E.trace_hdr.gq_cuts[j] = (size_t)o.cuts[j];
-        };
-        if (dev_eligible) {
-            E.stats.ms_gq = now_ms() - t0;
-            t0 = now_ms();
-            const int rc = lq_device_loop(E, N, K, weighted, inv_sums, bnd, qlq, -1, 1, 0, centers, len, max_members);
-            trace_header();
-            E.stats.n_base_clusters = (size_t)E.h_gqout.p->kbase;
-            if (rc != 0) return rc;
-            E.stats.n_clusters = len;
-            E.trace_hdr.n_clusters = (int32_t)len; E.trace_hdr.n_records = (int32_t)E.lq_commits.size();
-            E.cluster_centers = centers;
-            E.stats.ms_lq = now_ms() - t0;
-            return 0;
-        }
-        // the host-driven split loop: the count comes down with the base clusters' records (the first kbase of twelve)
-        std::vector<int> all(kGqMaxK);
-        for (int j = 0; j < kGqMaxK; j++) all[j] = 1 + j;
-        get_nodes(E, all, got);
-        if (E.h_gqout.p->error) return -1;
-        trace_header();
-        kbase = E.h_gqout.p->kbase;
-        for (int j = 0; j < kbase; j++) {
-            HNode c; c.buf = 1; c.begin = got[j].begin; c.n = got[j].n; c.gn = got[j].gn; c.sw = got[j].sw;
-            for (int q = 0; q < 3; q++) c.mean[q] = got[j].mean[q];
-            absorb_moments(c, got[j]);
-            leaf_bound(c);
-            base_ids.push_back((int)hn.size());
-            hn.push_back(c);
-        }
-    } else {
+    launch_minmax(C.qroot, E.tilesA.p, C.ntA0, C.N, E.nodes.p, s, C.mom_path);
+    if (C.sh) shard_exchange_keys(E, shard_upload_ids(E, {0}), 1);
+    launch_hist(C.qroot, true, E.tilesA.p, C.ntA0, C.N, E.nodes.p, E.hist.p, E.hsize.p, E.hcount.p, s, !C.mom_path, C.Nt >= ((size_t)1 << 18));
+    if (C.sh) { comm_sum_dev(E, E.hist.p, C.hs, 0); comm_sum_dev(E, E.hcount.p, kBuckets, 2); }
+    return true;
+}
+
+// what k_gq_control decided, into the head of the split trace (after a synchronisation)
+static void gq_trace_header(Engine &E) {
+    const GqOut &o = *E.h_gqout.p;
+    E.trace_hdr.n_base = o.kbase;
+    for (int j = 0; j <= o.kbase && j < 14; j++) E.trace_hdr.gq_cuts[j] = (size_t)o.cuts[j];
+}
+
+// The hand-over to the device-driven split loop, behind either turn of the global quantiser: no synchronisation here, the control
+// kernel takes the base clusters' moments itself.  kbase < 0: the count of base clusters is the device's too (k_gq_control).
+static int finish_device_loop(QuantCall &C, int kbase, int first_base, int nnodes) {
+    Engine &E = C.E;
+    if (kbase >= 0) E.stats.n_base_clusters = (size_t)kbase;
+    E.stats.ms_gq = now_ms() - C.t0;
+    C.t0 = now_ms();
+    const int rc = lq_device_loop(E, C.N, C.K, C.weighted, C.inv_sums, C.bnd, C.qlq, kbase, first_base, nnodes, C.centers, C.len, C.max_members);
+    if (kbase < 0) {
+        gq_trace_header(E);
+        E.stats.n_base_clusters = (size_t)E.h_gqout.p->kbase;
+    }
+    if (rc != 0) return rc;
+    E.stats.n_clusters = C.len;
+    E.trace_hdr.n_clusters = (int32_t)C.len; E.trace_hdr.n_records = (int32_t)E.lq_commits.size();
+    E.cluster_centers = C.centers;
+    E.stats.ms_lq = now_ms() - C.t0;
+    return 0;
+}
+
+// what the turns of the global quantiser answer besides a return code of the call: go on with the host-driven split loop
+constexpr int kHostLoop = 1;
+
+// The quantiser's decisions (global.c:189-298) on the device, the partition behind them without the host looking (k_gq_control):
+// one GPU, palettes of more than twelve colours (so that base clusters < K whatever the image), not verbose.  PAMD_GQ_DEVICE=0:
+// the host's turn everywhere (A/B; what sliced images, small palettes and verbose calls always take)
+static int gq_device_turn(QuantCall &C) {
+    Engine &E = C.E;
+    hipStream_t s = E.stream;
+    E.gq.reserve(1); E.gqout.reserve(1); E.h_gqout.reserve(1);
+    *E.h_gqout.p = GqOut{};
+    {
+        KTIME("k_gq_control", s, (double)C.hs * 8);
+        hipLaunchKernelGGL(k_gq_control, 1, 1024, 0, s, (const double *)E.hist.p, (const unsigned int *)E.hcount.p, E.gq.p, (int)std::min<size_t>(C.K, (size_t)1 << 30),
+                           C.weighted ? 1 : 0, E.nodes.p, 1, E.lut.p, E.gqout.p, E.h_gqout.p);
+        HIP_CHECK(hipGetLastError());
+    }
+    launch_partition(C.qroot, E.tilesP.p, C.ntP0, C.N, E.round_nodes.p, E.node_tile0.p, 1, E.nodes.p, E.lut.p, E.tilecnt.p, E.tileoff.p, true, s, C.inv_sums,
+                     C.mom_path, nullptr, nullptr, true);
+    launch_cov_children(C.qroot, E.tilesA.p, C.ntA0, C.N, E.nodes.p, s, !C.mom_path, true);
+    if (C.dev_eligible) return finish_device_loop(C, -1, 1, 0);
+    // the host-driven split loop: the count comes down with the base clusters' records (the first kbase of twelve)
+    std::vector<int> all(kGqMaxK);
+    for (int j = 0; j < kGqMaxK; j++) all[j] = 1 + j;
+    get_nodes(E, all, C.got);
+    if (E.h_gqout.p->error) return -1;
+    gq_trace_header(E);
+    C.kbase = E.h_gqout.p->kbase;
+    for (int j = 0; j < C.kbase; j++) {
+        const NodeOut &g = C.got[j];
+        HNode c; c.buf = 1; c.begin = g.begin; c.n = g.n; c.gn = g.gn; c.sw = g.sw;
+        for (int q = 0; q < 3; q++) c.mean[q] = g.mean[q];
+        absorb_moments(c, g);
+        leaf_bound(c);
+        C.base_ids.push_back((int)C.hn.size());
+        C.hn.push_back(c);
+    }
+    return kHostLoop;
+}
+
+// The host's turn of the global quantiser: the cell moments come down, hm::gq_principal_quantizer decides, the bucket table and the
+// base clusters' records go up, the partition follows
+static int gq_host_turn(QuantCall &C) {
+    Engine &E = C.E;
+    hipStream_t s = E.stream;
+    const size_t K = C.K, hs = C.hs;
+    const bool weighted = C.weighted;
+    std::vector<HNode> &hn = C.hn;
     const int gq_kmax = (int)std::min<size_t>(K, kGqMaxK);
     E.gq.reserve(1); E.h_gq.reserve(1);
     launch_gq_dp(E.hist.p, E.hcount.p, gq_kmax, E.gq.p, s);
@@ -1794,7 +1711,7 @@ static int quantize_clusters_run(Engine &E, size_t N, size_t K, bool weighted, c
     }
     std::vector<size_t> cuts = hm::gq_principal_quantizer(K, *cm, E.h_gq.p->cut);
     if (cuts.size() < 2) return -1;
-    kbase = (int)cuts.size() - 1;
+    const int kbase = C.kbase = (int)cuts.size() - 1;
     E.trace_hdr.n_base = kbase;
     for (int j = 0; j <= kbase && j < 14; j++) E.trace_hdr.gq_cuts[j] = cuts[j];
 
@@ -1808,6 +1725,7 @@ static int quantize_clusters_run(Engine &E, size_t N, size_t K, bool weighted, c
     // Two base clusters (what noise and most photographs give): the partition is a binary split like the local quantiser's, so
     // it takes the same pipelined kernel and the children's centred moments ride along instead of costing a sweep of their own
     const bool gq_binary = kbase == 2;
+    std::vector<int> &base_ids = C.base_ids;
     {
         unsigned long long pos = 0;
         for (int j = 0; j < kbase; j++) {
@@ -1832,257 +1750,272 @@ static int quantize_clusters_run(Engine &E, size_t N, size_t K, bool weighted, c
         }
     }
     {
-        NodeIn d = make_nodedev(hn[0], bnd);
-        for (int j = 0; j < 3; j++) d.axis[j] = axis[j];
+        NodeIn d = make_nodedev(hn[0], C.bnd);
+        for (int j = 0; j < 3; j++) d.axis[j] = C.axis[j];
         d.slot = 0; d.child0 = base_ids[0]; d.nchild = kbase;
         if (gq_binary) d.split = (int)cuts[1] - 1;               // bucket b is in cluster 0 iff b + 1 <= cuts[1] (global.c:328-335)
         std::vector<int> ids = {0};
         std::vector<NodeIn> recs = {d};
-        for (int id : base_ids) { ids.push_back(id); NodeIn c = make_nodedev(hn[id], bnd); c.klin = d.klin; c.kquad = d.kquad; recs.push_back(c); }
+        for (int id : base_ids) { ids.push_back(id); NodeIn c = make_nodedev(hn[id], C.bnd); c.klin = d.klin; c.kquad = d.kquad; recs.push_back(c); }
         put_nodes(E, ids, recs);
     }
     E.h_bytes.reserve(kBuckets);                                // pinned: no synchronisation before the partition
     std::memcpy(E.h_bytes.p, lut.data(), kBuckets);
     HIP_CHECK(hipMemcpyAsync(E.lut.p, E.h_bytes.p, kBuckets, hipMemcpyHostToDevice, s));
-    launch_partition(qroot, E.tilesP.p, ntP0, N, E.round_nodes.p, E.node_tile0.p, 1, E.nodes.p, E.lut.p, E.tilecnt.p, E.tileoff.p, gq_binary, s, inv_sums, mom_path);
-    if (sh) { hipLaunchKernelGGL(k_shard_children_local, 1, 64, 0, s, E.nodes.p, E.round_nodes.p, 1); HIP_CHECK(hipGetLastError()); }
-    if (!gq_binary) launch_cov_children(qroot, E.tilesA.p, ntA0, N, E.nodes.p, s, !mom_path);
-    if (sh) shard_exchange_acc(E, shard_upload_ids(E, base_ids), (int)base_ids.size());
-    if (dev_eligible && (size_t)kbase < K) {
-        // the split loop runs from the device: no synchronisation here, the control kernel takes the base clusters' moments itself
-        E.stats.n_base_clusters = (size_t)kbase;
-        E.stats.ms_gq = now_ms() - t0;
-        t0 = now_ms();
-        const int rc = lq_device_loop(E, N, K, weighted, inv_sums, bnd, qlq, kbase, base_ids[0], (int)hn.size(), centers, len, max_members);
-        if (rc != 0) return rc;
-        E.stats.n_clusters = len;
-        E.trace_hdr.n_clusters = (int32_t)len; E.trace_hdr.n_records = (int32_t)E.lq_commits.size();
-        E.cluster_centers = centers;
-        E.stats.ms_lq = now_ms() - t0;
-        return 0;
-    }
-    get_nodes(E, base_ids, got);
+    launch_partition(C.qroot, E.tilesP.p, C.ntP0, C.N, E.round_nodes.p, E.node_tile0.p, 1, E.nodes.p, E.lut.p, E.tilecnt.p, E.tileoff.p, gq_binary, s, C.inv_sums,
+                     C.mom_path);
+    if (C.sh) { hipLaunchKernelGGL(k_shard_children_local, 1, 64, 0, s, E.nodes.p, E.round_nodes.p, 1); HIP_CHECK(hipGetLastError()); }
+    if (!gq_binary) launch_cov_children(C.qroot, E.tilesA.p, C.ntA0, C.N, E.nodes.p, s, !C.mom_path);
+    if (C.sh) shard_exchange_acc(E, shard_upload_ids(E, base_ids), (int)base_ids.size());
+    if (C.dev_eligible && (size_t)kbase < K) return finish_device_loop(C, kbase, base_ids[0], (int)hn.size());
+    get_nodes(E, base_ids, C.got);
     for (size_t i = 0; i < base_ids.size(); i++) {
-        absorb_moments(hn[base_ids[i]], got[i]);
-        if (sh) { hn[base_ids[i]].begin = got[i].begin; hn[base_ids[i]].n = got[i].n; }
+        absorb_moments(hn[base_ids[i]], C.got[i]);
+        if (C.sh) { hn[base_ids[i]].begin = C.got[i].begin; hn[base_ids[i]].n = C.got[i].n; }
         leaf_bound(hn[base_ids[i]]);
     }
-    }                                                           // (the host's turn of the global quantiser)
-    E.stats.n_base_clusters = (size_t)kbase;
-    if (verbose) printf("patolette ======== Base cluster count: %zu\n", (size_t)kbase);     // patolette.c:227-229
-    E.stats.ms_gq = now_ms() - t0;
-    t0 = now_ms();
+    return kHostLoop;
+}
 
-    // ---------------- local quantiser (local.c:318-404) ----------------
-    std::vector<int> result(base_ids);                          // frontier in the reference's order
-    std::vector<int> leaves(base_ids);                          // candidate-tree nodes with moments but no split yet
-    size_t count = result.size();
-    E.stats.split_evals = 0; E.stats.split_px = 0; E.stats.lq_rounds = 0;
-    auto known = [&](const HNode &h) { return h.nosplit || h.gn <= 1 || h.split_done; };
-    auto benefit = [&](const HNode &h) -> double {
-        if (h.nosplit || h.gn <= 1) return 0;                    // children == NULL -> 0 (local.c:262-264)
-        return h.dist - (hn[h.left].dist + hn[h.right].dist);
-    };
-    if (count < K) {
-        result.resize(K, -1);
-        // the frontier as two flat arrays (benefit if the node's split is known, else its bound): the greedy steps between two
-        // rounds scan them a few hundred times
-        std::vector<double> fval(K, 0.0);
-        std::vector<char> fkn(K, 0);
-        auto refresh = [&](const size_t j) {
-            const HNode &h = hn[result[j]];
-            fkn[j] = known(h) ? 1 : 0;
-            fval[j] = fkn[j] ? benefit(h) : h.ub;
-        };
-        for (size_t j = 0; j < count; j++) refresh(j);
-        static const bool lq_times = getenv("PAMD_LQ_TIMES") != nullptr;       // diagnostic: where the host's turn between two rounds goes
-        double tm_greedy = 0, tm_select = 0, tm_axes = 0, tm_packet = 0, tm_enqueue = 0, tm_wait = 0, tm_children = 0, tm_mark = now_ms();
-        auto lap = [&](double &acc) { if (lq_times) { const double t = now_ms(); acc += t - tm_mark; tm_mark = t; } };
-        for (;;) {
-            if (count >= K) break;
-            // one greedy step, exact whenever every undecided node is provably not the arg-max
-            int best = -1; double bv = 0; double max_unknown = -1;
-            for (size_t j = 0; j < count; j++) {
-                if (fkn[j]) {
-                    if (best < 0 || fval[j] > bv) { bv = fval[j]; best = (int)j; }
-                } else if (fval[j] > max_unknown) max_unknown = fval[j];
-            }
-            // first maximum among ALL entries = first maximum among the known ones iff every unknown
-            // benefit (<= that node's distortion) is strictly below it
-            if (max_unknown < 0 || (best >= 0 && bv > max_unknown)) {
-                if (g_debug_fault.load(std::memory_order_relaxed) == 2) {   // tests only: a WRONG greedy step (the second best known one)
-                    int second = -1; double sv = -1;
-                    for (size_t j = 0; j < count; j++) if ((int)j != best && fkn[j] && fval[j] > sv) { sv = fval[j]; second = (int)j; }
-                    if (second >= 0 && sv >= kDelta && sv < bv) { best = second; bv = sv; }
-                }
-                if (!(bv >= kDelta)) { E.trace_hdr.stopped_early = 1; break; }   // benefit < DELTA: stop, keep `count` clusters
-                const HNode &h = hn[result[best]];
-                const int l = h.left, r = h.right;
-                {
-                    patolette_amd__SplitRecord tr{};
-                    tr.row = best; tr.new_row = (int32_t)count;
-                    tr.split = hn[l].psplit < 0 ? -1 : (hn[l].psplit & 0xffff); tr.degenerate = hn[l].psplit < 0 ? 0 : (hn[l].psplit >> 16) & 1;
-                    tr.n = h.gn; tr.n_left = hn[l].gn; tr.n_right = hn[r].gn; tr.sw = h.sw;
-                    for (int j = 0; j < 3; j++) tr.axis[j] = h.axis[j];
-                    for (int q = 0; q < 6; q++) tr.cov6[q] = h.cov6[q] / h.sw;
-                    tr.dist = h.dist; tr.dist_left = hn[l].dist; tr.dist_right = hn[r].dist; tr.benefit = bv;
-                    E.trace.push_back(tr);
-                }
-                result[count] = l;                              // local.c:375-376: palette ORDER
-                result[best] = r;
-                refresh(count); refresh((size_t)best);
-                count++;
-                if (verbose) { printf("patolette ======== Processed colors: %zu\r", count); fflush(stdout); }   // local.c:386-389
-                continue;
-            }
-            if (std::max(best >= 0 ? bv : 0.0, max_unknown) < kDelta) { E.trace_hdr.stopped_early = 1; break; }   // nothing can reach DELTA
-            // blocked: evaluate, in ONE round, the split of every leaf of the candidate tree that could still
-            // matter -- undecided frontier nodes and, speculatively, the children of decided ones (a node's
-            // split depends only on its members, never on the greedy order).  Leaves whose distortion (an
-            // upper bound of their benefit) is far below the current best benefit are left for later; the
-            // exactness test above catches them if they ever become relevant.
-            const double ref_b = std::max(best >= 0 ? bv : 0.0, max_unknown);
-            double thr = std::max(kDelta, kSpecBeta * ref_b);
-            {
-                // exact pruning: with R commits left, a leaf whose distortion is below the R-th largest
-                // KNOWN frontier benefit can never be chosen (its own and all its descendants' benefits are
-                // bounded by that distortion, and R better candidates outlast the remaining commits)
-                const size_t R = K - count;
-                std::vector<double> kb;
-                for (size_t j = 0; j < count; j++) if (fkn[j]) kb.push_back(fval[j]);
-                if (kb.size() >= R && R > 0) {
-                    std::nth_element(kb.begin(), kb.begin() + (R - 1), kb.end(), std::greater<double>());
-                    thr = std::max(thr, kb[R - 1] * (1.0 - 1e-9));
-                }
-            }
-            lap(tm_greedy);
-            round.clear();
-            {
-                std::vector<int> keep;
-                for (int id : leaves) {
-                    HNode &h = hn[id];
-                    if (known(h)) continue;                     // n <= 1 / nosplit: never split
-                    if (h.ub >= thr) round.push_back(id); else keep.push_back(id);
-                }
-                leaves.swap(keep);
-            }
-            if (round.empty()) {                                // every blocking node is a leaf with dist >= ref_b >= thr
-                throw HipError("patolette_amd: split loop blocked without candidates");
-            }
-            lap(tm_select);
-            // axes on the host (dsyev semantics), children ids, device records
-            HIP_CHECK(hipStreamSynchronize(s));
-            E.nodes.grow(hn.size() + 2 * round.size() + 2, hn.size());
-            std::vector<int> todo;
-            std::vector<NodeIn> recs;
-            std::vector<int> ids;
-            for (int id : round) {
-                double ax[3];
-                if (!node_axis(hn[id], ax)) { hn[id].nosplit = true; continue; }
-                NodeIn d = make_nodedev(hn[id], bnd);
-                for (int j = 0; j < 3; j++) d.axis[j] = ax[j];
-                d.slot = (int)todo.size();
-                d.child0 = (int)hn.size(); d.nchild = 2;
-                hn[id].left = (int)hn.size(); hn[id].right = (int)hn.size() + 1;
-                hn.push_back(HNode()); hn.push_back(HNode());
-                todo.push_back(id); ids.push_back(id); recs.push_back(d);
-            }
-            for (size_t j = 0; j < count; j++) refresh(j);      // a failed eigen-solve above makes a node known (no split)
-            lap(tm_axes);
-            if (todo.empty()) continue;
-            const int nr = (int)todo.size();
-            size_t rpx = 0;
-            for (int id : todo) rpx += hn[id].n;
-            static const bool lq_trace = getenv("PAMD_LQ_TRACE") != nullptr;       // one line per split round on stderr
-            if (lq_trace) fprintf(stderr, "patolette_amd: split round %zu: %d nodes, %zu pixels (%.2f of the image), %zu of %zu colours committed\n",
-                                  E.stats.lq_rounds + 1, nr, rpx, (double)rpx / (double)(N ? N : 1), count, K);
-            // one packet, one copy: node records, ids, children ids, the tile prefixes of both tilings.  (Measured and removed:
-            // the round issued chunk-major, groups of nodes of a few MB each taken through minmax -> hist -> cut -> count -> scan ->
-            // scatter before the next group starts, so that the second and third read of a node may find it in the Infinity Cache;
-            // profiles/r06_lq_chunk_major.txt.)
-            std::vector<int> cids;
-            for (int id : todo) { cids.push_back(hn[id].left); cids.push_back(hn[id].right); }
-            std::vector<int> tAg = {0}, tPg = {0};                   // the nodes' tile prefixes (nr + 1 entries each)
-            for (int id : todo) {
-                const unsigned long long n = hn[id].n;
-                tAg.push_back(tAg.back() + (int)((n + kTileA - 1) / kTileA)); tPg.push_back(tPg.back() + (int)((n + kTileP - 1) / kTileP));
-            }
-            const int ntA = tAg[nr], ntP = tPg[nr];
-            const size_t o_recs = 0, o_ids = o_recs + (size_t)nr * sizeof(NodeIn), o_cids = o_ids + (size_t)nr * sizeof(int),
-                         o_tA = o_cids + cids.size() * sizeof(int), o_tP = o_tA + tAg.size() * sizeof(int),
-                         pk_bytes = o_tP + tPg.size() * sizeof(int);
-            E.h_packet.reserve(pk_bytes); E.packet.reserve(pk_bytes);
-            // the round's tables and the children's pinned records: grown here, while the stream is idle (the last round ended with
-            // get_nodes_dev's synchronisation), not behind the packet's copy
-            const size_t lqs = (size_t)kNQ_LQ * 2 * kBuckets;
-            E.hist.reserve(std::max(hs, lqs * nr)); E.hsize.reserve((size_t)nr * kBuckets); E.hcount.reserve((size_t)nr * kBuckets);
-            E.lut.reserve((size_t)nr * kBuckets);
-            E.tilesA.reserve(ntA); E.tilesP.reserve(ntP);
-            E.tilecnt.reserve((size_t)ntP * kMaxChildren); E.tileoff.reserve((size_t)ntP * kMaxChildren);
-            E.h_stage_out.reserve(cids.size());
-            std::memcpy(E.h_packet.p + o_recs, recs.data(), (size_t)nr * sizeof(NodeIn));
-            std::memcpy(E.h_packet.p + o_ids, ids.data(), (size_t)nr * sizeof(int));
-            std::memcpy(E.h_packet.p + o_cids, cids.data(), cids.size() * sizeof(int));
-            std::memcpy(E.h_packet.p + o_tA, tAg.data(), tAg.size() * sizeof(int));
-            std::memcpy(E.h_packet.p + o_tP, tPg.data(), tPg.size() * sizeof(int));
-            lap(tm_packet);
-            HIP_CHECK(hipMemcpyAsync(E.packet.p, E.h_packet.p, pk_bytes, hipMemcpyHostToDevice, s));
-            // the sweeps of a round alternate their direction through the pixels (the first one runs against the partition that
-            // wrote them): each starts on what the previous one touched last
-            const bool rev = E.stats.lq_rounds % 2 == 1;     // (the base clusters' moments were taken back to front)
-            const int *d_ids = (const int *)(E.packet.p + o_ids);
-            const int *d_tA0 = (const int *)(E.packet.p + o_tA), *d_tP0 = (const int *)(E.packet.p + o_tP);
-            RoundSetup rs{(const NodeIn *)(E.packet.p + o_recs), d_ids, d_tA0, d_tP0, nr, ntA, ntP,
-                          E.tilesA.p, E.tilesP.p, E.hist.p, lqs * nr, E.hsize.p, E.hcount.p, (size_t)nr * kBuckets};
-            {
-                const size_t work = std::max<size_t>(std::max<size_t>(std::max<size_t>(ntP, lqs * nr / 4), (size_t)nr * kNodeResetElems), 256);
-                hipLaunchKernelGGL(k_round_setup, (unsigned)std::min<size_t>((work + 255) / 256, 2048), 256, 0, s, E.nodes.p, rs);
-                HIP_CHECK(hipGetLastError());
-            }
-            launch_minmax(qlq, E.tilesA.p, ntA, rpx, E.nodes.p, s, rev);
-            if (sh) shard_exchange_keys(E, d_ids, nr);
-            launch_hist(qlq, false, E.tilesA.p, ntA, rpx, E.nodes.p, E.hist.p, E.hsize.p, E.hcount.p, s, !rev);
-            if (sh) {
-                comm_sum_dev(E, E.hist.p, lqs * nr, 0);
-                if (weighted) comm_sum_dev(E, E.hsize.p, (size_t)nr * kBuckets, 1);
-                comm_sum_dev(E, E.hcount.p, (size_t)nr * kBuckets, 2);
-            }
-            launch_cut(weighted, E.nodes.p, d_ids, nr, E.hist.p, E.hsize.p, E.hcount.p, E.lut.p, s);
-            launch_partition(qlq, E.tilesP.p, ntP, rpx, d_ids, d_tP0, nr, E.nodes.p, E.lut.p, E.tilecnt.p, E.tileoff.p, true, s, inv_sums, rev);
-            if (sh) {
-                hipLaunchKernelGGL(k_shard_children_local, (nr + 63) / 64, 64, 0, s, E.nodes.p, d_ids, nr);
-                HIP_CHECK(hipGetLastError());
-                shard_exchange_acc(E, (const int *)(E.packet.p + o_cids), 2 * nr);
-            }
-            lap(tm_enqueue);
-            get_nodes_dev(E, (const int *)(E.packet.p + o_cids), (int)cids.size(), got);
-            lap(tm_wait);
-            for (size_t i = 0; i < cids.size(); i++) {
-                HNode &c = hn[cids[i]];
-                const NodeOut &d = got[i];
-                c.begin = d.begin; c.n = d.n; c.gn = d.gn; c.buf = d.buf; c.sw = d.sw; c.psplit = d.psplit;
-                for (int j = 0; j < 3; j++) c.mean[j] = d.mean[j];
-                absorb_moments(c, d);
-                leaf_bound(c);
-            }
-            for (int id : todo) { hn[id].split_done = true; E.stats.split_evals++; E.stats.split_px += hn[id].n; }
-            for (int id : cids) leaves.push_back(id);
-            for (size_t j = 0; j < count; j++) refresh(j);      // the round's nodes are known now
-            E.stats.lq_rounds++;
-            lap(tm_children);
-        }
-        if (lq_times) fprintf(stderr, "patolette_amd: split loop host ms: greedy %.3f select %.3f axes %.3f packet %.3f enqueue %.3f wait(gpu) %.3f children %.3f\n",
-                              tm_greedy, tm_select, tm_axes, tm_packet, tm_enqueue, tm_wait, tm_children);
-        result.resize(count);
+// ---------------- local quantiser (local.c:318-404), driven from the host ----------------
+static bool hn_known(const HNode &h) { return h.nosplit || h.gn <= 1 || h.split_done; }
+// the frontier's view of the host's node mirror: the benefit if the node's split is known, else its bound
+struct HnRec {
+    const std::vector<HNode> &hn;
+    FrontierRec operator()(int id) const {
+        const HNode &h = hn[id];
+        if (!hn_known(h)) return FrontierRec{h.ub, false, h.left};
+        if (h.nosplit || h.gn <= 1) return FrontierRec{0, true, h.left};       // children == NULL -> 0 (local.c:262-264)
+        return FrontierRec{h.dist - (hn[h.left].dist + hn[h.right].dist), true, h.left};
     }
-    len = count;
-    centers.assign(3 * len, 0.0);
-    for (size_t i = 0; i < len; i++) for (int j = 0; j < 3; j++) centers[(size_t)j * len + i] = hn[result[i]].mean[j];   // create.c:11-33
-    if (max_members) { *max_members = 0; for (size_t i = 0; i < len; i++) *max_members = std::max(*max_members, hn[result[i]].gn); }
+};
+// PAMD_LQ_TIMES, a diagnostic: where the host's turn between two rounds goes
+struct LqLaps {
+    static bool env() { static const bool v = getenv("PAMD_LQ_TIMES") != nullptr; return v; }
+    const bool on = env();
+    double greedy = 0, select = 0, axes = 0, packet = 0, enqueue = 0, wait = 0, children = 0, mark = now_ms();
+    void lap(double &acc) { if (on) { const double t = now_ms(); acc += t - mark; mark = t; } }
+};
+struct LqHostLoop {
+    SplitFrontier F;                                            // the frontier in the reference's order
+    std::vector<int> leaves;                                    // candidate-tree nodes with moments but no split yet
+    LqLaps laps;
+};
+
+// a child as its parent's round left it on the device: segment, centre, moments; then its axis and bound
+static void absorb_child(HNode &c, const NodeOut &d) {
+    c.begin = d.begin; c.n = d.n; c.gn = d.gn; c.buf = d.buf; c.sw = d.sw; c.psplit = d.psplit;
+    for (int j = 0; j < 3; j++) c.mean[j] = d.mean[j];
+    absorb_moments(c, d);
+    leaf_bound(c);
+}
+
+// The leaves worth a round's evaluation have a bound of at least this.  Leaves whose distortion (an upper bound of their benefit)
+// is far below the current best benefit are left for later; the exactness test of the greedy step catches them if they ever
+// become relevant.
+static double lq_round_threshold(const SplitFrontier &F, size_t K) {
+    double thr = std::max(kDelta, kSpecBeta * F.reference_benefit());
+    // exact pruning: with R commits left, a leaf whose distortion is below the R-th largest
+    // KNOWN frontier benefit can never be chosen (its own and all its descendants' benefits are
+    // bounded by that distortion, and R better candidates outlast the remaining commits)
+    const size_t R = K - F.count;
+    std::vector<double> kb;
+    F.known_values(kb);
+    if (kb.size() >= R && R > 0) {
+        std::nth_element(kb.begin(), kb.begin() + (R - 1), kb.end(), std::greater<double>());
+        thr = std::max(thr, kb[R - 1] * (1.0 - 1e-9));
+    }
+    return thr;
+}
+
+// The greedy step is blocked: evaluate, in ONE round, the split of every leaf of the candidate tree that could still
+// matter -- undecided frontier nodes and, speculatively, the children of decided ones (a node's
+// split depends only on its members, never on the greedy order).
+static void lq_host_round(QuantCall &C, LqHostLoop &L) {
+    Engine &E = C.E;
+    hipStream_t s = E.stream;
+    std::vector<HNode> &hn = C.hn;
+    LqLaps &laps = L.laps;
+    const HnRec rec{hn};
+    const double thr = lq_round_threshold(L.F, C.K);
+    laps.lap(laps.greedy);
+    std::vector<int> round;
+    {
+        std::vector<int> keep;
+        for (int id : L.leaves) {
+            HNode &h = hn[id];
+            if (hn_known(h)) continue;                          // n <= 1 / nosplit: never split
+            if (h.ub >= thr) round.push_back(id); else keep.push_back(id);
+        }
+        L.leaves.swap(keep);
+    }
+    if (round.empty()) {                                        // every blocking node is a leaf with dist >= ref_b >= thr
+        throw HipError("patolette_amd: split loop blocked without candidates");
+    }
+    laps.lap(laps.select);
+    // axes on the host (dsyev semantics), children ids, device records
+    HIP_CHECK(hipStreamSynchronize(s));
+    E.nodes.grow(hn.size() + 2 * round.size() + 2, hn.size());
+    std::vector<int> todo;
+    std::vector<NodeIn> recs;
+    for (int id : round) {
+        double ax[3];
+        if (!node_axis(hn[id], ax)) { hn[id].nosplit = true; continue; }
+        NodeIn d = make_nodedev(hn[id], C.bnd);
+        for (int j = 0; j < 3; j++) d.axis[j] = ax[j];
+        d.slot = (int)todo.size();
+        d.child0 = (int)hn.size(); d.nchild = 2;
+        hn[id].left = (int)hn.size(); hn[id].right = (int)hn.size() + 1;        // a consecutive pair (the frontier's right = left + 1)
+        hn.push_back(HNode()); hn.push_back(HNode());
+        todo.push_back(id); recs.push_back(d);
+    }
+    L.F.reload(rec);                                            // a failed eigen-solve above makes a node known (no split)
+    laps.lap(laps.axes);
+    if (todo.empty()) return;
+    const int nr = (int)todo.size();
+    size_t rpx = 0;
+    for (int id : todo) rpx += hn[id].n;
+    static const bool lq_trace = getenv("PAMD_LQ_TRACE") != nullptr;       // one line per split round on stderr
+    if (lq_trace) fprintf(stderr, "patolette_amd: split round %zu: %d nodes, %zu pixels (%.2f of the image), %zu of %zu colours committed\n",
+                          E.stats.lq_rounds + 1, nr, rpx, (double)rpx / (double)(C.N ? C.N : 1), L.F.count, C.K);
+    // one packet, one copy: node records, ids, children ids, the tile prefixes of both tilings.  (Measured and removed:
+    // the round issued chunk-major, groups of nodes of a few MB each taken through minmax -> hist -> cut -> count -> scan ->
+    // scatter before the next group starts, so that the second and third read of a node may find it in the Infinity Cache;
+    // profiles/r06_lq_chunk_major.txt.)
+    std::vector<int> cids;
+    for (int id : todo) { cids.push_back(hn[id].left); cids.push_back(hn[id].right); }
+    std::vector<int> tAg = {0}, tPg = {0};                       // the nodes' tile prefixes (nr + 1 entries each)
+    for (int id : todo) {
+        const unsigned long long n = hn[id].n;
+        tAg.push_back(tAg.back() + (int)((n + kTileA - 1) / kTileA)); tPg.push_back(tPg.back() + (int)((n + kTileP - 1) / kTileP));
+    }
+    const int ntA = tAg[nr], ntP = tPg[nr];
+    const size_t o_recs = 0, o_ids = o_recs + (size_t)nr * sizeof(NodeIn), o_cids = o_ids + (size_t)nr * sizeof(int),
+                 o_tA = o_cids + cids.size() * sizeof(int), o_tP = o_tA + tAg.size() * sizeof(int),
+                 pk_bytes = o_tP + tPg.size() * sizeof(int);
+    E.h_packet.reserve(pk_bytes); E.packet.reserve(pk_bytes);
+    // the round's tables and the children's pinned records: grown here, while the stream is idle (the last round ended with
+    // get_nodes_dev's synchronisation), not behind the packet's copy
+    const size_t lqs = (size_t)kNQ_LQ * 2 * kBuckets;
+    reserve_quant_tables(E, QuantSizes(C.N, C.weighted ? 4 : 3, (size_t)nr));
+    E.h_stage_out.reserve(cids.size());
+    std::memcpy(E.h_packet.p + o_recs, recs.data(), (size_t)nr * sizeof(NodeIn));
+    std::memcpy(E.h_packet.p + o_ids, todo.data(), (size_t)nr * sizeof(int));
+    std::memcpy(E.h_packet.p + o_cids, cids.data(), cids.size() * sizeof(int));
+    std::memcpy(E.h_packet.p + o_tA, tAg.data(), tAg.size() * sizeof(int));
+    std::memcpy(E.h_packet.p + o_tP, tPg.data(), tPg.size() * sizeof(int));
+    laps.lap(laps.packet);
+    HIP_CHECK(hipMemcpyAsync(E.packet.p, E.h_packet.p, pk_bytes, hipMemcpyHostToDevice, s));
+    // the sweeps of a round alternate their direction through the pixels (the first one runs against the partition that
+    // wrote them): each starts on what the previous one touched last
+    const bool rev = E.stats.lq_rounds % 2 == 1;                // (the base clusters' moments were taken back to front)
+    const int *d_ids = (const int *)(E.packet.p + o_ids), *d_cids = (const int *)(E.packet.p + o_cids);
+    const int *d_tA0 = (const int *)(E.packet.p + o_tA), *d_tP0 = (const int *)(E.packet.p + o_tP);
+    RoundSetup rs{(const NodeIn *)(E.packet.p + o_recs), d_ids, d_tA0, d_tP0, nr, ntA, ntP,
+                  E.tilesA.p, E.tilesP.p, E.hist.p, lqs * nr, E.hsize.p, E.hcount.p, (size_t)nr * kBuckets};
+    {
+        const size_t work = std::max<size_t>(std::max<size_t>(std::max<size_t>(ntP, lqs * nr / 4), (size_t)nr * kNodeResetElems), 256);
+        hipLaunchKernelGGL(k_round_setup, (unsigned)std::min<size_t>((work + 255) / 256, 2048), 256, 0, s, E.nodes.p, rs);
+        HIP_CHECK(hipGetLastError());
+    }
+    launch_minmax(C.qlq, E.tilesA.p, ntA, rpx, E.nodes.p, s, rev);
+    if (C.sh) shard_exchange_keys(E, d_ids, nr);
+    launch_hist(C.qlq, false, E.tilesA.p, ntA, rpx, E.nodes.p, E.hist.p, E.hsize.p, E.hcount.p, s, !rev);
+    if (C.sh) {
+        comm_sum_dev(E, E.hist.p, lqs * nr, 0);
+        if (C.weighted) comm_sum_dev(E, E.hsize.p, (size_t)nr * kBuckets, 1);
+        comm_sum_dev(E, E.hcount.p, (size_t)nr * kBuckets, 2);
+    }
+    launch_cut(C.weighted, E.nodes.p, d_ids, nr, E.hist.p, E.hsize.p, E.hcount.p, E.lut.p, s);
+    launch_partition(C.qlq, E.tilesP.p, ntP, rpx, d_ids, d_tP0, nr, E.nodes.p, E.lut.p, E.tilecnt.p, E.tileoff.p, true, s, C.inv_sums, rev);
+    if (C.sh) {
+        hipLaunchKernelGGL(k_shard_children_local, (nr + 63) / 64, 64, 0, s, E.nodes.p, d_ids, nr);
+        HIP_CHECK(hipGetLastError());
+        shard_exchange_acc(E, d_cids, 2 * nr);
+    }
+    laps.lap(laps.enqueue);
+    get_nodes_dev(E, d_cids, (int)cids.size(), C.got);
+    laps.lap(laps.wait);
+    for (size_t i = 0; i < cids.size(); i++) absorb_child(hn[cids[i]], C.got[i]);
+    for (int id : todo) { hn[id].split_done = true; E.stats.split_evals++; E.stats.split_px += hn[id].n; }
+    for (int id : cids) L.leaves.push_back(id);
+    L.F.reload(rec);                                            // the round's nodes are known now
+    E.stats.lq_rounds++;
+    laps.lap(laps.children);
+}
+
+// The greedy loop of local.c:347-390: commit while the step is exact, evaluate a round of candidates when it is blocked
+static void lq_host_loop(QuantCall &C, LqHostLoop &L) {
+    Engine &E = C.E;
+    const std::vector<HNode> &hn = C.hn;
+    const HnRec rec{hn};
+    SplitFrontier &F = L.F;
+    E.stats.split_evals = 0; E.stats.split_px = 0; E.stats.lq_rounds = 0;
+    if (F.count >= C.K) return;
+    while (F.count < C.K) {
+        const SplitFrontier::Step st = F.step(rec, g_debug_fault.load(std::memory_order_relaxed));
+        if (st.status == SplitFrontier::kBlocked) { lq_host_round(C, L); continue; }
+        if (st.status == SplitFrontier::kStopped) { E.trace_hdr.stopped_early = 1; break; }   // benefit < DELTA: stop, keep `count` clusters
+        const HNode &h = hn[st.commit.node];
+        const int l = st.commit.left, r = l + 1;
+        patolette_amd__SplitRecord tr{};
+        tr.row = st.commit.row; tr.new_row = st.commit.new_row;
+        tr.split = hn[l].psplit < 0 ? -1 : (hn[l].psplit & 0xffff); tr.degenerate = hn[l].psplit < 0 ? 0 : (hn[l].psplit >> 16) & 1;
+        tr.n = h.gn; tr.n_left = hn[l].gn; tr.n_right = hn[r].gn; tr.sw = h.sw;
+        for (int j = 0; j < 3; j++) tr.axis[j] = h.axis[j];
+        for (int q = 0; q < 6; q++) tr.cov6[q] = h.cov6[q] / h.sw;
+        tr.dist = h.dist; tr.dist_left = hn[l].dist; tr.dist_right = hn[r].dist; tr.benefit = st.benefit;
+        E.trace.push_back(tr);
+        if (C.verbose) { printf("patolette ======== Processed colors: %zu\r", F.count); fflush(stdout); }   // local.c:386-389
+    }
+    const LqLaps &t = L.laps;
+    if (t.on) fprintf(stderr, "patolette_amd: split loop host ms: greedy %.3f select %.3f axes %.3f packet %.3f enqueue %.3f wait(gpu) %.3f children %.3f\n",
+                      t.greedy, t.select, t.axes, t.packet, t.enqueue, t.wait, t.children);
+}
+
+// PALETTE_create (create.c:11-33) over the frontier's rows, the largest cluster, the stats
+static void lq_host_epilogue(QuantCall &C, const SplitFrontier &F) {
+    Engine &E = C.E;
+    const std::vector<HNode> &hn = C.hn;
+    const size_t len = C.len = F.count;
+    C.centers.assign(3 * len, 0.0);
+    for (size_t i = 0; i < len; i++) for (int j = 0; j < 3; j++) C.centers[(size_t)j * len + i] = hn[F.result[i]].mean[j];   // create.c:11-33
+    if (C.max_members) { *C.max_members = 0; for (size_t i = 0; i < len; i++) *C.max_members = std::max(*C.max_members, hn[F.result[i]].gn); }
     E.stats.n_clusters = len;
     E.trace_hdr.n_clusters = (int32_t)len; E.trace_hdr.n_records = (int32_t)E.trace.size();
-    E.cluster_centers = centers;
-    E.stats.ms_lq = now_ms() - t0;
+    E.cluster_centers = C.centers;
+    E.stats.ms_lq = now_ms() - C.t0;
+}
+
+static int quantize_clusters_run(Engine &E, size_t N, size_t K, bool weighted, const Bounds &bnd,
+                                 std::vector<double> &centers, size_t &len, bool verbose, unsigned long long *max_members, bool allow_device) {
+    const size_t planes = weighted ? 4 : 3;
+    const Shard *sh = E.shard;                                  // the image is dealt out over a group of GPUs: N is this GPU's part
+    if (E.prep_N != N || E.prep_planes != planes) gq_prepare(E, N, weighted);   // (the stage-level entry points come here unprepared)
+    E.prep_N = 0;
+    // PAMD_LQ_DEVICE=0: the host-driven split loop everywhere (A/B, and what sliced images, K > 256 and verbose calls always take)
+    const bool dev_eligible = lq_device_eligible(E, N, K, verbose, allow_device);
+    E.nodes.reserve(std::max<size_t>(4 * K + 64, dev_eligible ? (size_t)kLqNodeCap : 0));
+    const QuantSizes root(N, planes, 1);
+    QuantCall C{E, N, sh ? sh->total : N, K, weighted, sh || E.invariant, verbose, dev_eligible, sh, bnd, centers, len, max_members,
+                QuantBuffers{{E.cvt.p, E.bufA.p}, E.bkt.p, N, weighted}, QuantBuffers{{E.bufB.p, E.bufA.p}, E.bkt.p, N, weighted},
+                (int)root.tilesA, (int)root.tilesP, hist_slot_doubles(), now_ms()};
+    C.hn.reserve(4 * K + 64);
+
+    gq_root_mean(C);
+    gq_root_covariance(C);
+    if (!gq_root_histogram(C)) return -1;
+    const bool gq_dev = g_gq_device.load(std::memory_order_relaxed) != 0 && !sh && !verbose && K > (size_t)kGqMaxK;
+    const int rc = gq_dev ? gq_device_turn(C) : gq_host_turn(C);
+    if (rc != kHostLoop) return rc;                             // failed, or the device-driven split loop has finished the call
+    E.stats.n_base_clusters = (size_t)C.kbase;
+    if (verbose) printf("patolette ======== Base cluster count: %zu\n", (size_t)C.kbase);     // patolette.c:227-229
+    E.stats.ms_gq = now_ms() - C.t0;
+    C.t0 = now_ms();
+
+    LqHostLoop L{SplitFrontier(K, C.kbase, C.base_ids[0], kDelta, HnRec{C.hn}), C.base_ids, LqLaps{}};
+    lq_host_loop(C, L);
+    lq_host_epilogue(C, L.F);
     return 0;
 }
 
