@@ -191,6 +191,35 @@ void patolette_amd_remap_u8_device(size_t frames, size_t width, size_t height, c
  * Same map either way.  Process-wide; returns the previous setting. */
 int patolette_amd_debug_remap_two_pass(int on);
 
+/* ---- remap, ordered: a position-keyed (Bayer 8x8) dither, stable from frame to frame -----------
+ * The Riemersma walk makes every choice depend on the sixteen before it along the curve, so one changed code value re-rolls the
+ * rest of a frame: animations shimmer and their inter-frame deltas compress badly.  Here a choice depends on the pixel's bytes and
+ * its position alone.  Arguments, palette handling (exactly one of the two; trailing -1 rows of the f64 one dropped), outputs, exit
+ * codes and patolette_amd_last_error texts are those of patolette_amd_remap_u8; the pixel cap is that of dither == 0.
+ * For the pixel at column x, row y OF ITS OWN FRAME, with bytes b[0..2] (a 4th byte is ignored), palette P and spread >= 0:
+ *
+ *   B(x, y)   = 8x8 Bayer index: v = 0; for i in 0,1,2: v = (v << 2) | ((((x>>i) ^ (y>>i)) & 1) << 1) | ((y>>i) & 1)
+ *               taken on (x & 7, y & 7); first row 0 32 8 40 2 34 10 42, second row 48 16 56 24 50 18 58 26; a permutation of 0..63
+ *   t         = ((double)B + 0.5) / 64.0 - 0.5                            in (-0.5, 0.5), mean 0 over a tile
+ *   v[c]      = fmin(fmax((double)b[c] / 255.0 + spread * t, 0.0), 1.0)   the same grey shift on R, G, B; no FMA
+ *   index     = nearest row of P to v, both through sRGB -> ICtCp exactly as patolette_amd_remap_u8(dither == 0) converts and
+ *               compares: d = (d0*d0 + d1*d1) + d2*d2 in f64, ascending rows, strict '<' (lowest index on ties)
+ *
+ *   - spread == 0 is patolette_amd_remap_u8 with dither == 0, bit for bit.
+ *   - No state passes between pixels or frames: the tile pattern restarts at every frame's origin.
+ *   - quantized = pal8[index], as for the other remaps.
+ *   - The shift is a lightness shift in gamma-encoded sRGB, the space in which equal steps look roughly equal; the comparison stays in
+ *     ICtCp like every nearest map here.  A useful spread is the palette's typical per-channel step (Python: ordered_spread).
+ *   spread not finite or negative: -1 with a "patolette_amd_remap:" text; a failed call leaves the thread's engine usable.
+ *   Statistics: the ms_* fields as for a remap; every dither counter 0.  patolette_amd_last_map_palette: the palette in ICtCp.
+ * One kernel (k_ordered_map): shift, conversion and an exact f64 search of the palette held in LDS; no f64 image, no tables. */
+void patolette_amd_remap_ordered_u8(size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels,
+                                    const double *palette, const unsigned char *palette_u8, size_t palette_rows, double spread,
+                                    void *palette_map, int map_elem_bytes, unsigned char *quantized, int *exit_code);
+void patolette_amd_remap_ordered_u8_device(size_t frames, size_t width, size_t height, const unsigned char *d_pixels, int channels,
+                                           const double *palette, const unsigned char *palette_u8, size_t palette_rows, double spread,
+                                           void *d_palette_map, int map_elem_bytes, unsigned char *d_quantized, int *exit_code);
+
 /* ---- RGBA images: a transparent palette slot, an alpha-aware dither ---------------------------
  * pixels: width*height interleaved 8-bit RGBA.  Pixel i is TRANSPARENT iff alpha_i < alpha_threshold (an integer in [0, 256]);
  * every other pixel is OPAQUE.  M = number of opaque pixels, N = width*height.

@@ -12,7 +12,9 @@ per-pixel weights instead of the saliency-derived ones), `saliency_weights`, `qu
 batch form `quantize_u8_batch`, and `quantize_rgba` for RGBA images: a palette built from the visible pixels only, one reserved
 transparent index, and a dither that walks past transparent pixels as the reference's walks past positions outside the image;
 and `quantize_frames` for an animation: frames of one size that share one palette, each frame dithered along its own curve;
-and `remap`, which makes no palette: it maps 8-bit images or frames onto a palette the caller gives (a fixed one, an earlier call's).
+and `remap`, which makes no palette: it maps 8-bit images or frames onto a palette the caller gives (a fixed one, an earlier call's);
+`dither="ordered"` (in `remap`, `quantize_u8`, `quantize_frames`) is a position-keyed Bayer dither for animations, `ordered_spread` its
+default strength.
 """
 import ctypes as C
 
@@ -234,11 +236,13 @@ def _u8_result(code, palette_u8, pmap, quant, palette):
     return (True, palette_u8, pmap, quant, palette, message)
 
 
-def _quantize_stack(name, lead, px, shape, dev, w, tile_size, palette_size, opts, palette, want_quantized):
-    """patolette_amd_u8 (lead = ()) and patolette_amd_frames_u8 (lead = (frames,)) on pixels of `shape` = (..., H, W, channels)."""
+def _quantize_stack(name, lead, px, shape, dev, w, tile_size, palette_size, opts, palette, want_quantized, want_map=True):
+    """patolette_amd_u8 (lead = ()) and patolette_amd_frames_u8 (lead = (frames,)) on pixels of `shape` = (..., H, W, channels).
+    Neither map nor quantized image wanted, palette_only unset: the palettes as the full call returns them (in sRGB), no map stage."""
     height, width, channels = shape[-3:]
     palette_u8 = np.zeros((max(palette_size, 0), 3), dtype=np.uint8)
-    pmap, map_elem, quant = _outputs(shape[:-1], palette_size, 3, dev, not opts.palette_only, want_quantized and not opts.palette_only)
+    pmap, map_elem, quant = _outputs(shape[:-1], palette_size, 3, dev, want_map and not opts.palette_only,
+                                     want_quantized and not opts.palette_only)
     code = C.c_int(0)
     _call(name, dev, *lead, width, height, _vp(px), channels, _vp(w), float(tile_size), palette_size, C.byref(opts), _vp(palette),
           _vp(palette_u8), _vp(pmap), map_elem, _vp(quant), C.byref(code))
@@ -246,24 +250,31 @@ def _quantize_stack(name, lead, px, shape, dev, w, tile_size, palette_size, opts
 
 
 def quantize_u8(image, palette_size, dither=True, palette_only=False, color_space=ColorSpace_ICtCp, tile_size=512,
-                kmeans_niter=32, kmeans_max_samples=512 ** 2, weights=None, want_quantized=True):
+                kmeans_niter=32, kmeans_max_samples=512 ** 2, weights=None, want_quantized=True, spread=None):
     """8-bit adaptor (additive): `image` is an (H, W, 3|4) uint8 sRGB array as an image
     decoder returns it, or a torch CUDA tensor of that shape (then nothing but the palettes crosses PCIe).  Does on the GPU what callers of the reference do by hand around `quantize`
     (README.md:147-194): `colors = img/255`, `palette_u8 = clip(palette*255).astype(uint8)` and
     `quantized = palette_u8[palette_map]`; 3 bytes per pixel cross PCIe instead of 24.
 
+    dither="ordered" (with `spread`, see `remap`): composed in Python from two calls -- the palette this call returns with
+    dither=False (made without the map stage), then `remap(image, palette, dither="ordered", spread=spread)` with that float
+    palette.  A host array is uploaded twice (once per call); a tensor is not copied at all.
+
     Returns (success, palette_u8 (K,3) uint8, palette_map (H,W) uint8|uint16|uint32 or None,
     quantized (H,W,3) uint8 or None, palette (K,3) float64 as `quantize` returns it, message)."""
+    ordered, spread = isinstance(dither, str) and _dither_mode(dither) == 2, _spread_value(spread)   # (any other string: a ValueError)
     px, shape, dev = _u8_pixels(image, (3,), (3, 4), "image must be an (H, W, 3|4) uint8 %s")
     # (unlike its siblings: no tile_size < 0 check -- a negative one derives no weights -- and the palette's rows are not clamped)
     w = _weights(weights, shape[0] * shape[1], dev)
     palette = np.zeros((palette_size, 3), dtype=np.float64, order='F')
-    return _quantize_stack("patolette_amd_u8", (), px, shape, dev, w, tile_size, palette_size,
-                           _options(dither, palette_only, color_space, kmeans_niter, kmeans_max_samples), palette, want_quantized)
+    res = _quantize_stack("patolette_amd_u8", (), px, shape, dev, w, tile_size, palette_size,
+                          _options(dither and not ordered, palette_only, color_space, kmeans_niter, kmeans_max_samples), palette,
+                          want_quantized and not ordered, want_map=not ordered)
+    return _then_ordered(res, px, spread, want_quantized) if ordered and not palette_only else res
 
 
 def quantize_frames(frames, palette_size, dither=True, palette_only=False, color_space=ColorSpace_ICtCp, tile_size=512,
-                    kmeans_niter=32, kmeans_max_samples=512 ** 2, weights=None, want_quantized=True):
+                    kmeans_niter=32, kmeans_max_samples=512 ** 2, weights=None, want_quantized=True, spread=None):
     """Quantise an animation (additive; include/patolette_amd.h: patolette_amd_frames_u8): `frames` is an (F, H, W, 3|4) uint8 sRGB
     array, or a torch CUDA tensor of that shape (then the maps and the quantized frames stay in HBM, as in `quantize_u8`).  All
     frames share ONE palette; every frame gets its own index map.
@@ -278,14 +289,22 @@ def quantize_frames(frames, palette_size, dither=True, palette_only=False, color
     (F*H, W) image; with dithering the palette equals that call's, the maps do not (one curve would run through all frames).
 
     Returns (success, palette_u8 (K,3) uint8, maps (F,H,W) uint8|uint16|uint32 or None, quantized (F,H,W,3) uint8 or None
-    (= palette_u8[maps]), palette (K,3) float64 as `quantize` returns it, message)."""
+    (= palette_u8[maps]), palette (K,3) float64 as `quantize` returns it, message).
+
+    dither="ordered" (with `spread`, see `remap`) is the mode made for animations: a choice depends on the pixel and its position
+    only, so frames that barely differ get maps that barely differ.  It is composed in Python from two calls -- the palette this
+    call returns with dither=False (made without the map stage), then `remap(frames, palette, dither="ordered", spread=spread)`
+    with that float palette.  A host array is uploaded twice (once per call); a tensor is not copied at all."""
+    ordered, spread = isinstance(dither, str) and _dither_mode(dither) == 2, _spread_value(spread)   # (any other string: a ValueError)
     px, shape, dev = _u8_pixels(frames, (4,), (3, 4), "frames must be an (F, H, W, 3|4) uint8 %s")
     if tile_size < 0:
         raise ValueError(bad_tile_size)
     w = _weights(weights, shape[0] * shape[1] * shape[2], dev, "frames*width*height")
     palette = np.zeros((max(palette_size, 0), 3), dtype=np.float64, order='F')
-    return _quantize_stack("patolette_amd_frames_u8", shape[:1], px, shape, dev, w, tile_size, palette_size,
-                           _options(dither, palette_only, color_space, kmeans_niter, kmeans_max_samples), palette, want_quantized)
+    res = _quantize_stack("patolette_amd_frames_u8", shape[:1], px, shape, dev, w, tile_size, palette_size,
+                          _options(dither and not ordered, palette_only, color_space, kmeans_niter, kmeans_max_samples), palette,
+                          want_quantized and not ordered, want_map=not ordered)
+    return _then_ordered(res, px, spread, want_quantized) if ordered and not palette_only else res
 
 
 def _remap_palette(palette):
@@ -300,9 +319,73 @@ def _remap_palette(palette):
     return None, np.asfortranarray(pal, dtype=np.float64)
 
 
-def remap(image, palette, dither=True, want_quantized=True):
+def _palette_rows(pal8, palf):
+    """The used rows of _remap_palette's result as (k, 3) float64 sRGB: bytes / 255, or the float rows without the trailing fill."""
+    if pal8 is not None:
+        return pal8.astype(np.float64) / 255.0
+    k = palf.shape[0]
+    while k > 0 and np.all(palf[k - 1] == -1.0):
+        k -= 1
+    return np.ascontiguousarray(palf[:k])
+
+
+def ordered_spread(palette):
+    """The default strength of the ordered dither for `palette` ((K, 3) uint8 or float, taken as `remap` takes it): the mean over the
+    used rows of the Euclidean sRGB distance to the nearest OTHER row, divided by sqrt(3).  A grey shift of s per channel moves a
+    colour by s * sqrt(3), so this is the palette's typical per-channel step: exactly 1/3 for four evenly spaced greys, where 1/3 is
+    the optimum.  A one-row palette gives 0.0.  Pure numpy; no GPU."""
+    rows = _palette_rows(*_remap_palette(palette))
+    k = rows.shape[0]
+    if k < 2:
+        return 0.0
+    nearest = np.empty(k)
+    for a in range(0, k, 1024):                                    # (blocks of rows: K x K distances at once is too much for large K)
+        d2 = np.sum((rows[a:a + 1024, None, :] - rows[None, :, :]) ** 2, axis=2)
+        d2[np.arange(d2.shape[0]), a + np.arange(d2.shape[0])] = np.inf
+        nearest[a:a + 1024] = np.sqrt(np.min(d2, axis=1))
+    return float(np.mean(nearest) / np.sqrt(3.0))
+
+
+def _dither_mode(dither):
+    """0 nearest, 1 Riemersma, 2 ordered for dither = False, True, "ordered"; anything else is a ValueError."""
+    if isinstance(dither, str):
+        if dither == "ordered":
+            return 2
+    elif isinstance(dither, (bool, int, np.bool_, np.integer)) and dither in (0, 1):
+        return int(dither)
+    raise ValueError('dither must be True, False or "ordered"')
+
+
+def _spread_value(spread):
+    """None, or `spread` as a float: finite and not negative, else a ValueError."""
+    if spread is None:
+        return None
+    try:
+        value = float(spread)
+    except (TypeError, ValueError):
+        raise ValueError("spread must be None or a finite number >= 0") from None
+    if not (np.isfinite(value) and value >= 0.0):
+        raise ValueError("spread must be None or a finite number >= 0")
+    return value
+
+
+def _then_ordered(res, pixels, spread, want_quantized):
+    """dither="ordered" of quantize_u8 / quantize_frames: `res` is that call's return tuple with dither=False and no map stage; the
+    ordered remap of the same pixels onto its float palette fills in the map and the quantized image.  (Not the palette_only palette:
+    as in the reference, that one stays in the quantisation's colour space; this one has been through the way back to sRGB.  With
+    color_space sRGB it is what dither=False returns there, the reference's ICtCp -> sRGB of rows that never were ICtCp.)"""
+    if not res[0]:
+        return res
+    _, palette_u8, _, _, palette, _ = res
+    ok, pmap, quant, message = remap(pixels, palette, dither="ordered", want_quantized=want_quantized, spread=spread)
+    if not ok:
+        return (False, None, None, None, None, message)
+    return (True, palette_u8, pmap, quant, palette, message)
+
+
+def remap(image, palette, dither=True, want_quantized=True, spread=None):
     """Map an 8-bit image, or frames of one size, onto a palette the caller gives (additive; include/patolette_amd.h:
-    patolette_amd_remap_u8).  No palette is made.
+    patolette_amd_remap_u8, patolette_amd_remap_ordered_u8).  No palette is made.
 
       * image: (H, W, 3|4) or (F, H, W, 3|4) uint8 sRGB, a numpy array or a torch CUDA tensor (then the map and the quantized
         image stay in HBM, as in `quantize_u8`).  A 4th channel is ignored.
@@ -311,21 +394,33 @@ def remap(image, palette, dither=True, want_quantized=True):
         (unused rows) are dropped; indices are row numbers of the palette as given.
       * dither=False: the nearest entry in ICtCp; dither=True: the reference's Riemersma walk in linear Rec2020 over each frame's own
         W x H curve from an empty error queue.  No state passes between frames: remap(frames, p)[1][i] == remap(frames[i], p)[1].
+      * dither="ordered": the mode for animations.  Every pixel's R, G and B are shifted by the same spread * t, t in (-0.5, 0.5)
+        from the 8x8 Bayer matrix at the pixel's place in its own frame, then the nearest entry in ICtCp is taken (the header has the
+        exact definition).  A choice depends on the pixel and its position only, so a small change of a frame changes few indices,
+        where the Riemersma walk re-rolls the rest of the frame.  spread=None takes `ordered_spread(palette)`; spread=0 is
+        dither=False bit for bit.  `spread` is read in this mode only; it must be finite and not negative.
     Remapping a call's quantized image onto that call's `palette_u8` gives back its map.  Remapping the ORIGINAL image onto the float
     palette a `quantize*` call returned is close to, not bit for bit, that call's map (the header says why).
 
     Returns (success, palette_map (H,W) or (F,H,W) uint8|uint16|uint32 by K, quantized (..., 3) uint8 = pal8[palette_map] or None,
     message)."""
+    mode, spread = _dither_mode(dither), _spread_value(spread)
     px, shape, dev = _u8_pixels(image, (3, 4), (3, 4), "image must be an (H, W, 3|4) or (F, H, W, 3|4) uint8 %s")
     if dev is not None and hasattr(palette, "detach"):            # (a tensor image may come with a tensor palette: that one is host data)
         palette = palette.detach().cpu().numpy()
     pal8, palf = _remap_palette(palette)
+    if mode == 2 and spread is None:
+        spread = ordered_spread(pal8 if pal8 is not None else palf)
     count, (height, width), channels = (shape[0] if len(shape) == 4 else 1), shape[-3:-1], shape[-1]
     rows = (pal8 if pal8 is not None else palf).shape[0]
     pmap, map_elem, quant = _outputs(shape[:-1], rows, 3, dev, True, want_quantized)
     code = C.c_int(0)
-    _call("patolette_amd_remap_u8", dev, count, width, height, _vp(px), channels, _vp(palf), _vp(pal8), rows, 1 if dither else 0,
-          _vp(pmap), map_elem, _vp(quant), C.byref(code))
+    if mode == 2:
+        _call("patolette_amd_remap_ordered_u8", dev, count, width, height, _vp(px), channels, _vp(palf), _vp(pal8), rows, spread,
+              _vp(pmap), map_elem, _vp(quant), C.byref(code))
+    else:
+        _call("patolette_amd_remap_u8", dev, count, width, height, _vp(px), channels, _vp(palf), _vp(pal8), rows, mode,
+              _vp(pmap), map_elem, _vp(quant), C.byref(code))
     if code.value == -1 and _native.last_error().startswith("patolette_amd_remap:"):
         raise ValueError(_native.last_error())
     message = _message(code.value)
@@ -478,6 +573,7 @@ __all__ = [
     "quantize_rgba",
     "quantize_frames",
     "remap",
+    "ordered_spread",
     "saliency_weights",
     "ColorSpace_sRGB",
     "ColorSpace_CIELuv",

@@ -111,6 +111,10 @@ SYMBOLS = {
                                       C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
     "patolette_amd_remap_u8_device": (None, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, dp, C.c_void_p, C.c_size_t, C.c_int,
                                              C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
+    "patolette_amd_remap_ordered_u8": (None, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, dp, C.c_void_p, C.c_size_t, C.c_double,
+                                              C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
+    "patolette_amd_remap_ordered_u8_device": (None, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, dp, C.c_void_p, C.c_size_t,
+                                                     C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
     "patolette_amd_debug_remap_two_pass": (C.c_int, [C.c_int]),
     "patolette_amd_rgba": (None, [C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, dp, C.c_double, C.c_size_t,
                                   C.POINTER(QuantizationOptions), dp, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,

@@ -21,6 +21,7 @@
 #include "host_math.h"
 #include "kmeans.h"
 #include "map.h"
+#include "ordered.h"
 #include "saliency.h"
 #include "quant.h"
 #include "rgba.h"
@@ -2685,9 +2686,12 @@ static std::atomic<int> g_remap_two_pass{0};
 // LDS-table kernel runs): launch_nn_map_u8 converts in registers.  Dither, two-pass: pixels -> linear
 // Rec2020 planes -> launch_dither / launch_dither_frames.  Dither, fused (where the lane layout runs): launch_dither_u8 gathers the
 // bytes along the curve and converts them there; no f64 image is written.
+// Ordered (mode kRemapOrdered, `spread`): launch_ordered_map shifts, converts and searches in one kernel; palette in ICtCp, no f64 image.
+enum { kRemapNearest = 0, kRemapRiemersma = 1, kRemapOrdered = 2 };
 static void run_remap(Engine &E, size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels, std::vector<double> pal,
-                      size_t k, const std::vector<unsigned char> &p8, size_t K8, bool dither, void *map_out, int map_elem_out,
+                      size_t k, const std::vector<unsigned char> &p8, size_t K8, int mode, double spread, void *map_out, int map_elem_out,
                       unsigned char *quant_out, bool on_device) {
+    const bool dither = mode == kRemapRiemersma, ordered = mode == kRemapOrdered;
     const size_t n = width * height, N = frames * n;
     hipStream_t s = E.stream;
     const double t_start = now_ms();
@@ -2695,7 +2699,7 @@ static void run_remap(Engine &E, size_t frames, size_t width, size_t height, con
     E.stats = patolette_amd__Stats{};
     const int me = map_elem_for(K8);
     const bool lanes = dither && (frames > 1 ? dither_frames_lane_layout(frames, width, height, (int)k) : dither_lane_layout(width, height, (int)k));
-    const bool fused = !g_remap_two_pass.load(std::memory_order_relaxed) && (dither ? lanes : nn_map_u8_applies(N, (int)k));
+    const bool fused = ordered || (!g_remap_two_pass.load(std::memory_order_relaxed) && (dither ? lanes : nn_map_u8_applies(N, (int)k)));
     // the workspace, before anything is enqueued
     if (!on_device) E.src8.reserve(N * (size_t)channels);
     E.dpal.reserve(3 * k); E.h_pal.reserve(3 * k);
@@ -2716,7 +2720,9 @@ static void run_remap(Engine &E, size_t frames, size_t width, size_t height, con
     if (want) {
         std::memcpy(E.h_pal.p, pal.data(), 3 * k * sizeof(double));
         HIP_CHECK(hipMemcpyAsync(E.dpal.p, E.h_pal.p, 3 * k * sizeof(double), hipMemcpyHostToDevice, s));
-        if (!dither && fused) {
+        if (ordered) {
+            launch_ordered_map(d_px, channels, frames, width, height, spread, E.dpal.p, (int)k, d_map, me, s);
+        } else if (!dither && fused) {
             HIP_CHECK(hipStreamSynchronize(s));                                       // (the map kernels' tables are reserved on an idle stream)
             launch_nn_map_u8(d_px, channels, N, E.dpal.p, (int)k, d_map, me, E.nn, s);
         } else if (!dither) {
@@ -3144,8 +3150,10 @@ static const char *const kBadU8Args = "patolette_amd: bad channels / map_elem_by
 
 // 8-bit pixels onto the caller's palette (include/patolette_amd.h): the arguments, then run_remap
 static void remap_entry(bool on_device, size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels, const double *palette,
-                        const unsigned char *palette_u8, size_t palette_rows, int dither, void *palette_map, int map_elem_bytes,
+                        const unsigned char *palette_u8, size_t palette_rows, int mode, double spread, void *palette_map, int map_elem_bytes,
                         unsigned char *quantized, int *exit_code) {
+    // mode: kRemapNearest, kRemapRiemersma, or kRemapOrdered with its `spread` (the ordered map counts pixels as the nearest one does)
+    const bool dither = mode == kRemapRiemersma;
     *exit_code = frames == 0 ? -2 : validate(width, height, 1);
     if (*exit_code != 0) return;
     const size_t n = width * height;
@@ -3177,8 +3185,10 @@ static void remap_entry(bool on_device, size_t frames, size_t width, size_t heig
         }
         palette_to_u8(palette, palette_rows, p8.data());
     }
+    if (mode == kRemapOrdered && !(std::isfinite(spread) && spread >= 0.0))
+        return fail_args(exit_code, -1, "patolette_amd_remap: spread must be finite and not negative");
     *exit_code = guarded([&](Engine &E) {
-        run_remap(E, frames, width, height, pixels, channels, std::move(pal), k, p8, palette_rows, dither != 0, palette_map, map_elem_bytes, quantized,
+        run_remap(E, frames, width, height, pixels, channels, std::move(pal), k, p8, palette_rows, mode, spread, palette_map, map_elem_bytes, quantized,
                   on_device);
     });
 }
@@ -3216,15 +3226,29 @@ void patolette_amd_rgba_device(size_t width, size_t height, const unsigned char 
 void patolette_amd_remap_u8(size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels, const double *palette,
                             const unsigned char *palette_u8, size_t palette_rows, int dither, void *palette_map, int map_elem_bytes,
                             unsigned char *quantized, int *exit_code) {
-    remap_entry(false, frames, width, height, pixels, channels, palette, palette_u8, palette_rows, dither, palette_map, map_elem_bytes, quantized,
-                exit_code);
+    remap_entry(false, frames, width, height, pixels, channels, palette, palette_u8, palette_rows, dither ? kRemapRiemersma : kRemapNearest, 0.0,
+                palette_map, map_elem_bytes, quantized, exit_code);
 }
 
 void patolette_amd_remap_u8_device(size_t frames, size_t width, size_t height, const unsigned char *d_pixels, int channels, const double *palette,
                                    const unsigned char *palette_u8, size_t palette_rows, int dither, void *d_palette_map, int map_elem_bytes,
                                    unsigned char *d_quantized, int *exit_code) {
-    remap_entry(true, frames, width, height, d_pixels, channels, palette, palette_u8, palette_rows, dither, d_palette_map, map_elem_bytes,
-                d_quantized, exit_code);
+    remap_entry(true, frames, width, height, d_pixels, channels, palette, palette_u8, palette_rows, dither ? kRemapRiemersma : kRemapNearest, 0.0,
+                d_palette_map, map_elem_bytes, d_quantized, exit_code);
+}
+
+void patolette_amd_remap_ordered_u8(size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels, const double *palette,
+                                    const unsigned char *palette_u8, size_t palette_rows, double spread, void *palette_map, int map_elem_bytes,
+                                    unsigned char *quantized, int *exit_code) {
+    remap_entry(false, frames, width, height, pixels, channels, palette, palette_u8, palette_rows, kRemapOrdered, spread, palette_map,
+                map_elem_bytes, quantized, exit_code);
+}
+
+void patolette_amd_remap_ordered_u8_device(size_t frames, size_t width, size_t height, const unsigned char *d_pixels, int channels,
+                                           const double *palette, const unsigned char *palette_u8, size_t palette_rows, double spread,
+                                           void *d_palette_map, int map_elem_bytes, unsigned char *d_quantized, int *exit_code) {
+    remap_entry(true, frames, width, height, d_pixels, channels, palette, palette_u8, palette_rows, kRemapOrdered, spread, d_palette_map,
+                map_elem_bytes, d_quantized, exit_code);
 }
 
 int patolette_amd_debug_remap_two_pass(int on) { return g_remap_two_pass.exchange(on ? 1 : 0); }
