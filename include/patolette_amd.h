@@ -220,6 +220,62 @@ void patolette_amd_remap_ordered_u8_device(size_t frames, size_t width, size_t h
                                            const double *palette, const unsigned char *palette_u8, size_t palette_rows, double spread,
                                            void *d_palette_map, int map_elem_bytes, unsigned char *d_quantized, int *exit_code);
 
+/* ---- frame deltas: an animation's index maps with "same as what is on screen" made transparent --
+ * What a GIF or APNG encoder makes of every frame: the map with the unchanged positions replaced by a transparent index, and the dirty
+ * rectangle.  n = width * height; m[f][p]: the input maps, frame after frame, as every *_frames_u8 / remap entry writes them, with
+ * elements of map_elem_bytes (1, 2, 4 or 8; the *_device flavour: 1 or 4).  T = transparent_index: at least palette_rows and
+ * representable in an element, so that it is an index no entry uses (1-byte maps with 256 rows have none: make the palette with one
+ * row less).  palette_rows counts the rows of the palette as given, in [1, 2^31].
+ *
+ *   frame 0:      delta[0] = m[0], shown[0] = m[0]; the canvas is c = m[0]; rects[0] = (0, 0, width, height), changed[0] = n.
+ *   frame f >= 1, every position p on its own, with a = m[f][p]:
+ *     keep = (a == c[p]) || (tolerance > 0 && D <= tolerance * tolerance)
+ *     D    = distance between the SOURCE pixel pixels[f][p] and the entry ON THE CANVAS, row c[p] of the palette, both through
+ *            sRGB -> ICtCp exactly as patolette_amd_remap_u8(dither == 0) converts them (the pixel's bytes / 255.0, a byte palette
+ *            likewise): D = (d0*d0 + d1*d1) + d2*d2 in f64, no FMA; evaluated only when a != c[p]
+ *     keep:       delta[f][p] = T, the canvas stays.       otherwise: delta[f][p] = a, c[p] = a.       Both: shown[f][p] = c[p].
+ *   rects[f]   = (x0, y0, w, h), four int32 per frame: the tight bounding box of the positions with delta[f] != T; (0, 0, 0, 0)
+ *                when there is none.  changed[f] = their number.
+ *
+ * tolerance == 0 (the exact mode): pixels, channels and both palettes are not read; the pointers may be NULL.
+ * tolerance > 0 (the lossy mode): pixels (frames x n, interleaved, channels = 3 or 4 bytes each; a 4th byte is ignored) and exactly
+ *   one of palette (planar (palette_rows,3) f64 sRGB) and palette_u8, in the forms patolette_amd_remap_u8 takes; trailing
+ *   (-1, -1, -1) rows of the f64 one are dropped.
+ * Every element must be below palette_rows and must not name a dropped row: an element that does is never used as a palette
+ *   address, the kernel raises a flag, and the call fails with -1 and a "patolette_amd_frame_deltas:" text (checked in both modes;
+ *   what the outputs then hold is not defined).
+ * Consequences:
+ *   - Compositing the deltas gives back `shown`: start from delta[0]; in frame f overwrite the positions where delta[f] != T.
+ *   - tolerance == 0: shown == the input maps.
+ *   - tolerance > 0: every shown entry is the frame's own choice or lies within `tolerance` (ICtCp, Euclidean) of THAT frame's source
+ *     pixel.  The comparison is always with the current source, never with an earlier frame: no error accumulates.
+ *   - The device converts pixels with patolette_amd_pow (0.52 ulp): a D within an ulp or two of tolerance^2 may fall on the other
+ *     side than in libm arithmetic.
+ * Every output pointer may be NULL (delta_maps, shown_maps: frames x n elements of map_elem_bytes; rects: 4 * frames; changed:
+ * frames).  delta_maps may be palette_maps itself.  The *_device flavour takes device pointers for palette_maps, pixels, delta_maps
+ * and shown_maps; rects, changed and both palettes stay host memory.
+ * Exit codes: -2 frames == 0 or an empty image; -4 beyond the pixel cap of patolette_amd_remap_u8(dither == 0); -1 (with a
+ * "patolette_amd_frame_deltas:" text in patolette_amd_last_error) for a bad map_elem_bytes, no maps, bad channels, T < palette_rows,
+ * T not representable, a tolerance that is negative or not finite, missing pixels or both or neither palette in the lossy mode, a
+ * palette value that is not finite, or the flag above.  A failed call leaves the thread's engine usable.
+ * Statistics: the ms_* fields as for a remap (ms_map: the kernel and its results), every other field 0.
+ * Out of scope: maps that already carry a transparent entry (those of patolette_amd_rgba): their index 0 is compared like any other.
+ * One kernel for all frames (k_frame_deltas): a lane owns a position, walks the frames and keeps the canvas entry in a register. */
+void patolette_amd_frame_deltas(size_t frames, size_t width, size_t height, const void *palette_maps, int map_elem_bytes,
+                                size_t palette_rows, size_t transparent_index, const unsigned char *pixels, int channels,
+                                const double *palette, const unsigned char *palette_u8, double tolerance, void *delta_maps,
+                                void *shown_maps, int32_t *rects, uint64_t *changed, int *exit_code);
+void patolette_amd_frame_deltas_device(size_t frames, size_t width, size_t height, const void *d_palette_maps, int map_elem_bytes,
+                                       size_t palette_rows, size_t transparent_index, const unsigned char *d_pixels, int channels,
+                                       const double *palette, const unsigned char *palette_u8, double tolerance, void *d_delta_maps,
+                                       void *d_shown_maps, int32_t *rects, uint64_t *changed, int *exit_code);
+
+/* TESTS ONLY: k_frame_deltas gives a lane four consecutive positions (one 4- or 16-byte access) where width * height is a multiple of
+ * 4, the buffers are aligned for it and the frame is large enough to keep the GPU full with a quarter of the wavefronts (2^21 pixels
+ * on an MI355X); otherwise one.  1 takes four wherever sizes and addresses allow, 0 never, -1 restores that rule.  Same results
+ * either way.  Process-wide; returns the previous mode. */
+int patolette_amd_debug_delta_quad(int mode);
+
 /* ---- RGBA images: a transparent palette slot, an alpha-aware dither ---------------------------
  * pixels: width*height interleaved 8-bit RGBA.  Pixel i is TRANSPARENT iff alpha_i < alpha_threshold (an integer in [0, 256]);
  * every other pixel is OPAQUE.  M = number of opaque pixels, N = width*height.

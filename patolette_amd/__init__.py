@@ -14,7 +14,8 @@ transparent index, and a dither that walks past transparent pixels as the refere
 and `quantize_frames` for an animation: frames of one size that share one palette, each frame dithered along its own curve;
 and `remap`, which makes no palette: it maps 8-bit images or frames onto a palette the caller gives (a fixed one, an earlier call's);
 `dither="ordered"` (in `remap`, `quantize_u8`, `quantize_frames`) is a position-keyed Bayer dither for animations, `ordered_spread` its
-default strength.
+default strength; and `frame_deltas`, which turns an animation's maps into what an encoder writes per frame: unchanged positions made
+transparent, and the dirty rectangle.
 """
 import ctypes as C
 
@@ -429,6 +430,102 @@ def remap(image, palette, dither=True, want_quantized=True, spread=None):
     return (True, pmap, quant, message)
 
 
+def _delta_maps(maps):
+    """`maps` as contiguous (F, H, W) index maps -> (maps, shape, torch device or None, bytes per element, largest index an element
+    holds); numpy uint8 / uint16 / uint32, or a torch uint8 / int32 CUDA tensor (what the device entries write)."""
+    dev = maps.device if _is_cuda(maps) else None
+    if dev is not None:
+        import torch
+        m = maps.contiguous()
+        sizes = {torch.uint8: (1, 255), torch.int32: (4, 2 ** 31 - 1)}
+        elem = sizes.get(m.dtype)
+    else:
+        m = np.ascontiguousarray(maps)
+        elem = (m.dtype.itemsize, int(np.iinfo(m.dtype).max)) if m.dtype in (np.uint8, np.uint16, np.uint32) else None
+    shape = tuple(int(v) for v in m.shape)
+    if elem is None or len(shape) != 3:
+        raise ValueError("maps must be an (F, H, W) uint8 / uint16 / uint32 array or a uint8 / int32 CUDA tensor")
+    return m, shape, dev, elem[0], elem[1]
+
+
+def frame_deltas(maps, palette, transparent_index=None, frames=None, tolerance=0.0, want_shown=False):
+    """The inter-frame deltas of an animation's index maps (additive; include/patolette_amd.h: patolette_amd_frame_deltas): what a
+    GIF or APNG encoder makes of every frame -- the map with "same as what is already on screen" replaced by a transparent index, and
+    the dirty rectangle -- without the maps leaving the GPU.
+
+      * maps: (F, H, W) uint8 / uint16 / uint32 numpy array as `quantize_frames` / `remap` return it, or a torch uint8 / int32 CUDA
+        tensor (then the deltas and the shown maps stay on its device).
+      * palette: what `remap` takes ((K, 3) uint8 or float), or a plain int row count (allowed with tolerance 0 only, which reads
+        no colours).
+      * transparent_index: an index no palette entry uses; default K.  It must fit the maps' element type: uint8 maps of a 256-row
+        palette have no free index -- make the palette with one row less (`quantize_frames(frames, 255, ...)`).
+      * tolerance 0: a position is transparent in frame f iff its index equals what the canvas shows there.  tolerance > 0 (lossy,
+        the largest lever on GIF size): the displayed entry also stays while it lies within `tolerance` (ICtCp, Euclidean) of the
+        frame's SOURCE pixel, so `frames` -- the (F, H, W, 3|4) uint8 pixels, where the maps live -- is required; the comparison is
+        always with the current source, so no error accumulates.
+      * want_shown: also return what the canvas shows after every frame (== maps when tolerance is 0).
+    Frame 0 is the full first map.  Compositing the deltas (overwrite where delta != transparent_index) gives back `shown`.
+
+    Returns (success, deltas (F,H,W) as maps, rects (F,4) int32 rows (x0, y0, w, h) -- (0,0,0,0) for an unchanged frame --,
+    changed (F,) int64, shown (F,H,W) or None, message)."""
+    m, shape, dev, elem, elem_max = _delta_maps(maps)
+    try:
+        tol = float(tolerance)
+    except (TypeError, ValueError):
+        raise ValueError("tolerance must be a finite number >= 0") from None
+    if not (np.isfinite(tol) and tol >= 0.0):
+        raise ValueError("tolerance must be a finite number >= 0")
+    pal8 = palf = None
+    if isinstance(palette, (int, np.integer)) and not isinstance(palette, (bool, np.bool_)):
+        if tol > 0.0:
+            raise ValueError("a tolerance above 0 compares colours: pass the palette itself, not its row count")
+        rows = int(palette)
+        if rows < 1:
+            raise ValueError("the palette's row count must be at least 1")
+    else:
+        if hasattr(palette, "detach"):
+            palette = palette.detach().cpu().numpy()
+        pal8, palf = _remap_palette(palette)
+        rows = (pal8 if pal8 is not None else palf).shape[0]
+    T = rows if transparent_index is None else int(transparent_index)
+    if T < rows:
+        raise ValueError("transparent_index must be at least the palette's row count (%d): an index no entry uses" % rows)
+    if T > elem_max:
+        raise ValueError("no free index: transparent_index %d does not fit the maps' %d-byte elements -- make the palette with one row "
+                         "less, or pass wider maps" % (T, elem))
+    px, channels = None, 3
+    if frames is not None:
+        px, pshape, pdev = _u8_pixels(frames, (4,), (3, 4), "frames must be an (F, H, W, 3|4) uint8 %s")
+        if pshape[:3] != shape:
+            raise ValueError("frames of shape %s do not match maps of shape %s" % (pshape, shape))
+        if pdev != dev:
+            raise ValueError("frames and maps must live in the same place (both numpy arrays, or tensors of one device)")
+        channels = pshape[3]
+    if tol > 0.0 and px is None:
+        raise ValueError("a tolerance above 0 needs the frames' pixels: pass frames=")
+    if tol == 0.0:
+        px = pal8 = palf = None                                   # (the exact mode reads none of them)
+    count, height, width = shape
+    if dev is None:
+        deltas = np.zeros(shape, dtype=m.dtype)
+        shown = np.zeros(shape, dtype=m.dtype) if want_shown else None
+    else:
+        import torch
+        deltas = torch.zeros(shape, dtype=m.dtype, device=dev)
+        shown = torch.zeros(shape, dtype=m.dtype, device=dev) if want_shown else None
+    rects = np.zeros((count, 4), dtype=np.int32)
+    changed = np.zeros(count, dtype=np.uint64)
+    code = C.c_int(0)
+    _call("patolette_amd_frame_deltas", dev, count, width, height, _vp(m), elem, rows, T, _vp(px), channels, _vp(palf), _vp(pal8), tol,
+          _vp(deltas), _vp(shown), rects.ctypes.data_as(C.POINTER(C.c_int32)), changed.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(code))
+    if code.value == -1 and _native.last_error().startswith("patolette_amd_frame_deltas:"):
+        raise ValueError(_native.last_error())
+    message = _message(code.value)
+    if code.value != 0:
+        return (False, None, None, None, None, message)
+    return (True, deltas, rects, changed.astype(np.int64), shown, message)
+
+
 def quantize_rgba(image, palette_size, alpha_threshold=128, dither=True, palette_only=False, color_space=ColorSpace_ICtCp,
                   tile_size=512, kmeans_niter=32, kmeans_max_samples=512 ** 2, weights=None, want_quantized=True):
     """Quantise an (H, W, 4) uint8 RGBA image (additive; include/patolette_amd.h: patolette_amd_rgba).  `image` is a numpy array,
@@ -574,6 +671,7 @@ __all__ = [
     "quantize_frames",
     "remap",
     "ordered_spread",
+    "frame_deltas",
     "saliency_weights",
     "ColorSpace_sRGB",
     "ColorSpace_CIELuv",

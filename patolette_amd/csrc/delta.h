@@ -1,0 +1,35 @@
+// delta.h -- launcher of the frame-delta kernel (delta.hip).
+#pragma once
+
+#include "common.h"
+
+namespace pamd {
+
+// palette rows a block of k_frame_deltas<.., true> holds in LDS, as three planar f64 arrays (24 KB next to the 4 KB of pow tables
+// and the 2 KB companding table); a longer palette is indexed in global memory (a lookup by index, not a search)
+constexpr int kDeltaChunk = 1024;
+// same-address atomics serialise in L2: the per-frame results of k_delta_boxes' blocks are spread over this many slots, which the host folds
+constexpr int kDeltaSlots = 32;
+
+// what the kernels leave for the host, as unsigned long long words: per frame and slot a box of four unsigned ints, all kept as
+// maxima over zeroed memory (width - x0, height - y0, x1 + 1, y1 + 1), then per frame and slot a count, then one word whose low
+// bit says that some element was not below `rows`
+inline size_t frame_deltas_words(size_t frames) { return frames * (size_t)kDeltaSlots * 3 + 1; }
+// between the two kernels: per frame one 64-bit ballot per wavefront of positions (bit i of word w: position 64 w + i changed)
+inline size_t frame_deltas_masks(size_t frames, size_t n) { return frames * ceil_div(n, 64); }
+
+// The frame deltas of include/patolette_amd.h (patolette_amd_frame_deltas): `frames` index maps of width x height with elements of
+// 1 or 4 bytes; rows: the number every element must stay below (lossy: the palette's used rows, the stride of d_pal); T: the
+// transparent index.  lossy: d_px are the frames' interleaved 8-bit sRGB pixels, d_pal the palette in ICtCp, planar (rows,3), tol2
+// the squared tolerance; otherwise none of the three is read.  d_delta (may be d_maps) and d_shown may be null.  d_masks:
+// frame_deltas_masks(frames, n) words of scratch; d_words: frame_deltas_words(frames) words, zeroed here.  One kernel walks all
+// frames (k_frame_deltas), a small one folds its ballots into the boxes and counts (k_delta_boxes).
+void launch_frame_deltas(const void *d_maps, int elem_bytes, size_t frames, size_t width, size_t height, size_t rows, size_t T, bool lossy,
+                         const unsigned char *d_px, int channels, const double *d_pal, double tol2, void *d_delta, void *d_shown,
+                         unsigned long long *d_masks, unsigned long long *d_words, hipStream_t s);
+
+// TESTS ONLY: how many positions a lane of k_frame_deltas owns: -1 the launcher's rule (four from 32 wavefronts per CU on, where the
+// sizes and addresses allow vector accesses), 0 always one, 1 four wherever they are allowed.  Same results.  Returns the previous mode.
+int delta_debug_quad(int mode);
+
+}  // namespace pamd

@@ -1,0 +1,255 @@
+// delta.hip -- frame deltas of an animation's index maps on gfx950: include/patolette_amd.h, patolette_amd_frame_deltas.
+//
+// The step is a chain over frames and independent per position, so a lane owns one position, walks all frames and keeps the canvas
+// entry in a register: one launch, no canvas buffer, element bytes x (1 + outputs) of traffic per pixel-frame.  The loads of a
+// position's elements do not depend on the decisions: while one group of kDeltaAhead frames is decided the next group's elements are
+// already on their way (a small clip gives a CU few wavefronts to hide the latency with).  Where every frame starts on a vector boundary a lane owns four
+// consecutive positions and moves them as one 4- or 16-byte access.  delta may be the input buffer: a lane stores a frame's
+// elements only after it has loaded them, and no other lane touches those positions.
+// Lossy: a lane whose element differs from its canvas entry takes the frame's source pixel through the byte -> ICtCp route of the
+// nearest maps (the companding from a 256-entry table in LDS, then dev_convert_linear with the pow tables in LDS) and compares it
+// with the canvas entry's palette row, read by index from LDS (from global memory beyond kDeltaChunk rows).  Lanes that see no
+// difference convert nothing; whole frames are not converted ahead.
+// Rectangle and count in two stages, integers only (order-free).  The walk leaves one ballot per wavefront and frame -- which of its
+// 64 consecutive positions changed: one bit per pixel-frame, a plain vector store by one lane, no barrier and no atomic inside the
+// walk.  k_delta_boxes then reads the ballots: a count is a popcount, rows come from the first and the last set bit (positions
+// ascend), columns likewise while the 64 positions lie in one row and bit by bit where they wrap; blocks reduce in LDS and reach
+// global memory with one set of integer atomics per block, none for a block that saw no change.
+// (First form, measured and replaced: the walk itself reduced every frame -- shuffles, LDS atomics between two barriers per
+// kDeltaAhead frames, one set of global atomics per block and frame over kDeltaSlots slots.  64 frames of 640 x 360: 0.091 ms;
+// 2 frames of 4096 x 4096: 0.662 ms, where 65 536 blocks met on 160 addresses.  DESIGN.md 4.11 has both.)
+#include "delta.h"
+
+#define PAMD_POW_TABLES_IN_LDS
+#include "color_device.h"
+
+namespace pamd {
+
+// TESTS ONLY (patolette_amd_debug_delta_quad): -1 the rule of launch_frame_deltas, 0 one position per lane, 1 four wherever they can be
+static std::atomic<int> g_delta_quad{-1};
+int delta_debug_quad(int mode) { return g_delta_quad.exchange(mode < 0 ? -1 : (mode ? 1 : 0)); }
+
+constexpr int kDeltaAhead = 4;       // frames per group: a group's elements are loaded while the group before it is decided
+
+// V consecutive elements as one access (V = 4: a 4- or 16-byte vector)
+template <typename ElemT> struct Quad;
+template <> struct Quad<unsigned char> { using type = uchar4; };
+template <> struct Quad<unsigned int> { using type = uint4; };
+template <typename ElemT, int V>
+__device__ __forceinline__ void load_elems(const ElemT *at, unsigned (&out)[V]) {
+    if constexpr (V == 1) out[0] = at[0];
+    else { const typename Quad<ElemT>::type q = *reinterpret_cast<const typename Quad<ElemT>::type *>(at); out[0] = q.x; out[1] = q.y; out[2] = q.z; out[3] = q.w; }
+}
+template <typename ElemT, int V>
+__device__ __forceinline__ void store_elems(ElemT *at, const unsigned (&in)[V]) {
+    if constexpr (V == 1) at[0] = (ElemT)in[0];
+    else {
+        typename Quad<ElemT>::type q;
+        q.x = (ElemT)in[0]; q.y = (ElemT)in[1]; q.z = (ElemT)in[2]; q.w = (ElemT)in[3];
+        *reinterpret_cast<typename Quad<ElemT>::type *>(at) = q;
+    }
+}
+
+// V: positions a lane owns, consecutive ones.  4 needs n to be a multiple of 4 and buffers aligned for the vector accesses (every
+// frame then starts on a vector boundary, and a lane's positions lie all inside the frame or all past its end); launch_frame_deltas
+// takes it for large frames only.
+template <typename ElemT, bool Lossy, int V>
+__global__ __launch_bounds__(256) void k_frame_deltas(const ElemT *maps, size_t F, size_t n, size_t nw, unsigned rows, ElemT T,
+                                                      const unsigned char *__restrict__ px, int ch,
+                                                      const double *__restrict__ pal /* planar (rows,3), ICtCp */, double tol2,
+                                                      ElemT *delta, ElemT *shown, unsigned long long *masks, unsigned *flag) {
+    constexpr int A = kDeltaAhead;
+    __shared__ double s_pal[Lossy ? 3 : 1][Lossy ? kDeltaChunk : 1];
+    __shared__ double s_glut[Lossy ? 256 : 1];
+    const unsigned tid = threadIdx.x, lane = tid & 63u;
+    const bool resident = rows <= (unsigned)kDeltaChunk;
+    if constexpr (Lossy) {
+        pow_tables_to_lds();
+        __syncthreads();
+        s_glut[tid] = dc::gamma_decode((double)tid / 255.0);    // (256 threads) sRGB.c:70-89 of every byte value, as k_nn_map_u8 holds it
+        if (resident)
+            for (unsigned j = tid; j < rows; j += 256) { s_pal[0][j] = pal[j]; s_pal[1][j] = pal[(size_t)rows + j]; s_pal[2][j] = pal[2 * (size_t)rows + j]; }
+        __syncthreads();
+    }
+    const size_t p = ((size_t)blockIdx.x * 256 + tid) * V;       // the first of this lane's V positions
+    const bool active = p < n;                                   // (a lane past the end stays for the ballots)
+    unsigned c[V];                                               // the canvas entries
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < V; j++) c[j] = 0;
+    if (active) {
+        load_elems<ElemT, V>(maps + p, c);
+#pragma unroll
+        for (int j = 0; j < V; j++) bad |= c[j] >= rows;
+        if (delta) store_elems<ElemT, V>(delta + p, c);
+        if (shown) store_elems<ElemT, V>(shown + p, c);
+    }
+    unsigned a[A][V], b[A][V];
+#pragma unroll
+    for (int u = 0; u < A; u++) {
+#pragma unroll
+        for (int j = 0; j < V; j++) a[u][j] = 0;
+        if (active && 1 + u < F) load_elems<ElemT, V>(maps + (1 + u) * n + p, a[u]);
+    }
+    for (size_t f = 1; f < F; f += A) {
+#pragma unroll
+        for (int u = 0; u < A; u++) {
+#pragma unroll
+            for (int j = 0; j < V; j++) b[u][j] = 0;
+            if (active && f + A + u < F) load_elems<ElemT, V>(maps + (f + A + u) * n + p, b[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < A; u++) {
+            if (f + u >= F) break;                               // (the same for every lane)
+            const size_t at = (f + u) * n + p;
+            unsigned out[V], changes = 0;                        // bit j: this lane's position p + j changed
+#pragma unroll
+            for (int j = 0; j < V; j++) {
+                bool change = active && a[u][j] != c[j];
+                bad |= active && a[u][j] >= rows;
+                if constexpr (Lossy) {
+                    if (change && c[j] < rows) {                 // (an element that is no row is never an address: `bad` fails the call)
+                        const unsigned char *q = px + (at + j) * (size_t)ch;
+                        double v[3] = {s_glut[q[0]], s_glut[q[1]], s_glut[q[2]]};
+                        dev_convert_linear<PAMD_SRGB_TO_ICTCP>(v);
+                        double p0, p1, p2;
+                        if (resident) { p0 = s_pal[0][c[j]]; p1 = s_pal[1][c[j]]; p2 = s_pal[2][c[j]]; }
+                        else { p0 = pal[c[j]]; p1 = pal[(size_t)rows + c[j]]; p2 = pal[2 * (size_t)rows + c[j]]; }
+                        const double d0 = v[0] - p0, d1 = v[1] - p1, d2 = v[2] - p2;
+                        const double d = (d0 * d0 + d1 * d1) + d2 * d2;
+                        if (d <= tol2) change = false;           // the entry on the canvas still serves this frame's pixel
+                    }
+                }
+                if (change) { c[j] = a[u][j]; changes |= 1u << j; }
+                out[j] = change ? a[u][j] : (unsigned)T;
+            }
+            if (active) {
+                if (delta) store_elems<ElemT, V>(delta + at, out);
+                if (shown) store_elems<ElemT, V>(shown + at, c);
+            }
+            // the ballots: bit i of word w of a frame = position 64 w + i
+            if constexpr (V == 1) {
+                const unsigned long long moved = __ballot(changes != 0);
+                if (lane == 0 && (p >> 6) < nw) masks[(f + u) * nw + (p >> 6)] = moved;
+            } else {                                             // sixteen lanes hold a word's 64 positions, four bits each
+                unsigned long long w = (unsigned long long)changes << (4 * (lane & 15u));
+#pragma unroll
+                for (int o = 8; o > 0; o >>= 1) w |= __shfl_xor(w, o);
+                if ((lane & 15u) == 0 && (p >> 6) < nw) masks[(f + u) * nw + (p >> 6)] = w;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < A; u++)
+#pragma unroll
+            for (int j = 0; j < V; j++) a[u][j] = b[u][j];
+    }
+    if (__ballot(bad) && lane == 0) atomicOr(flag, 1u);
+}
+
+// The ballots of frames 1 .. F-1 (k_frame_deltas: word w of a frame = positions 64 w .. 64 w + 63) into every frame's box and count.
+// A block takes 256 words of one frame; `words` as delta.h lays it out.
+__global__ __launch_bounds__(256) void k_delta_boxes(const unsigned long long *__restrict__ masks, size_t F, size_t n, size_t nw, unsigned width,
+                                                     unsigned height, size_t blocks_per_frame, unsigned long long *words) {
+    __shared__ unsigned s_acc[5];
+    const unsigned tid = threadIdx.x, lane = tid & 63u;
+    if (tid < 5) s_acc[tid] = 0;
+    __syncthreads();
+    const size_t f = 1 + blockIdx.x / blocks_per_frame, chunk = blockIdx.x % blocks_per_frame;
+    const size_t wi = chunk * 256 + tid;
+    const unsigned long long m = wi < nw ? masks[f * nw + wi] : 0ull;
+    // as maxima over zero: width - x0, height - y0, x1 + 1, y1 + 1
+    unsigned v[4] = {0, 0, 0, 0}, cnt = 0;
+    if (m) {
+        const size_t p0 = wi * 64;
+        const int first = __ffsll((long long)m) - 1, last = 63 - __clzll((long long)m);
+        unsigned y0, y1, x0, x1;
+        if (!(n >> 32)) {                                        // positions fit 32 bits: no 64-bit division
+            const unsigned q0 = (unsigned)p0 + first, q1 = (unsigned)p0 + last;
+            y0 = q0 / width; y1 = q1 / width; x0 = q0 - y0 * width; x1 = q1 - y1 * width;
+        } else {
+            y0 = (unsigned)((p0 + first) / width); y1 = (unsigned)((p0 + last) / width);
+            x0 = (unsigned)((p0 + first) % width); x1 = (unsigned)((p0 + last) % width);
+        }
+        if (y0 != y1) {                                          // the 64 positions wrap: columns bit by bit, stepping along the rows
+            unsigned x = x0, lo = x0, hi = x0;
+            for (int bit = first + 1; bit <= last; bit++) {
+                if (++x == width) x = 0;
+                if ((m >> bit) & 1ull) { lo = min(lo, x); hi = max(hi, x); }
+            }
+            x0 = lo; x1 = hi;
+        }
+        v[0] = width - x0; v[1] = height - y0; v[2] = x1 + 1u; v[3] = y1 + 1u;
+        cnt = (unsigned)__popcll(m);
+    }
+    if (__ballot(m != 0)) {                                      // (wavefront-uniform)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+            for (int j = 0; j < 4; j++) v[j] = max(v[j], (unsigned)__shfl_xor((int)v[j], o));
+            cnt += (unsigned)__shfl_xor((int)cnt, o);
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int j = 0; j < 4; j++) atomicMax(&s_acc[j], v[j]);
+            atomicAdd(&s_acc[4], cnt);
+        }
+    }
+    __syncthreads();
+    if (tid == 0 && s_acc[4] != 0) {
+        const size_t cell = f * (size_t)kDeltaSlots + chunk % (unsigned)kDeltaSlots;
+        unsigned *box = reinterpret_cast<unsigned *>(words) + cell * 4;
+#pragma unroll
+        for (int j = 0; j < 4; j++) atomicMax(box + j, s_acc[j]);
+        atomicAdd(words + F * (size_t)kDeltaSlots * 2 + cell, (unsigned long long)s_acc[4]);
+    }
+}
+
+template <typename ElemT, int V>
+static void launch_typed(const void *d_maps, size_t frames, size_t n, size_t nw, size_t rows, size_t T, bool lossy, const unsigned char *d_px,
+                         int channels, const double *d_pal, double tol2, void *d_delta, void *d_shown, unsigned long long *d_masks,
+                         unsigned *d_flag, hipStream_t s) {
+    const unsigned blocks = (unsigned)ceil_div(n, (size_t)256 * V);
+    if (lossy)
+        hipLaunchKernelGGL((k_frame_deltas<ElemT, true, V>), blocks, 256, 0, s, (const ElemT *)d_maps, frames, n, nw, (unsigned)rows, (ElemT)T, d_px,
+                           channels, d_pal, tol2, (ElemT *)d_delta, (ElemT *)d_shown, d_masks, d_flag);
+    else
+        hipLaunchKernelGGL((k_frame_deltas<ElemT, false, V>), blocks, 256, 0, s, (const ElemT *)d_maps, frames, n, nw, (unsigned)rows, (ElemT)T, d_px,
+                           channels, d_pal, tol2, (ElemT *)d_delta, (ElemT *)d_shown, d_masks, d_flag);
+}
+
+void launch_frame_deltas(const void *d_maps, int elem_bytes, size_t frames, size_t width, size_t height, size_t rows, size_t T, bool lossy,
+                         const unsigned char *d_px, int channels, const double *d_pal, double tol2, void *d_delta, void *d_shown,
+                         unsigned long long *d_masks, unsigned long long *d_words, hipStream_t s) {
+    const size_t n = width * height, N = frames * n, nw = ceil_div(n, 64);
+    if (N == 0) return;
+    if (elem_bytes != 1 && elem_bytes != 4) throw HipError("patolette_amd: the frame deltas take elements of 1 or 4 bytes");
+    const size_t box_blocks = ceil_div(nw, 256);
+    if (width >> 31 || height >> 31 || rows >> 32 || T >> (8 * elem_bytes) || ceil_div(n, 256) >> 31 || (box_blocks * (frames - 1)) >> 31)
+        throw HipError("patolette_amd: frame deltas: a size does not fit the kernels' 32-bit fields");
+    if (lossy && (!d_px || !d_pal || rows < 1)) throw HipError("patolette_amd: the lossy frame deltas need pixels and a palette");
+    HIP_CHECK(hipMemsetAsync(d_words, 0, frame_deltas_words(frames) * sizeof(unsigned long long), s));
+    unsigned *d_flag = reinterpret_cast<unsigned *>(d_words + frames * (size_t)kDeltaSlots * 3);
+    {
+        const int outs = (d_delta ? 1 : 0) + (d_shown ? 1 : 0);
+        KTIME("k_frame_deltas", s, ((double)elem_bytes * (1 + outs) + (lossy ? channels : 0) + 0.125) * N);
+        // four positions per lane where every frame starts on a vector boundary -- and where that still leaves every SIMD its eight
+        // wavefronts: a quarter of the wavefronts moves 4096 x 4096 in 0.036 ms instead of 0.085, but 640 x 360 (225 blocks, fewer
+        // than CUs) in 0.056 instead of 0.027
+        const uintptr_t all = (uintptr_t)d_maps | (uintptr_t)d_delta | (uintptr_t)d_shown;
+        const int mode = g_delta_quad.load(std::memory_order_relaxed);
+        const bool quad = n % 4 == 0 && all % (4 * (uintptr_t)elem_bytes) == 0 && (mode < 0 ? n >= (size_t)num_cus() * 32 * 256 : mode == 1);
+#define PAMD_DELTA_LAUNCH(E, V) launch_typed<E, V>(d_maps, frames, n, nw, rows, T, lossy, d_px, channels, d_pal, tol2, d_delta, d_shown, d_masks, d_flag, s)
+        if (elem_bytes == 1) { if (quad) PAMD_DELTA_LAUNCH(unsigned char, 4); else PAMD_DELTA_LAUNCH(unsigned char, 1); }
+        else { if (quad) PAMD_DELTA_LAUNCH(unsigned int, 4); else PAMD_DELTA_LAUNCH(unsigned int, 1); }
+#undef PAMD_DELTA_LAUNCH
+        HIP_CHECK(hipGetLastError());
+    }
+    if (frames > 1) {
+        KTIME("k_delta_boxes", s, 8.0 * nw * (frames - 1));
+        hipLaunchKernelGGL(k_delta_boxes, (unsigned)(box_blocks * (frames - 1)), 256, 0, s, d_masks, frames, n, nw, (unsigned)width, (unsigned)height,
+                           box_blocks, d_words);
+        HIP_CHECK(hipGetLastError());
+    }
+}
+
+}  // namespace pamd

@@ -22,6 +22,7 @@
 #include "kmeans.h"
 #include "map.h"
 #include "ordered.h"
+#include "delta.h"
 #include "saliency.h"
 #include "quant.h"
 #include "rgba.h"
@@ -975,6 +976,8 @@ struct Engine {
     DevBuf<unsigned long long> hsize, tileoff;
     DevBuf<unsigned int> hcount, tilecnt;
     DevBuf<unsigned char> lut, dmap, src8, pal8, quant8;
+    DevBuf<unsigned char> dl_maps, dl_shown;     // frame deltas from host maps: the maps (the deltas replace them in place), the shown maps
+    DevBuf<unsigned long long> dl_words, dl_masks;   // ... the kernels' boxes, counts and flag; the ballots between them (delta.h)
     // the RGBA entry (run_rgba): tile counts / offsets + the opaque count, each pixel's compact number, the opaque pixels' RGB and
     // weights, the full index map on its way to the host, the count's pinned landing place
     DevBuf<unsigned> rgba_cnt;
@@ -2755,6 +2758,114 @@ static void run_remap(Engine &E, size_t frames, size_t width, size_t height, con
     E.stats.ms_total = now_ms() - t_start;
 }
 
+// --------------------------------------------------------------------------------------------
+// frame deltas: an animation's index maps with "as on screen" made transparent (include/patolette_amd.h, patolette_amd_frame_deltas)
+// --------------------------------------------------------------------------------------------
+// host elements of `eb` bytes <-> the device's `me` (eb itself, or 4 for the 2- and 8-byte ones).  On the way in a value beyond 32
+// bits saturates (it stays "not a row"); on the way out the device's transparent index Td becomes the caller's T
+static void delta_elems_in(const void *src, int eb, size_t N, unsigned *dst) {
+    for (size_t i = 0; i < N; i++) {
+        if (eb == 2) dst[i] = ((const unsigned short *)src)[i];
+        else { const unsigned long long v = ((const unsigned long long *)src)[i]; dst[i] = v > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)v; }
+    }
+}
+static void delta_elems_out(const unsigned *src, int eb, size_t N, unsigned Td, size_t T, void *dst) {
+    for (size_t i = 0; i < N; i++) {
+        if (eb == 2) ((unsigned short *)dst)[i] = (unsigned short)src[i];
+        else ((unsigned long long *)dst)[i] = src[i] == Td ? (unsigned long long)T : (unsigned long long)src[i];
+    }
+}
+
+// maps: frames x width x height elements of `eb` bytes; rows: what every element must stay below (lossy: the used rows of pal, planar
+// (rows,3) f64 sRGB; otherwise pal is empty and neither it nor the pixels are read).  `maps`, `pixels`, `delta_out`, `shown_out` are
+// device pointers when `on_device`; rects and changed are host memory.  Every output may be null; delta_out may be maps.
+static void run_frame_deltas(Engine &E, bool on_device, size_t frames, size_t width, size_t height, const void *maps, int eb, size_t rows, size_t T,
+                             const unsigned char *pixels, int channels, std::vector<double> pal, double tolerance, void *delta_out,
+                             void *shown_out, int32_t *rects, uint64_t *changed) {
+    const bool lossy = tolerance > 0.0;
+    const size_t n = width * height, N = frames * n;
+    hipStream_t s = E.stream;
+    const double t_start = now_ms();
+    WsGuard wg(&E.stream, &E.stream2);
+    E.stats = patolette_amd__Stats{};
+    const int me = (on_device || eb == 1) ? eb : 4;
+    const unsigned Td = T > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)T;            // (8-byte host elements only: rows <= 2^31 stays below it)
+    // the workspace, before anything is enqueued
+    const size_t words = frame_deltas_words(frames);
+    E.dl_words.reserve(words);
+    E.dl_masks.reserve(frame_deltas_masks(frames, n));
+    if (!on_device) {
+        E.dl_maps.reserve(N * (size_t)me);
+        if (shown_out) E.dl_shown.reserve(N * (size_t)me);
+        if (lossy) E.src8.reserve(N * (size_t)channels);
+    }
+    if (lossy) { E.dpal.reserve(3 * rows); E.h_pal.reserve(3 * rows); }
+    const void *d_maps = maps;
+    void *d_delta = delta_out, *d_shown = shown_out;
+    const unsigned char *d_px = pixels;
+    std::vector<unsigned> stage;                                                   // 2- and 8-byte host elements, widened or narrowed
+    if (!on_device) {
+        const void *src = maps;
+        if (eb != me) { stage.resize(N); delta_elems_in(maps, eb, N, stage.data()); src = stage.data(); }
+        HIP_CHECK(hipMemcpyAsync(E.dl_maps.p, src, N * (size_t)me, hipMemcpyHostToDevice, s));
+        if (lossy) { HIP_CHECK(hipMemcpyAsync(E.src8.p, pixels, N * (size_t)channels, hipMemcpyHostToDevice, s)); d_px = E.src8.p; }
+        HIP_CHECK(hipStreamSynchronize(s));
+        d_maps = E.dl_maps.p;
+        d_delta = delta_out ? E.dl_maps.p : nullptr;                               // in place: the kernel allows it
+        d_shown = shown_out ? E.dl_shown.p : nullptr;
+    }
+    E.stats.ms_upload = now_ms() - t_start;
+    double t0 = now_ms();
+    if (lossy) {
+        palette_rows(pal, rows, hm::color::srgb_to_ictcp);                         // as run_remap's nearest map takes its palette
+        std::memcpy(E.h_pal.p, pal.data(), 3 * rows * sizeof(double));
+        HIP_CHECK(hipMemcpyAsync(E.dpal.p, E.h_pal.p, 3 * rows * sizeof(double), hipMemcpyHostToDevice, s));
+    }
+    launch_frame_deltas(d_maps, me, frames, width, height, rows, Td, lossy, d_px, channels, lossy ? E.dpal.p : nullptr, tolerance * tolerance,
+                        d_delta, d_shown, E.dl_masks.p, E.dl_words.p, s);
+    std::vector<unsigned long long> w(words);
+    HIP_CHECK(hipMemcpyAsync(w.data(), E.dl_words.p, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    E.sync();
+    E.stats.ms_map = now_ms() - t0;
+    t0 = now_ms();
+    if (w[words - 1] & 1)
+        throw HipError("patolette_amd_frame_deltas: a map element is not below palette_rows, or names a dropped trailing (-1, -1, -1) row");
+    const unsigned *box = reinterpret_cast<const unsigned *>(w.data());
+    const unsigned long long *cnt = w.data() + frames * (size_t)kDeltaSlots * 2;
+    for (size_t f = 0; f < frames; f++) {
+        unsigned m[4] = {0, 0, 0, 0};
+        unsigned long long count = 0;
+        for (int j = 0; j < kDeltaSlots; j++) {
+            const size_t cell = f * (size_t)kDeltaSlots + j;
+            for (int a = 0; a < 4; a++) m[a] = std::max(m[a], box[cell * 4 + a]);
+            count += cnt[cell];
+        }
+        if (f == 0) { m[0] = (unsigned)width; m[1] = (unsigned)height; m[2] = (unsigned)width; m[3] = (unsigned)height; count = n; }
+        if (changed) changed[f] = count;
+        if (rects) {
+            int32_t *r = rects + 4 * f;
+            if (count == 0) { r[0] = r[1] = r[2] = r[3] = 0; }
+            else {
+                r[0] = (int32_t)(width - m[0]); r[1] = (int32_t)(height - m[1]);
+                r[2] = (int32_t)(m[2] - (width - m[0])); r[3] = (int32_t)(m[3] - (height - m[1]));
+            }
+        }
+    }
+    if (!on_device) {
+        void *outs[2] = {delta_out, shown_out};
+        const void *from[2] = {d_delta, d_shown};
+        for (int o = 0; o < 2; o++) {
+            if (!outs[o]) continue;
+            if (eb == me) { HIP_CHECK(hipMemcpy(outs[o], from[o], N * (size_t)me, hipMemcpyDeviceToHost)); continue; }
+            stage.resize(N);
+            HIP_CHECK(hipMemcpy(stage.data(), from[o], N * sizeof(unsigned), hipMemcpyDeviceToHost));
+            delta_elems_out(stage.data(), eb, N, Td, T, outs[o]);
+        }
+    }
+    E.stats.ms_download = now_ms() - t0;
+    E.stats.ms_total = now_ms() - t_start;
+}
+
 // The RGBA entry (include/patolette_amd.h, patolette_amd_rgba): the opaque pixels (alpha >= thr) are compacted in row-scan order and
 // the path runs on them as an M x 1 image with one palette row less (row 0 is the transparent entry); the dither walks the full image's
 // curve over them (DitherMask).  Every pixel opaque: the path runs on the image itself with the full palette, exactly as run_u8 does.
@@ -3193,6 +3304,56 @@ static void remap_entry(bool on_device, size_t frames, size_t width, size_t heig
     });
 }
 
+// an animation's maps made deltas (include/patolette_amd.h): the arguments, then run_frame_deltas
+static void frame_deltas_entry(bool on_device, size_t frames, size_t width, size_t height, const void *palette_maps, int map_elem_bytes,
+                               size_t palette_rows, size_t transparent_index, const unsigned char *pixels, int channels, const double *palette,
+                               const unsigned char *palette_u8, double tolerance, void *delta_maps, void *shown_maps, int32_t *rects,
+                               uint64_t *changed, int *exit_code) {
+    *exit_code = frames == 0 ? -2 : validate(width, height, 1);
+    if (*exit_code != 0) return;
+    if (frames > (size_t)40000 * 40000 / (width * height))                            // the nearest remap's cap
+        return fail_args(exit_code, -4, "patolette_amd_frame_deltas: frames * width * height is too big");
+    const int eb = map_elem_bytes;
+    if (on_device ? (eb != 1 && eb != 4) : (eb != 1 && eb != 2 && eb != 4 && eb != 8))
+        return fail_args(exit_code, -1, "patolette_amd_frame_deltas: map_elem_bytes must be 1, 2, 4 or 8 (device maps: 1 or 4)");
+    if (!palette_maps) return fail_args(exit_code, -1, "patolette_amd_frame_deltas: no maps");
+    if (palette_rows < 1 || palette_rows > ((size_t)1 << 31))
+        return fail_args(exit_code, -1, "patolette_amd_frame_deltas: palette_rows must lie in [1, 2^31]");
+    if (transparent_index < palette_rows)
+        return fail_args(exit_code, -1, "patolette_amd_frame_deltas: transparent_index must be at least palette_rows (an index no entry uses)");
+    if (eb < 8 && (transparent_index >> (8 * eb)) != 0)
+        return fail_args(exit_code, -1, "patolette_amd_frame_deltas: transparent_index does not fit an element of map_elem_bytes: no index is "
+                                        "free for it -- make the palette with one row less, or pass wider elements");
+    if (!(std::isfinite(tolerance) && tolerance >= 0.0))
+        return fail_args(exit_code, -1, "patolette_amd_frame_deltas: tolerance must be finite and not negative");
+    size_t k = palette_rows;
+    std::vector<double> pal;
+    if (tolerance > 0.0) {                                                            // the lossy mode reads pixels and one palette
+        if (channels != 3 && channels != 4) return fail_args(exit_code, -1, "patolette_amd_frame_deltas: channels must be 3 or 4");
+        if (!pixels) return fail_args(exit_code, -1, "patolette_amd_frame_deltas: a tolerance above 0 needs the frames' pixels");
+        if ((palette != nullptr) == (palette_u8 != nullptr))
+            return fail_args(exit_code, -1, "patolette_amd_frame_deltas: a tolerance above 0 needs exactly one of palette and palette_u8");
+        if (palette_u8) {
+            pal.resize(3 * k);
+            for (size_t i = 0; i < k; i++) for (int c = 0; c < 3; c++) pal[(size_t)c * k + i] = (double)palette_u8[3 * i + c] / 255.0;
+        } else {                                                                      // as remap_entry takes the f64 palette
+            auto row_is = [&](size_t i, double v) { return palette[i] == v && palette[palette_rows + i] == v && palette[2 * palette_rows + i] == v; };
+            while (k > 0 && row_is(k - 1, -1.0)) k--;
+            if (k == 0) return fail_args(exit_code, -1, "patolette_amd_frame_deltas: every palette row is the unused-row fill (-1, -1, -1)");
+            pal.resize(3 * k);
+            for (size_t i = 0; i < k; i++) for (int c = 0; c < 3; c++) {
+                const double v = palette[palette_rows * (size_t)c + i];
+                if (!std::isfinite(v)) return fail_args(exit_code, -1, "patolette_amd_frame_deltas: the palette holds a value that is not finite");
+                pal[(size_t)c * k + i] = v;
+            }
+        }
+    }
+    *exit_code = guarded([&](Engine &E) {
+        run_frame_deltas(E, on_device, frames, width, height, palette_maps, eb, k, transparent_index, pixels, channels, std::move(pal), tolerance,
+                         delta_maps, shown_maps, rects, changed);
+    });
+}
+
 static void rgba_entry(bool on_device, size_t width, size_t height, const unsigned char *pixels, int alpha_threshold, const double *weights,
                        double tile_size, size_t palette_size, const patolette__QuantizationOptions *options, double *palette,
                        unsigned char *palette_rgba, void *palette_map, int map_elem_bytes, unsigned char *quantized, int *transparent_index,
@@ -3252,6 +3413,24 @@ void patolette_amd_remap_ordered_u8_device(size_t frames, size_t width, size_t h
 }
 
 int patolette_amd_debug_remap_two_pass(int on) { return g_remap_two_pass.exchange(on ? 1 : 0); }
+
+int patolette_amd_debug_delta_quad(int mode) { return delta_debug_quad(mode); }
+
+void patolette_amd_frame_deltas(size_t frames, size_t width, size_t height, const void *palette_maps, int map_elem_bytes, size_t palette_rows,
+                                size_t transparent_index, const unsigned char *pixels, int channels, const double *palette,
+                                const unsigned char *palette_u8, double tolerance, void *delta_maps, void *shown_maps, int32_t *rects,
+                                uint64_t *changed, int *exit_code) {
+    frame_deltas_entry(false, frames, width, height, palette_maps, map_elem_bytes, palette_rows, transparent_index, pixels, channels, palette,
+                       palette_u8, tolerance, delta_maps, shown_maps, rects, changed, exit_code);
+}
+
+void patolette_amd_frame_deltas_device(size_t frames, size_t width, size_t height, const void *d_palette_maps, int map_elem_bytes,
+                                       size_t palette_rows, size_t transparent_index, const unsigned char *d_pixels, int channels,
+                                       const double *palette, const unsigned char *palette_u8, double tolerance, void *d_delta_maps,
+                                       void *d_shown_maps, int32_t *rects, uint64_t *changed, int *exit_code) {
+    frame_deltas_entry(true, frames, width, height, d_palette_maps, map_elem_bytes, palette_rows, transparent_index, d_pixels, channels, palette,
+                       palette_u8, tolerance, d_delta_maps, d_shown_maps, rects, changed, exit_code);
+}
 
 void patolette_amd_frames_u8(size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels, const double *weights,
                              double tile_size, size_t palette_size, const patolette__QuantizationOptions *options, double *palette,
