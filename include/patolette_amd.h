@@ -276,6 +276,59 @@ void patolette_amd_frame_deltas_device(size_t frames, size_t width, size_t heigh
  * either way.  Process-wide; returns the previous mode. */
 int patolette_amd_debug_delta_quad(int mode);
 
+/* ---- measure: what a map costs, per palette entry and per frame ---------------------------------
+ * The error of any map this library (or anything else) made of 8-bit pixels on a palette, without pixels, maps or quantized images
+ * leaving the GPU: the figures a caller needs to choose a palette size, a dither mode, a spread or a frame-delta tolerance, and the
+ * per-entry pixel counts encoders sort palettes by.  n = width * height, N = frames * n.
+ *   pixels, channels, palette, palette_u8, palette_rows: exactly as patolette_amd_remap_u8 takes them -- interleaved 8-bit sRGB with 3
+ *       or 4 channels (a 4th byte is ignored); exactly one of palette (column-major f64, trailing (-1, -1, -1) rows dropped) and
+ *       palette_u8.
+ *   palette_maps, map_elem_bytes: as patolette_amd_frame_deltas takes them -- m[f][p], frame after frame, elements of 1, 2, 4 or 8
+ *       bytes (the *_device flavour: 1 or 4).
+ *   skip_index: -1 for none, or an index whose positions are left out (a transparent index).
+ *
+ * For frame f and position p with a = m[f][p]:
+ *   skip_index >= 0 and a == skip_index: the position is SKIPPED and enters nothing.  This test comes first, so skip_index may be
+ *       a palette row (index 0 of patolette_amd_rgba's maps) or lie beyond the rows (the T of patolette_amd_frame_deltas).  A
+ *       skip_index that no element of map_elem_bytes can hold skips nothing.
+ *   otherwise a must be a used row (below palette_rows, not a dropped trailing row).  An element that is not is never used as an
+ *       address; the kernel raises a flag and the call fails with -1 and a "patolette_amd_measure:" text (what the outputs then hold
+ *       is not defined).
+ *   Integer part.  pal8 = the byte palette of the remap contract: palette_u8 as given, or clip(palette * 255, 0, 255) truncated.
+ *       e = sum over c of (b[c] - pal8[a][c])^2, an integer in [0, 195075], b the pixel's bytes.
+ *       entry_count[a] += 1; entry_sse[a] += e; entry_max_se[a] = max(entry_max_se[a], e); the same three for frame f.
+ *       Rows that nothing names hold 0, a frame with every position skipped holds 0.  Sums of integers: exact, independent of any
+ *       order.  This is the squared error, in code values, of the `quantized` image every entry here returns for that map;
+ *       3 * 255^2 * count / sse is the argument of the PSNR's logarithm.
+ *   ICtCp part, evaluated only when frame_d_sum or frame_d_max is given (otherwise no pixel is converted).
+ *       D = exactly the D of the frame-deltas contract: the pixel's bytes / 255.0 and row a of the palette AS GIVEN (the f64 rows,
+ *       not pal8; a byte palette's v / 255.0), both through sRGB -> ICtCp as patolette_amd_remap_u8(dither == 0) converts them;
+ *       D = (d0*d0 + d1*d1) + d2*d2 in f64, no FMA.  frame_d_sum[f] = sum of D, frame_d_max[f] = max of D, both 0 for a frame with
+ *       nothing in it.  This is the quantity the palette was fitted to, and the square of the unit of the frame deltas' tolerance.
+ *       frame_d_max is exact given the D's.  frame_d_sum is a sum in an order that depends on (frames, width, height, the number
+ *       of used palette rows) only: it is a function of the arguments alone -- the same call gives the same bits every time, on any
+ *       stream, engine or workspace history, from this entry and the *_device one alike.  No floating-point atomic is involved.
+ *       The device converts with patolette_amd_pow (0.52 ulp), so the D's agree with libm arithmetic to about 1e-15 relative.
+ * Outputs, host memory in both flavours, each may be NULL: entry_count, entry_sse (uint64) and entry_max_se (uint32), palette_rows
+ *   values each; frame_count, frame_sse (uint64), frame_max_se (uint32), frame_d_sum, frame_d_max (f64), `frames` values each.
+ * The *_device flavour takes device pointers for pixels and palette_maps; both palettes stay host memory.
+ * Exit codes: 0; -2 frames == 0 or an empty image; -4 beyond the pixel cap of patolette_amd_remap_u8(dither == 0); -1 (with a
+ *   "patolette_amd_measure:" text in patolette_amd_last_error) for bad channels or map_elem_bytes, no pixels, no maps, both or
+ *   neither palette, palette_rows outside [1, 2^31], no usable palette row or one that is not finite, skip_index < -1, or the flag
+ *   above.  A failed call leaves the thread's engine usable.
+ * Statistics: the ms_* fields as for a remap (ms_map: the kernels and their results), every other field 0.
+ * Two kernels: k_measure, one launch for all frames (integer LDS atomics per entry, a plain store per tile), and k_measure_fold. */
+void patolette_amd_measure(size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels,
+                           const void *palette_maps, int map_elem_bytes, const double *palette, const unsigned char *palette_u8,
+                           size_t palette_rows, long long skip_index, uint64_t *entry_count, uint64_t *entry_sse,
+                           uint32_t *entry_max_se, uint64_t *frame_count, uint64_t *frame_sse, uint32_t *frame_max_se,
+                           double *frame_d_sum, double *frame_d_max, int *exit_code);
+void patolette_amd_measure_device(size_t frames, size_t width, size_t height, const unsigned char *d_pixels, int channels,
+                                  const void *d_palette_maps, int map_elem_bytes, const double *palette,
+                                  const unsigned char *palette_u8, size_t palette_rows, long long skip_index, uint64_t *entry_count,
+                                  uint64_t *entry_sse, uint32_t *entry_max_se, uint64_t *frame_count, uint64_t *frame_sse,
+                                  uint32_t *frame_max_se, double *frame_d_sum, double *frame_d_max, int *exit_code);
+
 /* ---- RGBA images: a transparent palette slot, an alpha-aware dither ---------------------------
  * pixels: width*height interleaved 8-bit RGBA.  Pixel i is TRANSPARENT iff alpha_i < alpha_threshold (an integer in [0, 256]);
  * every other pixel is OPAQUE.  M = number of opaque pixels, N = width*height.

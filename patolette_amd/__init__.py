@@ -15,7 +15,9 @@ and `quantize_frames` for an animation: frames of one size that share one palett
 and `remap`, which makes no palette: it maps 8-bit images or frames onto a palette the caller gives (a fixed one, an earlier call's);
 `dither="ordered"` (in `remap`, `quantize_u8`, `quantize_frames`) is a position-keyed Bayer dither for animations, `ordered_spread` its
 default strength; and `frame_deltas`, which turns an animation's maps into what an encoder writes per frame: unchanged positions made
-transparent, and the dirty rectangle.
+transparent, and the dirty rectangle; and `measure`, which tells what any of these maps costs -- per palette entry and per frame the
+pixel count, the squared error in code values and its maximum, per frame also the squared ICtCp distance the palette was fitted to
+and `frame_deltas`' tolerance is stated in -- with `psnr` to read it in decibels.
 """
 import ctypes as C
 
@@ -526,6 +528,78 @@ def frame_deltas(maps, palette, transparent_index=None, frames=None, tolerance=0
     return (True, deltas, rects, changed.astype(np.int64), shown, message)
 
 
+def measure(image, maps, palette, skip_index=None, ictcp=True):
+    """What a map costs, per palette entry and per frame (additive; include/patolette_amd.h: patolette_amd_measure) -- the error of
+    any map on 8-bit pixels, computed where the pixels and the maps are.
+
+      * image: (H, W, 3|4) or (F, H, W, 3|4) uint8 sRGB, a numpy array or a torch CUDA tensor.  A 4th channel is ignored.
+      * maps: (H, W) or (F, H, W) index maps in the element types `frame_deltas` accepts (numpy uint8 / uint16 / uint32, torch uint8 /
+        int32), in the same place as the image: a map of `remap` / `quantize_*`, the `shown` of a lossy `frame_deltas`, its deltas.
+      * palette: what `remap` takes, (K, 3) uint8 or float; trailing (-1, -1, -1) rows of a float one are dropped.
+      * skip_index: positions whose element equals it enter nothing -- the transparent index of `frame_deltas`' deltas, index 0 of a
+        `quantize_rgba` map.  It may name a palette row.  Every other element must be a used row (else a ValueError).
+      * ictcp=False leaves out the ICtCp part: no pixel is converted.
+
+    Returns (success, entries (K, 3) int64, per_frame (F, 3) int64, ictcp (F, 2) float64 or None, message).  The columns of entries
+    and per_frame are count, sse, max_se: how many positions, the sum and the largest of their squared errors
+    e = sum_c (pixel[c] - pal8[index][c])^2 in code values, pal8 being the bytes `quantized` is made of -- all exact integers.  The
+    columns of ictcp are d_sum, d_max: sum and largest of the squared ICtCp distance D between the pixel and its entry, the D of
+    `frame_deltas`' tolerance (compare d_max with tolerance ** 2); d_sum has the same bits on every call with the same arguments.
+    The results are small and always numpy arrays.  `psnr` turns entries or per_frame into decibels."""
+    px, shape, dev = _u8_pixels(image, (3, 4), (3, 4), "image must be an (H, W, 3|4) or (F, H, W, 3|4) uint8 %s")
+    if not hasattr(maps, "shape") or len(maps.shape) not in (2, 3):
+        raise ValueError("maps must be an (H, W) or (F, H, W) uint8 / uint16 / uint32 array or a uint8 / int32 CUDA tensor")
+    m, mshape, mdev, elem, elem_max = _delta_maps(maps if len(maps.shape) == 3 else maps[None])
+    given = shape
+    if len(shape) == 3:
+        shape = (1,) + shape
+    if mshape != shape[:3] or len(maps.shape) + 1 != len(given):
+        raise ValueError("maps of shape %s do not match an image of shape %s" % (tuple(maps.shape), given))
+    if mdev != dev:
+        raise ValueError("image and maps must live in the same place (both numpy arrays, or tensors of one device)")
+    if hasattr(palette, "detach"):
+        palette = palette.detach().cpu().numpy()
+    pal8, palf = _remap_palette(palette)
+    rows = (pal8 if pal8 is not None else palf).shape[0]
+    skip = -1
+    if skip_index is not None:
+        if isinstance(skip_index, (bool, np.bool_)) or not isinstance(skip_index, (int, np.integer)) or int(skip_index) < 0:
+            raise ValueError("skip_index must be None or an index >= 0")
+        skip = int(skip_index)
+        if skip > elem_max:
+            skip = -1                                              # (no element can hold it: nothing is skipped)
+    count, height, width, channels = shape
+    ent = [np.zeros(rows, dtype=np.uint64), np.zeros(rows, dtype=np.uint64), np.zeros(rows, dtype=np.uint32)]
+    per = [np.zeros(count, dtype=np.uint64), np.zeros(count, dtype=np.uint64), np.zeros(count, dtype=np.uint32)]
+    dist = np.zeros((2, count), dtype=np.float64) if ictcp else None
+    u64, u32 = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+    code = C.c_int(0)
+    _call("patolette_amd_measure", dev, count, width, height, _vp(px), channels, _vp(m), elem, _vp(palf), _vp(pal8), rows, skip,
+          ent[0].ctypes.data_as(u64), ent[1].ctypes.data_as(u64), ent[2].ctypes.data_as(u32),
+          per[0].ctypes.data_as(u64), per[1].ctypes.data_as(u64), per[2].ctypes.data_as(u32),
+          dist[0].ctypes.data_as(_native.dp) if ictcp else None, dist[1].ctypes.data_as(_native.dp) if ictcp else None, C.byref(code))
+    if code.value == -1 and _native.last_error().startswith("patolette_amd_measure:"):
+        raise ValueError(_native.last_error())
+    message = _message(code.value)
+    if code.value != 0:
+        return (False, None, None, None, message)
+    return (True, np.stack([a.astype(np.int64) for a in ent], axis=1), np.stack([a.astype(np.int64) for a in per], axis=1),
+            np.ascontiguousarray(dist.T) if ictcp else None, message)
+
+
+def psnr(stats):
+    """Peak signal-to-noise ratio in dB of `measure`'s entries or per_frame ((.., 3) rows of count, sse, max_se; or one such row):
+    10 * log10(3 * 255^2 * count / sse) -- inf where sse is 0, nan where count is 0.  Pure numpy; no GPU."""
+    s = np.asarray(stats)
+    if s.ndim < 1 or s.shape[-1] != 3:
+        raise ValueError("psnr takes rows of (count, sse, max_se) as `measure` returns them")
+    count, sse = s[..., 0].astype(np.float64), s[..., 1].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out = 10.0 * np.log10(3.0 * 255.0 * 255.0 * count / sse)
+    out = np.where(count == 0, np.nan, np.where(sse == 0, np.inf, out))
+    return out if out.ndim else float(out)
+
+
 def quantize_rgba(image, palette_size, alpha_threshold=128, dither=True, palette_only=False, color_space=ColorSpace_ICtCp,
                   tile_size=512, kmeans_niter=32, kmeans_max_samples=512 ** 2, weights=None, want_quantized=True):
     """Quantise an (H, W, 4) uint8 RGBA image (additive; include/patolette_amd.h: patolette_amd_rgba).  `image` is a numpy array,
@@ -672,6 +746,8 @@ __all__ = [
     "remap",
     "ordered_spread",
     "frame_deltas",
+    "measure",
+    "psnr",
     "saliency_weights",
     "ColorSpace_sRGB",
     "ColorSpace_CIELuv",

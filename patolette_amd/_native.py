@@ -123,6 +123,13 @@ SYMBOLS = {
     "patolette_amd_frame_deltas_device": (None, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p,
                                                  C.c_int, dp, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32),
                                                  C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+    "patolette_amd_measure": (None, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, dp, C.c_void_p, C.c_size_t,
+                                     C.c_longlong, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), dp, dp, C.POINTER(C.c_int)]),
+    "patolette_amd_measure_device": (None, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, dp, C.c_void_p,
+                                            C.c_size_t, C.c_longlong, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), dp, dp,
+                                            C.POINTER(C.c_int)]),
     "patolette_amd_rgba": (None, [C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, dp, C.c_double, C.c_size_t,
                                   C.POINTER(QuantizationOptions), dp, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                   C.POINTER(C.c_int), C.POINTER(C.c_int)]),

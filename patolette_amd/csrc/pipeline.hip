@@ -23,6 +23,7 @@
 #include "map.h"
 #include "ordered.h"
 #include "delta.h"
+#include "measure.h"
 #include "saliency.h"
 #include "quant.h"
 #include "rgba.h"
@@ -978,6 +979,9 @@ struct Engine {
     DevBuf<unsigned char> lut, dmap, src8, pal8, quant8;
     DevBuf<unsigned char> dl_maps, dl_shown;     // frame deltas from host maps: the maps (the deltas replace them in place), the shown maps
     DevBuf<unsigned long long> dl_words, dl_masks;   // ... the kernels' boxes, counts and flag; the ballots between them (delta.h)
+    DevBuf<unsigned long long> ms_words;         // measure: the entries' slots, the flag and the folded results (measure.h)
+    DevBuf<MeasureTile> ms_tiles;                // ... the tiles' records between its two kernels
+    DevBuf<unsigned> ms_p8;                      // ... the palette's bytes, a word per row
     // the RGBA entry (run_rgba): tile counts / offsets + the opaque count, each pixel's compact number, the opaque pixels' RGB and
     // weights, the full index map on its way to the host, the count's pinned landing place
     DevBuf<unsigned> rgba_cnt;
@@ -2866,6 +2870,99 @@ static void run_frame_deltas(Engine &E, bool on_device, size_t frames, size_t wi
     E.stats.ms_total = now_ms() - t_start;
 }
 
+// --------------------------------------------------------------------------------------------
+// measure: a map's error per palette entry and frame (include/patolette_amd.h, patolette_amd_measure)
+// --------------------------------------------------------------------------------------------
+struct MeasureOut {                                // host memory, each may be null
+    uint64_t *entry_count, *entry_sse; uint32_t *entry_max_se;          // K8 each
+    uint64_t *frame_count, *frame_sse; uint32_t *frame_max_se;          // frames each
+    double *frame_d_sum, *frame_d_max;                                  // frames each
+};
+// host elements of 2 or 8 bytes into the device's 4.  An 8-byte value beyond 32 bits stays "not a row" unless it is the skip index
+// itself, which arrives as Sd; `beyond` is a value above every row (rows <= 2^31) that is not Sd
+static void measure_elems_in(const void *src, int eb, size_t N, bool skip_on, unsigned long long skip, unsigned Sd, unsigned *dst) {
+    const unsigned beyond = Sd == 0xFFFFFFFFu ? 0xFFFFFFFEu : 0xFFFFFFFFu;
+    for (size_t i = 0; i < N; i++) {
+        if (eb == 2) { dst[i] = ((const unsigned short *)src)[i]; continue; }
+        const unsigned long long v = ((const unsigned long long *)src)[i];
+        dst[i] = (skip_on && v == skip) ? Sd : (v > 0xFFFFFFFFull || (skip_on && v == Sd) ? beyond : (unsigned)v);
+    }
+}
+
+// maps: frames x width x height elements of `eb` bytes; pal: the k used rows, planar (k,3) f64 sRGB; p8: the bytes of the K8 rows as
+// given.  skip < 0: none.  `maps` and `pixels` are device pointers when `on_device`; the outputs are host memory.
+static void run_measure(Engine &E, bool on_device, size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels,
+                        const void *maps, int eb, std::vector<double> pal, size_t k, const std::vector<unsigned char> &p8, size_t K8,
+                        long long skip, const MeasureOut &out) {
+    const size_t n = width * height, N = frames * n;
+    hipStream_t s = E.stream;
+    const double t_start = now_ms();
+    WsGuard wg(&E.stream, &E.stream2);
+    E.stats = patolette_amd__Stats{};
+    const int me = (on_device || eb == 1) ? eb : 4;
+    const bool with_d = out.frame_d_sum || out.frame_d_max;
+    // a skip index that does not fit the device's element names no position
+    bool skip_on = skip >= 0;
+    unsigned Sd = 0;
+    if (skip_on) {
+        const unsigned long long v = (unsigned long long)skip;
+        if (me == 1 || on_device || eb != 8) { skip_on = (v >> (8 * (eb < me ? eb : me))) == 0; Sd = (unsigned)v; }
+        else Sd = v > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)v;
+    }
+    // the workspace, before anything is enqueued
+    const size_t words = measure_words(frames, k), from = measure_flag_word(k);
+    E.ms_words.reserve(words);
+    E.ms_tiles.reserve(measure_tile_count(frames, n));
+    E.ms_p8.reserve(k);
+    if (!on_device) { E.dl_maps.reserve(N * (size_t)me); E.src8.reserve(N * (size_t)channels); }
+    if (with_d) { E.dpal.reserve(3 * k); E.h_pal.reserve(3 * k); }
+    const void *d_maps = maps;
+    const unsigned char *d_px = pixels;
+    std::vector<unsigned> stage;                                                   // 2- and 8-byte host elements, widened or narrowed
+    if (!on_device) {
+        const void *src = maps;
+        if (eb != me) { stage.resize(N); measure_elems_in(maps, eb, N, skip_on, (unsigned long long)skip, Sd, stage.data()); src = stage.data(); }
+        HIP_CHECK(hipMemcpyAsync(E.dl_maps.p, src, N * (size_t)me, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(E.src8.p, pixels, N * (size_t)channels, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        d_maps = E.dl_maps.p;
+        d_px = E.src8.p;
+    }
+    E.stats.ms_upload = now_ms() - t_start;
+    double t0 = now_ms();
+    std::vector<unsigned> rows8(k);
+    for (size_t i = 0; i < k; i++) rows8[i] = (unsigned)p8[3 * i] | (unsigned)p8[3 * i + 1] << 8 | (unsigned)p8[3 * i + 2] << 16;
+    HIP_CHECK(hipMemcpyAsync(E.ms_p8.p, rows8.data(), k * sizeof(unsigned), hipMemcpyHostToDevice, s));
+    if (with_d) {
+        palette_rows(pal, k, hm::color::srgb_to_ictcp);                            // as run_remap's nearest map takes its palette
+        std::memcpy(E.h_pal.p, pal.data(), 3 * k * sizeof(double));
+        HIP_CHECK(hipMemcpyAsync(E.dpal.p, E.h_pal.p, 3 * k * sizeof(double), hipMemcpyHostToDevice, s));
+    }
+    launch_measure(d_maps, me, frames, n, d_px, channels, k, skip_on, Sd, E.ms_p8.p, with_d ? E.dpal.p : nullptr, E.ms_words.p, E.ms_tiles.p, s);
+    std::vector<unsigned long long> w(words - from);
+    HIP_CHECK(hipMemcpyAsync(w.data(), E.ms_words.p + from, w.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    E.sync();
+    E.stats.ms_map = now_ms() - t0;
+    t0 = now_ms();
+    if (w[0] & 1)
+        throw HipError("patolette_amd_measure: a map element is neither skip_index nor below palette_rows, or names a dropped trailing (-1, -1, -1) row");
+    const unsigned long long *er = w.data() + 1, *fr = er + 3 * k;
+    for (size_t i = 0; i < K8; i++) {                                              // (dropped rows: nothing names them)
+        if (out.entry_count) out.entry_count[i] = i < k ? er[3 * i] : 0;
+        if (out.entry_sse) out.entry_sse[i] = i < k ? er[3 * i + 1] : 0;
+        if (out.entry_max_se) out.entry_max_se[i] = i < k ? (uint32_t)er[3 * i + 2] : 0;
+    }
+    for (size_t f = 0; f < frames; f++) {
+        if (out.frame_count) out.frame_count[f] = fr[5 * f];
+        if (out.frame_sse) out.frame_sse[f] = fr[5 * f + 1];
+        if (out.frame_max_se) out.frame_max_se[f] = (uint32_t)fr[5 * f + 2];
+        if (out.frame_d_sum) std::memcpy(out.frame_d_sum + f, fr + 5 * f + 3, sizeof(double));
+        if (out.frame_d_max) std::memcpy(out.frame_d_max + f, fr + 5 * f + 4, sizeof(double));
+    }
+    E.stats.ms_download = now_ms() - t0;
+    E.stats.ms_total = now_ms() - t_start;
+}
+
 // The RGBA entry (include/patolette_amd.h, patolette_amd_rgba): the opaque pixels (alpha >= thr) are compacted in row-scan order and
 // the path runs on them as an M x 1 image with one palette row less (row 0 is the transparent entry); the dither walks the full image's
 // curve over them (DitherMask).  Every pixel opaque: the path runs on the image itself with the full palette, exactly as run_u8 does.
@@ -3354,6 +3451,48 @@ static void frame_deltas_entry(bool on_device, size_t frames, size_t width, size
     });
 }
 
+// a map's error per entry and frame (include/patolette_amd.h): the arguments, then run_measure
+static void measure_entry(bool on_device, size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels,
+                          const void *palette_maps, int map_elem_bytes, const double *palette, const unsigned char *palette_u8, size_t palette_rows,
+                          long long skip_index, const MeasureOut &out, int *exit_code) {
+    *exit_code = frames == 0 ? -2 : validate(width, height, 1);
+    if (*exit_code != 0) return;
+    if (frames > (size_t)40000 * 40000 / (width * height))                            // the nearest remap's cap
+        return fail_args(exit_code, -4, "patolette_amd_measure: frames * width * height is too big");
+    const int eb = map_elem_bytes;
+    if (channels != 3 && channels != 4) return fail_args(exit_code, -1, "patolette_amd_measure: channels must be 3 or 4");
+    if (on_device ? (eb != 1 && eb != 4) : (eb != 1 && eb != 2 && eb != 4 && eb != 8))
+        return fail_args(exit_code, -1, "patolette_amd_measure: map_elem_bytes must be 1, 2, 4 or 8 (device maps: 1 or 4)");
+    if (!pixels) return fail_args(exit_code, -1, "patolette_amd_measure: no pixels");
+    if (!palette_maps) return fail_args(exit_code, -1, "patolette_amd_measure: no maps");
+    if ((palette != nullptr) == (palette_u8 != nullptr)) return fail_args(exit_code, -1, "patolette_amd_measure: pass exactly one of palette and palette_u8");
+    if (palette_rows < 1 || palette_rows > ((size_t)1 << 31)) return fail_args(exit_code, -1, "patolette_amd_measure: palette_rows must lie in [1, 2^31]");
+    if (skip_index < -1) return fail_args(exit_code, -1, "patolette_amd_measure: skip_index must be -1 (none) or an index");
+    // the used rows, planar (k,3) f64 sRGB, and the bytes the integer part compares with: as remap_entry takes them
+    size_t k = palette_rows;
+    std::vector<double> pal;
+    std::vector<unsigned char> p8(3 * palette_rows);
+    if (palette_u8) {
+        pal.resize(3 * k);
+        for (size_t i = 0; i < k; i++) for (int c = 0; c < 3; c++) pal[(size_t)c * k + i] = (double)palette_u8[3 * i + c] / 255.0;
+        std::memcpy(p8.data(), palette_u8, 3 * palette_rows);
+    } else {
+        auto row_is = [&](size_t i, double v) { return palette[i] == v && palette[palette_rows + i] == v && palette[2 * palette_rows + i] == v; };
+        while (k > 0 && row_is(k - 1, -1.0)) k--;
+        if (k == 0) return fail_args(exit_code, -1, "patolette_amd_measure: every palette row is the unused-row fill (-1, -1, -1)");
+        pal.resize(3 * k);
+        for (size_t i = 0; i < k; i++) for (int c = 0; c < 3; c++) {
+            const double v = palette[palette_rows * (size_t)c + i];
+            if (!std::isfinite(v)) return fail_args(exit_code, -1, "patolette_amd_measure: the palette holds a value that is not finite");
+            pal[(size_t)c * k + i] = v;
+        }
+        palette_to_u8(palette, palette_rows, p8.data());
+    }
+    *exit_code = guarded([&](Engine &E) {
+        run_measure(E, on_device, frames, width, height, pixels, channels, palette_maps, eb, std::move(pal), k, p8, palette_rows, skip_index, out);
+    });
+}
+
 static void rgba_entry(bool on_device, size_t width, size_t height, const unsigned char *pixels, int alpha_threshold, const double *weights,
                        double tile_size, size_t palette_size, const patolette__QuantizationOptions *options, double *palette,
                        unsigned char *palette_rgba, void *palette_map, int map_elem_bytes, unsigned char *quantized, int *transparent_index,
@@ -3430,6 +3569,23 @@ void patolette_amd_frame_deltas_device(size_t frames, size_t width, size_t heigh
                                        void *d_shown_maps, int32_t *rects, uint64_t *changed, int *exit_code) {
     frame_deltas_entry(true, frames, width, height, d_palette_maps, map_elem_bytes, palette_rows, transparent_index, d_pixels, channels, palette,
                        palette_u8, tolerance, d_delta_maps, d_shown_maps, rects, changed, exit_code);
+}
+
+void patolette_amd_measure(size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels, const void *palette_maps,
+                           int map_elem_bytes, const double *palette, const unsigned char *palette_u8, size_t palette_rows, long long skip_index,
+                           uint64_t *entry_count, uint64_t *entry_sse, uint32_t *entry_max_se, uint64_t *frame_count, uint64_t *frame_sse,
+                           uint32_t *frame_max_se, double *frame_d_sum, double *frame_d_max, int *exit_code) {
+    measure_entry(false, frames, width, height, pixels, channels, palette_maps, map_elem_bytes, palette, palette_u8, palette_rows, skip_index,
+                  MeasureOut{entry_count, entry_sse, entry_max_se, frame_count, frame_sse, frame_max_se, frame_d_sum, frame_d_max}, exit_code);
+}
+
+void patolette_amd_measure_device(size_t frames, size_t width, size_t height, const unsigned char *d_pixels, int channels,
+                                  const void *d_palette_maps, int map_elem_bytes, const double *palette, const unsigned char *palette_u8,
+                                  size_t palette_rows, long long skip_index, uint64_t *entry_count, uint64_t *entry_sse, uint32_t *entry_max_se,
+                                  uint64_t *frame_count, uint64_t *frame_sse, uint32_t *frame_max_se, double *frame_d_sum, double *frame_d_max,
+                                  int *exit_code) {
+    measure_entry(true, frames, width, height, d_pixels, channels, d_palette_maps, map_elem_bytes, palette, palette_u8, palette_rows, skip_index,
+                  MeasureOut{entry_count, entry_sse, entry_max_se, frame_count, frame_sse, frame_max_se, frame_d_sum, frame_d_max}, exit_code);
 }
 
 void patolette_amd_frames_u8(size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels, const double *weights,
