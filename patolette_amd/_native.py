@@ -54,6 +54,11 @@ class Comm(C.Structure):
                 ("host_buffers", C.c_int)]
 
 
+def _pair(name, res, args):
+    """A host entry and its `_device` twin: one signature (the twin's buffers are device addresses)."""
+    return {name: (res, args), name + "_device": (res, args)}
+
+
 # every symbol include/patolette.h and include/patolette_amd.h declare
 SYMBOLS = {
     # --- include/patolette.h (the reference's ABI)
@@ -95,45 +100,26 @@ SYMBOLS = {
                                            zp, C.POINTER(C.c_int)]),
     "patolette_amd_saliency_weights": (C.c_int, [C.c_size_t, C.c_size_t, dp, C.c_double, dp]),
     "patolette_amd_mbd": (C.c_int, [C.c_size_t, C.c_size_t, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_float)]),
-    "patolette_amd_u8": (None, [C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, dp, C.c_double, C.c_size_t,
-                                C.POINTER(QuantizationOptions), dp, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                C.POINTER(C.c_int)]),
-    "patolette_amd_u8_device": (None, [C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_size_t,
-                                       C.POINTER(QuantizationOptions), dp, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                       C.POINTER(C.c_int)]),
-    "patolette_amd_frames_u8": (None, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, dp, C.c_double, C.c_size_t,
-                                       C.POINTER(QuantizationOptions), dp, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                       C.POINTER(C.c_int)]),
-    "patolette_amd_frames_u8_device": (None, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_size_t,
+    # (weights: host f64 or a device address, so void*)
+    **_pair("patolette_amd_u8", None, [C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_size_t,
+                                       C.POINTER(QuantizationOptions), dp, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
+    **_pair("patolette_amd_frames_u8", None, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_size_t,
                                               C.POINTER(QuantizationOptions), dp, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                               C.POINTER(C.c_int)]),
-    "patolette_amd_remap_u8": (None, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, dp, C.c_void_p, C.c_size_t, C.c_int,
-                                      C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
-    "patolette_amd_remap_u8_device": (None, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, dp, C.c_void_p, C.c_size_t, C.c_int,
+    **_pair("patolette_amd_remap_u8", None, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, dp, C.c_void_p, C.c_size_t, C.c_int,
                                              C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
-    "patolette_amd_remap_ordered_u8": (None, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, dp, C.c_void_p, C.c_size_t, C.c_double,
-                                              C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
-    "patolette_amd_remap_ordered_u8_device": (None, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, dp, C.c_void_p, C.c_size_t,
+    **_pair("patolette_amd_remap_ordered_u8", None, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, dp, C.c_void_p, C.c_size_t,
                                                      C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
     "patolette_amd_debug_remap_two_pass": (C.c_int, [C.c_int]),
-    "patolette_amd_frame_deltas": (None, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int,
-                                          dp, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint64),
-                                          C.POINTER(C.c_int)]),
-    "patolette_amd_debug_delta_quad": (C.c_int, [C.c_int]),
-    "patolette_amd_frame_deltas_device": (None, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p,
+    **_pair("patolette_amd_frame_deltas", None, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p,
                                                  C.c_int, dp, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32),
                                                  C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
-    "patolette_amd_measure": (None, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, dp, C.c_void_p, C.c_size_t,
-                                     C.c_longlong, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
-                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), dp, dp, C.POINTER(C.c_int)]),
-    "patolette_amd_measure_device": (None, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, dp, C.c_void_p,
+    "patolette_amd_debug_delta_quad": (C.c_int, [C.c_int]),
+    **_pair("patolette_amd_measure", None, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, dp, C.c_void_p,
                                             C.c_size_t, C.c_longlong, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
                                             C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), dp, dp,
                                             C.POINTER(C.c_int)]),
-    "patolette_amd_rgba": (None, [C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, dp, C.c_double, C.c_size_t,
-                                  C.POINTER(QuantizationOptions), dp, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                  C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "patolette_amd_rgba_device": (None, [C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_size_t,
+    **_pair("patolette_amd_rgba", None, [C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_size_t,
                                          C.POINTER(QuantizationOptions), dp, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                          C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "patolette_amd_batch": (None, [C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(dp), C.POINTER(dp), C.c_double, C.c_size_t,

@@ -15,6 +15,7 @@
 #include <mutex>
 #include <thread>
 #include <future>
+#include <type_traits>
 
 #include "color_device.h"
 #include "common.h"
@@ -29,6 +30,7 @@
 #include "rgba.h"
 #include "compact.h"
 #include "split_frontier.h"
+#include "given.h"
 
 namespace pamd {
 
@@ -2164,6 +2166,14 @@ static void palette_rows(std::vector<double> &pal, size_t len, void (*f)(double[
     }
 }
 
+// pal's `rows` rows into E.dpal, which the caller has reserved as it has E.h_pal.  From a pinned copy: no wait for the transfer (a
+// pageable source is staged and waited for, ~15 us with nothing queued behind it); the copy is this engine's and is next written by
+// its next call, after this one's final synchronisation
+static void upload_palette(Engine &E, const std::vector<double> &pal, size_t rows) {
+    std::memcpy(E.h_pal.p, pal.data(), 3 * rows * sizeof(double));
+    HIP_CHECK(hipMemcpyAsync(E.dpal.p, E.h_pal.p, 3 * rows * sizeof(double), hipMemcpyHostToDevice, E.stream));
+}
+
 // between_copy_and_wait: work to enqueue behind the statistics' download while the host is still waiting for it
 static Bounds read_bounds(Engine &E, bool weighted, const std::function<void()> &between_copy_and_wait = nullptr) {
     E.h_cstats.reserve(1);
@@ -2367,11 +2377,8 @@ static void run_device(Engine &E, size_t width, size_t height, Pixels px, const 
             }
             E.map_palette = pal;
             if (d_map) {
-                // from a pinned copy: no wait for the transfer (a pageable source is staged and waited for, ~15 us with nothing queued
-                // behind it); the copy is this engine's and is next written by its next call, after this one's final synchronisation
                 E.h_pal.reserve(3 * len);
-                std::memcpy(E.h_pal.p, pal.data(), 3 * len * sizeof(double));
-                HIP_CHECK(hipMemcpyAsync(E.dpal.p, E.h_pal.p, 3 * len * sizeof(double), hipMemcpyHostToDevice, s));
+                upload_palette(E, pal, len);
                 launch_nn_map(pixels, N, N, E.dpal.p, (int)len, d_map, map_elem, blo, bhi, E.nn, s);
             }
             palette_rows(pal, len, hm::color::ictcp_to_rec2020);
@@ -2442,8 +2449,7 @@ static void download_map_widened(Engine &E, const void *d_map, int me, size_t N,
             const size_t lo = c * chunk, cnt = std::min(chunk, N - lo);
             const size_t a = cnt * (size_t)tid / (size_t)T, b = cnt * (size_t)(tid + 1) / (size_t)T;
             const unsigned char *src = E.h_mapstage.p + (c & 1) * chunk * (size_t)me;
-            if (me == 1) for (size_t i = a; i < b; i++) out[lo + i] = (size_t)src[i];
-            else { const unsigned int *s4 = (const unsigned int *)src; for (size_t i = a; i < b; i++) out[lo + i] = (size_t)s4[i]; }
+            given_elems_out(src, me, out + lo, 8, a, b);
             done[c].fetch_add(1, std::memory_order_release);
         }
     };
@@ -2469,8 +2475,7 @@ static void download_map_widened(Engine &E, const void *d_map, int me, size_t N,
                 const size_t lo = c * chunk, cnt = std::min(chunk, N - lo);
                 const size_t b = cnt / (size_t)T;
                 const unsigned char *src = E.h_mapstage.p + (c & 1) * chunk * (size_t)me;
-                if (me == 1) for (size_t i = 0; i < b; i++) out[lo + i] = (size_t)src[i];
-                else { const unsigned int *s4 = (const unsigned int *)src; for (size_t i = 0; i < b; i++) out[lo + i] = (size_t)s4[i]; }
+                given_elems_out(src, me, out + lo, 8, 0, b);
                 done[c].fetch_add(1, std::memory_order_release);
             }
         }
@@ -2569,31 +2574,15 @@ static void run_host(Engine &E, size_t width, size_t height, const double *data,
     E.stats.ms_total += up + E.stats.ms_download;
 }
 
-// palette_u8 = clip(palette * 255, 0, 255) truncated (README.md:178-181); unused rows (-1) become 0
-static void palette_to_u8(const double *palette, size_t K, unsigned char *out) {
-    for (size_t i = 0; i < K; i++)
-        for (int c = 0; c < 3; c++) {
-            double v = palette[K * (size_t)c + i] * 255.0;
-            v = v < 0.0 ? 0.0 : (v > 255.0 ? 255.0 : v);
-            out[3 * i + c] = (unsigned char)v;
-        }
-}
-
 // the device's index map (elements of me: 1 or 4 bytes) into a host buffer with elements of map_elem_out (1, 2, 4 or 8)
 static void download_map(const void *d_map, int me, size_t N, void *map_out, int map_elem_out) {
     if (map_elem_out == me) { HIP_CHECK(hipMemcpy(map_out, d_map, N * (size_t)me, hipMemcpyDeviceToHost)); return; }
     std::vector<unsigned char> tmp(N * (size_t)me);
     HIP_CHECK(hipMemcpy(tmp.data(), d_map, tmp.size(), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < N; i++) {
-        const size_t v = me == 1 ? (size_t)tmp[i] : (size_t)reinterpret_cast<unsigned int *>(tmp.data())[i];
-        switch (map_elem_out) {
-            case 1: ((unsigned char *)map_out)[i] = (unsigned char)v; break;
-            case 2: ((unsigned short *)map_out)[i] = (unsigned short)v; break;
-            case 4: ((unsigned int *)map_out)[i] = (unsigned int)v; break;
-            default: ((size_t *)map_out)[i] = v; break;
-        }
-    }
+    given_elems_out(tmp.data(), me, map_out, map_elem_out, 0, N);
 }
+
+static const char *const kBadDeviceMapElem = "patolette_amd: device map_elem_bytes must be 1 for K <= 256, else 4";
 
 // Where the 8-bit entries' index map (elements of map_elem_for(K8) bytes) lands: in the caller's buffer when that is device memory, else
 // in E.dmap; null when no map-derived output is wanted (the map kernels are then skipped).  Reserves that place and what u8_outputs
@@ -2603,7 +2592,7 @@ static void *u8_map_place(Engine &E, size_t N, size_t K8, bool want, void *map_o
     if (!want) return nullptr;
     if (quant_out) { E.pal8.reserve(3 * K8); if (!quant_on_device) E.quant8.reserve(3 * N); }
     if (map_out && map_on_device) {
-        if (map_elem_out != map_elem_for(K8)) throw HipError("patolette_amd: device map_elem_bytes must be 1 for K <= 256, else 4");
+        if (map_elem_out != map_elem_for(K8)) throw HipError(kBadDeviceMapElem);
         return map_out;
     }
     E.dmap.reserve(N * (size_t)map_elem_for(K8));
@@ -2725,8 +2714,7 @@ static void run_remap(Engine &E, size_t frames, size_t width, size_t height, con
     palette_rows(pal, k, dither ? hm::color::srgb_to_rec2020 : hm::color::srgb_to_ictcp);
     E.map_palette = pal;
     if (want) {
-        std::memcpy(E.h_pal.p, pal.data(), 3 * k * sizeof(double));
-        HIP_CHECK(hipMemcpyAsync(E.dpal.p, E.h_pal.p, 3 * k * sizeof(double), hipMemcpyHostToDevice, s));
+        upload_palette(E, pal, k);
         if (ordered) {
             launch_ordered_map(d_px, channels, frames, width, height, spread, E.dpal.p, (int)k, d_map, me, s);
         } else if (!dither && fused) {
@@ -2765,19 +2753,19 @@ static void run_remap(Engine &E, size_t frames, size_t width, size_t height, con
 // --------------------------------------------------------------------------------------------
 // frame deltas: an animation's index maps with "as on screen" made transparent (include/patolette_amd.h, patolette_amd_frame_deltas)
 // --------------------------------------------------------------------------------------------
-// host elements of `eb` bytes <-> the device's `me` (eb itself, or 4 for the 2- and 8-byte ones).  On the way in a value beyond 32
-// bits saturates (it stays "not a row"); on the way out the device's transparent index Td becomes the caller's T
-static void delta_elems_in(const void *src, int eb, size_t N, unsigned *dst) {
-    for (size_t i = 0; i < N; i++) {
-        if (eb == 2) dst[i] = ((const unsigned short *)src)[i];
-        else { const unsigned long long v = ((const unsigned long long *)src)[i]; dst[i] = v > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)v; }
-    }
-}
-static void delta_elems_out(const unsigned *src, int eb, size_t N, unsigned Td, size_t T, void *dst) {
-    for (size_t i = 0; i < N; i++) {
-        if (eb == 2) ((unsigned short *)dst)[i] = (unsigned short)src[i];
-        else ((unsigned long long *)dst)[i] = src[i] == Td ? (unsigned long long)T : (unsigned long long)src[i];
-    }
+// Host maps of N elements (eb bytes each; given.h: the 2- and 8-byte ones as the device's 4) up into E.dl_maps and, where `pixels` is
+// given, the 8-bit pixels into E.src8.  Reserves both: the caller has enqueued nothing yet.  Waits for the copies.
+// stage: the caller's, for the 2- and 8-byte host elements widened or narrowed (its pages are the caller's to use again, and to free
+// outside what it times)
+static void stage_given(Engine &E, const void *maps, int eb, int me, size_t N, GivenSkip skip, unsigned long long skip_index,
+                        const unsigned char *pixels, int channels, std::vector<unsigned> &stage) {
+    hipStream_t s = E.stream;
+    E.dl_maps.reserve(N * (size_t)me);
+    if (pixels) E.src8.reserve(N * (size_t)channels);
+    if (eb != me) { stage.resize(N); given_elems_in(maps, eb, N, skip, skip_index, stage.data()); maps = stage.data(); }
+    HIP_CHECK(hipMemcpyAsync(E.dl_maps.p, maps, N * (size_t)me, hipMemcpyHostToDevice, s));
+    if (pixels) HIP_CHECK(hipMemcpyAsync(E.src8.p, pixels, N * (size_t)channels, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipStreamSynchronize(s));
 }
 
 // maps: frames x width x height elements of `eb` bytes; rows: what every element must stay below (lossy: the used rows of pal, planar
@@ -2792,28 +2780,21 @@ static void run_frame_deltas(Engine &E, bool on_device, size_t frames, size_t wi
     const double t_start = now_ms();
     WsGuard wg(&E.stream, &E.stream2);
     E.stats = patolette_amd__Stats{};
-    const int me = (on_device || eb == 1) ? eb : 4;
-    const unsigned Td = T > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)T;            // (8-byte host elements only: rows <= 2^31 stays below it)
+    const int me = given_device_elem(eb, on_device);
+    const unsigned Td = given_transparent_on_device(T);
     // the workspace, before anything is enqueued
     const size_t words = frame_deltas_words(frames);
     E.dl_words.reserve(words);
     E.dl_masks.reserve(frame_deltas_masks(frames, n));
-    if (!on_device) {
-        E.dl_maps.reserve(N * (size_t)me);
-        if (shown_out) E.dl_shown.reserve(N * (size_t)me);
-        if (lossy) E.src8.reserve(N * (size_t)channels);
-    }
+    if (!on_device && shown_out) E.dl_shown.reserve(N * (size_t)me);
     if (lossy) { E.dpal.reserve(3 * rows); E.h_pal.reserve(3 * rows); }
     const void *d_maps = maps;
     void *d_delta = delta_out, *d_shown = shown_out;
     const unsigned char *d_px = pixels;
-    std::vector<unsigned> stage;                                                   // 2- and 8-byte host elements, widened or narrowed
+    std::vector<unsigned> stage;
     if (!on_device) {
-        const void *src = maps;
-        if (eb != me) { stage.resize(N); delta_elems_in(maps, eb, N, stage.data()); src = stage.data(); }
-        HIP_CHECK(hipMemcpyAsync(E.dl_maps.p, src, N * (size_t)me, hipMemcpyHostToDevice, s));
-        if (lossy) { HIP_CHECK(hipMemcpyAsync(E.src8.p, pixels, N * (size_t)channels, hipMemcpyHostToDevice, s)); d_px = E.src8.p; }
-        HIP_CHECK(hipStreamSynchronize(s));
+        stage_given(E, maps, eb, me, N, GivenSkip{}, 0, lossy ? pixels : nullptr, channels, stage);
+        if (lossy) d_px = E.src8.p;
         d_maps = E.dl_maps.p;
         d_delta = delta_out ? E.dl_maps.p : nullptr;                               // in place: the kernel allows it
         d_shown = shown_out ? E.dl_shown.p : nullptr;
@@ -2822,8 +2803,7 @@ static void run_frame_deltas(Engine &E, bool on_device, size_t frames, size_t wi
     double t0 = now_ms();
     if (lossy) {
         palette_rows(pal, rows, hm::color::srgb_to_ictcp);                         // as run_remap's nearest map takes its palette
-        std::memcpy(E.h_pal.p, pal.data(), 3 * rows * sizeof(double));
-        HIP_CHECK(hipMemcpyAsync(E.dpal.p, E.h_pal.p, 3 * rows * sizeof(double), hipMemcpyHostToDevice, s));
+        upload_palette(E, pal, rows);
     }
     launch_frame_deltas(d_maps, me, frames, width, height, rows, Td, lossy, d_px, channels, lossy ? E.dpal.p : nullptr, tolerance * tolerance,
                         d_delta, d_shown, E.dl_masks.p, E.dl_words.p, s);
@@ -2861,9 +2841,8 @@ static void run_frame_deltas(Engine &E, bool on_device, size_t frames, size_t wi
         for (int o = 0; o < 2; o++) {
             if (!outs[o]) continue;
             if (eb == me) { HIP_CHECK(hipMemcpy(outs[o], from[o], N * (size_t)me, hipMemcpyDeviceToHost)); continue; }
-            stage.resize(N);
-            HIP_CHECK(hipMemcpy(stage.data(), from[o], N * sizeof(unsigned), hipMemcpyDeviceToHost));
-            delta_elems_out(stage.data(), eb, N, Td, T, outs[o]);
+            HIP_CHECK(hipMemcpy(stage.data(), from[o], N * sizeof(unsigned), hipMemcpyDeviceToHost));   // (stage_given sized it; Td becomes T)
+            given_elems_out(stage.data(), me, outs[o], eb, 0, N, true, Td, T);
         }
     }
     E.stats.ms_download = now_ms() - t0;
@@ -2878,16 +2857,6 @@ struct MeasureOut {                                // host memory, each may be n
     uint64_t *frame_count, *frame_sse; uint32_t *frame_max_se;          // frames each
     double *frame_d_sum, *frame_d_max;                                  // frames each
 };
-// host elements of 2 or 8 bytes into the device's 4.  An 8-byte value beyond 32 bits stays "not a row" unless it is the skip index
-// itself, which arrives as Sd; `beyond` is a value above every row (rows <= 2^31) that is not Sd
-static void measure_elems_in(const void *src, int eb, size_t N, bool skip_on, unsigned long long skip, unsigned Sd, unsigned *dst) {
-    const unsigned beyond = Sd == 0xFFFFFFFFu ? 0xFFFFFFFEu : 0xFFFFFFFFu;
-    for (size_t i = 0; i < N; i++) {
-        if (eb == 2) { dst[i] = ((const unsigned short *)src)[i]; continue; }
-        const unsigned long long v = ((const unsigned long long *)src)[i];
-        dst[i] = (skip_on && v == skip) ? Sd : (v > 0xFFFFFFFFull || (skip_on && v == Sd) ? beyond : (unsigned)v);
-    }
-}
 
 // maps: frames x width x height elements of `eb` bytes; pal: the k used rows, planar (k,3) f64 sRGB; p8: the bytes of the K8 rows as
 // given.  skip < 0: none.  `maps` and `pixels` are device pointers when `on_device`; the outputs are host memory.
@@ -2899,32 +2868,20 @@ static void run_measure(Engine &E, bool on_device, size_t frames, size_t width, 
     const double t_start = now_ms();
     WsGuard wg(&E.stream, &E.stream2);
     E.stats = patolette_amd__Stats{};
-    const int me = (on_device || eb == 1) ? eb : 4;
+    const int me = given_device_elem(eb, on_device);
     const bool with_d = out.frame_d_sum || out.frame_d_max;
-    // a skip index that does not fit the device's element names no position
-    bool skip_on = skip >= 0;
-    unsigned Sd = 0;
-    if (skip_on) {
-        const unsigned long long v = (unsigned long long)skip;
-        if (me == 1 || on_device || eb != 8) { skip_on = (v >> (8 * (eb < me ? eb : me))) == 0; Sd = (unsigned)v; }
-        else Sd = v > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)v;
-    }
+    const GivenSkip sk = given_skip_on_device(skip, eb, me, on_device);
     // the workspace, before anything is enqueued
     const size_t words = measure_words(frames, k), from = measure_flag_word(k);
     E.ms_words.reserve(words);
     E.ms_tiles.reserve(measure_tile_count(frames, n));
     E.ms_p8.reserve(k);
-    if (!on_device) { E.dl_maps.reserve(N * (size_t)me); E.src8.reserve(N * (size_t)channels); }
     if (with_d) { E.dpal.reserve(3 * k); E.h_pal.reserve(3 * k); }
     const void *d_maps = maps;
     const unsigned char *d_px = pixels;
-    std::vector<unsigned> stage;                                                   // 2- and 8-byte host elements, widened or narrowed
+    std::vector<unsigned> stage;
     if (!on_device) {
-        const void *src = maps;
-        if (eb != me) { stage.resize(N); measure_elems_in(maps, eb, N, skip_on, (unsigned long long)skip, Sd, stage.data()); src = stage.data(); }
-        HIP_CHECK(hipMemcpyAsync(E.dl_maps.p, src, N * (size_t)me, hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipMemcpyAsync(E.src8.p, pixels, N * (size_t)channels, hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipStreamSynchronize(s));
+        stage_given(E, maps, eb, me, N, sk, (unsigned long long)skip, pixels, channels, stage);
         d_maps = E.dl_maps.p;
         d_px = E.src8.p;
     }
@@ -2935,10 +2892,9 @@ static void run_measure(Engine &E, bool on_device, size_t frames, size_t width, 
     HIP_CHECK(hipMemcpyAsync(E.ms_p8.p, rows8.data(), k * sizeof(unsigned), hipMemcpyHostToDevice, s));
     if (with_d) {
         palette_rows(pal, k, hm::color::srgb_to_ictcp);                            // as run_remap's nearest map takes its palette
-        std::memcpy(E.h_pal.p, pal.data(), 3 * k * sizeof(double));
-        HIP_CHECK(hipMemcpyAsync(E.dpal.p, E.h_pal.p, 3 * k * sizeof(double), hipMemcpyHostToDevice, s));
+        upload_palette(E, pal, k);
     }
-    launch_measure(d_maps, me, frames, n, d_px, channels, k, skip_on, Sd, E.ms_p8.p, with_d ? E.dpal.p : nullptr, E.ms_words.p, E.ms_tiles.p, s);
+    launch_measure(d_maps, me, frames, n, d_px, channels, k, sk.on, sk.Sd, E.ms_p8.p, with_d ? E.dpal.p : nullptr, E.ms_words.p, E.ms_tiles.p, s);
     std::vector<unsigned long long> w(words - from);
     HIP_CHECK(hipMemcpyAsync(w.data(), E.ms_words.p + from, w.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     E.sync();
@@ -3110,14 +3066,6 @@ static const char *kMessages[9] = {                                        // pa
     "channel mean); the reference's weights are NaN for this image.",
     nullptr};
 
-#define PAMD_GUARD_BEGIN try { Engine &E = engine(); E.init(); (void)E;
-#define PAMD_GUARD_END(ret_fail)                                             \
-    } catch (const std::exception &ex) {                                     \
-        engine().last_error = ex.what();                                     \
-        fprintf(stderr, "%s\n", ex.what());                                  \
-        return ret_fail;                                                     \
-    }
-
 static int comm_ok(const patolette_amd__Comm *comm) {
     return comm && comm->allreduce_sum && comm->size >= 1 && comm->rank >= 0 && comm->rank < comm->size;
 }
@@ -3126,15 +3074,15 @@ static int slice_args_ok(size_t total_pixels, size_t slice_begin, size_t slice_p
     return slice_pixels > 0 && slice_begin <= total_pixels && slice_pixels <= total_pixels - slice_begin && slice_data &&
            (options->palette_only || slice_map);
 }
-// Runs body(E) on the calling thread's engine, initialised.  Returns 0; a CodeError's own code (its message recorded, nothing printed);
-// or -1 for any other failure (its message recorded for patolette_amd_last_error, and printed)
+// Runs body(E) on the calling thread's engine, initialised.  Returns 0, or what a body that returns an int returns; a CodeError's own
+// code (its message recorded, nothing printed); or -1 for any other failure (its message recorded for patolette_amd_last_error, and printed)
 template <typename F>
 static int guarded(F body) {
     try {
         Engine &E = engine();
         E.init();
-        body(E);
-        return 0;
+        if constexpr (std::is_void_v<decltype(body(E))>) { body(E); return 0; }
+        else return body(E);
     } catch (const CodeError &ex) {
         engine().last_error = ex.what();
         return ex.code;
@@ -3150,6 +3098,30 @@ static void fail_args(int *exit_code, int code, const char *msg) {
     fprintf(stderr, "%s\n", msg);
     *exit_code = code;
 }
+// The palette-given entries' arguments: fail() reports "<name>: <text>" through fail_args and returns false, as do the checks they share
+struct ArgCheck {
+    const char *name;
+    int *exit_code;
+    bool fail(int code, const char *text) const { fail_args(exit_code, code, (std::string(name) + ": " + text).c_str()); return false; }
+    // frames of width x height: validate()'s codes with nothing recorded, then at most `cap` pixels in all
+    bool shape(size_t frames, size_t width, size_t height, size_t cap, const char *beyond_cap) const {
+        *exit_code = frames == 0 ? -2 : validate(width, height, 1);
+        if (*exit_code != 0) return false;
+        return frames > cap / (width * height) ? fail(-4, beyond_cap) : true;      // (n <= 1.6e9: no overflow before this)
+    }
+    bool map_elem_bytes(bool on_device, int eb) const {
+        return (on_device ? (eb != 1 && eb != 4) : (eb != 1 && eb != 2 && eb != 4 && eb != 8))
+                   ? fail(-1, "map_elem_bytes must be 1, 2, 4 or 8 (device maps: 1 or 4)") : true;
+    }
+    bool rows(size_t palette_rows, const char *text = "palette_rows must lie in [1, 2^31]") const {
+        return palette_rows < 1 || palette_rows > ((size_t)1 << 31) ? fail(-1, text) : true;
+    }
+    bool palette(const double *palette, const unsigned char *palette_u8, size_t palette_rows, bool want_bytes, GivenPalette &out) const {
+        const GivenPaletteError e = given_palette(palette, palette_u8, palette_rows, want_bytes, out);
+        return e == kGivenPaletteAllFill ? fail(-1, "every palette row is the unused-row fill (-1, -1, -1)")
+             : e == kGivenPaletteNotFinite ? fail(-1, "the palette holds a value that is not finite") : true;
+    }
+};
 
 // runs `body` on the calling thread's engine with the slice description attached
 // args_ok: this rank's arguments passed slice_args_ok.  A rank that returned early on bad arguments would leave its peers
@@ -3246,30 +3218,21 @@ int patolette_amd_set_kmeans_update(int mode) {
 int patolette_amd_saliency_weights(size_t width, size_t height, const double *data, double tile_size, double *weights_out) {
     const size_t N = width * height;
     if (N == 0) return kSalBadShape;
-    try {
-        Engine &E = engine();
-        E.init();
+    const int rc = guarded([&](Engine &E) {
         E.src.reserve(3 * N);
         HIP_CHECK(hipMemcpyAsync(E.src.p, data, 3 * N * sizeof(double), hipMemcpyHostToDevice, E.stream));
         const double *d_w = derive_weights(E, E.src.p, nullptr, 3, width, height, tile_size);
         HIP_CHECK(hipMemcpy(weights_out, d_w, N * sizeof(double), hipMemcpyDeviceToHost));
-        return 0;
-    } catch (const CodeError &ex) {
-        engine().last_error = ex.what();
-        return ex.code == -5 ? kSalBadShape : ex.code == -6 ? kSalSingular : kSalDegenerate;
-    } catch (const std::exception &ex) {
-        engine().last_error = ex.what();
-        fprintf(stderr, "patolette: %s\n", ex.what());
-        return -1;
-    }
+    });
+    return rc == -5 ? kSalBadShape : rc == -6 ? kSalSingular : rc == -7 ? kSalDegenerate : rc;   // (derive_weights' codes)
 }
 
 int patolette_amd_mbd(size_t rows, size_t cols, const float *img, int iters, float *out) {
-    PAMD_GUARD_BEGIN
-    const int rc = mbd_device(E.sal, img, rows, cols, iters, out, E.stream);
-    if (ktimer().enabled) ktimer().collect();
-    return rc;
-    PAMD_GUARD_END(-1)
+    return guarded([&](Engine &E) {
+        const int rc = mbd_device(E.sal, img, rows, cols, iters, out, E.stream);
+        if (ktimer().enabled) ktimer().collect();
+        return rc;
+    });
 }
 
 const char *get_patolette_exit_code_info_message(int exit_code) {
@@ -3316,10 +3279,10 @@ int patolette_amd_memcpy_h2d(void *dst, const void *src, size_t bytes) { return 
 int patolette_amd_memcpy_d2h(void *dst, const void *src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1; }
 int patolette_amd_synchronize(void) { return hipDeviceSynchronize() == hipSuccess ? 0 : -1; }
 int patolette_amd_fill_image(double *d, size_t n, uint64_t seed) {
-    PAMD_GUARD_BEGIN launch_fill_image(d, n, seed, E.stream); E.sync(); return 0; PAMD_GUARD_END(-1)
+    return guarded([&](Engine &E) { launch_fill_image(d, n, seed, E.stream); E.sync(); });
 }
 int patolette_amd_fill_weights(double *d, size_t n, uint64_t seed) {
-    PAMD_GUARD_BEGIN launch_fill_weights(d, n, seed, E.stream); E.sync(); return 0; PAMD_GUARD_END(-1)
+    return guarded([&](Engine &E) { launch_fill_weights(d, n, seed, E.stream); E.sync(); });
 }
 
 void patolette_amd_device(size_t width, size_t height, const double *d_data, const double *d_weights, size_t palette_size,
@@ -3362,42 +3325,21 @@ static void remap_entry(bool on_device, size_t frames, size_t width, size_t heig
                         unsigned char *quantized, int *exit_code) {
     // mode: kRemapNearest, kRemapRiemersma, or kRemapOrdered with its `spread` (the ordered map counts pixels as the nearest one does)
     const bool dither = mode == kRemapRiemersma;
-    *exit_code = frames == 0 ? -2 : validate(width, height, 1);
-    if (*exit_code != 0) return;
-    const size_t n = width * height;
-    if (frames > (dither ? kDitherFramesMaxPixels : (size_t)40000 * 40000) / n)
-        return fail_args(exit_code, -4, dither ? "patolette_amd_remap: frames * width * height exceeds 2^31 pixels (the dither numbers pixels with 32 bits)"
-                               : "patolette_amd_remap: frames * width * height is too big");
-    if ((palette != nullptr) == (palette_u8 != nullptr)) return fail_args(exit_code, -1, "patolette_amd_remap: pass exactly one of palette and palette_u8");
-    if (palette_rows < 1 || palette_rows > ((size_t)1 << 31)) return fail_args(exit_code, -1, "patolette_amd_remap: the palette needs at least one row");
+    const ArgCheck arg{"patolette_amd_remap", exit_code};
+    if (!arg.shape(frames, width, height, dither ? kDitherFramesMaxPixels : (size_t)40000 * 40000,
+                   dither ? "frames * width * height exceeds 2^31 pixels (the dither numbers pixels with 32 bits)"
+                          : "frames * width * height is too big")) return;
+    if ((palette != nullptr) == (palette_u8 != nullptr)) return (void)arg.fail(-1, "pass exactly one of palette and palette_u8");
+    if (!arg.rows(palette_rows, "the palette needs at least one row")) return;
     if (validate_u8(palette_rows, channels, palette_map, map_elem_bytes) != 0)
-        return fail_args(exit_code, -1, "patolette_amd_remap: bad channels / map_elem_bytes (1, 2, 4 or 8, able to hold palette_rows - 1)");
-    if (!pixels) return fail_args(exit_code, -1, "patolette_amd_remap: no pixels");
-    // the rows, planar (k,3) f64 sRGB, and the bytes `quantized` is made of
-    size_t k = palette_rows;
-    std::vector<double> pal;
-    std::vector<unsigned char> p8(3 * palette_rows);
-    if (palette_u8) {
-        pal.resize(3 * k);
-        for (size_t i = 0; i < k; i++) for (int c = 0; c < 3; c++) pal[(size_t)c * k + i] = (double)palette_u8[3 * i + c] / 255.0;
-        std::memcpy(p8.data(), palette_u8, 3 * palette_rows);
-    } else {
-        auto row_is = [&](size_t i, double v) { return palette[i] == v && palette[palette_rows + i] == v && palette[2 * palette_rows + i] == v; };
-        while (k > 0 && row_is(k - 1, -1.0)) k--;                          // the reference's fill of unused rows (patolette.c:327-336)
-        if (k == 0) return fail_args(exit_code, -1, "patolette_amd_remap: every palette row is the unused-row fill (-1, -1, -1)");
-        pal.resize(3 * k);
-        for (size_t i = 0; i < k; i++) for (int c = 0; c < 3; c++) {
-            const double v = palette[palette_rows * (size_t)c + i];
-            if (!std::isfinite(v)) return fail_args(exit_code, -1, "patolette_amd_remap: the palette holds a value that is not finite");
-            pal[(size_t)c * k + i] = v;
-        }
-        palette_to_u8(palette, palette_rows, p8.data());
-    }
-    if (mode == kRemapOrdered && !(std::isfinite(spread) && spread >= 0.0))
-        return fail_args(exit_code, -1, "patolette_amd_remap: spread must be finite and not negative");
+        return (void)arg.fail(-1, "bad channels / map_elem_bytes (1, 2, 4 or 8, able to hold palette_rows - 1)");
+    if (!pixels) return (void)arg.fail(-1, "no pixels");
+    GivenPalette g;                                                        // with the bytes `quantized` is made of
+    if (!arg.palette(palette, palette_u8, palette_rows, true, g)) return;
+    if (mode == kRemapOrdered && !(std::isfinite(spread) && spread >= 0.0)) return (void)arg.fail(-1, "spread must be finite and not negative");
     *exit_code = guarded([&](Engine &E) {
-        run_remap(E, frames, width, height, pixels, channels, std::move(pal), k, p8, palette_rows, mode, spread, palette_map, map_elem_bytes, quantized,
-                  on_device);
+        run_remap(E, frames, width, height, pixels, channels, std::move(g.pal), g.k, g.p8, palette_rows, mode, spread, palette_map, map_elem_bytes,
+                  quantized, on_device);
     });
 }
 
@@ -3406,47 +3348,27 @@ static void frame_deltas_entry(bool on_device, size_t frames, size_t width, size
                                size_t palette_rows, size_t transparent_index, const unsigned char *pixels, int channels, const double *palette,
                                const unsigned char *palette_u8, double tolerance, void *delta_maps, void *shown_maps, int32_t *rects,
                                uint64_t *changed, int *exit_code) {
-    *exit_code = frames == 0 ? -2 : validate(width, height, 1);
-    if (*exit_code != 0) return;
-    if (frames > (size_t)40000 * 40000 / (width * height))                            // the nearest remap's cap
-        return fail_args(exit_code, -4, "patolette_amd_frame_deltas: frames * width * height is too big");
+    const ArgCheck arg{"patolette_amd_frame_deltas", exit_code};
+    if (!arg.shape(frames, width, height, (size_t)40000 * 40000, "frames * width * height is too big")) return;   // the nearest remap's cap
     const int eb = map_elem_bytes;
-    if (on_device ? (eb != 1 && eb != 4) : (eb != 1 && eb != 2 && eb != 4 && eb != 8))
-        return fail_args(exit_code, -1, "patolette_amd_frame_deltas: map_elem_bytes must be 1, 2, 4 or 8 (device maps: 1 or 4)");
-    if (!palette_maps) return fail_args(exit_code, -1, "patolette_amd_frame_deltas: no maps");
-    if (palette_rows < 1 || palette_rows > ((size_t)1 << 31))
-        return fail_args(exit_code, -1, "patolette_amd_frame_deltas: palette_rows must lie in [1, 2^31]");
-    if (transparent_index < palette_rows)
-        return fail_args(exit_code, -1, "patolette_amd_frame_deltas: transparent_index must be at least palette_rows (an index no entry uses)");
+    if (!arg.map_elem_bytes(on_device, eb)) return;
+    if (!palette_maps) return (void)arg.fail(-1, "no maps");
+    if (!arg.rows(palette_rows)) return;
+    if (transparent_index < palette_rows) return (void)arg.fail(-1, "transparent_index must be at least palette_rows (an index no entry uses)");
     if (eb < 8 && (transparent_index >> (8 * eb)) != 0)
-        return fail_args(exit_code, -1, "patolette_amd_frame_deltas: transparent_index does not fit an element of map_elem_bytes: no index is "
-                                        "free for it -- make the palette with one row less, or pass wider elements");
-    if (!(std::isfinite(tolerance) && tolerance >= 0.0))
-        return fail_args(exit_code, -1, "patolette_amd_frame_deltas: tolerance must be finite and not negative");
-    size_t k = palette_rows;
-    std::vector<double> pal;
+        return (void)arg.fail(-1, "transparent_index does not fit an element of map_elem_bytes: no index is free for it -- make the palette with "
+                                  "one row less, or pass wider elements");
+    if (!(std::isfinite(tolerance) && tolerance >= 0.0)) return (void)arg.fail(-1, "tolerance must be finite and not negative");
+    GivenPalette g;
+    g.k = palette_rows;
     if (tolerance > 0.0) {                                                            // the lossy mode reads pixels and one palette
-        if (channels != 3 && channels != 4) return fail_args(exit_code, -1, "patolette_amd_frame_deltas: channels must be 3 or 4");
-        if (!pixels) return fail_args(exit_code, -1, "patolette_amd_frame_deltas: a tolerance above 0 needs the frames' pixels");
-        if ((palette != nullptr) == (palette_u8 != nullptr))
-            return fail_args(exit_code, -1, "patolette_amd_frame_deltas: a tolerance above 0 needs exactly one of palette and palette_u8");
-        if (palette_u8) {
-            pal.resize(3 * k);
-            for (size_t i = 0; i < k; i++) for (int c = 0; c < 3; c++) pal[(size_t)c * k + i] = (double)palette_u8[3 * i + c] / 255.0;
-        } else {                                                                      // as remap_entry takes the f64 palette
-            auto row_is = [&](size_t i, double v) { return palette[i] == v && palette[palette_rows + i] == v && palette[2 * palette_rows + i] == v; };
-            while (k > 0 && row_is(k - 1, -1.0)) k--;
-            if (k == 0) return fail_args(exit_code, -1, "patolette_amd_frame_deltas: every palette row is the unused-row fill (-1, -1, -1)");
-            pal.resize(3 * k);
-            for (size_t i = 0; i < k; i++) for (int c = 0; c < 3; c++) {
-                const double v = palette[palette_rows * (size_t)c + i];
-                if (!std::isfinite(v)) return fail_args(exit_code, -1, "patolette_amd_frame_deltas: the palette holds a value that is not finite");
-                pal[(size_t)c * k + i] = v;
-            }
-        }
+        if (channels != 3 && channels != 4) return (void)arg.fail(-1, "channels must be 3 or 4");
+        if (!pixels) return (void)arg.fail(-1, "a tolerance above 0 needs the frames' pixels");
+        if ((palette != nullptr) == (palette_u8 != nullptr)) return (void)arg.fail(-1, "a tolerance above 0 needs exactly one of palette and palette_u8");
+        if (!arg.palette(palette, palette_u8, palette_rows, false, g)) return;
     }
     *exit_code = guarded([&](Engine &E) {
-        run_frame_deltas(E, on_device, frames, width, height, palette_maps, eb, k, transparent_index, pixels, channels, std::move(pal), tolerance,
+        run_frame_deltas(E, on_device, frames, width, height, palette_maps, eb, g.k, transparent_index, pixels, channels, std::move(g.pal), tolerance,
                          delta_maps, shown_maps, rects, changed);
     });
 }
@@ -3455,41 +3377,20 @@ static void frame_deltas_entry(bool on_device, size_t frames, size_t width, size
 static void measure_entry(bool on_device, size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels,
                           const void *palette_maps, int map_elem_bytes, const double *palette, const unsigned char *palette_u8, size_t palette_rows,
                           long long skip_index, const MeasureOut &out, int *exit_code) {
-    *exit_code = frames == 0 ? -2 : validate(width, height, 1);
-    if (*exit_code != 0) return;
-    if (frames > (size_t)40000 * 40000 / (width * height))                            // the nearest remap's cap
-        return fail_args(exit_code, -4, "patolette_amd_measure: frames * width * height is too big");
+    const ArgCheck arg{"patolette_amd_measure", exit_code};
+    if (!arg.shape(frames, width, height, (size_t)40000 * 40000, "frames * width * height is too big")) return;   // the nearest remap's cap
     const int eb = map_elem_bytes;
-    if (channels != 3 && channels != 4) return fail_args(exit_code, -1, "patolette_amd_measure: channels must be 3 or 4");
-    if (on_device ? (eb != 1 && eb != 4) : (eb != 1 && eb != 2 && eb != 4 && eb != 8))
-        return fail_args(exit_code, -1, "patolette_amd_measure: map_elem_bytes must be 1, 2, 4 or 8 (device maps: 1 or 4)");
-    if (!pixels) return fail_args(exit_code, -1, "patolette_amd_measure: no pixels");
-    if (!palette_maps) return fail_args(exit_code, -1, "patolette_amd_measure: no maps");
-    if ((palette != nullptr) == (palette_u8 != nullptr)) return fail_args(exit_code, -1, "patolette_amd_measure: pass exactly one of palette and palette_u8");
-    if (palette_rows < 1 || palette_rows > ((size_t)1 << 31)) return fail_args(exit_code, -1, "patolette_amd_measure: palette_rows must lie in [1, 2^31]");
-    if (skip_index < -1) return fail_args(exit_code, -1, "patolette_amd_measure: skip_index must be -1 (none) or an index");
-    // the used rows, planar (k,3) f64 sRGB, and the bytes the integer part compares with: as remap_entry takes them
-    size_t k = palette_rows;
-    std::vector<double> pal;
-    std::vector<unsigned char> p8(3 * palette_rows);
-    if (palette_u8) {
-        pal.resize(3 * k);
-        for (size_t i = 0; i < k; i++) for (int c = 0; c < 3; c++) pal[(size_t)c * k + i] = (double)palette_u8[3 * i + c] / 255.0;
-        std::memcpy(p8.data(), palette_u8, 3 * palette_rows);
-    } else {
-        auto row_is = [&](size_t i, double v) { return palette[i] == v && palette[palette_rows + i] == v && palette[2 * palette_rows + i] == v; };
-        while (k > 0 && row_is(k - 1, -1.0)) k--;
-        if (k == 0) return fail_args(exit_code, -1, "patolette_amd_measure: every palette row is the unused-row fill (-1, -1, -1)");
-        pal.resize(3 * k);
-        for (size_t i = 0; i < k; i++) for (int c = 0; c < 3; c++) {
-            const double v = palette[palette_rows * (size_t)c + i];
-            if (!std::isfinite(v)) return fail_args(exit_code, -1, "patolette_amd_measure: the palette holds a value that is not finite");
-            pal[(size_t)c * k + i] = v;
-        }
-        palette_to_u8(palette, palette_rows, p8.data());
-    }
+    if (channels != 3 && channels != 4) return (void)arg.fail(-1, "channels must be 3 or 4");
+    if (!arg.map_elem_bytes(on_device, eb)) return;
+    if (!pixels) return (void)arg.fail(-1, "no pixels");
+    if (!palette_maps) return (void)arg.fail(-1, "no maps");
+    if ((palette != nullptr) == (palette_u8 != nullptr)) return (void)arg.fail(-1, "pass exactly one of palette and palette_u8");
+    if (!arg.rows(palette_rows)) return;
+    if (skip_index < -1) return (void)arg.fail(-1, "skip_index must be -1 (none) or an index");
+    GivenPalette g;                                                        // with the bytes the integer part compares with
+    if (!arg.palette(palette, palette_u8, palette_rows, true, g)) return;
     *exit_code = guarded([&](Engine &E) {
-        run_measure(E, on_device, frames, width, height, pixels, channels, palette_maps, eb, std::move(pal), k, p8, palette_rows, skip_index, out);
+        run_measure(E, on_device, frames, width, height, pixels, channels, palette_maps, eb, std::move(g.pal), g.k, g.p8, palette_rows, skip_index, out);
     });
 }
 
@@ -3713,10 +3614,7 @@ void patolette_amd_batch_dmap(size_t count, size_t width, size_t height, const v
                               int map_elem_bytes, int *exit_codes) {
     int v = validate(width, height, palette_size);
     if (v == 0 && pixel_format != 0 && pixel_format != 1 && pixel_format != 3 && pixel_format != 4) v = -1;
-    if (v == 0 && d_palette_maps && map_elem_bytes != map_elem_for(palette_size)) {
-        fprintf(stderr, "patolette_amd: device map_elem_bytes must be 1 for K <= 256, else 4\n");
-        v = -1;
-    }
+    if (v == 0 && d_palette_maps && map_elem_bytes != map_elem_for(palette_size)) fail_args(&v, -1, kBadDeviceMapElem);
     if (v != 0) { for (size_t i = 0; i < count; i++) exit_codes[i] = v; return; }
     const size_t N = width * height;
     batch_run(count, width, height, options, exit_codes, [&](Engine &E, size_t i) {
@@ -3770,106 +3668,100 @@ void patolette_amd_batch_rows(size_t count, size_t width, size_t height, const d
 }
 
 int patolette_amd_pow(const double *x, double y, double *out, size_t n) {
-    PAMD_GUARD_BEGIN
-    if (n == 0) return 0;
-    E.src.reserve(2 * n);
-    HIP_CHECK(hipMemcpyAsync(E.src.p, x, n * sizeof(double), hipMemcpyHostToDevice, E.stream));
-    launch_pow(E.src.p, y, E.src.p + n, n, E.stream);
-    HIP_CHECK(hipMemcpyAsync(out, E.src.p + n, n * sizeof(double), hipMemcpyDeviceToHost, E.stream));
-    E.sync();
-    return 0;
-    PAMD_GUARD_END(-1)
+    return guarded([&](Engine &E) -> int {
+        if (n == 0) return 0;
+        E.src.reserve(2 * n);
+        HIP_CHECK(hipMemcpyAsync(E.src.p, x, n * sizeof(double), hipMemcpyHostToDevice, E.stream));
+        launch_pow(E.src.p, y, E.src.p + n, n, E.stream);
+        HIP_CHECK(hipMemcpyAsync(out, E.src.p + n, n * sizeof(double), hipMemcpyDeviceToHost, E.stream));
+        E.sync();
+        return 0;
+    });
 }
 
 int patolette_amd_convert(int which, double *planar, size_t n) {
-    PAMD_GUARD_BEGIN
-    if (n == 0) return 0;
-    E.src.reserve(3 * n); E.aux.reserve(3 * n);
-    HIP_CHECK(hipMemcpy(E.src.p, planar, 3 * n * sizeof(double), hipMemcpyHostToDevice));
-    launch_convert(which, E.src.p, E.aux.p, n, nullptr, E.stream);
-    E.sync();
-    HIP_CHECK(hipMemcpy(planar, E.aux.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
-    PAMD_GUARD_END(-1)
+    return guarded([&](Engine &E) -> int {
+        if (n == 0) return 0;
+        E.src.reserve(3 * n); E.aux.reserve(3 * n);
+        HIP_CHECK(hipMemcpy(E.src.p, planar, 3 * n * sizeof(double), hipMemcpyHostToDevice));
+        launch_convert(which, E.src.p, E.aux.p, n, nullptr, E.stream);
+        E.sync();
+        HIP_CHECK(hipMemcpy(planar, E.aux.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
+        return 0;
+    });
 }
 
 int patolette_amd_quantize_clusters(const double *colors, const double *weights, size_t n, size_t K, double *centers, size_t *n_clusters) {
-    PAMD_GUARD_BEGIN
-    if (n == 0 || K == 0) return -1;
-    const bool weighted = weights != nullptr;
-    E.src.reserve(3 * n);
-    E.cvt.reserve((weighted ? 4 : 3) * n);
-    E.cstats.reserve(1);
-    HIP_CHECK(hipMemcpy(E.src.p, colors, 3 * n * sizeof(double), hipMemcpyHostToDevice));
-    launch_convert(PAMD_COPY, E.src.p, E.cvt.p, n, E.cstats.p, E.stream);
-    if (weighted) {
-        HIP_CHECK(hipMemcpyAsync(E.cvt.p + 3 * n, weights, n * sizeof(double), hipMemcpyHostToDevice, E.stream));
-        launch_weight_stats(E.cvt.p + 3 * n, n, E.cstats.p, E.stream);
-    }
-    Bounds b = read_bounds(E, weighted);
-    E.stats = patolette_amd__Stats{};
-    std::vector<double> pal;
-    size_t len = 0;
-    if (quantize_clusters(E, n, K, weighted, b, pal, len) != 0) return -1;
-    for (size_t j = 0; j < 3 * K; j++) centers[j] = NAN;
-    for (int j = 0; j < 3; j++) for (size_t i = 0; i < len; i++) centers[(size_t)j * K + i] = pal[(size_t)j * len + i];
-    *n_clusters = len;
-    return 0;
-    PAMD_GUARD_END(-1)
+    return guarded([&](Engine &E) -> int {
+        if (n == 0 || K == 0) return -1;
+        const bool weighted = weights != nullptr;
+        E.src.reserve(3 * n);
+        E.cvt.reserve((weighted ? 4 : 3) * n);
+        E.cstats.reserve(1);
+        HIP_CHECK(hipMemcpy(E.src.p, colors, 3 * n * sizeof(double), hipMemcpyHostToDevice));
+        launch_convert(PAMD_COPY, E.src.p, E.cvt.p, n, E.cstats.p, E.stream);
+        if (weighted) {
+            HIP_CHECK(hipMemcpyAsync(E.cvt.p + 3 * n, weights, n * sizeof(double), hipMemcpyHostToDevice, E.stream));
+            launch_weight_stats(E.cvt.p + 3 * n, n, E.cstats.p, E.stream);
+        }
+        Bounds b = read_bounds(E, weighted);
+        E.stats = patolette_amd__Stats{};
+        std::vector<double> pal;
+        size_t len = 0;
+        if (quantize_clusters(E, n, K, weighted, b, pal, len) != 0) return -1;
+        for (size_t j = 0; j < 3 * K; j++) centers[j] = NAN;
+        for (int j = 0; j < 3; j++) for (size_t i = 0; i < len; i++) centers[(size_t)j * K + i] = pal[(size_t)j * len + i];
+        *n_clusters = len;
+        return 0;
+    });
 }
 
 int patolette_amd_kmeans_refine(const double *colors, const double *weights, size_t n, double *centers_io, size_t k, int niter, size_t max_samples) {
-    PAMD_GUARD_BEGIN
-    const bool weighted = weights != nullptr;
-    E.cvt.reserve((weighted ? 4 : 3) * n);
-    HIP_CHECK(hipMemcpy(E.cvt.p, colors, 3 * n * sizeof(double), hipMemcpyHostToDevice));
-    if (weighted) HIP_CHECK(hipMemcpy(E.cvt.p + 3 * n, weights, n * sizeof(double), hipMemcpyHostToDevice));
-    std::vector<double> pal(centers_io, centers_io + 3 * k);
-    bool nonfinite = false;                                     // Clustering.cpp:295-304 over every colour value as f32
-    for (size_t i = 0; i < 3 * n && !nonfinite; i++) nonfinite = !(std::fabs(colors[i]) < 0x1.ffffffp127);
-    double bx = 0, bw = 1;
-    if (!nonfinite && km_update_order_free()) {
-        for (size_t i = 0; i < 3 * n; i++) bx = std::max(bx, std::fabs(colors[i]));
-        if (weighted) for (size_t i = 0; i < n; i++) bw = std::max(bw, std::fabs(weights[i]));
-    }
-    kmeans_refine(E, n, weighted, pal, k, niter, max_samples, nonfinite, 0, bx, bw);
-    std::memcpy(centers_io, pal.data(), 3 * k * sizeof(double));
-    return 0;
-    PAMD_GUARD_END(-1)
+    return guarded([&](Engine &E) -> int {
+        const bool weighted = weights != nullptr;
+        E.cvt.reserve((weighted ? 4 : 3) * n);
+        HIP_CHECK(hipMemcpy(E.cvt.p, colors, 3 * n * sizeof(double), hipMemcpyHostToDevice));
+        if (weighted) HIP_CHECK(hipMemcpy(E.cvt.p + 3 * n, weights, n * sizeof(double), hipMemcpyHostToDevice));
+        std::vector<double> pal(centers_io, centers_io + 3 * k);
+        bool nonfinite = false;                                     // Clustering.cpp:295-304 over every colour value as f32
+        for (size_t i = 0; i < 3 * n && !nonfinite; i++) nonfinite = !(std::fabs(colors[i]) < 0x1.ffffffp127);
+        double bx = 0, bw = 1;
+        if (!nonfinite && km_update_order_free()) {
+            for (size_t i = 0; i < 3 * n; i++) bx = std::max(bx, std::fabs(colors[i]));
+            if (weighted) for (size_t i = 0; i < n; i++) bw = std::max(bw, std::fabs(weights[i]));
+        }
+        kmeans_refine(E, n, weighted, pal, k, niter, max_samples, nonfinite, 0, bx, bw);
+        std::memcpy(centers_io, pal.data(), 3 * k * sizeof(double));
+        return 0;
+    });
 }
 
 int patolette_amd_nn_map(const double *colors, size_t n, const double *palette, size_t k, size_t *map) {
-    PAMD_GUARD_BEGIN
-    if (n == 0) return 0;
-    E.src.reserve(3 * n); E.dpal.reserve(3 * k); E.dmap.reserve(n * 4);
-    HIP_CHECK(hipMemcpy(E.src.p, colors, 3 * n * sizeof(double), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(E.dpal.p, palette, 3 * k * sizeof(double), hipMemcpyHostToDevice));
-    launch_nn_map(E.src.p, n, n, E.dpal.p, (int)k, E.dmap.p, 4, nullptr, nullptr, E.nn, E.stream);
-    E.sync();
-    std::vector<unsigned int> tmp(n);
-    HIP_CHECK(hipMemcpy(tmp.data(), E.dmap.p, n * 4, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < n; i++) map[i] = tmp[i];
-    return 0;
-    PAMD_GUARD_END(-1)
+    return guarded([&](Engine &E) -> int {
+        if (n == 0) return 0;
+        E.src.reserve(3 * n); E.dpal.reserve(3 * k); E.dmap.reserve(n * 4);
+        HIP_CHECK(hipMemcpy(E.src.p, colors, 3 * n * sizeof(double), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(E.dpal.p, palette, 3 * k * sizeof(double), hipMemcpyHostToDevice));
+        launch_nn_map(E.src.p, n, n, E.dpal.p, (int)k, E.dmap.p, 4, nullptr, nullptr, E.nn, E.stream);
+        E.sync();
+        download_map(E.dmap.p, 4, n, map, 8);
+        return 0;
+    });
 }
 
 int patolette_amd_dither(const double *colors, size_t width, size_t height, const double *palette, size_t k, size_t *map) {
-    PAMD_GUARD_BEGIN
-    const size_t n = width * height;
-    if (n == 0) return 0;
-    E.src.reserve(3 * n); E.dpal.reserve(3 * k); E.dmap.reserve(n * 4);
-    HIP_CHECK(hipMemcpy(E.src.p, colors, 3 * n * sizeof(double), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(E.dpal.p, palette, 3 * k * sizeof(double), hipMemcpyHostToDevice));
-    launch_dither(E.src.p, n, PAMD_COPY, width, height, E.dpal.p, palette, (int)k, E.dmap.p, 4, E.nn, E.stream);
-    copy_dither_stats(E);
-    E.sync();
-    if (map_touched(true, width, height)) {
-        std::vector<unsigned int> tmp(n);
-        HIP_CHECK(hipMemcpy(tmp.data(), E.dmap.p, n * 4, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < n; i++) map[i] = tmp[i];
-    }
-    return 0;
-    PAMD_GUARD_END(-1)
+    return guarded([&](Engine &E) -> int {
+        const size_t n = width * height;
+        if (n == 0) return 0;
+        E.src.reserve(3 * n); E.dpal.reserve(3 * k); E.dmap.reserve(n * 4);
+        HIP_CHECK(hipMemcpy(E.src.p, colors, 3 * n * sizeof(double), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(E.dpal.p, palette, 3 * k * sizeof(double), hipMemcpyHostToDevice));
+        launch_dither(E.src.p, n, PAMD_COPY, width, height, E.dpal.p, palette, (int)k, E.dmap.p, 4, E.nn, E.stream);
+        copy_dither_stats(E);
+        E.sync();
+        if (map_touched(true, width, height)) download_map(E.dmap.p, 4, n, map, 8);
+        return 0;
+    });
 }
 
 int patolette_amd_debug_fault(int which) { return g_debug_fault.exchange(which); }
