@@ -259,7 +259,8 @@ void patolette_amd_remap_ordered_u8_device(size_t frames, size_t width, size_t h
  * T not representable, a tolerance that is negative or not finite, missing pixels or both or neither palette in the lossy mode, a
  * palette value that is not finite, or the flag above.  A failed call leaves the thread's engine usable.
  * Statistics: the ms_* fields as for a remap (ms_map: the kernel and its results), every other field 0.
- * Out of scope: maps that already carry a transparent entry (those of patolette_amd_rgba): their index 0 is compared like any other.
+ * Out of scope: maps that already carry a transparent entry (those of patolette_amd_rgba and patolette_amd_remap_rgba_u8): their index 0
+ * is compared like any other row, which is all the exact mode needs; the lossy mode on them stays out of scope.
  * One kernel for all frames (k_frame_deltas): a lane owns a position, walks the frames and keeps the canvas entry in a register. */
 void patolette_amd_frame_deltas(size_t frames, size_t width, size_t height, const void *palette_maps, int map_elem_bytes,
                                 size_t palette_rows, size_t transparent_index, const unsigned char *pixels, int channels,
@@ -359,6 +360,61 @@ void patolette_amd_rgba_device(size_t width, size_t height, const unsigned char 
                                double tile_size, size_t palette_size, const patolette__QuantizationOptions *options, double *palette,
                                unsigned char *palette_rgba, void *d_palette_map, int map_elem_bytes, unsigned char *d_quantized,
                                int *transparent_index, int *exit_code);
+
+/* ---- remap with alpha: RGBA images and frames onto a palette the CALLER gives -------------------
+ * What patolette_amd_remap_u8 is to patolette_amd_u8, this is to patolette_amd_rgba: no palette is made; `frames` images of
+ * width x height, interleaved 8-bit RGBA (4 bytes per pixel), one after another, are mapped onto the given palette, of which row 0 may
+ * be a transparent entry.  n = width * height, N = frames * n.
+ *   Transparency.  A pixel is TRANSPARENT iff its alpha < alpha_threshold (an integer in [0, 256]), else OPAQUE: the rule of
+ *       patolette_amd_rgba.
+ *   Palette.  palette / palette_u8 / palette_rows exactly as patolette_amd_remap_u8 takes them (exactly one of the two; trailing
+ *       (-1, -1, -1) rows of the f64 one are dropped as there; every remaining row finite).
+ *       transparent_index ==  0: row 0 is the transparent entry.  Its colour is never a candidate for any pixel and its quantized
+ *                                value is (0, 0, 0, 0), whatever the row holds.
+ *       transparent_index == -1: there is no transparent entry; every row is a candidate.
+ *       The OPAQUE ROWS are the used rows without the transparent entry; at least one must remain, else -1.  off = 1 when row 0 is
+ *       the transparent entry, else 0.
+ *   mode 0 (nearest), 2 (ordered; `spread` is read in this mode only).  An opaque pixel's element is off + e, where e is exactly the
+ *       element patolette_amd_remap_u8(dither == 0) resp. patolette_amd_remap_ordered_u8(spread) writes for that pixel -- its bytes, at
+ *       its place in its own frame -- with the palette made of the opaque rows only.  Both maps are per pixel, so the RGB hidden under
+ *       transparent pixels cannot matter.
+ *   mode 1 (Riemersma).  Frame by frame the reference's walk over that frame's own width x height curve from an empty error queue, on
+ *       the opaque rows, with transparent pixels treated exactly like positions outside the image (no choice, the queue unchanged) --
+ *       the rule of patolette_amd_rgba; element off + the walk's choice.  No state passes between frames.  A frame without a
+ *       transparent pixel is therefore the walk of patolette_amd_remap_u8(dither != 0) on its RGB; a 1 x 1 frame gets entry off.
+ *   Transparent pixels: element 0 and quantized (0, 0, 0, 0).
+ *   Opaque pixels: quantized = (pal8[element], 255), pal8 as the remap contract defines it (palette_u8 as given, or
+ *       clip(palette * 255, 0, 255) truncated).
+ *   A transparent pixel while transparent_index == -1 has no element to take: it is never used as an address, a kernel raises a flag
+ *       (modes 0 and 2: the stamp; mode 1: the frames' opaque counts), and the call fails with -1 and a "patolette_amd_remap_rgba:"
+ *       text in patolette_amd_last_error; what the outputs then hold is not defined.  The next call works.
+ *   Outputs, each optional (NULL): palette_map, N elements of map_elem_bytes (1, 2, 4 or 8; able to hold palette_rows - 1: the
+ *       elements are sized by palette_rows, transparent row included), frame after frame; quantized, N x 4 interleaved.  With both
+ *       NULL the call still checks the arguments and the flag.
+ *   Exit codes: 0; -2 an empty image or frames == 0; -4 more than 2^31 pixels in all in mode 1 (more than 40000^2 otherwise); -1 (with
+ *       a "patolette_amd_remap_rgba:" text) for a mode other than 0, 1, 2, an alpha_threshold outside [0, 256], a transparent_index
+ *       other than -1 and 0, both or neither palette, no palette row, a bad map_elem_bytes, no pixels, no usable or a non-finite
+ *       palette row, no opaque row left, a spread that is negative or not finite in mode 2, or the flag above.  A failed call leaves
+ *       the thread's engine usable.
+ *   Statistics: the ms_* fields as for a remap; the dither counters summed over the frames in mode 1, else 0.
+ *       patolette_amd_last_map_palette: the opaque rows in the map's space.
+ * Modes 0 and 2 run the mappers of the RGB remaps unchanged over every pixel; one more kernel for all frames (k_rgba_stamp) reads the
+ * alpha byte and the mapper's element and writes the final element and the RGBA word.  Mode 1 goes frame after frame through the
+ * RGBA entry's compaction, masked walk and expansion; every frame's opaque count reaches the host with one wait.
+ * The *_device flavour takes device pointers for pixels / palette_map / quantized (palette_map and quantized aligned to their element
+ * size, as hipMalloc returns them; pixels that are not 4-byte aligned are copied once); both palettes stay host memory. */
+void patolette_amd_remap_rgba_u8(size_t frames, size_t width, size_t height, const unsigned char *pixels, int alpha_threshold,
+                                 const double *palette, const unsigned char *palette_u8, size_t palette_rows, int transparent_index,
+                                 int mode, double spread, void *palette_map, int map_elem_bytes, unsigned char *quantized,
+                                 int *exit_code);
+void patolette_amd_remap_rgba_u8_device(size_t frames, size_t width, size_t height, const unsigned char *d_pixels, int alpha_threshold,
+                                        const double *palette, const unsigned char *palette_u8, size_t palette_rows,
+                                        int transparent_index, int mode, double spread, void *d_palette_map, int map_elem_bytes,
+                                        unsigned char *d_quantized, int *exit_code);
+/* TESTS ONLY: k_rgba_stamp gives a lane four consecutive pixels (16-byte accesses) wherever the stack has at least four pixels and every
+ * buffer is aligned for its vector access, otherwise one.  0 takes one everywhere, 1 and -1 restore that rule.  Same results either
+ * way.  Process-wide; returns the previous mode. */
+int patolette_amd_debug_rgba_stamp_quad(int mode);
 
 /* ---- batch of independent images (SURVEY.md 8(b) "Batch extension") -----------------------
  * count images of identical width x height; data[i] / weights[i] (weights may be NULL or hold

@@ -17,7 +17,10 @@ and `remap`, which makes no palette: it maps 8-bit images or frames onto a palet
 default strength; and `frame_deltas`, which turns an animation's maps into what an encoder writes per frame: unchanged positions made
 transparent, and the dirty rectangle; and `measure`, which tells what any of these maps costs -- per palette entry and per frame the
 pixel count, the squared error in code values and its maximum, per frame also the squared ICtCp distance the palette was fitted to
-and `frame_deltas`' tolerance is stated in -- with `psnr` to read it in decibels.
+and `frame_deltas`' tolerance is stated in -- with `psnr` to read it in decibels;
+and, for animations with transparency, `remap_rgba` (RGBA images or frames onto a given palette whose row 0 may be a transparent
+entry) and `quantize_rgba_frames` (one shared palette and one transparent index for all frames, composed from `quantize_rgba`'s
+palette stage and `remap_rgba`).
 """
 import ctypes as C
 
@@ -467,6 +470,8 @@ def frame_deltas(maps, palette, transparent_index=None, frames=None, tolerance=0
         always with the current source, so no error accumulates.
       * want_shown: also return what the canvas shows after every frame (== maps when tolerance is 0).
     Frame 0 is the full first map.  Compositing the deltas (overwrite where delta != transparent_index) gives back `shown`.
+    Maps that carry a transparent entry of their own (`remap_rgba`, `quantize_rgba_frames`) work with the exact mode -- their index 0
+    compares like any row -- and with `measure(..., skip_index=0)`; the lossy mode on them stays out of scope.
 
     Returns (success, deltas (F,H,W) as maps, rects (F,4) int32 rows (x0, y0, w, h) -- (0,0,0,0) for an unchanged frame --,
     changed (F,) int64, shown (F,H,W) or None, message)."""
@@ -642,6 +647,141 @@ def quantize_rgba(image, palette_size, alpha_threshold=128, dither=True, palette
     return (True, palette_rgba, pmap, quant, palette, tidx.value, message)
 
 
+def _alpha_threshold(alpha_threshold):
+    if isinstance(alpha_threshold, (bool, np.bool_)) or not isinstance(alpha_threshold, (int, np.integer)) or not 0 <= alpha_threshold <= 256:
+        raise ValueError("alpha_threshold must be an integer in [0, 256]")
+    return int(alpha_threshold)
+
+
+def _rgba_palette(palette, transparent_index):
+    """The palette of `remap_rgba` -> (bytes (k, 3) or None, float (k, 3) column-major or None, rows the maps are sized by, 0 or -1,
+    the opaque rows as `ordered_spread` takes them).  Every rule of the docstring; ValueError for what breaks one."""
+    if transparent_index is not None and (isinstance(transparent_index, (bool, np.bool_)) or not isinstance(transparent_index, (int, np.integer))
+                                          or int(transparent_index) not in (-1, 0)):
+        raise ValueError("transparent_index must be None, -1 (no transparent entry) or 0 (row 0)")
+    pal = np.asarray(palette)
+    if pal.ndim == 2 and pal.shape[1] == 4:
+        if pal.dtype != np.uint8 or pal.shape[0] < 1:
+            raise ValueError("a (K, 4) palette must be uint8 RGBA rows, as quantize_rgba returns palette_rgba")
+        k = pal.shape[0]
+        while k > 0 and not pal[k - 1].any():
+            k -= 1                                                 # (trailing (0, 0, 0, 0) rows: unused)
+        used = pal[:k]
+        tidx = 0 if k > 0 and used[0, 3] == 0 else -1
+        if np.any(used[1:, 3] == 0):
+            raise ValueError("palette row %d has alpha 0: only row 0 can be the transparent entry" % (1 + int(np.argmax(used[1:, 3] == 0))))
+        opaque = used[1:] if tidx == 0 else used
+        if np.any(opaque[:, 3] != 255):
+            raise ValueError("palette rows must have alpha 255 (or 0 in row 0, the transparent entry)")
+        if transparent_index is not None and int(transparent_index) != tidx:
+            raise ValueError("transparent_index %d contradicts the palette's alpha column (which says %d)" % (int(transparent_index), tidx))
+        if opaque.shape[0] < 1:
+            raise ValueError("the palette has no opaque row")
+        pal8 = np.ascontiguousarray(used[:, :3])
+        return pal8, None, pal.shape[0], tidx, pal8[1:] if tidx == 0 else pal8
+    pal8, palf = _remap_palette(palette)
+    tidx = -1 if transparent_index is None else int(transparent_index)
+    opaque = _palette_rows(pal8, palf)[1 if tidx == 0 else 0:]
+    if opaque.shape[0] < 1:
+        raise ValueError("the palette has no opaque row")
+    return pal8, palf, (pal8 if pal8 is not None else palf).shape[0], tidx, opaque
+
+
+def remap_rgba(image, palette, transparent_index=None, alpha_threshold=128, dither=True, want_quantized=True, spread=None):
+    """Map an RGBA image, or RGBA frames of one size, onto a palette the caller gives, of which row 0 may be a transparent entry
+    (additive; include/patolette_amd.h: patolette_amd_remap_rgba_u8).  What `remap` is to `quantize_u8`, this is to `quantize_rgba`.
+
+      * image: (H, W, 4) or (F, H, W, 4) uint8, a numpy array or a torch CUDA tensor (then the map and the quantized image stay in
+        HBM).  A pixel is transparent iff its alpha < alpha_threshold (an integer in [0, 256]).
+      * palette, one of
+          - (K, 4) uint8, as `quantize_rgba` returns `palette_rgba`: trailing (0, 0, 0, 0) rows are unused and dropped; row 0 with
+            alpha 0 is the transparent entry; every other used row must have alpha 255.  transparent_index may be left None, and must
+            not contradict the rows.
+          - (K, 3) uint8 or float, as `remap` takes it: transparent_index=0 makes row 0 the transparent entry (its colour is never a
+            candidate), None or -1 means there is none.
+      * Opaque pixels take the entry `remap` would give them with the opaque rows alone, plus 1 when row 0 is the transparent entry:
+        dither=False the nearest in ICtCp, dither="ordered" the Bayer dither (spread=None: `ordered_spread` of the opaque rows),
+        dither=True the Riemersma walk over each frame's own curve, on which transparent pixels are skipped like positions outside
+        the image (as in `quantize_rgba`).  No state passes between frames.
+      * Transparent pixels get index 0 and quantized (0, 0, 0, 0); a transparent pixel while the palette has no transparent entry
+        is a ValueError.
+    These maps go into `frame_deltas` (exact mode: index 0 compares like any row) and `measure(..., skip_index=0)`.
+
+    Returns (success, palette_map (H,W) or (F,H,W) uint8|uint16|uint32 by K, quantized (..., 4) uint8 or None, message)."""
+    mode, spread = _dither_mode(dither), _spread_value(spread)
+    px, shape, dev = _u8_pixels(image, (3, 4), (4,), "image must be an (H, W, 4) or (F, H, W, 4) uint8 %s")
+    thr = _alpha_threshold(alpha_threshold)
+    if hasattr(palette, "detach"):
+        palette = palette.detach().cpu().numpy()
+    pal8, palf, rows, tidx, opaque = _rgba_palette(palette, transparent_index)
+    if mode == 2 and spread is None:
+        spread = ordered_spread(opaque)
+    count, (height, width) = (shape[0] if len(shape) == 4 else 1), shape[-3:-1]
+    pmap, map_elem, quant = _outputs(shape[:-1], rows, 4, dev, True, want_quantized)
+    code = C.c_int(0)
+    _call("patolette_amd_remap_rgba_u8", dev, count, width, height, _vp(px), thr, _vp(palf), _vp(pal8),
+          (pal8 if pal8 is not None else palf).shape[0], tidx, mode, 0.0 if spread is None else spread, _vp(pmap), map_elem, _vp(quant),
+          C.byref(code))
+    if code.value == -1 and _native.last_error().startswith("patolette_amd_remap_rgba:"):
+        raise ValueError(_native.last_error())
+    message = _message(code.value)
+    if code.value != 0:
+        return (False, None, None, message)
+    return (True, pmap, quant, message)
+
+
+def quantize_rgba_frames(frames, palette_size, alpha_threshold=128, dither=True, palette_only=False, color_space=ColorSpace_ICtCp,
+                         tile_size=512, kmeans_niter=32, kmeans_max_samples=512 ** 2, weights=None, want_quantized=True, spread=None):
+    """Quantise an animation with transparency: (F, H, W, 4) uint8 RGBA frames (numpy, or a torch CUDA tensor) get ONE shared palette
+    with ONE transparent index, and every frame its own map.  Composed in Python from two library calls, as dither="ordered" is:
+
+      * Palette: `quantize_rgba`'s entry on the frames viewed as one (F*H, W, 4) image, without its map stage -- the palette of the
+        opaque pixels of all frames, entry 0 transparent iff any pixel of any frame is.
+      * weights: None or F*H*W values in frame order.  tile_size > 0 without weights: every frame's weights are `saliency_weights` of
+        that frame's RGB as an image of its own, handed over as explicit weights -- one host round trip per frame.
+      * Maps: `remap_rgba(frames, palette, transparent_index, alpha_threshold, dither, spread=spread)` with the float palette just
+        made; dither may be "ordered".  As with dither="ordered" elsewhere, the maps are the remap of the RETURNED palette: close to,
+        not bit for bit, the map the pipeline itself would have made (the palette has been through the way back to sRGB).
+      * palette_only stops after the first call (and, as in the reference, leaves the palette in the quantisation's colour space).
+
+    Returns (success, palette_rgba (K,4) uint8, maps (F,H,W) or None, quantized (F,H,W,4) uint8 or None (= palette_rgba[maps]),
+    palette (K,3) float64, transparent_index (0 or -1), message)."""
+    mode, spread = _dither_mode(dither), _spread_value(spread)
+    px, shape, dev = _u8_pixels(frames, (4,), (4,), "frames must be an (F, H, W, 4) uint8 %s")
+    if tile_size < 0:
+        raise ValueError(bad_tile_size)
+    thr = _alpha_threshold(alpha_threshold)
+    count, height, width = shape[:3]
+    n = width * height
+    w = _weights(weights, count * n, dev, "frames*width*height")
+    if w is None and tile_size > 0:
+        host = px.cpu().numpy() if dev is not None else px
+        w = _weights(np.concatenate([saliency_weights(width, height, host[f, :, :, :3].reshape(n, 3) / 255.0, tile_size)
+                                     for f in range(count)]), count * n, dev)
+    rows = max(palette_size, 0)
+    palette = np.zeros((rows, 3), dtype=np.float64, order='F')
+    palette_rgba = np.zeros((rows, 4), dtype=np.uint8)
+    code, tidx = C.c_int(0), C.c_int(-1)
+    opts = _options(False, palette_only, color_space, kmeans_niter, kmeans_max_samples)
+    _call("patolette_amd_rgba", dev, width, count * height, _vp(px), thr, _vp(w), 0.0, palette_size, C.byref(opts), _vp(palette),
+          _vp(palette_rgba), None, 1, None, C.byref(tidx), C.byref(code))
+    message = _message(code.value)
+    _raise_saliency(code.value, message)
+    if code.value == -1 and _native.last_error().startswith("patolette_amd_rgba:"):
+        raise ValueError(_native.last_error())
+    if code.value != 0:
+        return (False, None, None, None, None, None, message)
+    if palette_only:
+        return (True, palette_rgba, None, None, palette, tidx.value, message)
+    if tidx.value == 0 and not palette_rgba[1:].any():            # every pixel of every frame transparent: index 0 throughout
+        pmap, _, quant = _outputs(shape[:3], rows, 4, dev, True, want_quantized)
+        return (True, palette_rgba, pmap, quant, palette, 0, message)
+    ok, pmap, quant, message = remap_rgba(px, palette, tidx.value, thr, dither if mode != 2 else "ordered", want_quantized, spread)
+    if not ok:
+        return (False, None, None, None, None, None, message)
+    return (True, palette_rgba, pmap, quant, palette, tidx.value, message)
+
+
 def quantize_batch(width, height, images, palette_size, weights=None, dither=True, palette_only=False,
                    color_space=ColorSpace_ICtCp, tile_size=512, kmeans_niter=32, kmeans_max_samples=512 ** 2, verbose=False):
     """Quantise a list of independent images of identical size on the current GPU through
@@ -742,8 +882,10 @@ __all__ = [
     "quantize_u8",
     "quantize_u8_batch",
     "quantize_rgba",
+    "quantize_rgba_frames",
     "quantize_frames",
     "remap",
+    "remap_rgba",
     "ordered_spread",
     "frame_deltas",
     "measure",

@@ -991,6 +991,9 @@ struct Engine {
     DevBuf<unsigned char> rgba_rgb, rgba_map;
     DevBuf<double> rgba_w;
     PinBuf<unsigned> h_rgba_m;
+    // the remap with alpha (run_remap_rgba): the stamp's flag and, behind it, every frame's opaque count; their pinned landing place
+    DevBuf<unsigned> rr_words;
+    PinBuf<unsigned> h_rr_words;
     DevBuf<ConvertStats> cstats;
     PinBuf<NodeIn> h_stage_in;
     PinBuf<NodeOut> h_stage_out;
@@ -2684,6 +2687,28 @@ static std::atomic<int> g_remap_two_pass{0};
 // bytes along the curve and converts them there; no f64 image is written.
 // Ordered (mode kRemapOrdered, `spread`): launch_ordered_map shifts, converts and searches in one kernel; palette in ICtCp, no f64 image.
 enum { kRemapNearest = 0, kRemapRiemersma = 1, kRemapOrdered = 2 };
+// The remaps' Riemersma walk over `frames` frames of 8-bit pixels (N in all) with the Rec2020 palette in E.dpal and in `pal`: fused, or
+// through the planes in E.cvt, which the caller has reserved (3 * N) unless `fused`
+static void remap_dither(Engine &E, const unsigned char *d_px, int channels, size_t frames, size_t width, size_t height, const std::vector<double> &pal,
+                         size_t k, void *d_map, int me, bool fused, bool lanes) {
+    const size_t N = frames * width * height;
+    hipStream_t s = E.stream;
+    bool done = false;
+    if (fused) {
+        HIP_CHECK(hipStreamSynchronize(s));
+        done = launch_dither_u8(d_px, channels, frames, width, height, E.dpal.p, pal.data(), (int)k, d_map, me, E.nn, s);
+        // the lane walk's verification stalled beyond patolette_amd_debug_dither_solo_cap: the planes after all, for the wavefront layout
+        if (!done) { HIP_CHECK(hipStreamSynchronize(s)); E.cvt.reserve(3 * N); }
+    }
+    if (!done) {
+        const int layout = (lanes && !fused) ? 1 : 0;                         // (after a stalled lane walk: not the same walk again)
+        launch_convert_u8(PAMD_SRGB_TO_REC2020, d_px, channels, E.cvt.p, N, nullptr, s);
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (frames > 1) launch_dither_frames(E.cvt.p, N, PAMD_COPY, frames, width, height, E.dpal.p, pal.data(), (int)k, d_map, me, E.nn, s, layout);
+        else launch_dither(E.cvt.p, N, PAMD_COPY, width, height, E.dpal.p, pal.data(), (int)k, d_map, me, E.nn, s, layout);
+    }
+}
+
 static void run_remap(Engine &E, size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels, std::vector<double> pal,
                       size_t k, const std::vector<unsigned char> &p8, size_t K8, int mode, double spread, void *map_out, int map_elem_out,
                       unsigned char *quant_out, bool on_device) {
@@ -2725,20 +2750,7 @@ static void run_remap(Engine &E, size_t frames, size_t width, size_t height, con
             const Bounds b = read_bounds(E, false);                                   // (waits: the map kernels' tables are reserved on an idle stream)
             launch_nn_map(E.cvt.p, N, N, E.dpal.p, (int)k, d_map, me, b.lo, b.hi, E.nn, s);
         } else {
-            bool done = false;
-            if (fused) {
-                HIP_CHECK(hipStreamSynchronize(s));
-                done = launch_dither_u8(d_px, channels, frames, width, height, E.dpal.p, pal.data(), (int)k, d_map, me, E.nn, s);
-                // the lane walk's verification stalled beyond patolette_amd_debug_dither_solo_cap: the planes after all, for the wavefront layout
-                if (!done) { HIP_CHECK(hipStreamSynchronize(s)); E.cvt.reserve(3 * N); }
-            }
-            if (!done) {
-                const int layout = (lanes && !fused) ? 1 : 0;                         // (after a stalled lane walk: not the same walk again)
-                launch_convert_u8(PAMD_SRGB_TO_REC2020, d_px, channels, E.cvt.p, N, nullptr, s);
-                HIP_CHECK(hipStreamSynchronize(s));
-                if (frames > 1) launch_dither_frames(E.cvt.p, N, PAMD_COPY, frames, width, height, E.dpal.p, pal.data(), (int)k, d_map, me, E.nn, s, layout);
-                else launch_dither(E.cvt.p, N, PAMD_COPY, width, height, E.dpal.p, pal.data(), (int)k, d_map, me, E.nn, s, layout);
-            }
+            remap_dither(E, d_px, channels, frames, width, height, pal, k, d_map, me, fused, lanes);
             copy_dither_stats(E);
         }
         E.sync();
@@ -2746,6 +2758,143 @@ static void run_remap(Engine &E, size_t frames, size_t width, size_t height, con
     E.stats.ms_map = now_ms() - t0;
     t0 = now_ms();
     if (want && map_touched(dither, width, height)) u8_outputs(E, d_map, N, p8.data(), K8, map_out, map_elem_out, quant_out, on_device);
+    E.stats.ms_download = now_ms() - t0;
+    E.stats.ms_total = now_ms() - t_start;
+}
+
+// --------------------------------------------------------------------------------------------
+// remap with alpha: RGBA frames onto a palette the caller gives (include/patolette_amd.h, patolette_amd_remap_rgba_u8)
+// --------------------------------------------------------------------------------------------
+// The map half of the RGBA entry for one width x height frame of which M pixels (0 < M < n) are opaque, from 8-bit pixels and a GIVEN
+// palette: compaction (with the offsets launch_alpha_count left at d_offsets), the opaque pixels' bytes into linear Rec2020 planes,
+// the masked walk over the frame's curve, and the expansion into the caller's elements and RGBA words.  pal: the k opaque rows in
+// linear Rec2020 (also in E.dpal); d_palw: rows RGBA words.  The caller has reserved E.rgba_cpos (n), E.rgba_rgb (3 n), E.cvt (3 n),
+// E.dmap (n elements of me bytes) and the masked dither's tables.  (run_rgba's own map stage stays inside run_device: it walks the
+// pipeline's working image, ICtCp -> Rec2020, and another conversion route would change its bits.)
+static void rgba_masked_frame(Engine &E, const unsigned char *d_px, size_t width, size_t height, int thr, size_t M, const unsigned *d_offsets,
+                              const std::vector<double> &pal, size_t k, unsigned off, const unsigned char *d_palw, size_t rows, int me, void *d_map,
+                              int map_elem, unsigned char *d_quant) {
+    const size_t n = width * height;
+    hipStream_t s = E.stream;
+    launch_alpha_compact(d_px, n, M, thr, d_offsets, nullptr, E.rgba_cpos.p, E.rgba_rgb.p, nullptr, s);
+    launch_convert_u8(PAMD_SRGB_TO_REC2020, E.rgba_rgb.p, 3, E.cvt.p, M, nullptr, s);
+    HIP_CHECK(hipStreamSynchronize(s));                               // (the dither launchers size their workspace before they enqueue)
+    launch_dither_masked(E.cvt.p, M, PAMD_COPY, width, height, E.rgba_cpos.p, M, E.dpal.p, pal.data(), (int)k, E.dmap.p, me, E.nn, s);
+    launch_rgba_expand(E.dmap.p, me, E.rgba_cpos.p, n, M, off, d_palw, (int)rows, d_map, map_elem, d_quant, s);
+}
+
+// pal: the k OPAQUE rows, planar (k,3) f64 sRGB; palw: one RGBA word per row of the palette as the maps number it (off + k rows: row 0
+// the transparent entry's (0, 0, 0, 0) when off == 1; the others (pal8, 255)).
+// `pixels`, `map_out`, `quant_out` are device pointers when `on_device`.
+// Nearest and ordered: run_remap's mappers over all N pixels with channels = 4 and the opaque rows, into E.dmap; then k_rgba_stamp, one
+// launch, writes the caller's elements and the RGBA words and raises the flag.  Riemersma: frame after frame -- every frame's opaque
+// count first (one wait for all of them), then per frame nothing (M == 0), run_remap's walk (M == n) or rgba_masked_frame.
+static void run_remap_rgba(Engine &E, size_t frames, size_t width, size_t height, const unsigned char *pixels, int thr, std::vector<double> pal, size_t k,
+                           const std::vector<unsigned> &palw, unsigned off, int mode, double spread, void *map_out, int map_elem_out,
+                           unsigned char *quant_out, bool on_device) {
+    const bool dither = mode == kRemapRiemersma, ordered = mode == kRemapOrdered;
+    const size_t n = width * height, N = frames * n, rows = off + k;
+    hipStream_t s = E.stream;
+    const double t_start = now_ms();
+    WsGuard wg(&E.stream, &E.stream2);
+    E.stats = patolette_amd__Stats{};
+    auto aligned = [](const void *p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; };
+    if (on_device && ((map_out && !aligned(map_out, (size_t)map_elem_out)) || (quant_out && !aligned(quant_out, 4))))
+        throw HipError("patolette_amd_remap_rgba_device: palette_map and quantized must be aligned to their element size");
+    const bool stage_px = !on_device || !aligned(pixels, 4);         // the kernels read one 32-bit word per pixel
+    const int me = map_elem_for(k);                                   // the mappers' elements: choices among the opaque rows
+    const bool want = map_out || quant_out;
+    const bool lanes = dither && dither_lane_layout(width, height, (int)k);
+    const bool two_pass = g_remap_two_pass.load(std::memory_order_relaxed) != 0;
+    const bool fused = ordered || (!two_pass && (dither ? lanes : nn_map_u8_applies(N, (int)k)));
+    const size_t tiles = compact_tiles(n);
+    // the workspace, before anything is enqueued
+    if (stage_px) E.src8.reserve(4 * N);
+    E.dpal.reserve(3 * k); E.h_pal.reserve(3 * k);
+    E.pal8.reserve(4 * rows);
+    E.rr_words.reserve(1 + frames); E.h_rr_words.reserve(1 + frames);
+    if (want) {
+        E.dmap.reserve((dither ? n : N) * (size_t)me);
+        if (!on_device && map_out) E.rgba_map.reserve(N * (size_t)map_elem_out);
+        if (!on_device && quant_out) E.quant8.reserve(4 * N);
+        if (dither) { E.cvt.reserve(3 * n); E.rgba_cpos.reserve(n); E.rgba_rgb.reserve(3 * n); dither_mask_reserve(E.nn, n); }
+        else if (!fused) { E.cvt.reserve(3 * N); E.cstats.reserve(1); E.h_cstats.reserve(1); }
+    }
+    if (dither) E.rgba_cnt.reserve(frames * tiles);
+    const unsigned char *d_px = pixels;
+    if (stage_px) {
+        HIP_CHECK(hipMemcpyAsync(E.src8.p, pixels, 4 * N, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        d_px = E.src8.p;
+    }
+    E.stats.ms_upload = now_ms() - t_start;
+    double t0 = now_ms();
+    palette_rows(pal, k, dither ? hm::color::srgb_to_rec2020 : hm::color::srgb_to_ictcp);   // as run_remap takes its palette
+    E.map_palette = pal;
+    void *d_map = map_out ? (on_device ? map_out : (void *)E.rgba_map.p) : nullptr;
+    unsigned char *d_q = quant_out ? (on_device ? quant_out : E.quant8.p) : nullptr;
+    unsigned *d_flag = E.rr_words.p, *h_words = E.h_rr_words.p;
+    HIP_CHECK(hipMemsetAsync(d_flag, 0, sizeof(unsigned), s));
+    HIP_CHECK(hipMemcpyAsync(E.pal8.p, palw.data(), 4 * rows, hipMemcpyHostToDevice, s));
+    const char *const kNoEntry = "patolette_amd_remap_rgba: a pixel is transparent (alpha < alpha_threshold) and the palette has no transparent entry "
+                                 "(transparent_index -1)";
+    if (!dither) {
+        if (want) {
+            upload_palette(E, pal, k);
+            if (ordered) {
+                launch_ordered_map(d_px, 4, frames, width, height, spread, E.dpal.p, (int)k, E.dmap.p, me, s);
+            } else if (fused) {
+                HIP_CHECK(hipStreamSynchronize(s));                                   // (the map kernels' tables are reserved on an idle stream)
+                launch_nn_map_u8(d_px, 4, N, E.dpal.p, (int)k, E.dmap.p, me, E.nn, s);
+            } else {
+                launch_convert_u8(PAMD_SRGB_TO_ICTCP, d_px, 4, E.cvt.p, N, E.cstats.p, s);
+                const Bounds b = read_bounds(E, false);                               // (waits, as in run_remap)
+                launch_nn_map(E.cvt.p, N, N, E.dpal.p, (int)k, E.dmap.p, me, b.lo, b.hi, E.nn, s);
+            }
+        }
+        launch_rgba_stamp(d_px, want ? E.dmap.p : nullptr, me, N, thr, off, E.pal8.p, rows, d_map, map_elem_out, d_q, d_flag, s);
+        HIP_CHECK(hipMemcpyAsync(h_words, d_flag, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    } else {
+        for (size_t f = 0; f < frames; f++)
+            launch_alpha_count(d_px + 4 * n * f, n, thr, E.rgba_cnt.p + f * tiles, E.rr_words.p + 1 + f, s);
+        HIP_CHECK(hipMemcpyAsync(h_words, E.rr_words.p, (1 + frames) * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));                           // every frame's opaque count, with one wait
+        if (off == 0) for (size_t f = 0; f < frames; f++) if (h_words[1 + f] < n) throw HipError(kNoEntry);
+        if (want) {
+            upload_palette(E, pal, k);
+            const size_t mb = (size_t)map_elem_out;
+            for (size_t f = 0; f < frames; f++) {
+                const size_t M = h_words[1 + f];
+                const unsigned char *px_f = d_px + 4 * n * f;
+                void *map_f = d_map ? (void *)((unsigned char *)d_map + n * f * mb) : nullptr;
+                unsigned char *q_f = d_q ? d_q + 4 * n * f : nullptr;
+                if (M == 0) {                                          // nothing to walk: element 0 and (0, 0, 0, 0) throughout
+                    if (map_f) HIP_CHECK(hipMemsetAsync(map_f, 0, n * mb, s));
+                    if (q_f) HIP_CHECK(hipMemsetAsync(q_f, 0, 4 * n, s));
+                } else if (M == n) {                                   // no transparent pixel: the plain walk of run_remap
+                    if (map_touched(true, width, height)) remap_dither(E, px_f, 4, 1, width, height, pal, k, E.dmap.p, me, fused, lanes);
+                    else HIP_CHECK(hipMemsetAsync(E.dmap.p, 0, n * (size_t)me, s));       // (a 1x1 dither writes nothing: entry 0)
+                    launch_rgba_expand(E.dmap.p, me, nullptr, n, n, off, E.pal8.p, (int)rows, map_f, map_elem_out, q_f, s);
+                } else {
+                    rgba_masked_frame(E, px_f, width, height, thr, M, E.rgba_cnt.p + f * tiles, pal, k, off, E.pal8.p, rows, me, map_f, map_elem_out,
+                                      q_f);
+                }
+                if (M > 0 && map_touched(true, width, height)) {      // the walks' counters, summed over the frames
+                    E.stats.dither_segments += E.nn.dither_segments; E.stats.dither_repairs += E.nn.dither_repairs;
+                    E.stats.dither_rounds += E.nn.dither_rounds; E.stats.dither_through += E.nn.dither_through;
+                    E.stats.dither_jumps += E.nn.dither_jumps; E.stats.dither_solo += E.nn.dither_solo;
+                }
+            }
+        }
+        h_words[0] = 0;
+    }
+    E.sync();                                                         // (palw is the caller's local: the copy must have left the host)
+    E.stats.ms_map = now_ms() - t0;
+    t0 = now_ms();
+    if (h_words[0] & 1) throw HipError(kNoEntry);
+    if (!on_device && map_out) HIP_CHECK(hipMemcpyAsync(map_out, d_map, N * (size_t)map_elem_out, hipMemcpyDeviceToHost, s));
+    if (!on_device && quant_out) HIP_CHECK(hipMemcpyAsync(quant_out, d_q, 4 * N, hipMemcpyDeviceToHost, s));
+    E.sync();
     E.stats.ms_download = now_ms() - t0;
     E.stats.ms_total = now_ms() - t_start;
 }
@@ -3343,6 +3492,40 @@ static void remap_entry(bool on_device, size_t frames, size_t width, size_t heig
     });
 }
 
+// RGBA pixels onto the caller's palette (include/patolette_amd.h): the arguments, then run_remap_rgba
+static void remap_rgba_entry(bool on_device, size_t frames, size_t width, size_t height, const unsigned char *pixels, int alpha_threshold,
+                             const double *palette, const unsigned char *palette_u8, size_t palette_rows, int transparent_index, int mode,
+                             double spread, void *palette_map, int map_elem_bytes, unsigned char *quantized, int *exit_code) {
+    const bool dither = mode == kRemapRiemersma;
+    const ArgCheck arg{"patolette_amd_remap_rgba", exit_code};
+    if (!arg.shape(frames, width, height, dither ? kDitherFramesMaxPixels : (size_t)40000 * 40000,
+                   dither ? "frames * width * height exceeds 2^31 pixels (the dither numbers pixels with 32 bits)"
+                          : "frames * width * height is too big")) return;
+    if (mode != kRemapNearest && mode != kRemapRiemersma && mode != kRemapOrdered) return (void)arg.fail(-1, "mode must be 0 (nearest), 1 (Riemersma) or 2 (ordered)");
+    if (alpha_threshold < 0 || alpha_threshold > 256) return (void)arg.fail(-1, "alpha_threshold must lie in [0, 256]");
+    if (transparent_index != -1 && transparent_index != 0) return (void)arg.fail(-1, "transparent_index must be -1 (none) or 0 (row 0)");
+    if ((palette != nullptr) == (palette_u8 != nullptr)) return (void)arg.fail(-1, "pass exactly one of palette and palette_u8");
+    if (!arg.rows(palette_rows, "the palette needs at least one row")) return;
+    if (validate_u8(palette_rows, 4, palette_map, map_elem_bytes) != 0)
+        return (void)arg.fail(-1, "bad map_elem_bytes (1, 2, 4 or 8, able to hold palette_rows - 1)");
+    if (!pixels) return (void)arg.fail(-1, "no pixels");
+    GivenPalette g;                                                        // with the bytes `quantized` is made of
+    if (!arg.palette(palette, palette_u8, palette_rows, true, g)) return;
+    const size_t off = transparent_index == 0 ? 1 : 0;
+    if (g.k <= off) return (void)arg.fail(-1, "no opaque palette row remains beside the transparent entry");
+    if (mode == kRemapOrdered && !(std::isfinite(spread) && spread >= 0.0)) return (void)arg.fail(-1, "spread must be finite and not negative");
+    // the opaque rows, and every used row's RGBA word
+    const size_t k = g.k - off;
+    std::vector<double> pal(3 * k);
+    for (int c = 0; c < 3; c++) for (size_t i = 0; i < k; i++) pal[(size_t)c * k + i] = g.pal[(size_t)c * g.k + off + i];
+    std::vector<unsigned> palw(g.k, 0u);
+    for (size_t i = off; i < g.k; i++) palw[i] = (unsigned)g.p8[3 * i] | (unsigned)g.p8[3 * i + 1] << 8 | (unsigned)g.p8[3 * i + 2] << 16 | 0xFF000000u;
+    *exit_code = guarded([&](Engine &E) {
+        run_remap_rgba(E, frames, width, height, pixels, alpha_threshold, std::move(pal), k, palw, (unsigned)off, mode, spread, palette_map,
+                       map_elem_bytes, quantized, on_device);
+    });
+}
+
 // an animation's maps made deltas (include/patolette_amd.h): the arguments, then run_frame_deltas
 static void frame_deltas_entry(bool on_device, size_t frames, size_t width, size_t height, const void *palette_maps, int map_elem_bytes,
                                size_t palette_rows, size_t transparent_index, const unsigned char *pixels, int channels, const double *palette,
@@ -3453,6 +3636,23 @@ void patolette_amd_remap_ordered_u8_device(size_t frames, size_t width, size_t h
 }
 
 int patolette_amd_debug_remap_two_pass(int on) { return g_remap_two_pass.exchange(on ? 1 : 0); }
+
+void patolette_amd_remap_rgba_u8(size_t frames, size_t width, size_t height, const unsigned char *pixels, int alpha_threshold,
+                                 const double *palette, const unsigned char *palette_u8, size_t palette_rows, int transparent_index, int mode,
+                                 double spread, void *palette_map, int map_elem_bytes, unsigned char *quantized, int *exit_code) {
+    remap_rgba_entry(false, frames, width, height, pixels, alpha_threshold, palette, palette_u8, palette_rows, transparent_index, mode, spread,
+                     palette_map, map_elem_bytes, quantized, exit_code);
+}
+
+void patolette_amd_remap_rgba_u8_device(size_t frames, size_t width, size_t height, const unsigned char *d_pixels, int alpha_threshold,
+                                        const double *palette, const unsigned char *palette_u8, size_t palette_rows, int transparent_index,
+                                        int mode, double spread, void *d_palette_map, int map_elem_bytes, unsigned char *d_quantized,
+                                        int *exit_code) {
+    remap_rgba_entry(true, frames, width, height, d_pixels, alpha_threshold, palette, palette_u8, palette_rows, transparent_index, mode, spread,
+                     d_palette_map, map_elem_bytes, d_quantized, exit_code);
+}
+
+int patolette_amd_debug_rgba_stamp_quad(int mode) { return rgba_stamp_debug_quad(mode); }
 
 int patolette_amd_debug_delta_quad(int mode) { return delta_debug_quad(mode); }
 
