@@ -330,6 +330,56 @@ void patolette_amd_measure_device(size_t frames, size_t width, size_t height, co
                                   uint64_t *entry_sse, uint32_t *entry_max_se, uint64_t *frame_count, uint64_t *frame_sse,
                                   uint32_t *frame_max_se, double *frame_d_sum, double *frame_d_max, int *exit_code);
 
+/* ---- gif_lzw: index maps LZW-compressed as a GIF's image data, on the device ------------------
+ * The last step of the animation pipeline: the GIF flavour of LZW over every frame's map (or over its dirty rectangle), so that what
+ * leaves the GPU is the compressed stream and not the map.  A GIF decoder forgets its dictionary at every Clear code, so a frame's
+ * symbols are cut into segments that are compressed independently, each ending in a Clear, and the segments' bit strings are put end
+ * to end: any decoder reads the result as one stream.
+ *   maps: frames x width x height elements of ONE byte (a GIF palette has at most 256 entries), frame after frame, as every
+ *       *_frames_u8 / remap / frame_deltas entry writes 1-byte maps.  Host memory; the *_device flavour takes a device pointer.
+ *   rects: host memory, int32[4 * frames], rows (x0, y0, w, h) as patolette_amd_frame_deltas writes them, or NULL for the full frame
+ *       every time.  Every rectangle must lie inside the frame and have w, h >= 1 (an empty one -- frame_deltas' (0, 0, 0, 0) -- is
+ *       a -1: pass (0, 0, 1, 1), whose one delta is the transparent index).  Elements outside the rectangles are not read by the kernels.
+ *   min_code_size m, in [2, 8]: every element inside a rectangle must be below 2^m.
+ *   segment: symbols per segment; 0 takes the default 8192, otherwise it must lie in [1, 2^24].  Segments cost size (the dictionary
+ *       starts again at each) and buy parallelism: one chain per segment.
+ * Outputs, host memory in both flavours: out, with `capacity` bytes; offsets, uint64[frames + 1].  Frame f's stream is
+ *   out[offsets[f] : offsets[f + 1]]; the streams lie back to back and each starts on a byte.  A stream is the raw LZW byte stream,
+ *   NOT yet cut into the container's 255-byte sub-blocks.
+ *
+ * Per frame: the elements of its rectangle in row-scan order, q -> (y0 + q / w, x0 + q % w), are a sequence of area = w * h symbols,
+ * cut into nseg = ceil(area / segment) segments of `segment` symbols, the last one shorter.  clear = 2^m, eoi = clear + 1; codes are
+ * packed least-significant bit first.
+ *   - The stream opens with `clear` at width m + 1.
+ *   - Every segment starts from an empty dictionary with free = eoi + 1 and width = m + 1 and runs the classic greedy LZW over its
+ *     symbols, the first symbol being the first prefix.  For every further symbol `byte`: if (prefix, byte) is in the dictionary, its
+ *     code becomes the prefix.  On a miss: emit prefix at width; then, if free < 4096, enter the pair as code `free`, increment width
+ *     if free == 2^width and width < 12, then increment free; otherwise (the dictionary is full) emit clear at width and reset the
+ *     dictionary, free and width.  Either way `byte` becomes the new prefix.
+ *   - At the segment's end: emit the pending prefix at width; then, if free < 4096, free == 2^width and width < 12, increment width
+ *     (the decoder makes an entry on that code too); then emit the closing code at width: clear for every segment but the last,
+ *     eoi for the last.
+ *   - The last byte is padded with zero bits.
+ *   tests/lzw_ref.py states the same in Python; the device's bytes equal its bytes.
+ * The flag: an element >= 2^m inside a rectangle is never used as a dictionary key; the kernel raises a flag and the call fails with
+ *   -1 and a "patolette_amd_gif_lzw:" text (what `out` then holds is not defined).
+ * Capacity: a frame emits at most area + 2 * nseg + area / 3000 + 2 codes of at most 12 bits, so
+ *   sum over the frames of ceil(12 * (area + 2 * nseg + area / 3000 + 2) / 8) bytes always suffice.  If `capacity` is smaller than the
+ *   streams, the call fails with -1, offsets (all of them; offsets[frames] = the bytes needed) are written and nothing is copied to out.
+ * Exit codes: 0; -2 frames == 0 or an empty image; -4 beyond the pixel cap of patolette_amd_remap_u8(dither == 0); -1 (with a
+ *   "patolette_amd_gif_lzw:" text in patolette_amd_last_error) for no maps, no offsets, no out with a capacity, min_code_size or
+ *   segment out of range, a rectangle that is empty or not inside the frame, the flag, or the capacity.  A
+ *   failed call leaves the thread's engine usable.
+ * Statistics: the ms_* fields as for a remap (ms_map: the kernels and the offsets), every other field 0.
+ * Three kernels, one launch each for all frames, integers only: k_lzw_segments (a wavefront per segment, its dictionary a hash table in
+ *   LDS), k_lzw_offsets (the segments' and frames' places), k_lzw_pack (the segments' bits shifted together).
+ * Out of scope: the container (Python: write_gif), interlaced images, local colour tables. */
+void patolette_amd_gif_lzw(size_t frames, size_t width, size_t height, const unsigned char *maps, const int32_t *rects,
+                           int min_code_size, size_t segment, unsigned char *out, size_t capacity, uint64_t *offsets, int *exit_code);
+void patolette_amd_gif_lzw_device(size_t frames, size_t width, size_t height, const unsigned char *d_maps, const int32_t *rects,
+                                  int min_code_size, size_t segment, unsigned char *out, size_t capacity, uint64_t *offsets,
+                                  int *exit_code);
+
 /* ---- RGBA images: a transparent palette slot, an alpha-aware dither ---------------------------
  * pixels: width*height interleaved 8-bit RGBA.  Pixel i is TRANSPARENT iff alpha_i < alpha_threshold (an integer in [0, 256]);
  * every other pixel is OPAQUE.  M = number of opaque pixels, N = width*height.

@@ -20,7 +20,8 @@ pixel count, the squared error in code values and its maximum, per frame also th
 and `frame_deltas`' tolerance is stated in -- with `psnr` to read it in decibels;
 and, for animations with transparency, `remap_rgba` (RGBA images or frames onto a given palette whose row 0 may be a transparent
 entry) and `quantize_rgba_frames` (one shared palette and one transparent index for all frames, composed from `quantize_rgba`'s
-palette stage and `remap_rgba`).
+palette stage and `remap_rgba`);
+and `gif_lzw`, which LZW-compresses maps or deltas on the device, with `write_gif`, the GIF89a container around it.
 """
 import ctypes as C
 
@@ -470,6 +471,7 @@ def frame_deltas(maps, palette, transparent_index=None, frames=None, tolerance=0
         always with the current source, so no error accumulates.
       * want_shown: also return what the canvas shows after every frame (== maps when tolerance is 0).
     Frame 0 is the full first map.  Compositing the deltas (overwrite where delta != transparent_index) gives back `shown`.
+    `write_gif(file, deltas, palette, rects, transparent_index=...)` writes them as a GIF.
     Maps that carry a transparent entry of their own (`remap_rgba`, `quantize_rgba_frames`) work with the exact mode -- their index 0
     compares like any row -- and with `measure(..., skip_index=0)`; the lossy mode on them stays out of scope.
 
@@ -603,6 +605,153 @@ def psnr(stats):
         out = 10.0 * np.log10(3.0 * 255.0 * 255.0 * count / sse)
     out = np.where(count == 0, np.nan, np.where(sse == 0, np.inf, out))
     return out if out.ndim else float(out)
+
+
+def _gif_rects(rects, count, height, width):
+    """`rects` as (count, 4) int32 rows (x0, y0, w, h) inside the frame; None: the full frame every time; an empty one, as
+    `frame_deltas` reports an unchanged frame, becomes (0, 0, 1, 1)."""
+    if rects is None:
+        return np.tile(np.array([0, 0, width, height], dtype=np.int32), (count, 1))
+    r = np.asarray(rects)
+    if r.shape != (count, 4) or r.dtype.kind not in "iu":
+        raise ValueError("rects must be None or (F, 4) integer rows (x0, y0, w, h), one per frame")
+    r = r.astype(np.int64)
+    r[(r[:, 2] == 0) & (r[:, 3] == 0)] = (0, 0, 1, 1)
+    if width > 0 and height > 0 and count > 0:
+        if np.any(r[:, :2] < 0) or np.any(r[:, 2:] < 1) or np.any(r[:, 0] + r[:, 2] > width) or np.any(r[:, 1] + r[:, 3] > height):
+            raise ValueError("every rectangle must lie inside the frame and have w, h >= 1 (or be the empty (0, 0, 0, 0))")
+    return np.ascontiguousarray(r.astype(np.int32))
+
+
+def _gif_maps(maps):
+    """`maps` as contiguous (F, H, W) one-byte maps -> (maps, shape, torch device or None)."""
+    if not hasattr(maps, "shape") or len(maps.shape) not in (2, 3):
+        raise ValueError("maps must be an (H, W) or (F, H, W) uint8 array or a uint8 CUDA tensor")
+    m, shape, dev, elem, _ = _delta_maps(maps if len(maps.shape) == 3 else maps[None])
+    if elem != 1:
+        raise ValueError("maps must be uint8: a GIF palette has at most 256 entries")
+    return m, shape, dev
+
+
+def _gif_segment(segment):
+    if segment is None:
+        return 0
+    if isinstance(segment, (bool, np.bool_)) or not isinstance(segment, (int, np.integer)) or not 1 <= int(segment) <= 2 ** 24:
+        raise ValueError("segment must be None (the default, 8192) or an integer in [1, 2^24]")
+    return int(segment)
+
+
+def gif_lzw_bound(rects, segment=None):
+    """Bytes that always hold the streams of `gif_lzw` for these (F, 4) rectangles: 12 bits for each of at most
+    area + 2 * nseg + area / 3000 + 2 codes per frame (include/patolette_amd.h)."""
+    seg = _gif_segment(segment) or 8192
+    area = np.asarray(rects)[:, 2].astype(np.int64) * np.asarray(rects)[:, 3].astype(np.int64)
+    nseg = (area + seg - 1) // seg
+    return int(np.sum((12 * (area + 2 * nseg + area // 3000 + 2) + 7) // 8))
+
+
+def gif_lzw(maps, rects=None, min_code_size=8, segment=None):
+    """Index maps LZW-compressed as a GIF's image data, on the device (additive; include/patolette_amd.h: patolette_amd_gif_lzw).
+
+      * maps: (F, H, W) or (H, W) uint8 numpy array, or a torch uint8 CUDA tensor (the maps then never leave the GPU; only the
+        compressed streams do).  Maps, deltas and shown maps of the other entries all qualify.
+      * rects: None, or (F, 4) rows (x0, y0, w, h) as `frame_deltas` returns them: only the rectangle is compressed.  An empty
+        rectangle (an unchanged frame) is replaced by (0, 0, 1, 1): its one delta is the transparent index by definition, so a
+        decoder keeps the canvas.
+      * min_code_size: 2 .. 8; every element inside a rectangle must be below 2 ** min_code_size (else a ValueError).
+      * segment: symbols per independently compressed segment (default 8192): smaller is more parallel and a little larger.
+
+    Returns (success, data uint8 numpy array, offsets (F + 1,) int64, message): frame f's raw LZW stream -- not yet cut into
+    sub-blocks -- is data[offsets[f]:offsets[f + 1]].  The result is always numpy.  `write_gif` wraps it in the container."""
+    m, shape, dev = _gif_maps(maps)
+    count, height, width = shape
+    if isinstance(min_code_size, (bool, np.bool_)) or not isinstance(min_code_size, (int, np.integer)) or not 2 <= int(min_code_size) <= 8:
+        raise ValueError("min_code_size must be an integer in [2, 8]")
+    seg = _gif_segment(segment)
+    r = _gif_rects(rects, count, height, width)
+    out = np.empty(gif_lzw_bound(r, segment), dtype=np.uint8)
+    offsets = np.zeros(count + 1, dtype=np.uint64)
+    code = C.c_int(0)
+    _call("patolette_amd_gif_lzw", dev, count, width, height, _vp(m), r.ctypes.data_as(C.POINTER(C.c_int32)) if count else None,
+          int(min_code_size), seg, out.ctypes.data_as(C.c_void_p), out.size, offsets.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(code))
+    if code.value == -1 and _native.last_error().startswith("patolette_amd_gif_lzw:"):
+        raise ValueError(_native.last_error())
+    message = _message(code.value)
+    if code.value != 0:
+        return (False, None, None, message)
+    return (True, out[:int(offsets[count])], offsets.astype(np.int64), message)
+
+
+def write_gif(file, maps, palette_u8, rects=None, transparent_index=None, delay=0.04, loop=0, disposal=1, segment=None):
+    """Write an animation's maps as a GIF89a file: a small pure-Python container around `gif_lzw`, so that
+    `quantize_frames(frames, 255, dither="ordered")` -> `frame_deltas` -> `write_gif` yields a file any viewer opens.
+
+      * file: a path, an object with `write`, or None.  The bytes are always returned.
+      * maps: (F, H, W) or (H, W) uint8 maps or deltas (numpy, or a torch CUDA tensor); rects: as `gif_lzw` takes them.
+      * palette_u8: (K, 3) uint8, K <= 256: the global colour table, padded with zero rows to the next power of two that holds every
+        row and, if given, transparent_index (<= 255).  That power of two is 2 ** min_code_size (at least 4).
+      * delay: seconds per frame, a number or one per frame (written in 1/100 s); loop: the NETSCAPE2.0 repeat count (0 = for ever),
+        None for no loop block; disposal: every frame's disposal method (1: leave in place, what `frame_deltas`' deltas need).
+    Out of scope: local colour tables, interlace, APNG, and any decision about disposal for RGBA maps beyond the one `disposal` the
+    caller passes."""
+    import os
+    m, shape, dev = _gif_maps(maps)
+    count, height, width = shape
+    pal = np.asarray(palette_u8.detach().cpu().numpy() if hasattr(palette_u8, "detach") else palette_u8)
+    if pal.ndim != 2 or pal.shape[1] != 3 or pal.dtype != np.uint8 or pal.shape[0] < 1:
+        raise ValueError("palette_u8 must be a (K, 3) uint8 array")
+    if pal.shape[0] > 256:
+        raise ValueError("a GIF colour table holds at most 256 rows")
+    need = pal.shape[0]
+    if transparent_index is not None:
+        if isinstance(transparent_index, (bool, np.bool_)) or not isinstance(transparent_index, (int, np.integer)) \
+                or not 0 <= int(transparent_index) <= 255:
+            raise ValueError("transparent_index must be None or an index in [0, 255]")
+        need = max(need, int(transparent_index) + 1)
+    bits = max(1, int(need - 1).bit_length())                      # the table has 2 ** bits rows
+    mcs = max(2, bits)
+    if count < 1 or not 1 <= width <= 65535 or not 1 <= height <= 65535:
+        raise ValueError("a GIF needs at least one frame, of 1 .. 65535 pixels a side")
+    r = _gif_rects(rects, count, height, width)
+    delays = np.asarray(delay, dtype=np.float64)
+    if delays.ndim == 0:
+        delays = np.full(count, float(delays))
+    if delays.shape != (count,) or not np.all(np.isfinite(delays)) or np.any(delays < 0) or np.any(np.round(delays * 100) > 65535):
+        raise ValueError("delay must be a number of seconds or one per frame, each in [0, 655.35]")
+    if loop is not None and (isinstance(loop, (bool, np.bool_)) or not isinstance(loop, (int, np.integer)) or not 0 <= int(loop) <= 65535):
+        raise ValueError("loop must be None or a repeat count in [0, 65535]")
+    if isinstance(disposal, (bool, np.bool_)) or not isinstance(disposal, (int, np.integer)) or not 0 <= int(disposal) <= 3:
+        raise ValueError("disposal must be 0, 1, 2 or 3")
+    _gif_segment(segment)
+    ok, data, offsets, message = gif_lzw(m, r, mcs, segment)
+    if not ok:
+        raise RuntimeError(message)
+    table = np.zeros((1 << bits, 3), dtype=np.uint8)
+    table[:pal.shape[0]] = pal
+    u16 = lambda v: int(v).to_bytes(2, "little")
+    parts = [b"GIF89a", u16(width), u16(height), bytes([0x80 | 7 << 4 | (bits - 1), 0, 0]), table.tobytes()]
+    if loop is not None:
+        parts += [b"\x21\xff\x0bNETSCAPE2.0\x03\x01", u16(loop), b"\x00"]
+    flag, tidx = (1, int(transparent_index)) if transparent_index is not None else (0, 0)
+    raw = data.tobytes()
+    for f in range(count):
+        parts += [b"\x21\xf9\x04", bytes([int(disposal) << 2 | flag]), u16(int(np.round(delays[f] * 100))), bytes([tidx, 0])]
+        x0, y0, w, h = (int(v) for v in r[f])
+        parts += [b"\x2c", u16(x0), u16(y0), u16(w), u16(h), b"\x00", bytes([mcs])]
+        stream = raw[int(offsets[f]):int(offsets[f + 1])]
+        for i in range(0, len(stream), 255):
+            block = stream[i:i + 255]
+            parts += [bytes([len(block)]), block]
+        parts.append(b"\x00")
+    parts.append(b"\x3b")
+    blob = b"".join(parts)
+    if file is not None:
+        if hasattr(file, "write"):
+            file.write(blob)
+        else:
+            with open(os.fspath(file), "wb") as fh:
+                fh.write(blob)
+    return blob
 
 
 def quantize_rgba(image, palette_size, alpha_threshold=128, dither=True, palette_only=False, color_space=ColorSpace_ICtCp,
@@ -890,6 +1039,9 @@ __all__ = [
     "frame_deltas",
     "measure",
     "psnr",
+    "gif_lzw",
+    "gif_lzw_bound",
+    "write_gif",
     "saliency_weights",
     "ColorSpace_sRGB",
     "ColorSpace_CIELuv",

@@ -25,6 +25,7 @@
 #include "ordered.h"
 #include "delta.h"
 #include "measure.h"
+#include "lzw.h"
 #include "saliency.h"
 #include "quant.h"
 #include "rgba.h"
@@ -984,6 +985,9 @@ struct Engine {
     DevBuf<unsigned long long> ms_words;         // measure: the entries' slots, the flag and the folded results (measure.h)
     DevBuf<MeasureTile> ms_tiles;                // ... the tiles' records between its two kernels
     DevBuf<unsigned> ms_p8;                      // ... the palette's bytes, a word per row
+    DevBuf<LzwFrame> lz_frames;                  // gif_lzw: the frames' rectangles and first segments (lzw.h)
+    DevBuf<unsigned> lz_stage, lz_bits, lz_out;  // ... the segments' staging areas and bit lengths; the packed streams
+    DevBuf<unsigned long long> lz_gbit, lz_words;   // ... every segment's first bit in the output; the flag and the frames' offsets
     // the RGBA entry (run_rgba): tile counts / offsets + the opaque count, each pixel's compact number, the opaque pixels' RGB and
     // weights, the full index map on its way to the host, the count's pinned landing place
     DevBuf<unsigned> rgba_cnt;
@@ -3068,6 +3072,54 @@ static void run_measure(Engine &E, bool on_device, size_t frames, size_t width, 
     E.stats.ms_total = now_ms() - t_start;
 }
 
+// --------------------------------------------------------------------------------------------
+// gif_lzw: index maps LZW-compressed as a GIF's image data (include/patolette_amd.h, patolette_amd_gif_lzw)
+// --------------------------------------------------------------------------------------------
+// maps: frames x width x height one-byte elements, a device pointer when `on_device`; recs: the frames' rectangles with their first
+// segments, frames + 1 records (lzw.h); seg: a segment's pixels; cap: the largest rectangle's area.  out, offsets: host memory.
+static void run_gif_lzw(Engine &E, bool on_device, size_t frames, size_t width, size_t height, const unsigned char *maps,
+                        const std::vector<LzwFrame> &recs, size_t seg, size_t cap, size_t bound, int m, unsigned char *out, size_t capacity,
+                        uint64_t *offsets) {
+    const size_t n = width * height, N = frames * n, S = recs[frames].seg0;
+    hipStream_t s = E.stream;
+    const double t_start = now_ms();
+    WsGuard wg(&E.stream, &E.stream2);
+    E.stats = patolette_amd__Stats{};
+    // the workspace, before anything is enqueued
+    const size_t stride = lzw_stage_words(std::min(seg, cap)), words = lzw_words(frames), out_words = bound / 4 + 1;
+    E.lz_frames.reserve(frames + 1);
+    E.lz_stage.reserve(S * stride);
+    E.lz_bits.reserve(S);
+    E.lz_gbit.reserve(S + 1);
+    E.lz_words.reserve(words);
+    E.lz_out.reserve(out_words);
+    const unsigned char *d_maps = maps;
+    if (!on_device) {
+        std::vector<unsigned> none;
+        stage_given(E, maps, 1, 1, N, GivenSkip{}, 0, nullptr, 0, none);
+        d_maps = E.dl_maps.p;
+    }
+    E.stats.ms_upload = now_ms() - t_start;
+    double t0 = now_ms();
+    HIP_CHECK(hipMemcpyAsync(E.lz_frames.p, recs.data(), (frames + 1) * sizeof(LzwFrame), hipMemcpyHostToDevice, s));
+    launch_lzw(d_maps, frames, n, width, E.lz_frames.p, S, seg, stride, m, E.lz_stage.p, E.lz_bits.p, E.lz_gbit.p, E.lz_words.p, E.lz_out.p,
+               out_words, s);
+    std::vector<unsigned long long> w(words);
+    HIP_CHECK(hipMemcpyAsync(w.data(), E.lz_words.p, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    E.sync();
+    E.stats.ms_map = now_ms() - t0;
+    t0 = now_ms();
+    if (w[0] & 1) throw HipError("patolette_amd_gif_lzw: a map element inside a rectangle is not below 2^min_code_size");
+    for (size_t f = 0; f <= frames; f++) offsets[f] = w[1 + f];
+    const size_t total = (size_t)w[1 + frames];
+    if (total > bound) throw HipError("patolette_amd_gif_lzw: the streams exceed the stated bound (internal error)");
+    if (total > capacity)
+        throw HipError("patolette_amd_gif_lzw: capacity is too small: offsets[frames] holds the bytes needed, nothing was copied");
+    HIP_CHECK(hipMemcpy(out, E.lz_out.p, total, hipMemcpyDeviceToHost));
+    E.stats.ms_download = now_ms() - t0;
+    E.stats.ms_total = now_ms() - t_start;
+}
+
 // The RGBA entry (include/patolette_amd.h, patolette_amd_rgba): the opaque pixels (alpha >= thr) are compacted in row-scan order and
 // the path runs on them as an M x 1 image with one palette row less (row 0 is the transparent entry); the dither walks the full image's
 // curve over them (DitherMask).  Every pixel opaque: the path runs on the image itself with the full palette, exactly as run_u8 does.
@@ -3577,6 +3629,37 @@ static void measure_entry(bool on_device, size_t frames, size_t width, size_t he
     });
 }
 
+// index maps LZW-compressed (include/patolette_amd.h): the arguments, then run_gif_lzw
+static void gif_lzw_entry(bool on_device, size_t frames, size_t width, size_t height, const unsigned char *maps, const int32_t *rects,
+                          int min_code_size, size_t segment, unsigned char *out, size_t capacity, uint64_t *offsets, int *exit_code) {
+    const ArgCheck arg{"patolette_amd_gif_lzw", exit_code};
+    if (!arg.shape(frames, width, height, (size_t)40000 * 40000, "frames * width * height is too big")) return;   // the nearest remap's cap
+    if (!maps) return (void)arg.fail(-1, "no maps");
+    if (!offsets) return (void)arg.fail(-1, "no offsets");
+    if (!out && capacity > 0) return (void)arg.fail(-1, "no out");
+    if (min_code_size < 2 || min_code_size > 8) return (void)arg.fail(-1, "min_code_size must lie in [2, 8]");
+    if (segment > kLzwSegmentMax) return (void)arg.fail(-1, "segment must be 0 (the default) or lie in [1, 2^24]");
+    const size_t seg = segment ? segment : kLzwSegment;
+    std::vector<LzwFrame> recs;
+    try { recs.resize(frames + 1); } catch (const std::bad_alloc &) { return (void)arg.fail(-1, "no memory for the frames' table"); }
+    size_t S = 0, cap = 0, bound = 0;                                      // (S <= frames * width * height <= 1.6e9: 31 bits)
+    for (size_t f = 0; f < frames; f++) {
+        long long x0 = 0, y0 = 0, w = (long long)width, h = (long long)height;
+        if (rects) { x0 = rects[4 * f]; y0 = rects[4 * f + 1]; w = rects[4 * f + 2]; h = rects[4 * f + 3]; }
+        if (x0 < 0 || y0 < 0 || w < 1 || h < 1 || x0 + w > (long long)width || y0 + h > (long long)height)
+            return (void)arg.fail(-1, "every rectangle must lie inside the frame and have w, h >= 1");
+        const size_t area = (size_t)w * (size_t)h, nseg = ceil_div(area, seg);
+        recs[f] = LzwFrame{(unsigned)x0, (unsigned)y0, (unsigned)w, (unsigned)area, (unsigned)S};
+        S += nseg;
+        cap = std::max(cap, area);
+        bound += lzw_frame_bound(area, nseg);
+    }
+    recs[frames] = LzwFrame{0, 0, 0, 0, (unsigned)S};
+    *exit_code = guarded([&](Engine &E) {
+        run_gif_lzw(E, on_device, frames, width, height, maps, recs, seg, cap, bound, min_code_size, out, capacity, offsets);
+    });
+}
+
 static void rgba_entry(bool on_device, size_t width, size_t height, const unsigned char *pixels, int alpha_threshold, const double *weights,
                        double tile_size, size_t palette_size, const patolette__QuantizationOptions *options, double *palette,
                        unsigned char *palette_rgba, void *palette_map, int map_elem_bytes, unsigned char *quantized, int *transparent_index,
@@ -3687,6 +3770,16 @@ void patolette_amd_measure_device(size_t frames, size_t width, size_t height, co
                                   int *exit_code) {
     measure_entry(true, frames, width, height, d_pixels, channels, d_palette_maps, map_elem_bytes, palette, palette_u8, palette_rows, skip_index,
                   MeasureOut{entry_count, entry_sse, entry_max_se, frame_count, frame_sse, frame_max_se, frame_d_sum, frame_d_max}, exit_code);
+}
+
+void patolette_amd_gif_lzw(size_t frames, size_t width, size_t height, const unsigned char *maps, const int32_t *rects, int min_code_size,
+                           size_t segment, unsigned char *out, size_t capacity, uint64_t *offsets, int *exit_code) {
+    gif_lzw_entry(false, frames, width, height, maps, rects, min_code_size, segment, out, capacity, offsets, exit_code);
+}
+
+void patolette_amd_gif_lzw_device(size_t frames, size_t width, size_t height, const unsigned char *d_maps, const int32_t *rects, int min_code_size,
+                                  size_t segment, unsigned char *out, size_t capacity, uint64_t *offsets, int *exit_code) {
+    gif_lzw_entry(true, frames, width, height, d_maps, rects, min_code_size, segment, out, capacity, offsets, exit_code);
 }
 
 void patolette_amd_frames_u8(size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels, const double *weights,
