@@ -259,8 +259,9 @@ void patolette_amd_remap_ordered_u8_device(size_t frames, size_t width, size_t h
  * T not representable, a tolerance that is negative or not finite, missing pixels or both or neither palette in the lossy mode, a
  * palette value that is not finite, or the flag above.  A failed call leaves the thread's engine usable.
  * Statistics: the ms_* fields as for a remap (ms_map: the kernel and its results), every other field 0.
- * Out of scope: maps that already carry a transparent entry (those of patolette_amd_rgba and patolette_amd_remap_rgba_u8): their index 0
- * is compared like any other row, which is all the exact mode needs; the lossy mode on them stays out of scope.
+ * Maps that already carry a transparent entry (those of patolette_amd_rgba and patolette_amd_remap_rgba_u8): here their index 0 is
+ * compared like any other row; patolette_amd_frame_deltas_rgba below is the entry for them -- 0 as the deltas' transparent index,
+ * per-frame disposal, and the lossy mode.
  * One kernel for all frames (k_frame_deltas): a lane owns a position, walks the frames and keeps the canvas entry in a register. */
 void patolette_amd_frame_deltas(size_t frames, size_t width, size_t height, const void *palette_maps, int map_elem_bytes,
                                 size_t palette_rows, size_t transparent_index, const unsigned char *pixels, int channels,
@@ -271,7 +272,69 @@ void patolette_amd_frame_deltas_device(size_t frames, size_t width, size_t heigh
                                        const double *palette, const unsigned char *palette_u8, double tolerance, void *d_delta_maps,
                                        void *d_shown_maps, int32_t *rects, uint64_t *changed, int *exit_code);
 
-/* TESTS ONLY: k_frame_deltas gives a lane four consecutive positions (one 4- or 16-byte access) where width * height is a multiple of
+/* ---- frame deltas of RGBA maps: index 0 is the transparent entry, per-frame disposal -----------
+ * The same step for the maps of patolette_amd_rgba / patolette_amd_remap_rgba_u8 with a transparent entry: index 0 means "this pixel
+ * is transparent", indices 1 .. palette_rows-1 are opaque rows.  A GIF frame has one transparent index, and in a delta it has to mean
+ * "leave the canvas as it is" -- which is what a decoder does with it under disposal 1 -- so here 0 in a delta means exactly that, and
+ * no free index is needed (a one-byte map may use all 256 rows).  What a delta drawn over the canvas cannot express is a pixel that
+ * turns from opaque to transparent: the frame BEFORE must be disposed to background (disposal 2) over a rectangle that covers the
+ * pixel, and whatever was unchanged inside that rectangle is drawn again.
+ *   frames, width, height, palette_maps, map_elem_bytes, palette_rows, pixels, channels, tolerance, the outputs' element sizes and the
+ *       host / device flavours: as patolette_amd_frame_deltas takes them.  m[f][p]: the maps.
+ *   palette, palette_u8: read in the lossy mode only, exactly one of them, in the forms patolette_amd_remap_rgba_u8 takes (trailing
+ *       (-1, -1, -1) rows of the f64 one dropped).  Row 0's colour is never read, whatever it holds.
+ *   loop: 1 when the animation repeats (frame 0 follows the last frame), 0 when it is shown once.
+ *
+ * Frame after frame; the canvas c starts as all 0.
+ *   next(f) = f + 1; for the last frame 0 with loop, none without.
+ *   V[f] = the tight box of the positions with m[f][p] != 0 && m[next(f)][p] == 0; empty without a next frame.  From the maps alone.
+ *   disposals[f] = 2 if V[f] is not empty, otherwise 1.
+ *   every position p on its own, with a = m[f][p]:
+ *     a == 0: delta[f][p] = 0 (the canvas entry is 0 there already).
+ *     a != 0: keep = c[p] != 0 && (a == c[p] || (tolerance > 0 && D <= tolerance * tolerance))
+ *             D: exactly the D of patolette_amd_frame_deltas -- the source pixel pixels[f][p] against palette row c[p], through
+ *             sRGB -> ICtCp, (d0*d0 + d1*d1) + d2*d2 in f64, no FMA; evaluated only where c[p] != 0 && a != c[p].
+ *             keep: delta[f][p] = 0.     otherwise: delta[f][p] = a, c[p] = a.
+ *     shown[f][p] = c[p].
+ *   C[f] = the tight box of delta[f] != 0; changed[f] = their number.
+ *   rects[f] = (x0, y0, w, h) of the smallest box holding C[f] and V[f]; (0, 0, 0, 0) when both are empty.
+ *   then, if disposals[f] == 2: c[p] = 0 for every p inside rects[f].
+ * Consequences:
+ *   - shown[f] != 0 exactly where m[f] != 0: transparency is never lossy.
+ *   - tolerance == 0: shown == the input maps.
+ *   - A viewer that draws delta[f] inside rects[f] wherever it is not 0, then clears rects[f] where disposals[f] == 2, shows shown[f].
+ *   - With loop the same holds on every later pass, whether or not the player resets the canvas at the restart: frame 0's deltas
+ *     are all of its opaque positions, and V of the last frame clears what frame 0 shows as transparent.
+ *   - An empty rectangle only occurs with disposal 1.  A frame whose deltas are all 0 can still have a rectangle (its V).
+ *   - Maps without any 0 (fully opaque): every disposal is 1, and from frame 1 on deltas, shown, rects and changed are those of
+ *     patolette_amd_frame_deltas with T read as 0.
+ * Outputs, each may be NULL: delta_maps, shown_maps (frames x n elements of map_elem_bytes; delta_maps may be palette_maps itself);
+ *   rects (int32[4 * frames]); disposals (int32[frames], each 1 or 2); changed (uint64[frames]).  The *_device flavour takes device
+ *   pointers for palette_maps, pixels, delta_maps and shown_maps; rects, disposals, changed and both palettes stay host memory.
+ * Every element must be below palette_rows and must not name a dropped row: an element that does is never used as a palette
+ *   address, the kernel raises a flag, and the call fails with -1 and a "patolette_amd_frame_deltas_rgba:" text (both modes; what the
+ *   outputs then hold is not defined).
+ * Exit codes: -2 frames == 0 or an empty image; -4 beyond the pixel cap of patolette_amd_remap_u8(dither == 0); -1 (with a
+ *   "patolette_amd_frame_deltas_rgba:" text in patolette_amd_last_error) for a bad map_elem_bytes, no maps, palette_rows outside
+ *   [1, 2^31], a tolerance that is negative or not finite, a loop that is not 0 or 1, and in the lossy mode bad channels, missing
+ *   pixels, both or neither palette, a palette value that is not finite; or the flag above.  A failed call leaves the thread's engine
+ *   usable.
+ * Statistics: as patolette_amd_frame_deltas.
+ * Kernels: k_rgba_vanish, one launch for every frame's V and the flag; then k_frame_delta_rgba once per frame on the library's
+ *   stream -- rects[f - 1] is a grid-wide result that frame f's canvas needs, so the chain over frames is a chain of launches; no
+ *   host turn and no wait in between.  The host unites C and V once at the end.
+ * Out of scope: disposal 3, local colour tables, APNG. */
+void patolette_amd_frame_deltas_rgba(size_t frames, size_t width, size_t height, const void *palette_maps, int map_elem_bytes,
+                                     size_t palette_rows, const unsigned char *pixels, int channels, const double *palette,
+                                     const unsigned char *palette_u8, double tolerance, int loop, void *delta_maps, void *shown_maps,
+                                     int32_t *rects, int32_t *disposals, uint64_t *changed, int *exit_code);
+void patolette_amd_frame_deltas_rgba_device(size_t frames, size_t width, size_t height, const void *d_palette_maps, int map_elem_bytes,
+                                            size_t palette_rows, const unsigned char *d_pixels, int channels, const double *palette,
+                                            const unsigned char *palette_u8, double tolerance, int loop, void *d_delta_maps,
+                                            void *d_shown_maps, int32_t *rects, int32_t *disposals, uint64_t *changed, int *exit_code);
+
+/* TESTS ONLY: k_frame_deltas (and the kernels of patolette_amd_frame_deltas_rgba) give a lane four consecutive positions (one 4- or
+ * 16-byte access) where width * height is a multiple of
  * 4, the buffers are aligned for it and the frame is large enough to keep the GPU full with a quarter of the wavefronts (2^21 pixels
  * on an MI355X); otherwise one.  1 takes four wherever sizes and addresses allow, 0 never, -1 restores that rule.  Same results
  * either way.  Process-wide; returns the previous mode. */

@@ -20,7 +20,8 @@ pixel count, the squared error in code values and its maximum, per frame also th
 and `frame_deltas`' tolerance is stated in -- with `psnr` to read it in decibels;
 and, for animations with transparency, `remap_rgba` (RGBA images or frames onto a given palette whose row 0 may be a transparent
 entry) and `quantize_rgba_frames` (one shared palette and one transparent index for all frames, composed from `quantize_rgba`'s
-palette stage and `remap_rgba`);
+palette stage and `remap_rgba`) and `frame_deltas_rgba` (the deltas of such maps: 0 means "leave the canvas", every frame gets its
+own disposal, and the rectangle also covers what the next frame makes transparent);
 and `gif_lzw`, which LZW-compresses maps or deltas on the device, with `write_gif`, the GIF89a container around it.
 """
 import ctypes as C
@@ -472,8 +473,8 @@ def frame_deltas(maps, palette, transparent_index=None, frames=None, tolerance=0
       * want_shown: also return what the canvas shows after every frame (== maps when tolerance is 0).
     Frame 0 is the full first map.  Compositing the deltas (overwrite where delta != transparent_index) gives back `shown`.
     `write_gif(file, deltas, palette, rects, transparent_index=...)` writes them as a GIF.
-    Maps that carry a transparent entry of their own (`remap_rgba`, `quantize_rgba_frames`) work with the exact mode -- their index 0
-    compares like any row -- and with `measure(..., skip_index=0)`; the lossy mode on them stays out of scope.
+    Maps that carry a transparent entry of their own (`remap_rgba`, `quantize_rgba_frames`) go to `frame_deltas_rgba`: 0 as the
+    deltas' transparent index, a disposal per frame, and the lossy mode (here their index 0 compares like any row).
 
     Returns (success, deltas (F,H,W) as maps, rects (F,4) int32 rows (x0, y0, w, h) -- (0,0,0,0) for an unchanged frame --,
     changed (F,) int64, shown (F,H,W) or None, message)."""
@@ -533,6 +534,91 @@ def frame_deltas(maps, palette, transparent_index=None, frames=None, tolerance=0
     if code.value != 0:
         return (False, None, None, None, None, message)
     return (True, deltas, rects, changed.astype(np.int64), shown, message)
+
+
+def frame_deltas_rgba(maps, palette, frames=None, tolerance=0.0, loop=True, want_shown=False, transparent_index=None):
+    """`frame_deltas` for maps whose index 0 is the transparent entry -- those of `remap_rgba` / `quantize_rgba_frames` (additive;
+    include/patolette_amd.h: patolette_amd_frame_deltas_rgba).  In the deltas 0 means "leave the canvas as it is", which is what a GIF
+    decoder does with the transparent index under disposal 1, so no free index is needed.  A pixel that turns from opaque to
+    transparent cannot be drawn over the canvas: the frame before it gets disposal 2 over a rectangle that covers the pixel, and what
+    was unchanged inside that rectangle is drawn again.  Every frame so has its own disposal (1 or 2) and a rectangle that holds its
+    changed positions and the positions that vanish in the next frame.
+
+      * maps: (F, H, W) uint8 / uint16 / uint32 numpy array, or a torch uint8 / int32 CUDA tensor, as in `frame_deltas`.
+      * palette: as `remap_rgba` takes it -- (K, 4) uint8 RGBA whose row 0 has alpha 0, or (K, 3) uint8 / float with
+        transparent_index=0 -- or a plain int row count (tolerance 0 only).  Row 0's colour is never read.  A palette without a
+        transparent entry is a ValueError: such maps go to `frame_deltas`.
+      * frames, tolerance, want_shown: as in `frame_deltas`; frames are (F, H, W, 3|4) uint8 (the alpha byte is not read: the maps
+        say what is transparent).  The lossy mode never changes whether a position is transparent.
+      * loop: whether the animation repeats: then the last frame's disposal and rectangle look at frame 0.
+    `write_gif(file, deltas, palette_rgba[:, :3], rects, transparent_index=0, disposal=disposals)` writes the result as a GIF; a viewer
+    then shows `shown` (== maps when tolerance is 0), on every pass of the loop.
+
+    Returns (success, deltas (F,H,W) as maps, rects (F,4) int32 rows (x0, y0, w, h) -- (0,0,0,0) for a frame that changes and clears
+    nothing --, disposals (F,) int32 of 1 or 2, changed (F,) int64, shown (F,H,W) or None, message)."""
+    m, shape, dev, elem, elem_max = _delta_maps(maps)
+    try:
+        tol = float(tolerance)
+    except (TypeError, ValueError):
+        raise ValueError("tolerance must be a finite number >= 0") from None
+    if not (np.isfinite(tol) and tol >= 0.0):
+        raise ValueError("tolerance must be a finite number >= 0")
+    if not isinstance(loop, (bool, np.bool_)) and not (isinstance(loop, (int, np.integer)) and int(loop) in (0, 1)):
+        raise ValueError("loop must be True or False")
+    no_entry = "the palette has no transparent entry: maps without one go to frame_deltas"
+    pal8 = palf = None
+    if isinstance(palette, (int, np.integer)) and not isinstance(palette, (bool, np.bool_)):
+        if tol > 0.0:
+            raise ValueError("a tolerance above 0 compares colours: pass the palette itself, not its row count")
+        rows = int(palette)
+        if rows < 1:
+            raise ValueError("the palette's row count must be at least 1")
+        if transparent_index is not None:                         # (a row count has no alpha column: row 0 is the entry unless told otherwise)
+            if isinstance(transparent_index, (bool, np.bool_)) or not isinstance(transparent_index, (int, np.integer)) \
+                    or int(transparent_index) not in (-1, 0):
+                raise ValueError("transparent_index must be None, -1 (no transparent entry) or 0 (row 0)")
+            if int(transparent_index) == -1:
+                raise ValueError(no_entry)
+    else:
+        if hasattr(palette, "detach"):
+            palette = palette.detach().cpu().numpy()
+        pal8, palf, _, tidx, _ = _rgba_palette(palette, transparent_index)
+        if tidx != 0:
+            raise ValueError(no_entry)
+        rows = (pal8 if pal8 is not None else palf).shape[0]
+    px, channels = None, 3
+    if frames is not None:
+        px, pshape, pdev = _u8_pixels(frames, (4,), (3, 4), "frames must be an (F, H, W, 3|4) uint8 %s")
+        if pshape[:3] != shape:
+            raise ValueError("frames of shape %s do not match maps of shape %s" % (pshape, shape))
+        if pdev != dev:
+            raise ValueError("frames and maps must live in the same place (both numpy arrays, or tensors of one device)")
+        channels = pshape[3]
+    if tol > 0.0 and px is None:
+        raise ValueError("a tolerance above 0 needs the frames' pixels: pass frames=")
+    if tol == 0.0:
+        px = pal8 = palf = None                                   # (the exact mode reads none of them)
+    count, height, width = shape
+    if dev is None:
+        deltas = np.zeros(shape, dtype=m.dtype)
+        shown = np.zeros(shape, dtype=m.dtype) if want_shown else None
+    else:
+        import torch
+        deltas = torch.zeros(shape, dtype=m.dtype, device=dev)
+        shown = torch.zeros(shape, dtype=m.dtype, device=dev) if want_shown else None
+    rects = np.zeros((count, 4), dtype=np.int32)
+    disposals = np.zeros(count, dtype=np.int32)
+    changed = np.zeros(count, dtype=np.uint64)
+    code = C.c_int(0)
+    _call("patolette_amd_frame_deltas_rgba", dev, count, width, height, _vp(m), elem, rows, _vp(px), channels, _vp(palf), _vp(pal8), tol,
+          1 if loop else 0, _vp(deltas), _vp(shown), rects.ctypes.data_as(C.POINTER(C.c_int32)),
+          disposals.ctypes.data_as(C.POINTER(C.c_int32)), changed.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(code))
+    if code.value == -1 and _native.last_error().startswith("patolette_amd_frame_deltas_rgba:"):
+        raise ValueError(_native.last_error())
+    message = _message(code.value)
+    if code.value != 0:
+        return (False, None, None, None, None, None, message)
+    return (True, deltas, rects, disposals, changed.astype(np.int64), shown, message)
 
 
 def measure(image, maps, palette, skip_index=None, ictcp=True):
@@ -691,9 +777,10 @@ def write_gif(file, maps, palette_u8, rects=None, transparent_index=None, delay=
       * palette_u8: (K, 3) uint8, K <= 256: the global colour table, padded with zero rows to the next power of two that holds every
         row and, if given, transparent_index (<= 255).  That power of two is 2 ** min_code_size (at least 4).
       * delay: seconds per frame, a number or one per frame (written in 1/100 s); loop: the NETSCAPE2.0 repeat count (0 = for ever),
-        None for no loop block; disposal: every frame's disposal method (1: leave in place, what `frame_deltas`' deltas need).
-    Out of scope: local colour tables, interlace, APNG, and any decision about disposal for RGBA maps beyond the one `disposal` the
-    caller passes."""
+        None for no loop block; disposal: every frame's disposal method (1: leave in place, what `frame_deltas`' deltas need), or a
+        sequence of F of them, one per frame: `frame_deltas_rgba` returns the ones its deltas need --
+        `write_gif(file, deltas, palette_rgba[:, :3], rects, transparent_index=0, disposal=disposals)`.
+    Out of scope: local colour tables, interlace, APNG."""
     import os
     m, shape, dev = _gif_maps(maps)
     count, height, width = shape
@@ -720,8 +807,15 @@ def write_gif(file, maps, palette_u8, rects=None, transparent_index=None, delay=
         raise ValueError("delay must be a number of seconds or one per frame, each in [0, 655.35]")
     if loop is not None and (isinstance(loop, (bool, np.bool_)) or not isinstance(loop, (int, np.integer)) or not 0 <= int(loop) <= 65535):
         raise ValueError("loop must be None or a repeat count in [0, 65535]")
-    if isinstance(disposal, (bool, np.bool_)) or not isinstance(disposal, (int, np.integer)) or not 0 <= int(disposal) <= 3:
-        raise ValueError("disposal must be 0, 1, 2 or 3")
+    if isinstance(disposal, (list, tuple, np.ndarray)) or hasattr(disposal, "detach"):
+        disposals = np.asarray(disposal.detach().cpu().numpy() if hasattr(disposal, "detach") else disposal)
+        if disposals.shape != (count,) or disposals.dtype.kind not in "iu" or np.any(disposals < 0) or np.any(disposals > 3):
+            raise ValueError("disposal must be 0, 1, 2 or 3, or one such integer per frame")
+        disposals = [int(v) for v in disposals]
+    else:
+        if isinstance(disposal, (bool, np.bool_)) or not isinstance(disposal, (int, np.integer)) or not 0 <= int(disposal) <= 3:
+            raise ValueError("disposal must be 0, 1, 2 or 3")
+        disposals = [int(disposal)] * count
     _gif_segment(segment)
     ok, data, offsets, message = gif_lzw(m, r, mcs, segment)
     if not ok:
@@ -735,7 +829,7 @@ def write_gif(file, maps, palette_u8, rects=None, transparent_index=None, delay=
     flag, tidx = (1, int(transparent_index)) if transparent_index is not None else (0, 0)
     raw = data.tobytes()
     for f in range(count):
-        parts += [b"\x21\xf9\x04", bytes([int(disposal) << 2 | flag]), u16(int(np.round(delays[f] * 100))), bytes([tidx, 0])]
+        parts += [b"\x21\xf9\x04", bytes([disposals[f] << 2 | flag]), u16(int(np.round(delays[f] * 100))), bytes([tidx, 0])]
         x0, y0, w, h = (int(v) for v in r[f])
         parts += [b"\x2c", u16(x0), u16(y0), u16(w), u16(h), b"\x00", bytes([mcs])]
         stream = raw[int(offsets[f]):int(offsets[f + 1])]
@@ -854,7 +948,7 @@ def remap_rgba(image, palette, transparent_index=None, alpha_threshold=128, dith
         the image (as in `quantize_rgba`).  No state passes between frames.
       * Transparent pixels get index 0 and quantized (0, 0, 0, 0); a transparent pixel while the palette has no transparent entry
         is a ValueError.
-    These maps go into `frame_deltas` (exact mode: index 0 compares like any row) and `measure(..., skip_index=0)`.
+    These maps go into `frame_deltas_rgba` and `measure(..., skip_index=0)`.
 
     Returns (success, palette_map (H,W) or (F,H,W) uint8|uint16|uint32 by K, quantized (..., 4) uint8 or None, message)."""
     mode, spread = _dither_mode(dither), _spread_value(spread)
@@ -1037,6 +1131,7 @@ __all__ = [
     "remap_rgba",
     "ordered_spread",
     "frame_deltas",
+    "frame_deltas_rgba",
     "measure",
     "psnr",
     "gif_lzw",

@@ -1,4 +1,4 @@
-// delta.h -- launcher of the frame-delta kernel (delta.hip).
+// delta.h -- launchers of the frame-delta kernels (delta.hip): plain maps, and maps whose index 0 is a transparent entry.
 #pragma once
 
 #include "common.h"
@@ -28,7 +28,21 @@ void launch_frame_deltas(const void *d_maps, int elem_bytes, size_t frames, size
                          const unsigned char *d_px, int channels, const double *d_pal, double tol2, void *d_delta, void *d_shown,
                          unsigned long long *d_masks, unsigned long long *d_words, hipStream_t s);
 
-// TESTS ONLY: how many positions a lane of k_frame_deltas owns: -1 the launcher's rule (four from 32 wavefronts per CU on, where the
+// what the kernels of the RGBA flavour leave for the host, as unsigned long long words: per frame and slot the box of the changed
+// positions (C), then per frame and slot the box of the positions that vanish in the next frame (V), both as above and 16 bytes a
+// cell; then per frame and slot the count of C; then the flag word
+inline size_t frame_deltas_rgba_words(size_t frames) { return frames * (size_t)kDeltaSlots * 5 + 1; }
+
+// The frame deltas of maps whose index 0 is the transparent entry (include/patolette_amd.h, patolette_amd_frame_deltas_rgba): the
+// arguments of launch_frame_deltas without T; loop: whether frame 0 follows the last one.  d_delta (may be d_maps) may be null.
+// d_shown: frames x n elements or null; without it d_canvas is one frame of workspace (n elements) that holds the canvas between the
+// launches.  d_words: frame_deltas_rgba_words(frames) words, zeroed here.  One launch of k_rgba_vanish for every frame's V box and
+// the flag, then one of k_frame_delta_rgba per frame, all on `s`; nothing waits in between.
+void launch_frame_deltas_rgba(const void *d_maps, int elem_bytes, size_t frames, size_t width, size_t height, size_t rows, int loop, bool lossy,
+                              const unsigned char *d_px, int channels, const double *d_pal, double tol2, void *d_delta, void *d_shown,
+                              void *d_canvas, unsigned long long *d_words, hipStream_t s);
+
+// TESTS ONLY: how many positions a lane of k_frame_deltas (and of the RGBA flavour's kernels) owns: -1 the launcher's rule (four from 32 wavefronts per CU on, where the
 // sizes and addresses allow vector accesses), 0 always one, 1 four wherever they are allowed.  Same results.  Returns the previous mode.
 int delta_debug_quad(int mode);
 

@@ -252,4 +252,239 @@ void launch_frame_deltas(const void *d_maps, int elem_bytes, size_t frames, size
     }
 }
 
+// --------------------------------------------------------------------------------------------
+// RGBA maps (include/patolette_amd.h, patolette_amd_frame_deltas_rgba): index 0 is the transparent entry, 0 in a delta means "leave the
+// canvas", and a frame whose successor makes a pixel transparent is disposed to background over a rectangle that covers the pixel.
+// That rectangle is a grid-wide result the next frame's decisions need, so the frames are a chain of launches: k_rgba_vanish once for
+// every frame's V box (from the maps alone), then k_frame_delta_rgba frame after frame on one stream, each reading the slots its
+// predecessor filled.  No host turn in between; the host folds the slots once at the end.
+// Boxes are kept as maxima over zeroed memory (width - x0, height - y0, x1 + 1, y1 + 1): the union of two boxes is the element-wise
+// maximum, an empty one is all zero.  Integers only, so no result depends on the order of the atomics.
+// --------------------------------------------------------------------------------------------
+constexpr int kRgbaBlocksPerCu = 8;     // 256 threads each: the 32 wavefronts a CU holds
+
+// column and row of a lane's j-th position, from those of its first one (x0 < width; at most j steps)
+__device__ __forceinline__ void step_xy(unsigned x0, unsigned y0, unsigned j, unsigned width, unsigned &x, unsigned &y) {
+    x = x0 + j; y = y0;
+    while (x >= width) { x -= width; y++; }
+}
+
+// A lane's maxima v and count into the block's s_acc[5] (zeroed, and a barrier since): shuffles, then one set of LDS atomics per
+// wavefront that has something.  `some`: this lane has.
+__device__ __forceinline__ void fold_box(unsigned (&v)[4], unsigned cnt, bool some, unsigned *s_acc) {
+    if (!__ballot(some)) return;                                 // (wavefront-uniform)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) v[j] = max(v[j], (unsigned)__shfl_xor((int)v[j], o));
+        cnt += (unsigned)__shfl_xor((int)cnt, o);
+    }
+    if ((threadIdx.x & 63u) == 0) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) atomicMax(&s_acc[j], v[j]);
+        atomicAdd(&s_acc[4], cnt);
+    }
+}
+
+// Every frame's V: the box of the positions that are opaque in frame f and transparent in its successor (frame 0 after the last one
+// with `loop`, none otherwise).  Block b takes 256 * V positions of frame b / blocks_per_frame; every element is also tested against
+// `rows` here, once (the flag).  `words` as delta.h lays it out.
+template <typename ElemT, int V>
+__global__ __launch_bounds__(256) void k_rgba_vanish(const ElemT *__restrict__ maps, size_t F, size_t n, unsigned rows, unsigned width, unsigned height,
+                                                     int loop, size_t blocks_per_frame, unsigned long long *words) {
+    __shared__ unsigned s_acc[5];
+    const unsigned tid = threadIdx.x;
+    if (tid < 5) s_acc[tid] = 0;
+    __syncthreads();
+    const size_t f = blockIdx.x / blocks_per_frame, chunk = blockIdx.x % blocks_per_frame;
+    const size_t p = (chunk * 256 + tid) * V;
+    const bool has_next = f + 1 < F || loop != 0;
+    const size_t g = f + 1 < F ? f + 1 : 0;
+    unsigned a[V], b[V], gone = 0;                               // bit j: position p + j vanishes
+    bool bad = false;
+    if (p < n) {
+        load_elems<ElemT, V>(maps + f * n + p, a);
+#pragma unroll
+        for (int j = 0; j < V; j++) bad |= a[j] >= rows;
+        if (has_next) {
+            load_elems<ElemT, V>(maps + g * n + p, b);
+#pragma unroll
+            for (int j = 0; j < V; j++) gone |= (a[j] != 0 && b[j] == 0) ? 1u << j : 0u;
+        }
+    }
+    unsigned v[4] = {0, 0, 0, 0};
+    if (gone) {
+        const unsigned y0 = (unsigned)p / width, x0 = (unsigned)p - y0 * width;      // (n < 2^32: launch_frame_deltas_rgba)
+#pragma unroll
+        for (int j = 0; j < V; j++) {
+            if (!(gone >> j & 1u)) continue;
+            unsigned x, y;
+            step_xy(x0, y0, j, width, x, y);
+            v[0] = max(v[0], width - x); v[1] = max(v[1], height - y); v[2] = max(v[2], x + 1u); v[3] = max(v[3], y + 1u);
+        }
+    }
+    fold_box(v, gone ? 1u : 0u, gone != 0, s_acc);
+    __syncthreads();
+    if (tid == 0 && s_acc[4] != 0) {
+        unsigned *box = reinterpret_cast<unsigned *>(words) + ((F + f) * (size_t)kDeltaSlots + chunk % (unsigned)kDeltaSlots) * 4;
+#pragma unroll
+        for (int j = 0; j < 4; j++) atomicMax(box + j, s_acc[j]);
+    }
+    if (__ballot(bad) && (tid & 63u) == 0) atomicOr(reinterpret_cast<unsigned *>(words + F * (size_t)kDeltaSlots * 5), 1u);
+}
+
+// Frame f of the chain.  m, delta, px: frame f's; canvas_in: what the canvas showed after frame f - 1, before that frame's disposal
+// (shown[f - 1], or the one-frame workspace; null for f == 0, where the canvas is empty); canvas_out: shown[f] or the workspace again
+// (a lane reads and writes its own positions only).  The predecessor's rectangle and disposal come from its slots and its V slots,
+// folded once per block by the first wavefront.
+template <typename ElemT, bool Lossy, int V>
+__global__ __launch_bounds__(256) void k_frame_delta_rgba(const ElemT *m, const ElemT *canvas_in, ElemT *canvas_out, ElemT *delta, size_t F, size_t f,
+                                                          size_t n, size_t tiles, unsigned rows, unsigned width, unsigned height,
+                                                          const unsigned char *__restrict__ px, int ch,
+                                                          const double *__restrict__ pal /* planar (rows,3), ICtCp */, double tol2,
+                                                          unsigned long long *words) {
+    __shared__ double s_pal[Lossy ? 3 : 1][Lossy ? kDeltaChunk : 1];
+    __shared__ double s_glut[Lossy ? 256 : 1];
+    __shared__ unsigned s_acc[5], s_prev[5];                     // s_prev: x0, y0, x1, y1 (exclusive) of what frame f - 1 cleared; whether it did
+    const unsigned tid = threadIdx.x;
+    const bool resident = rows <= (unsigned)kDeltaChunk;
+    if (tid < 5) s_acc[tid] = 0;
+    if (tid < 64) {
+        unsigned r[4] = {0, 0, 0, 0}, vanish = 0;
+        if (f > 0) {                                             // lanes 0 .. 31: the slots of C[f - 1]; 32 .. 63: those of V[f - 1]
+            const uint4 q = reinterpret_cast<const uint4 *>(words)[((tid < 32 ? 0 : F) + (f - 1)) * (size_t)kDeltaSlots + (tid & 31u)];
+            r[0] = q.x; r[1] = q.y; r[2] = q.z; r[3] = q.w;
+            vanish = tid < 32 ? 0u : q.z;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+            for (int j = 0; j < 4; j++) r[j] = max(r[j], (unsigned)__shfl_xor((int)r[j], o));
+            vanish = max(vanish, (unsigned)__shfl_xor((int)vanish, o));
+        }
+        if (tid == 0) { s_prev[0] = width - r[0]; s_prev[1] = height - r[1]; s_prev[2] = r[2]; s_prev[3] = r[3]; s_prev[4] = vanish != 0; }
+    }
+    if constexpr (Lossy) {
+        pow_tables_to_lds();
+        __syncthreads();
+        s_glut[tid] = dc::gamma_decode((double)tid / 255.0);    // (256 threads) as k_frame_deltas holds it
+        if (resident)
+            for (unsigned j = tid; j < rows; j += 256) { s_pal[0][j] = pal[j]; s_pal[1][j] = pal[(size_t)rows + j]; s_pal[2][j] = pal[2 * (size_t)rows + j]; }
+    }
+    __syncthreads();
+    unsigned cnt = 0;
+    unsigned v[4] = {0, 0, 0, 0};
+    const bool cleared = s_prev[4] != 0;
+    const unsigned cx0 = s_prev[0], cy0 = s_prev[1], cx1 = s_prev[2], cy1 = s_prev[3];
+    for (size_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {            // (no barrier inside: lanes past the end just pass)
+        const size_t p = (tile * 256 + tid) * V;
+        const bool active = p < n;
+        unsigned a[V], c[V], out[V];
+#pragma unroll
+        for (int j = 0; j < V; j++) { a[j] = 0; c[j] = 0; }
+        if (active) {
+            load_elems<ElemT, V>(m + p, a);
+            if (canvas_in) load_elems<ElemT, V>(canvas_in + p, c);
+        }
+        const unsigned y0 = (unsigned)p / width, x0 = (unsigned)p - y0 * width;      // (n < 2^32: launch_frame_deltas_rgba)
+#pragma unroll
+        for (int j = 0; j < V; j++) {
+            unsigned x, y;
+            step_xy(x0, y0, j, width, x, y);
+            if (cleared && x >= cx0 && x < cx1 && y >= cy0 && y < cy1) c[j] = 0;
+            bool change = false;
+            if (a[j] == 0) c[j] = 0;                             // (it is 0 there already: the position lay in V[f - 1], or never showed)
+            else if (c[j] == 0) change = true;
+            else if (a[j] != c[j]) {
+                change = true;
+                if constexpr (Lossy) {
+                    if (c[j] < rows) {                           // (an element that is no row is never an address: the flag fails the call)
+                        const unsigned char *q = px + (p + j) * (size_t)ch;
+                        double w[3] = {s_glut[q[0]], s_glut[q[1]], s_glut[q[2]]};
+                        dev_convert_linear<PAMD_SRGB_TO_ICTCP>(w);
+                        double p0, p1, p2;
+                        if (resident) { p0 = s_pal[0][c[j]]; p1 = s_pal[1][c[j]]; p2 = s_pal[2][c[j]]; }
+                        else { p0 = pal[c[j]]; p1 = pal[(size_t)rows + c[j]]; p2 = pal[2 * (size_t)rows + c[j]]; }
+                        const double d0 = w[0] - p0, d1 = w[1] - p1, d2 = w[2] - p2;
+                        const double d = (d0 * d0 + d1 * d1) + d2 * d2;
+                        if (d <= tol2) change = false;           // the entry on the canvas still serves this frame's pixel
+                    }
+                }
+            }
+            if (change) {
+                c[j] = a[j]; cnt++;
+                v[0] = max(v[0], width - x); v[1] = max(v[1], height - y); v[2] = max(v[2], x + 1u); v[3] = max(v[3], y + 1u);
+            }
+            out[j] = change ? a[j] : 0u;
+        }
+        if (active) {
+            if (delta) store_elems<ElemT, V>(delta + p, out);
+            store_elems<ElemT, V>(canvas_out + p, c);
+        }
+    }
+    fold_box(v, cnt, cnt != 0, s_acc);
+    __syncthreads();
+    if (tid == 0 && s_acc[4] != 0) {
+        const size_t cell = f * (size_t)kDeltaSlots + blockIdx.x % (unsigned)kDeltaSlots;
+        unsigned *box = reinterpret_cast<unsigned *>(words) + cell * 4;
+#pragma unroll
+        for (int j = 0; j < 4; j++) atomicMax(box + j, s_acc[j]);
+        atomicAdd(words + F * (size_t)kDeltaSlots * 4 + cell, (unsigned long long)s_acc[4]);
+    }
+}
+
+template <typename ElemT, int V>
+static void launch_rgba_typed(const void *d_maps, size_t frames, size_t width, size_t height, size_t rows, int loop, bool lossy,
+                              const unsigned char *d_px, int channels, const double *d_pal, double tol2, void *d_delta, void *d_shown,
+                              void *d_canvas, unsigned long long *d_words, hipStream_t s) {
+    const size_t n = width * height, blocks = ceil_div(n, (size_t)256 * V);
+    const ElemT *maps = (const ElemT *)d_maps;
+    // a frame's launch: at most kRgbaBlocksPerCu blocks per CU, each walking its tiles -- one set of atomics per block, and 2 x 4096 x
+    // 4096 (16 384 tiles of four positions per lane) then meets on the slots with 2048 blocks instead of 16 384: 0.134 ms per
+    // frame became 0.036
+    const unsigned grid = (unsigned)std::min(blocks, (size_t)num_cus() * kRgbaBlocksPerCu);
+    {
+        KTIME("k_rgba_vanish", s, 2.0 * sizeof(ElemT) * n * frames);
+        hipLaunchKernelGGL((k_rgba_vanish<ElemT, V>), (unsigned)(blocks * frames), 256, 0, s, maps, frames, n, (unsigned)rows, (unsigned)width,
+                           (unsigned)height, loop, blocks, d_words);
+        HIP_CHECK(hipGetLastError());
+    }
+    for (size_t f = 0; f < frames; f++) {
+        const ElemT *m = maps + f * n;
+        ElemT *delta = d_delta ? (ElemT *)d_delta + f * n : nullptr;
+        const ElemT *in = f == 0 ? nullptr : (d_shown ? (const ElemT *)d_shown + (f - 1) * n : (const ElemT *)d_canvas);
+        ElemT *out = d_shown ? (ElemT *)d_shown + f * n : (ElemT *)d_canvas;
+        const unsigned char *px = lossy ? d_px + f * n * (size_t)channels : nullptr;
+        KTIME("k_frame_delta_rgba", s, ((double)sizeof(ElemT) * (f == 0 ? 2 : 3) + (d_delta ? sizeof(ElemT) : 0) + (lossy ? channels : 0)) * n);
+        if (lossy)
+            hipLaunchKernelGGL((k_frame_delta_rgba<ElemT, true, V>), grid, 256, 0, s, m, in, out, delta, frames, f, n, blocks, (unsigned)rows,
+                               (unsigned)width, (unsigned)height, px, channels, d_pal, tol2, d_words);
+        else
+            hipLaunchKernelGGL((k_frame_delta_rgba<ElemT, false, V>), grid, 256, 0, s, m, in, out, delta, frames, f, n, blocks, (unsigned)rows,
+                               (unsigned)width, (unsigned)height, px, channels, d_pal, tol2, d_words);
+        HIP_CHECK(hipGetLastError());
+    }
+}
+
+void launch_frame_deltas_rgba(const void *d_maps, int elem_bytes, size_t frames, size_t width, size_t height, size_t rows, int loop, bool lossy,
+                              const unsigned char *d_px, int channels, const double *d_pal, double tol2, void *d_delta, void *d_shown,
+                              void *d_canvas, unsigned long long *d_words, hipStream_t s) {
+    const size_t n = width * height;
+    if (frames * n == 0) return;
+    if (elem_bytes != 1 && elem_bytes != 4) throw HipError("patolette_amd: the frame deltas take elements of 1 or 4 bytes");
+    if (width >> 31 || height >> 31 || n >> 32 || rows >> 32 || (ceil_div(n, 256) * frames) >> 31)
+        throw HipError("patolette_amd: frame deltas: a size does not fit the kernels' 32-bit fields");
+    if (lossy && (!d_px || !d_pal || rows < 1)) throw HipError("patolette_amd: the lossy frame deltas need pixels and a palette");
+    if (!d_shown && !d_canvas) throw HipError("patolette_amd: the RGBA frame deltas need a canvas");
+    HIP_CHECK(hipMemsetAsync(d_words, 0, frame_deltas_rgba_words(frames) * sizeof(unsigned long long), s));
+    // four positions per lane by the rule of launch_frame_deltas
+    const uintptr_t all = (uintptr_t)d_maps | (uintptr_t)d_delta | (uintptr_t)d_shown | (uintptr_t)d_canvas;
+    const int mode = g_delta_quad.load(std::memory_order_relaxed);
+    const bool quad = n % 4 == 0 && all % (4 * (uintptr_t)elem_bytes) == 0 && (mode < 0 ? n >= (size_t)num_cus() * 32 * 256 : mode == 1);
+#define PAMD_DELTA_LAUNCH(E, V) launch_rgba_typed<E, V>(d_maps, frames, width, height, rows, loop, lossy, d_px, channels, d_pal, tol2, d_delta, d_shown, d_canvas, d_words, s)
+    if (elem_bytes == 1) { if (quad) PAMD_DELTA_LAUNCH(unsigned char, 4); else PAMD_DELTA_LAUNCH(unsigned char, 1); }
+    else { if (quad) PAMD_DELTA_LAUNCH(unsigned int, 4); else PAMD_DELTA_LAUNCH(unsigned int, 1); }
+#undef PAMD_DELTA_LAUNCH
+}
+
 }  // namespace pamd

@@ -3002,6 +3002,86 @@ static void run_frame_deltas(Engine &E, bool on_device, size_t frames, size_t wi
     E.stats.ms_total = now_ms() - t_start;
 }
 
+// The same for maps whose index 0 is the transparent entry (include/patolette_amd.h, patolette_amd_frame_deltas_rgba): pointers and
+// palette as run_frame_deltas takes them (row 0 of pal is never read); disposals: host memory like rects.
+static void run_frame_deltas_rgba(Engine &E, bool on_device, size_t frames, size_t width, size_t height, const void *maps, int eb, size_t rows,
+                                  const unsigned char *pixels, int channels, std::vector<double> pal, double tolerance, int loop, void *delta_out,
+                                  void *shown_out, int32_t *rects, int32_t *disposals, uint64_t *changed) {
+    const bool lossy = tolerance > 0.0;
+    const size_t n = width * height, N = frames * n;
+    hipStream_t s = E.stream;
+    const double t_start = now_ms();
+    WsGuard wg(&E.stream, &E.stream2);
+    E.stats = patolette_amd__Stats{};
+    const int me = given_device_elem(eb, on_device);
+    // the workspace, before anything is enqueued
+    const size_t words = frame_deltas_rgba_words(frames);
+    E.dl_words.reserve(words);
+    if (!on_device && shown_out) E.dl_shown.reserve(N * (size_t)me);
+    else if (!shown_out) E.dl_shown.reserve(n * (size_t)me);                       // the canvas between the frames' launches
+    if (lossy) { E.dpal.reserve(3 * rows); E.h_pal.reserve(3 * rows); }
+    const void *d_maps = maps;
+    void *d_delta = delta_out, *d_shown = shown_out;
+    const unsigned char *d_px = pixels;
+    std::vector<unsigned> stage;
+    if (!on_device) {
+        stage_given(E, maps, eb, me, N, GivenSkip{}, 0, lossy ? pixels : nullptr, channels, stage);
+        if (lossy) d_px = E.src8.p;
+        d_maps = E.dl_maps.p;
+        d_delta = delta_out ? E.dl_maps.p : nullptr;                               // in place: the kernels allow it
+        d_shown = shown_out ? E.dl_shown.p : nullptr;
+    }
+    E.stats.ms_upload = now_ms() - t_start;
+    double t0 = now_ms();
+    if (lossy) {
+        palette_rows(pal, rows, hm::color::srgb_to_ictcp);
+        upload_palette(E, pal, rows);
+    }
+    launch_frame_deltas_rgba(d_maps, me, frames, width, height, rows, loop, lossy, d_px, channels, lossy ? E.dpal.p : nullptr, tolerance * tolerance,
+                             d_delta, d_shown, d_shown ? nullptr : E.dl_shown.p, E.dl_words.p, s);
+    std::vector<unsigned long long> w(words);
+    HIP_CHECK(hipMemcpyAsync(w.data(), E.dl_words.p, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    E.sync();
+    E.stats.ms_map = now_ms() - t0;
+    t0 = now_ms();
+    if (w[words - 1] & 1)
+        throw HipError("patolette_amd_frame_deltas_rgba: a map element is not below palette_rows, or names a dropped trailing (-1, -1, -1) row");
+    const unsigned *box = reinterpret_cast<const unsigned *>(w.data());
+    const unsigned long long *cnt = w.data() + frames * (size_t)kDeltaSlots * 4;
+    for (size_t f = 0; f < frames; f++) {
+        unsigned m[4] = {0, 0, 0, 0}, vanish = 0;                                  // C[f] and V[f] united: the maxima of both
+        unsigned long long count = 0;
+        for (int j = 0; j < kDeltaSlots; j++) {
+            const size_t c_cell = f * (size_t)kDeltaSlots + j, v_cell = (frames + f) * (size_t)kDeltaSlots + j;
+            for (int a = 0; a < 4; a++) m[a] = std::max(m[a], std::max(box[c_cell * 4 + a], box[v_cell * 4 + a]));
+            vanish = std::max(vanish, box[v_cell * 4 + 2]);
+            count += cnt[c_cell];
+        }
+        if (changed) changed[f] = count;
+        if (disposals) disposals[f] = vanish ? 2 : 1;
+        if (rects) {
+            int32_t *r = rects + 4 * f;
+            if (m[2] == 0) { r[0] = r[1] = r[2] = r[3] = 0; }
+            else {
+                r[0] = (int32_t)(width - m[0]); r[1] = (int32_t)(height - m[1]);
+                r[2] = (int32_t)(m[2] - (width - m[0])); r[3] = (int32_t)(m[3] - (height - m[1]));
+            }
+        }
+    }
+    if (!on_device) {
+        void *outs[2] = {delta_out, shown_out};
+        const void *from[2] = {d_delta, d_shown};
+        for (int o = 0; o < 2; o++) {
+            if (!outs[o]) continue;
+            if (eb == me) { HIP_CHECK(hipMemcpy(outs[o], from[o], N * (size_t)me, hipMemcpyDeviceToHost)); continue; }
+            HIP_CHECK(hipMemcpy(stage.data(), from[o], N * sizeof(unsigned), hipMemcpyDeviceToHost));   // (stage_given sized it)
+            given_elems_out(stage.data(), me, outs[o], eb, 0, N);
+        }
+    }
+    E.stats.ms_download = now_ms() - t0;
+    E.stats.ms_total = now_ms() - t_start;
+}
+
 // --------------------------------------------------------------------------------------------
 // measure: a map's error per palette entry and frame (include/patolette_amd.h, patolette_amd_measure)
 // --------------------------------------------------------------------------------------------
@@ -3608,6 +3688,38 @@ static void frame_deltas_entry(bool on_device, size_t frames, size_t width, size
     });
 }
 
+// the deltas of maps whose index 0 is the transparent entry (include/patolette_amd.h): the arguments, then run_frame_deltas_rgba
+static void frame_deltas_rgba_entry(bool on_device, size_t frames, size_t width, size_t height, const void *palette_maps, int map_elem_bytes,
+                                    size_t palette_rows, const unsigned char *pixels, int channels, const double *palette,
+                                    const unsigned char *palette_u8, double tolerance, int loop, void *delta_maps, void *shown_maps, int32_t *rects,
+                                    int32_t *disposals, uint64_t *changed, int *exit_code) {
+    const ArgCheck arg{"patolette_amd_frame_deltas_rgba", exit_code};
+    if (!arg.shape(frames, width, height, (size_t)40000 * 40000, "frames * width * height is too big")) return;   // the nearest remap's cap
+    const int eb = map_elem_bytes;
+    if (!arg.map_elem_bytes(on_device, eb)) return;
+    if (!palette_maps) return (void)arg.fail(-1, "no maps");
+    if (!arg.rows(palette_rows)) return;
+    if (!(std::isfinite(tolerance) && tolerance >= 0.0)) return (void)arg.fail(-1, "tolerance must be finite and not negative");
+    if (loop != 0 && loop != 1) return (void)arg.fail(-1, "loop must be 0 or 1");
+    GivenPalette g;
+    g.k = palette_rows;
+    if (tolerance > 0.0) {                                                            // the lossy mode reads pixels and one palette
+        if (channels != 3 && channels != 4) return (void)arg.fail(-1, "channels must be 3 or 4");
+        if (!pixels) return (void)arg.fail(-1, "a tolerance above 0 needs the frames' pixels");
+        if ((palette != nullptr) == (palette_u8 != nullptr)) return (void)arg.fail(-1, "a tolerance above 0 needs exactly one of palette and palette_u8");
+        std::vector<double> opaque;                                                   // row 0 is the transparent entry: its colour is never read
+        if (palette) {
+            opaque.assign(palette, palette + 3 * palette_rows);
+            for (int c = 0; c < 3; c++) opaque[(size_t)c * palette_rows] = 0.0;
+        }
+        if (!arg.palette(palette ? opaque.data() : nullptr, palette_u8, palette_rows, false, g)) return;
+    }
+    *exit_code = guarded([&](Engine &E) {
+        run_frame_deltas_rgba(E, on_device, frames, width, height, palette_maps, eb, g.k, pixels, channels, std::move(g.pal), tolerance, loop,
+                              delta_maps, shown_maps, rects, disposals, changed);
+    });
+}
+
 // a map's error per entry and frame (include/patolette_amd.h): the arguments, then run_measure
 static void measure_entry(bool on_device, size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels,
                           const void *palette_maps, int map_elem_bytes, const double *palette, const unsigned char *palette_u8, size_t palette_rows,
@@ -3753,6 +3865,22 @@ void patolette_amd_frame_deltas_device(size_t frames, size_t width, size_t heigh
                                        void *d_shown_maps, int32_t *rects, uint64_t *changed, int *exit_code) {
     frame_deltas_entry(true, frames, width, height, d_palette_maps, map_elem_bytes, palette_rows, transparent_index, d_pixels, channels, palette,
                        palette_u8, tolerance, d_delta_maps, d_shown_maps, rects, changed, exit_code);
+}
+
+void patolette_amd_frame_deltas_rgba(size_t frames, size_t width, size_t height, const void *palette_maps, int map_elem_bytes,
+                                     size_t palette_rows, const unsigned char *pixels, int channels, const double *palette,
+                                     const unsigned char *palette_u8, double tolerance, int loop, void *delta_maps, void *shown_maps,
+                                     int32_t *rects, int32_t *disposals, uint64_t *changed, int *exit_code) {
+    frame_deltas_rgba_entry(false, frames, width, height, palette_maps, map_elem_bytes, palette_rows, pixels, channels, palette, palette_u8,
+                            tolerance, loop, delta_maps, shown_maps, rects, disposals, changed, exit_code);
+}
+
+void patolette_amd_frame_deltas_rgba_device(size_t frames, size_t width, size_t height, const void *d_palette_maps, int map_elem_bytes,
+                                            size_t palette_rows, const unsigned char *d_pixels, int channels, const double *palette,
+                                            const unsigned char *palette_u8, double tolerance, int loop, void *d_delta_maps,
+                                            void *d_shown_maps, int32_t *rects, int32_t *disposals, uint64_t *changed, int *exit_code) {
+    frame_deltas_rgba_entry(true, frames, width, height, d_palette_maps, map_elem_bytes, palette_rows, d_pixels, channels, palette, palette_u8,
+                            tolerance, loop, d_delta_maps, d_shown_maps, rects, disposals, changed, exit_code);
 }
 
 void patolette_amd_measure(size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels, const void *palette_maps,
