@@ -685,6 +685,18 @@ int patolette_amd_kmeans_refine(const double *colors, const double *weights, siz
 
 /* patolette__PALETTE_fill_palette_map_nearest (palette/nearest.c:150-209) */
 int patolette_amd_nn_map(const double *colors, size_t n, const double *palette, size_t k, size_t *map);
+/* TESTS ONLY: which kernels the nearest map takes is decided by the pixel count -- brute force below 16 384 pixels, a 32^3 candidate
+ * table from there, a 64^3 table from 2^22 (with up to 256 palette rows: read through a four-candidate table in LDS).  route 1, 2, 3
+ * make every nearest map (this stage, the full paths, remap) take the route of the first, second, third size class whatever its
+ * size; 0 restores the default.  The limits on the palette stay: outside 8 .. 4096 rows every route is brute force, above 256 rows
+ * route 3 reads the 64^3 table directly; and the remap's byte-source kernel (2^22 pixels and more by default) runs under route 3 at
+ * any size and never under routes 1 and 2.  Same map for every setting.  Process-wide; returns the previous setting. */
+int patolette_amd_debug_nn_route(int route);
+/* TESTS ONLY: patolette_amd_nn_map with map elements of map_elem_bytes = 1 (k <= 256; what every image of up to 256 colours takes), 4
+ * or 8 bytes in the host buffer `map` (n elements).  misalign = 1 (1-byte elements only) starts the device's output one byte into
+ * its allocation: the odd address that image i of a batch with an odd pixel count gets.  0, or -1 (patolette_amd_last_error). */
+int patolette_amd_debug_nn_map_elem(const double *colors, size_t n, const double *palette, size_t k, int map_elem_bytes, int misalign,
+                                    void *map);
 
 /* patolette__DITHER_riemersma (dither/riemersma.c:437-459); colors/palette in linear Rec2020 */
 int patolette_amd_dither(const double *colors, size_t width, size_t height, const double *palette,

@@ -43,6 +43,9 @@ struct NNWork {                        // scratch of the pruned NN map
 // lo/hi: exact per-plane min/max of the colours if known (else nullptr: computed with one more pass)
 void launch_nn_map(const double *d_colors, size_t plane_stride, size_t n, const double *d_pal, int k,
                    void *d_out, int elem_bytes, const double *lo, const double *hi, NNWork &w, hipStream_t s);
+// TESTS ONLY: the size class launch_nn_map and nn_map_u8_applies pretend (0 = the one of n, 1 = below 16 384 pixels, 2 = from 16 384,
+// 3 = from 2^22); the limits on k are untouched.  Process-wide; returns the previous setting.
+int nn_debug_route(int route);
 // The same map straight from interleaved 8-bit sRGB pixels (`channels` 3 or 4 bytes each; palette in ICtCp): the LDS-table kernel with
 // a byte source that converts in registers, no f64 image.  Only where nn_map_u8_applies (the sizes and palettes that kernel takes);
 // elements of 1 or 4 bytes.

@@ -883,6 +883,17 @@ static void srgb8_ictcp_bounds(NNWork &w, hipStream_t s, double lo[3], double hi
     for (int a = 0; a < 3; a++) { lo[a] = b.lo[a]; hi[a] = b.hi[a]; }
 }
 
+// The size class that routes a map of n pixels: 0 = brute force (k_nn_map), 1 = the 32^3 table (k_nn_map_lut), 2 = the 64^3 table
+// (k_nn_map_mid around its LDS table for up to 256 rows, k_nn_map_lut above).  TESTS ONLY (patolette_amd_debug_nn_route): a route
+// other than 0 names the class whatever n is; the limits on k stay with the callers.
+static std::atomic<int> g_nn_route{0};
+int nn_debug_route(int route) { return g_nn_route.exchange(route >= 1 && route <= 3 ? route : 0); }
+static int nn_size_class(size_t n) {
+    const int route = g_nn_route.load(std::memory_order_relaxed);
+    if (route != 0) return route - 1;
+    return n >= ((size_t)1 << 22) ? 2 : (n >= 16384 ? 1 : 0);
+}
+
 static NNGrid nn_grid(const double blo[3], const double bhi[3], int G) {
     NNGrid g;
     g.G = G;
@@ -899,7 +910,7 @@ static NNGrid nn_grid(const double blo[3], const double bhi[3], int G) {
 // The nearest map straight from interleaved 8-bit sRGB pixels (the remap entry; palette in ICtCp): k_nn_map_mid with the byte source.
 // The grid spans the image of the whole 8-bit sRGB cube (the kernel takes a pixel's cell without a clamp: the box must enclose every
 // pixel, and exact bounds of THIS image would cost its conversion a second time).
-bool nn_map_u8_applies(size_t n, int k) { return n >= ((size_t)1 << 22) && !(n >> 32) && k >= 8 && k <= 256; }
+bool nn_map_u8_applies(size_t n, int k) { return nn_size_class(n) == 2 && !(n >> 32) && k >= 8 && k <= 256; }
 template <typename OutT>
 static void launch_nn_mid_u8(const unsigned char *d_px, int channels, size_t n, const double *d_pal, int k, OutT *out, NNWork &w, hipStream_t s) {
     double blo[3], bhi[3];
@@ -938,7 +949,26 @@ void launch_nn_map_u8(const unsigned char *d_px, int channels, size_t n, const d
 void launch_nn_map(const double *d_colors, size_t plane_stride, size_t n, const double *d_pal, int k, void *d_out, int elem_bytes,
                    const double *lo, const double *hi, NNWork &w, hipStream_t s) {
     if (elem_bytes != 1 && elem_bytes != 4 && elem_bytes != 8) throw HipError("patolette_amd: map element size must be 1, 4 or 8");
-    const bool use_lut = n >= 16384 && k >= 8 && k <= 4096;
+    const int cls = nn_size_class(n);
+    bool use_lut = cls >= 1 && k >= 8 && k <= 4096;
+    double blo[3] = {0, 0, 0}, bhi[3] = {0, 0, 0};
+    if (use_lut) {
+        if (lo && hi) { for (int a = 0; a < 3; a++) { blo[a] = lo[a]; bhi[a] = hi[a]; } }
+        else {
+            w.keys.reserve(6);
+            unsigned long long init[6] = {~0ULL, ~0ULL, ~0ULL, 0ULL, 0ULL, 0ULL}, got[6];
+            HIP_CHECK(hipMemcpyAsync(w.keys.p, init, sizeof init, hipMemcpyHostToDevice, s));
+            { KTIME("k_minmax3", s, 24.0 * n); hipLaunchKernelGGL(k_minmax3, stream_blocks(n, 16), 256, 0, s, d_colors, plane_stride, n, w.keys.p); }
+            HIP_CHECK(hipMemcpyAsync(got, w.keys.p, sizeof got, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+            for (int a = 0; a < 3; a++) { blo[a] = key_f64(got[a]); bhi[a] = key_f64(got[3 + a]); }
+        }
+        // An infinite pixel makes its plane's bound infinite: no grid spans that box (nn_grid would give the axis one cell of width
+        // zero at `lo`, and the finite pixels, which do spread over the axis, would be handed a list pruned for that point).  Such an
+        // image takes the brute-force kernel.  (A NaN never reaches the bounds -- fmin / fmax drop it -- and its pixel clamps into
+        // cell 0, where every distance is NaN and index 0 stays, as in the reference.)
+        for (int a = 0; a < 3; a++) use_lut = use_lut && std::isfinite(blo[a]) && std::isfinite(bhi[a]);
+    }
     if (!use_lut) {
         if (elem_bytes == 1) launch_nn_brute<unsigned char>(d_colors, plane_stride, n, d_pal, k, (unsigned char *)d_out, s);
         else if (elem_bytes == 4) launch_nn_brute<unsigned int>(d_colors, plane_stride, n, d_pal, k, (unsigned int *)d_out, s);
@@ -946,18 +976,12 @@ void launch_nn_map(const double *d_colors, size_t plane_stride, size_t n, const 
         HIP_CHECK(hipGetLastError());
         return;
     }
-    double blo[3], bhi[3];
-    if (lo && hi) { for (int a = 0; a < 3; a++) { blo[a] = lo[a]; bhi[a] = hi[a]; } }
-    else {
-        w.keys.reserve(6);
-        unsigned long long init[6] = {~0ULL, ~0ULL, ~0ULL, 0ULL, 0ULL, 0ULL}, got[6];
-        HIP_CHECK(hipMemcpyAsync(w.keys.p, init, sizeof init, hipMemcpyHostToDevice, s));
-        { KTIME("k_minmax3", s, 24.0 * n); hipLaunchKernelGGL(k_minmax3, stream_blocks(n, 16), 256, 0, s, d_colors, plane_stride, n, w.keys.p); }
-        HIP_CHECK(hipMemcpyAsync(got, w.keys.p, sizeof got, hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        for (int a = 0; a < 3; a++) { blo[a] = key_f64(got[a]); bhi[a] = key_f64(got[3 + a]); }
-    }
-    const NNGrid g = nn_grid(blo, bhi, n >= ((size_t)1 << 22) ? 64 : 32);
+    // k_nn_map_mid takes a pixel's cell from fl32(x - lo) * fl32(32 / range) WITHOUT a clamp: a range beyond what f32 holds (a finite
+    // pixel of 1e39: the difference rounds to +Inf and the product converts to 2^32 - 1, an index far outside the LDS table; a range
+    // below 1e-37: the factor is +Inf) must not reach it.  Such a box takes the 32^3 table, whose cell index is f64 and clamped.
+    bool f32_range = true;
+    for (int a = 0; a < 3; a++) { const double r = bhi[a] - blo[a]; f32_range = f32_range && (!(r > 0) || (r >= 1e-30 && r <= 1e30)); }
+    const NNGrid g = nn_grid(blo, bhi, cls == 2 && (f32_range || k > 256) ? 64 : 32);
     if (elem_bytes == 1) launch_nn_lut<unsigned char>(d_colors, plane_stride, n, d_pal, k, (unsigned char *)d_out, g, w, s);
     else if (elem_bytes == 4) launch_nn_lut<unsigned int>(d_colors, plane_stride, n, d_pal, k, (unsigned int *)d_out, g, w, s);
     else launch_nn_lut<unsigned long long>(d_colors, plane_stride, n, d_pal, k, (unsigned long long *)d_out, g, w, s);

@@ -4157,6 +4157,24 @@ int patolette_amd_kmeans_refine(const double *colors, const double *weights, siz
     });
 }
 
+int patolette_amd_debug_nn_route(int route) { return nn_debug_route(route); }
+
+int patolette_amd_debug_nn_map_elem(const double *colors, size_t n, const double *palette, size_t k, int map_elem_bytes, int misalign, void *map) {
+    return guarded([&](Engine &E) -> int {
+        const int eb = map_elem_bytes;
+        if ((eb != 1 && eb != 4 && eb != 8) || (eb == 1 && k > 256) || k == 0 || (misalign != 0 && (misalign != 1 || eb != 1)))
+            throw HipError("patolette_amd_debug_nn_map_elem: elements of 1 (up to 256 rows), 4 or 8 bytes; misalign 0, or 1 with 1-byte elements");
+        if (n == 0) return 0;
+        E.src.reserve(3 * n); E.dpal.reserve(3 * k); E.dmap.reserve(n * (size_t)eb + 1);
+        HIP_CHECK(hipMemcpy(E.src.p, colors, 3 * n * sizeof(double), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(E.dpal.p, palette, 3 * k * sizeof(double), hipMemcpyHostToDevice));
+        launch_nn_map(E.src.p, n, n, E.dpal.p, (int)k, E.dmap.p + misalign, eb, nullptr, nullptr, E.nn, E.stream);
+        E.sync();
+        HIP_CHECK(hipMemcpy(map, E.dmap.p + misalign, n * (size_t)eb, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
+
 int patolette_amd_nn_map(const double *colors, size_t n, const double *palette, size_t k, size_t *map) {
     return guarded([&](Engine &E) -> int {
         if (n == 0) return 0;
