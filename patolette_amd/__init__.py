@@ -25,6 +25,7 @@ own disposal, and the rectangle also covers what the next frame makes transparen
 and `gif_lzw`, which LZW-compresses maps or deltas on the device, with `write_gif`, the GIF89a container around it.
 """
 import ctypes as C
+import types
 
 import numpy as np
 
@@ -455,6 +456,61 @@ def _delta_maps(maps):
     return m, shape, dev, elem[0], elem[1]
 
 
+def _delta_row_count(palette, tol):
+    """`palette` given as a plain int row count (tolerance 0 only, which reads no colours) -> the count; None for a palette."""
+    if not isinstance(palette, (int, np.integer)) or isinstance(palette, (bool, np.bool_)):
+        return None
+    if tol > 0.0:
+        raise ValueError("a tolerance above 0 compares colours: pass the palette itself, not its row count")
+    if int(palette) < 1:
+        raise ValueError("the palette's row count must be at least 1")
+    return int(palette)
+
+
+def _delta_setup(maps, tolerance, frames, want_shown, palette_rules):
+    """What `frame_deltas` and `frame_deltas_rgba` do around their own palette rules, in the order their errors have always come: the
+    maps, the tolerance, then palette_rules(tol, elem, elem_max) -> (pal8, palf, rows), then the frames against the maps.  The exact
+    mode drops what it does not read; the outputs are allocated where the maps live.  Returns a namespace of what the entry takes."""
+    m, shape, dev, elem, elem_max = _delta_maps(maps)
+    try:
+        tol = float(tolerance)
+    except (TypeError, ValueError):
+        raise ValueError("tolerance must be a finite number >= 0") from None
+    if not (np.isfinite(tol) and tol >= 0.0):
+        raise ValueError("tolerance must be a finite number >= 0")
+    pal8, palf, rows = palette_rules(tol, elem, elem_max)
+    px, channels = None, 3
+    if frames is not None:
+        px, pshape, pdev = _u8_pixels(frames, (4,), (3, 4), "frames must be an (F, H, W, 3|4) uint8 %s")
+        if pshape[:3] != shape:
+            raise ValueError("frames of shape %s do not match maps of shape %s" % (pshape, shape))
+        if pdev != dev:
+            raise ValueError("frames and maps must live in the same place (both numpy arrays, or tensors of one device)")
+        channels = pshape[3]
+    if tol > 0.0 and px is None:
+        raise ValueError("a tolerance above 0 needs the frames' pixels: pass frames=")
+    if tol == 0.0:
+        px = pal8 = palf = None                                   # (the exact mode reads none of them)
+    if dev is None:
+        deltas = np.zeros(shape, dtype=m.dtype)
+        shown = np.zeros(shape, dtype=m.dtype) if want_shown else None
+    else:
+        import torch
+        deltas = torch.zeros(shape, dtype=m.dtype, device=dev)
+        shown = torch.zeros(shape, dtype=m.dtype, device=dev) if want_shown else None
+    count, height, width = shape
+    return types.SimpleNamespace(m=m, dev=dev, elem=elem, count=count, width=width, height=height, rows=rows, px=px, channels=channels,
+                                 pal8=pal8, palf=palf, tol=tol, deltas=deltas, shown=shown, rects=np.zeros((count, 4), dtype=np.int32),
+                                 changed=np.zeros(count, dtype=np.uint64), code=C.c_int(0))
+
+
+def _delta_message(name, code):
+    """The entry's own complaints about its arguments are the caller's mistake: a ValueError.  Otherwise the code's message."""
+    if code == -1 and _native.last_error().startswith(name + ":"):
+        raise ValueError(_native.last_error())
+    return _message(code)
+
+
 def frame_deltas(maps, palette, transparent_index=None, frames=None, tolerance=0.0, want_shown=False):
     """The inter-frame deltas of an animation's index maps (additive; include/patolette_amd.h: patolette_amd_frame_deltas): what a
     GIF or APNG encoder makes of every frame -- the map with "same as what is already on screen" replaced by a transparent index, and
@@ -478,62 +534,31 @@ def frame_deltas(maps, palette, transparent_index=None, frames=None, tolerance=0
 
     Returns (success, deltas (F,H,W) as maps, rects (F,4) int32 rows (x0, y0, w, h) -- (0,0,0,0) for an unchanged frame --,
     changed (F,) int64, shown (F,H,W) or None, message)."""
-    m, shape, dev, elem, elem_max = _delta_maps(maps)
-    try:
-        tol = float(tolerance)
-    except (TypeError, ValueError):
-        raise ValueError("tolerance must be a finite number >= 0") from None
-    if not (np.isfinite(tol) and tol >= 0.0):
-        raise ValueError("tolerance must be a finite number >= 0")
-    pal8 = palf = None
-    if isinstance(palette, (int, np.integer)) and not isinstance(palette, (bool, np.bool_)):
-        if tol > 0.0:
-            raise ValueError("a tolerance above 0 compares colours: pass the palette itself, not its row count")
-        rows = int(palette)
-        if rows < 1:
-            raise ValueError("the palette's row count must be at least 1")
-    else:
-        if hasattr(palette, "detach"):
-            palette = palette.detach().cpu().numpy()
-        pal8, palf = _remap_palette(palette)
-        rows = (pal8 if pal8 is not None else palf).shape[0]
-    T = rows if transparent_index is None else int(transparent_index)
-    if T < rows:
-        raise ValueError("transparent_index must be at least the palette's row count (%d): an index no entry uses" % rows)
-    if T > elem_max:
-        raise ValueError("no free index: transparent_index %d does not fit the maps' %d-byte elements -- make the palette with one row "
-                         "less, or pass wider maps" % (T, elem))
-    px, channels = None, 3
-    if frames is not None:
-        px, pshape, pdev = _u8_pixels(frames, (4,), (3, 4), "frames must be an (F, H, W, 3|4) uint8 %s")
-        if pshape[:3] != shape:
-            raise ValueError("frames of shape %s do not match maps of shape %s" % (pshape, shape))
-        if pdev != dev:
-            raise ValueError("frames and maps must live in the same place (both numpy arrays, or tensors of one device)")
-        channels = pshape[3]
-    if tol > 0.0 and px is None:
-        raise ValueError("a tolerance above 0 needs the frames' pixels: pass frames=")
-    if tol == 0.0:
-        px = pal8 = palf = None                                   # (the exact mode reads none of them)
-    count, height, width = shape
-    if dev is None:
-        deltas = np.zeros(shape, dtype=m.dtype)
-        shown = np.zeros(shape, dtype=m.dtype) if want_shown else None
-    else:
-        import torch
-        deltas = torch.zeros(shape, dtype=m.dtype, device=dev)
-        shown = torch.zeros(shape, dtype=m.dtype, device=dev) if want_shown else None
-    rects = np.zeros((count, 4), dtype=np.int32)
-    changed = np.zeros(count, dtype=np.uint64)
-    code = C.c_int(0)
-    _call("patolette_amd_frame_deltas", dev, count, width, height, _vp(m), elem, rows, T, _vp(px), channels, _vp(palf), _vp(pal8), tol,
-          _vp(deltas), _vp(shown), rects.ctypes.data_as(C.POINTER(C.c_int32)), changed.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(code))
-    if code.value == -1 and _native.last_error().startswith("patolette_amd_frame_deltas:"):
-        raise ValueError(_native.last_error())
-    message = _message(code.value)
-    if code.value != 0:
+    T = None
+
+    def palette_rules(tol, elem, elem_max):
+        nonlocal T
+        pal8 = palf = None
+        rows = _delta_row_count(palette, tol)
+        if rows is None:
+            pal8, palf = _remap_palette(palette.detach().cpu().numpy() if hasattr(palette, "detach") else palette)
+            rows = (pal8 if pal8 is not None else palf).shape[0]
+        T = rows if transparent_index is None else int(transparent_index)
+        if T < rows:
+            raise ValueError("transparent_index must be at least the palette's row count (%d): an index no entry uses" % rows)
+        if T > elem_max:
+            raise ValueError("no free index: transparent_index %d does not fit the maps' %d-byte elements -- make the palette with one row "
+                             "less, or pass wider maps" % (T, elem))
+        return pal8, palf, rows
+
+    d = _delta_setup(maps, tolerance, frames, want_shown, palette_rules)
+    _call("patolette_amd_frame_deltas", d.dev, d.count, d.width, d.height, _vp(d.m), d.elem, d.rows, T, _vp(d.px), d.channels, _vp(d.palf),
+          _vp(d.pal8), d.tol, _vp(d.deltas), _vp(d.shown), d.rects.ctypes.data_as(C.POINTER(C.c_int32)),
+          d.changed.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(d.code))
+    message = _delta_message("patolette_amd_frame_deltas", d.code.value)
+    if d.code.value != 0:
         return (False, None, None, None, None, message)
-    return (True, deltas, rects, changed.astype(np.int64), shown, message)
+    return (True, d.deltas, d.rects, d.changed.astype(np.int64), d.shown, message)
 
 
 def frame_deltas_rgba(maps, palette, frames=None, tolerance=0.0, loop=True, want_shown=False, transparent_index=None):
@@ -556,69 +581,36 @@ def frame_deltas_rgba(maps, palette, frames=None, tolerance=0.0, loop=True, want
 
     Returns (success, deltas (F,H,W) as maps, rects (F,4) int32 rows (x0, y0, w, h) -- (0,0,0,0) for a frame that changes and clears
     nothing --, disposals (F,) int32 of 1 or 2, changed (F,) int64, shown (F,H,W) or None, message)."""
-    m, shape, dev, elem, elem_max = _delta_maps(maps)
-    try:
-        tol = float(tolerance)
-    except (TypeError, ValueError):
-        raise ValueError("tolerance must be a finite number >= 0") from None
-    if not (np.isfinite(tol) and tol >= 0.0):
-        raise ValueError("tolerance must be a finite number >= 0")
-    if not isinstance(loop, (bool, np.bool_)) and not (isinstance(loop, (int, np.integer)) and int(loop) in (0, 1)):
-        raise ValueError("loop must be True or False")
     no_entry = "the palette has no transparent entry: maps without one go to frame_deltas"
-    pal8 = palf = None
-    if isinstance(palette, (int, np.integer)) and not isinstance(palette, (bool, np.bool_)):
-        if tol > 0.0:
-            raise ValueError("a tolerance above 0 compares colours: pass the palette itself, not its row count")
-        rows = int(palette)
-        if rows < 1:
-            raise ValueError("the palette's row count must be at least 1")
-        if transparent_index is not None:                         # (a row count has no alpha column: row 0 is the entry unless told otherwise)
-            if isinstance(transparent_index, (bool, np.bool_)) or not isinstance(transparent_index, (int, np.integer)) \
-                    or int(transparent_index) not in (-1, 0):
-                raise ValueError("transparent_index must be None, -1 (no transparent entry) or 0 (row 0)")
-            if int(transparent_index) == -1:
+
+    def palette_rules(tol, elem, elem_max):
+        if not isinstance(loop, (bool, np.bool_)) and not (isinstance(loop, (int, np.integer)) and int(loop) in (0, 1)):
+            raise ValueError("loop must be True or False")
+        pal8 = palf = None
+        rows = _delta_row_count(palette, tol)
+        if rows is not None:
+            if transparent_index is not None:                     # (a row count has no alpha column: row 0 is the entry unless told otherwise)
+                if isinstance(transparent_index, (bool, np.bool_)) or not isinstance(transparent_index, (int, np.integer)) \
+                        or int(transparent_index) not in (-1, 0):
+                    raise ValueError("transparent_index must be None, -1 (no transparent entry) or 0 (row 0)")
+                if int(transparent_index) == -1:
+                    raise ValueError(no_entry)
+        else:
+            pal8, palf, _, tidx, _ = _rgba_palette(palette.detach().cpu().numpy() if hasattr(palette, "detach") else palette, transparent_index)
+            if tidx != 0:
                 raise ValueError(no_entry)
-    else:
-        if hasattr(palette, "detach"):
-            palette = palette.detach().cpu().numpy()
-        pal8, palf, _, tidx, _ = _rgba_palette(palette, transparent_index)
-        if tidx != 0:
-            raise ValueError(no_entry)
-        rows = (pal8 if pal8 is not None else palf).shape[0]
-    px, channels = None, 3
-    if frames is not None:
-        px, pshape, pdev = _u8_pixels(frames, (4,), (3, 4), "frames must be an (F, H, W, 3|4) uint8 %s")
-        if pshape[:3] != shape:
-            raise ValueError("frames of shape %s do not match maps of shape %s" % (pshape, shape))
-        if pdev != dev:
-            raise ValueError("frames and maps must live in the same place (both numpy arrays, or tensors of one device)")
-        channels = pshape[3]
-    if tol > 0.0 and px is None:
-        raise ValueError("a tolerance above 0 needs the frames' pixels: pass frames=")
-    if tol == 0.0:
-        px = pal8 = palf = None                                   # (the exact mode reads none of them)
-    count, height, width = shape
-    if dev is None:
-        deltas = np.zeros(shape, dtype=m.dtype)
-        shown = np.zeros(shape, dtype=m.dtype) if want_shown else None
-    else:
-        import torch
-        deltas = torch.zeros(shape, dtype=m.dtype, device=dev)
-        shown = torch.zeros(shape, dtype=m.dtype, device=dev) if want_shown else None
-    rects = np.zeros((count, 4), dtype=np.int32)
-    disposals = np.zeros(count, dtype=np.int32)
-    changed = np.zeros(count, dtype=np.uint64)
-    code = C.c_int(0)
-    _call("patolette_amd_frame_deltas_rgba", dev, count, width, height, _vp(m), elem, rows, _vp(px), channels, _vp(palf), _vp(pal8), tol,
-          1 if loop else 0, _vp(deltas), _vp(shown), rects.ctypes.data_as(C.POINTER(C.c_int32)),
-          disposals.ctypes.data_as(C.POINTER(C.c_int32)), changed.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(code))
-    if code.value == -1 and _native.last_error().startswith("patolette_amd_frame_deltas_rgba:"):
-        raise ValueError(_native.last_error())
-    message = _message(code.value)
-    if code.value != 0:
+            rows = (pal8 if pal8 is not None else palf).shape[0]
+        return pal8, palf, rows
+
+    d = _delta_setup(maps, tolerance, frames, want_shown, palette_rules)
+    disposals = np.zeros(d.count, dtype=np.int32)
+    _call("patolette_amd_frame_deltas_rgba", d.dev, d.count, d.width, d.height, _vp(d.m), d.elem, d.rows, _vp(d.px), d.channels, _vp(d.palf),
+          _vp(d.pal8), d.tol, 1 if loop else 0, _vp(d.deltas), _vp(d.shown), d.rects.ctypes.data_as(C.POINTER(C.c_int32)),
+          disposals.ctypes.data_as(C.POINTER(C.c_int32)), d.changed.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(d.code))
+    message = _delta_message("patolette_amd_frame_deltas_rgba", d.code.value)
+    if d.code.value != 0:
         return (False, None, None, None, None, None, message)
-    return (True, deltas, rects, disposals, changed.astype(np.int64), shown, message)
+    return (True, d.deltas, d.rects, disposals, d.changed.astype(np.int64), d.shown, message)
 
 
 def measure(image, maps, palette, skip_index=None, ictcp=True):

@@ -5,15 +5,15 @@
 
 namespace pamd {
 
-// palette rows a block of k_frame_deltas<.., true> holds in LDS, as three planar f64 arrays (24 KB next to the 4 KB of pow tables
-// and the 2 KB companding table); a longer palette is indexed in global memory (a lookup by index, not a search)
+// palette rows a block of the lossy kernels holds in LDS (given_device.h, LossyLds: 24 KB next to the 4 KB of pow tables and the
+// 2 KB companding table); a longer palette is indexed in global memory
 constexpr int kDeltaChunk = 1024;
-// same-address atomics serialise in L2: the per-frame results of k_delta_boxes' blocks are spread over this many slots, which the host folds
+// same-address atomics serialise in L2: a frame's box and count are spread over this many slots, which the host folds
+// (given.h, given_fold_frame)
 constexpr int kDeltaSlots = 32;
 
-// what the kernels leave for the host, as unsigned long long words: per frame and slot a box of four unsigned ints, all kept as
-// maxima over zeroed memory (width - x0, height - y0, x1 + 1, y1 + 1), then per frame and slot a count, then one word whose low
-// bit says that some element was not below `rows`
+// what the kernels leave for the host, as unsigned long long words: per frame and slot a box of four unsigned ints (given_device.h
+// says how a box is kept), then per frame and slot a count, then one word whose low bit says that some element was not below `rows`
 inline size_t frame_deltas_words(size_t frames) { return frames * (size_t)kDeltaSlots * 3 + 1; }
 // between the two kernels: per frame one 64-bit ballot per wavefront of positions (bit i of word w: position 64 w + i changed)
 inline size_t frame_deltas_masks(size_t frames, size_t n) { return frames * ceil_div(n, 64); }

@@ -6,22 +6,21 @@
 // already on their way (a small clip gives a CU few wavefronts to hide the latency with).  Where every frame starts on a vector boundary a lane owns four
 // consecutive positions and moves them as one 4- or 16-byte access.  delta may be the input buffer: a lane stores a frame's
 // elements only after it has loaded them, and no other lane touches those positions.
-// Lossy: a lane whose element differs from its canvas entry takes the frame's source pixel through the byte -> ICtCp route of the
-// nearest maps (the companding from a 256-entry table in LDS, then dev_convert_linear with the pow tables in LDS) and compares it
-// with the canvas entry's palette row, read by index from LDS (from global memory beyond kDeltaChunk rows).  Lanes that see no
+// Lossy: a lane whose element differs from its canvas entry compares the frame's source pixel with the canvas entry's palette row
+// (given_device.h, LossyLds: the conversion, the palette in LDS up to kDeltaChunk rows, the distance).  Lanes that see no
 // difference convert nothing; whole frames are not converted ahead.
 // Rectangle and count in two stages, integers only (order-free).  The walk leaves one ballot per wavefront and frame -- which of its
 // 64 consecutive positions changed: one bit per pixel-frame, a plain vector store by one lane, no barrier and no atomic inside the
 // walk.  k_delta_boxes then reads the ballots: a count is a popcount, rows come from the first and the last set bit (positions
 // ascend), columns likewise while the 64 positions lie in one row and bit by bit where they wrap; blocks reduce in LDS and reach
-// global memory with one set of integer atomics per block, none for a block that saw no change.
+// global memory with one set of integer atomics per block, none for a block that saw no change (given_device.h: fold_box, publish_box).
 // (First form, measured and replaced: the walk itself reduced every frame -- shuffles, LDS atomics between two barriers per
 // kDeltaAhead frames, one set of global atomics per block and frame over kDeltaSlots slots.  64 frames of 640 x 360: 0.091 ms;
 // 2 frames of 4096 x 4096: 0.662 ms, where 65 536 blocks met on 160 addresses.  DESIGN.md 4.11 has both.)
 #include "delta.h"
 
 #define PAMD_POW_TABLES_IN_LDS
-#include "color_device.h"
+#include "given_device.h"
 
 namespace pamd {
 
@@ -29,6 +28,7 @@ namespace pamd {
 static std::atomic<int> g_delta_quad{-1};
 int delta_debug_quad(int mode) { return g_delta_quad.exchange(mode < 0 ? -1 : (mode ? 1 : 0)); }
 
+using DeltaLossy = LossyLds<kDeltaChunk>;   // the lossy compare (given_device.h)
 constexpr int kDeltaAhead = 4;       // frames per group: a group's elements are loaded while the group before it is decided
 
 // V consecutive elements as one access (V = 4: a 4- or 16-byte vector)
@@ -59,16 +59,9 @@ __global__ __launch_bounds__(256) void k_frame_deltas(const ElemT *maps, size_t 
                                                       const double *__restrict__ pal /* planar (rows,3), ICtCp */, double tol2,
                                                       ElemT *delta, ElemT *shown, unsigned long long *masks, unsigned *flag) {
     constexpr int A = kDeltaAhead;
-    __shared__ double s_pal[Lossy ? 3 : 1][Lossy ? kDeltaChunk : 1];
-    __shared__ double s_glut[Lossy ? 256 : 1];
     const unsigned tid = threadIdx.x, lane = tid & 63u;
-    const bool resident = rows <= (unsigned)kDeltaChunk;
     if constexpr (Lossy) {
-        pow_tables_to_lds();
-        __syncthreads();
-        s_glut[tid] = dc::gamma_decode((double)tid / 255.0);    // (256 threads) sRGB.c:70-89 of every byte value, as k_nn_map_u8 holds it
-        if (resident)
-            for (unsigned j = tid; j < rows; j += 256) { s_pal[0][j] = pal[j]; s_pal[1][j] = pal[(size_t)rows + j]; s_pal[2][j] = pal[2 * (size_t)rows + j]; }
+        DeltaLossy::fill(pal, rows);
         __syncthreads();
     }
     const size_t p = ((size_t)blockIdx.x * 256 + tid) * V;       // the first of this lane's V positions
@@ -110,14 +103,7 @@ __global__ __launch_bounds__(256) void k_frame_deltas(const ElemT *maps, size_t 
                 if constexpr (Lossy) {
                     if (change && c[j] < rows) {                 // (an element that is no row is never an address: `bad` fails the call)
                         const unsigned char *q = px + (at + j) * (size_t)ch;
-                        double v[3] = {s_glut[q[0]], s_glut[q[1]], s_glut[q[2]]};
-                        dev_convert_linear<PAMD_SRGB_TO_ICTCP>(v);
-                        double p0, p1, p2;
-                        if (resident) { p0 = s_pal[0][c[j]]; p1 = s_pal[1][c[j]]; p2 = s_pal[2][c[j]]; }
-                        else { p0 = pal[c[j]]; p1 = pal[(size_t)rows + c[j]]; p2 = pal[2 * (size_t)rows + c[j]]; }
-                        const double d0 = v[0] - p0, d1 = v[1] - p1, d2 = v[2] - p2;
-                        const double d = (d0 * d0 + d1 * d1) + d2 * d2;
-                        if (d <= tol2) change = false;           // the entry on the canvas still serves this frame's pixel
+                        if (DeltaLossy::dist2(c[j], q, pal, rows) <= tol2) change = false;   // the canvas entry still serves
                     }
                 }
                 if (change) { c[j] = a[u][j]; changes |= 1u << j; }
@@ -151,7 +137,7 @@ __global__ __launch_bounds__(256) void k_frame_deltas(const ElemT *maps, size_t 
 __global__ __launch_bounds__(256) void k_delta_boxes(const unsigned long long *__restrict__ masks, size_t F, size_t n, size_t nw, unsigned width,
                                                      unsigned height, size_t blocks_per_frame, unsigned long long *words) {
     __shared__ unsigned s_acc[5];
-    const unsigned tid = threadIdx.x, lane = tid & 63u;
+    const unsigned tid = threadIdx.x;
     if (tid < 5) s_acc[tid] = 0;
     __syncthreads();
     const size_t f = 1 + blockIdx.x / blocks_per_frame, chunk = blockIdx.x % blocks_per_frame;
@@ -181,40 +167,28 @@ __global__ __launch_bounds__(256) void k_delta_boxes(const unsigned long long *_
         v[0] = width - x0; v[1] = height - y0; v[2] = x1 + 1u; v[3] = y1 + 1u;
         cnt = (unsigned)__popcll(m);
     }
-    if (__ballot(m != 0)) {                                      // (wavefront-uniform)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-            for (int j = 0; j < 4; j++) v[j] = max(v[j], (unsigned)__shfl_xor((int)v[j], o));
-            cnt += (unsigned)__shfl_xor((int)cnt, o);
-        }
-        if (lane == 0) {
-#pragma unroll
-            for (int j = 0; j < 4; j++) atomicMax(&s_acc[j], v[j]);
-            atomicAdd(&s_acc[4], cnt);
-        }
-    }
+    fold_box(v, cnt, m != 0, s_acc);
     __syncthreads();
-    if (tid == 0 && s_acc[4] != 0) {
-        const size_t cell = f * (size_t)kDeltaSlots + chunk % (unsigned)kDeltaSlots;
-        unsigned *box = reinterpret_cast<unsigned *>(words) + cell * 4;
-#pragma unroll
-        for (int j = 0; j < 4; j++) atomicMax(box + j, s_acc[j]);
-        atomicAdd(words + F * (size_t)kDeltaSlots * 2 + cell, (unsigned long long)s_acc[4]);
-    }
+    publish_box(words, f * (size_t)kDeltaSlots + chunk % (unsigned)kDeltaSlots, F * (size_t)kDeltaSlots * 2, s_acc);
 }
 
-template <typename ElemT, int V>
-static void launch_typed(const void *d_maps, size_t frames, size_t n, size_t nw, size_t rows, size_t T, bool lossy, const unsigned char *d_px,
-                         int channels, const double *d_pal, double tol2, void *d_delta, void *d_shown, unsigned long long *d_masks,
-                         unsigned *d_flag, hipStream_t s) {
-    const unsigned blocks = (unsigned)ceil_div(n, (size_t)256 * V);
-    if (lossy)
-        hipLaunchKernelGGL((k_frame_deltas<ElemT, true, V>), blocks, 256, 0, s, (const ElemT *)d_maps, frames, n, nw, (unsigned)rows, (ElemT)T, d_px,
-                           channels, d_pal, tol2, (ElemT *)d_delta, (ElemT *)d_shown, d_masks, d_flag);
-    else
-        hipLaunchKernelGGL((k_frame_deltas<ElemT, false, V>), blocks, 256, 0, s, (const ElemT *)d_maps, frames, n, nw, (unsigned)rows, (ElemT)T, d_px,
-                           channels, d_pal, tol2, (ElemT *)d_delta, (ElemT *)d_shown, d_masks, d_flag);
+// Four positions per lane (V = 4) where every frame starts on a vector boundary (`all`: the buffers' addresses or-ed) -- and where that
+// still leaves every SIMD its eight wavefronts: a quarter of the wavefronts moves 4096 x 4096 in 0.036 ms instead of 0.085, but
+// 640 x 360 (225 blocks, fewer than CUs) in 0.056 instead of 0.027.  Both flavours' launchers ask here.
+static bool delta_quad(size_t n, uintptr_t all, int elem_bytes) {
+    const int mode = g_delta_quad.load(std::memory_order_relaxed);
+    return n % 4 == 0 && all % (4 * (uintptr_t)elem_bytes) == 0 && (mode < 0 ? n >= (size_t)num_cus() * 32 * 256 : mode == 1);
+}
+
+// The kernels' instantiation for elements of 1 or 4 bytes, one or four positions per lane, exact or lossy: f(ElemT(), V, Lossy), the last
+// two as std::integral_constant
+template <typename F>
+static void delta_dispatch(int elem_bytes, bool quad, bool lossy, F f) {
+    auto by_v = [&](auto elem, auto is_lossy) {
+        if (quad) f(elem, std::integral_constant<int, 4>{}, is_lossy); else f(elem, std::integral_constant<int, 1>{}, is_lossy);
+    };
+    auto by_lossy = [&](auto elem) { if (lossy) by_v(elem, std::true_type{}); else by_v(elem, std::false_type{}); };
+    if (elem_bytes == 1) by_lossy((unsigned char)0); else by_lossy(0u);
 }
 
 void launch_frame_deltas(const void *d_maps, int elem_bytes, size_t frames, size_t width, size_t height, size_t rows, size_t T, bool lossy,
@@ -232,16 +206,14 @@ void launch_frame_deltas(const void *d_maps, int elem_bytes, size_t frames, size
     {
         const int outs = (d_delta ? 1 : 0) + (d_shown ? 1 : 0);
         KTIME("k_frame_deltas", s, ((double)elem_bytes * (1 + outs) + (lossy ? channels : 0) + 0.125) * N);
-        // four positions per lane where every frame starts on a vector boundary -- and where that still leaves every SIMD its eight
-        // wavefronts: a quarter of the wavefronts moves 4096 x 4096 in 0.036 ms instead of 0.085, but 640 x 360 (225 blocks, fewer
-        // than CUs) in 0.056 instead of 0.027
-        const uintptr_t all = (uintptr_t)d_maps | (uintptr_t)d_delta | (uintptr_t)d_shown;
-        const int mode = g_delta_quad.load(std::memory_order_relaxed);
-        const bool quad = n % 4 == 0 && all % (4 * (uintptr_t)elem_bytes) == 0 && (mode < 0 ? n >= (size_t)num_cus() * 32 * 256 : mode == 1);
-#define PAMD_DELTA_LAUNCH(E, V) launch_typed<E, V>(d_maps, frames, n, nw, rows, T, lossy, d_px, channels, d_pal, tol2, d_delta, d_shown, d_masks, d_flag, s)
-        if (elem_bytes == 1) { if (quad) PAMD_DELTA_LAUNCH(unsigned char, 4); else PAMD_DELTA_LAUNCH(unsigned char, 1); }
-        else { if (quad) PAMD_DELTA_LAUNCH(unsigned int, 4); else PAMD_DELTA_LAUNCH(unsigned int, 1); }
-#undef PAMD_DELTA_LAUNCH
+        const bool quad = delta_quad(n, (uintptr_t)d_maps | (uintptr_t)d_delta | (uintptr_t)d_shown, elem_bytes);
+        delta_dispatch(elem_bytes, quad, lossy, [&](auto elem, auto v, auto is_lossy) {
+            using ElemT = decltype(elem);
+            constexpr int V = decltype(v)::value;
+            hipLaunchKernelGGL((k_frame_deltas<ElemT, decltype(is_lossy)::value, V>), (unsigned)ceil_div(n, (size_t)256 * V), 256, 0, s,
+                               (const ElemT *)d_maps, frames, n, nw, (unsigned)rows, (ElemT)T, d_px, channels, d_pal, tol2, (ElemT *)d_delta,
+                               (ElemT *)d_shown, d_masks, d_flag);
+        });
         HIP_CHECK(hipGetLastError());
     }
     if (frames > 1) {
@@ -258,8 +230,7 @@ void launch_frame_deltas(const void *d_maps, int elem_bytes, size_t frames, size
 // That rectangle is a grid-wide result the next frame's decisions need, so the frames are a chain of launches: k_rgba_vanish once for
 // every frame's V box (from the maps alone), then k_frame_delta_rgba frame after frame on one stream, each reading the slots its
 // predecessor filled.  No host turn in between; the host folds the slots once at the end.
-// Boxes are kept as maxima over zeroed memory (width - x0, height - y0, x1 + 1, y1 + 1): the union of two boxes is the element-wise
-// maximum, an empty one is all zero.  Integers only, so no result depends on the order of the atomics.
+// Boxes as given_device.h keeps them: no result depends on the order of the atomics.
 // --------------------------------------------------------------------------------------------
 constexpr int kRgbaBlocksPerCu = 8;     // 256 threads each: the 32 wavefronts a CU holds
 
@@ -267,23 +238,6 @@ constexpr int kRgbaBlocksPerCu = 8;     // 256 threads each: the 32 wavefronts a
 __device__ __forceinline__ void step_xy(unsigned x0, unsigned y0, unsigned j, unsigned width, unsigned &x, unsigned &y) {
     x = x0 + j; y = y0;
     while (x >= width) { x -= width; y++; }
-}
-
-// A lane's maxima v and count into the block's s_acc[5] (zeroed, and a barrier since): shuffles, then one set of LDS atomics per
-// wavefront that has something.  `some`: this lane has.
-__device__ __forceinline__ void fold_box(unsigned (&v)[4], unsigned cnt, bool some, unsigned *s_acc) {
-    if (!__ballot(some)) return;                                 // (wavefront-uniform)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int j = 0; j < 4; j++) v[j] = max(v[j], (unsigned)__shfl_xor((int)v[j], o));
-        cnt += (unsigned)__shfl_xor((int)cnt, o);
-    }
-    if ((threadIdx.x & 63u) == 0) {
-#pragma unroll
-        for (int j = 0; j < 4; j++) atomicMax(&s_acc[j], v[j]);
-        atomicAdd(&s_acc[4], cnt);
-    }
 }
 
 // Every frame's V: the box of the positions that are opaque in frame f and transparent in its successor (frame 0 after the last one
@@ -325,11 +279,7 @@ __global__ __launch_bounds__(256) void k_rgba_vanish(const ElemT *__restrict__ m
     }
     fold_box(v, gone ? 1u : 0u, gone != 0, s_acc);
     __syncthreads();
-    if (tid == 0 && s_acc[4] != 0) {
-        unsigned *box = reinterpret_cast<unsigned *>(words) + ((F + f) * (size_t)kDeltaSlots + chunk % (unsigned)kDeltaSlots) * 4;
-#pragma unroll
-        for (int j = 0; j < 4; j++) atomicMax(box + j, s_acc[j]);
-    }
+    publish_box(words, (F + f) * (size_t)kDeltaSlots + chunk % (unsigned)kDeltaSlots, kNoCount, s_acc);
     if (__ballot(bad) && (tid & 63u) == 0) atomicOr(reinterpret_cast<unsigned *>(words + F * (size_t)kDeltaSlots * 5), 1u);
 }
 
@@ -343,11 +293,8 @@ __global__ __launch_bounds__(256) void k_frame_delta_rgba(const ElemT *m, const 
                                                           const unsigned char *__restrict__ px, int ch,
                                                           const double *__restrict__ pal /* planar (rows,3), ICtCp */, double tol2,
                                                           unsigned long long *words) {
-    __shared__ double s_pal[Lossy ? 3 : 1][Lossy ? kDeltaChunk : 1];
-    __shared__ double s_glut[Lossy ? 256 : 1];
     __shared__ unsigned s_acc[5], s_prev[5];                     // s_prev: x0, y0, x1, y1 (exclusive) of what frame f - 1 cleared; whether it did
     const unsigned tid = threadIdx.x;
-    const bool resident = rows <= (unsigned)kDeltaChunk;
     if (tid < 5) s_acc[tid] = 0;
     if (tid < 64) {
         unsigned r[4] = {0, 0, 0, 0}, vanish = 0;
@@ -364,14 +311,8 @@ __global__ __launch_bounds__(256) void k_frame_delta_rgba(const ElemT *m, const 
         }
         if (tid == 0) { s_prev[0] = width - r[0]; s_prev[1] = height - r[1]; s_prev[2] = r[2]; s_prev[3] = r[3]; s_prev[4] = vanish != 0; }
     }
-    if constexpr (Lossy) {
-        pow_tables_to_lds();
-        __syncthreads();
-        s_glut[tid] = dc::gamma_decode((double)tid / 255.0);    // (256 threads) as k_frame_deltas holds it
-        if (resident)
-            for (unsigned j = tid; j < rows; j += 256) { s_pal[0][j] = pal[j]; s_pal[1][j] = pal[(size_t)rows + j]; s_pal[2][j] = pal[2 * (size_t)rows + j]; }
-    }
-    __syncthreads();
+    if constexpr (Lossy) DeltaLossy::fill(pal, rows);
+    __syncthreads();                                             // (s_acc, s_prev and what fill left)
     unsigned cnt = 0;
     unsigned v[4] = {0, 0, 0, 0};
     const bool cleared = s_prev[4] != 0;
@@ -400,14 +341,7 @@ __global__ __launch_bounds__(256) void k_frame_delta_rgba(const ElemT *m, const 
                 if constexpr (Lossy) {
                     if (c[j] < rows) {                           // (an element that is no row is never an address: the flag fails the call)
                         const unsigned char *q = px + (p + j) * (size_t)ch;
-                        double w[3] = {s_glut[q[0]], s_glut[q[1]], s_glut[q[2]]};
-                        dev_convert_linear<PAMD_SRGB_TO_ICTCP>(w);
-                        double p0, p1, p2;
-                        if (resident) { p0 = s_pal[0][c[j]]; p1 = s_pal[1][c[j]]; p2 = s_pal[2][c[j]]; }
-                        else { p0 = pal[c[j]]; p1 = pal[(size_t)rows + c[j]]; p2 = pal[2 * (size_t)rows + c[j]]; }
-                        const double d0 = w[0] - p0, d1 = w[1] - p1, d2 = w[2] - p2;
-                        const double d = (d0 * d0 + d1 * d1) + d2 * d2;
-                        if (d <= tol2) change = false;           // the entry on the canvas still serves this frame's pixel
+                        if (DeltaLossy::dist2(c[j], q, pal, rows) <= tol2) change = false;   // the canvas entry still serves
                     }
                 }
             }
@@ -424,17 +358,11 @@ __global__ __launch_bounds__(256) void k_frame_delta_rgba(const ElemT *m, const 
     }
     fold_box(v, cnt, cnt != 0, s_acc);
     __syncthreads();
-    if (tid == 0 && s_acc[4] != 0) {
-        const size_t cell = f * (size_t)kDeltaSlots + blockIdx.x % (unsigned)kDeltaSlots;
-        unsigned *box = reinterpret_cast<unsigned *>(words) + cell * 4;
-#pragma unroll
-        for (int j = 0; j < 4; j++) atomicMax(box + j, s_acc[j]);
-        atomicAdd(words + F * (size_t)kDeltaSlots * 4 + cell, (unsigned long long)s_acc[4]);
-    }
+    publish_box(words, f * (size_t)kDeltaSlots + blockIdx.x % (unsigned)kDeltaSlots, F * (size_t)kDeltaSlots * 4, s_acc);
 }
 
-template <typename ElemT, int V>
-static void launch_rgba_typed(const void *d_maps, size_t frames, size_t width, size_t height, size_t rows, int loop, bool lossy,
+template <typename ElemT, int V, bool Lossy>
+static void launch_rgba_typed(const void *d_maps, size_t frames, size_t width, size_t height, size_t rows, int loop,
                               const unsigned char *d_px, int channels, const double *d_pal, double tol2, void *d_delta, void *d_shown,
                               void *d_canvas, unsigned long long *d_words, hipStream_t s) {
     const size_t n = width * height, blocks = ceil_div(n, (size_t)256 * V);
@@ -454,14 +382,10 @@ static void launch_rgba_typed(const void *d_maps, size_t frames, size_t width, s
         ElemT *delta = d_delta ? (ElemT *)d_delta + f * n : nullptr;
         const ElemT *in = f == 0 ? nullptr : (d_shown ? (const ElemT *)d_shown + (f - 1) * n : (const ElemT *)d_canvas);
         ElemT *out = d_shown ? (ElemT *)d_shown + f * n : (ElemT *)d_canvas;
-        const unsigned char *px = lossy ? d_px + f * n * (size_t)channels : nullptr;
-        KTIME("k_frame_delta_rgba", s, ((double)sizeof(ElemT) * (f == 0 ? 2 : 3) + (d_delta ? sizeof(ElemT) : 0) + (lossy ? channels : 0)) * n);
-        if (lossy)
-            hipLaunchKernelGGL((k_frame_delta_rgba<ElemT, true, V>), grid, 256, 0, s, m, in, out, delta, frames, f, n, blocks, (unsigned)rows,
-                               (unsigned)width, (unsigned)height, px, channels, d_pal, tol2, d_words);
-        else
-            hipLaunchKernelGGL((k_frame_delta_rgba<ElemT, false, V>), grid, 256, 0, s, m, in, out, delta, frames, f, n, blocks, (unsigned)rows,
-                               (unsigned)width, (unsigned)height, px, channels, d_pal, tol2, d_words);
+        const unsigned char *px = Lossy ? d_px + f * n * (size_t)channels : nullptr;
+        KTIME("k_frame_delta_rgba", s, ((double)sizeof(ElemT) * (f == 0 ? 2 : 3) + (d_delta ? sizeof(ElemT) : 0) + (Lossy ? channels : 0)) * n);
+        hipLaunchKernelGGL((k_frame_delta_rgba<ElemT, Lossy, V>), grid, 256, 0, s, m, in, out, delta, frames, f, n, blocks, (unsigned)rows,
+                           (unsigned)width, (unsigned)height, px, channels, d_pal, tol2, d_words);
         HIP_CHECK(hipGetLastError());
     }
 }
@@ -477,14 +401,11 @@ void launch_frame_deltas_rgba(const void *d_maps, int elem_bytes, size_t frames,
     if (lossy && (!d_px || !d_pal || rows < 1)) throw HipError("patolette_amd: the lossy frame deltas need pixels and a palette");
     if (!d_shown && !d_canvas) throw HipError("patolette_amd: the RGBA frame deltas need a canvas");
     HIP_CHECK(hipMemsetAsync(d_words, 0, frame_deltas_rgba_words(frames) * sizeof(unsigned long long), s));
-    // four positions per lane by the rule of launch_frame_deltas
-    const uintptr_t all = (uintptr_t)d_maps | (uintptr_t)d_delta | (uintptr_t)d_shown | (uintptr_t)d_canvas;
-    const int mode = g_delta_quad.load(std::memory_order_relaxed);
-    const bool quad = n % 4 == 0 && all % (4 * (uintptr_t)elem_bytes) == 0 && (mode < 0 ? n >= (size_t)num_cus() * 32 * 256 : mode == 1);
-#define PAMD_DELTA_LAUNCH(E, V) launch_rgba_typed<E, V>(d_maps, frames, width, height, rows, loop, lossy, d_px, channels, d_pal, tol2, d_delta, d_shown, d_canvas, d_words, s)
-    if (elem_bytes == 1) { if (quad) PAMD_DELTA_LAUNCH(unsigned char, 4); else PAMD_DELTA_LAUNCH(unsigned char, 1); }
-    else { if (quad) PAMD_DELTA_LAUNCH(unsigned int, 4); else PAMD_DELTA_LAUNCH(unsigned int, 1); }
-#undef PAMD_DELTA_LAUNCH
+    const bool quad = delta_quad(n, (uintptr_t)d_maps | (uintptr_t)d_delta | (uintptr_t)d_shown | (uintptr_t)d_canvas, elem_bytes);
+    delta_dispatch(elem_bytes, quad, lossy, [&](auto elem, auto v, auto is_lossy) {
+        launch_rgba_typed<decltype(elem), decltype(v)::value, decltype(is_lossy)::value>(d_maps, frames, width, height, rows, loop, d_px, channels, d_pal,
+                                                                                        tol2, d_delta, d_shown, d_canvas, d_words, s);
+    });
 }
 
 }  // namespace pamd

@@ -1,9 +1,11 @@
-// given.h -- what the caller gives the palette-given entries (remap, frame_deltas, measure; include/patolette_amd.h) and what their index
-// maps look like on either side of the link: each rule once.  Host code only (no HIP header): tests/given_check.cpp runs it under
-// sanitizers over buffers of exactly the sizes the ABI documents.
+// given.h -- what the caller gives the palette-given entries (remap, frame_deltas, measure; include/patolette_amd.h), what their index
+// maps look like on either side of the link, and what the host makes of the frame deltas' slots: each rule once.  Host code only (no
+// HIP header): tests/given_check.cpp runs it under sanitizers over buffers of exactly the sizes the ABI documents.  The device's side
+// of the shared rules is given_device.h.
 #pragma once
 #include <cmath>
 #include <cstddef>
+#include <cstdint>
 #include <vector>
 
 namespace pamd {
@@ -50,6 +52,14 @@ inline GivenPaletteError given_palette(const double *palette, const unsigned cha
     }
     out.k = k;
     return kGivenPaletteOk;
+}
+
+// Rows first .. rows - 1 of p8 ((r, g, b) bytes) as one word each, r in the low byte, with `high` or-ed in (0xFF000000: the row's
+// opaque RGBA word); the rows below `first` are 0
+inline std::vector<unsigned> given_row_words(const std::vector<unsigned char> &p8, size_t rows, size_t first = 0, unsigned high = 0) {
+    std::vector<unsigned> w(rows, 0u);
+    for (size_t i = first; i < rows; i++) w[i] = (unsigned)p8[3 * i] | (unsigned)p8[3 * i + 1] << 8 | (unsigned)p8[3 * i + 2] << 16 | high;
+    return w;
 }
 
 // An index map's elements: `eb` bytes each as the caller holds them, `me` on the device.  Device maps are used as they are; of host
@@ -104,6 +114,34 @@ inline void given_elems_out(const void *src, int me, void *dst, int eb, size_t l
                             unsigned long long T = 0) {
     auto from = [&](auto *s) { subst ? given_elems_out_to<true>(s, dst, eb, lo, hi, Td, T) : given_elems_out_to<false>(s, dst, eb, lo, hi, Td, T); };
     if (me == 1) from((const unsigned char *)src); else from((const unsigned int *)src);
+}
+
+// What the frame-delta kernels leave for one frame, folded into what the caller gets.  A box arrives spread over `slots` cells of
+// four unsigned each, every cell as maxima over zero of (width - x0, height - y0, x1 + 1, y1 + 1): an empty box is all zero, a union
+// the element-wise maximum.  c_box, cnt: the cells and counts of the changed positions (C).  v_box: the cells of the positions that
+// vanish in the next frame (V), or null for plain maps, which have no such box.  full: the frame is the whole first map whatever the
+// cells hold (plain maps, frame 0).
+//   rect   (x0, y0, w, h) of the smallest box that holds C and V; (0, 0, 0, 0) when both are empty (no cell has an x1 + 1)
+//   count  the changed positions;  vanish: V is not empty (RGBA maps: disposal 2)
+struct GivenFrameFold { int32_t rect[4]; unsigned long long count; bool vanish; };
+inline GivenFrameFold given_fold_frame(const unsigned *c_box, const unsigned *v_box, const unsigned long long *cnt, int slots, size_t width,
+                                       size_t height, bool full) {
+    unsigned m[4] = {0, 0, 0, 0};
+    GivenFrameFold out{{0, 0, 0, 0}, 0, false};
+    for (int j = 0; j < slots; j++) {
+        for (int a = 0; a < 4; a++) {
+            if (c_box[4 * j + a] > m[a]) m[a] = c_box[4 * j + a];
+            if (v_box && v_box[4 * j + a] > m[a]) m[a] = v_box[4 * j + a];
+        }
+        if (v_box && v_box[4 * j + 2] != 0) out.vanish = true;
+        out.count += cnt[j];
+    }
+    if (full) { m[0] = m[2] = (unsigned)width; m[1] = m[3] = (unsigned)height; out.count = (unsigned long long)width * height; }
+    if (m[2] != 0) {
+        const unsigned x0 = (unsigned)width - m[0], y0 = (unsigned)height - m[1];
+        out.rect[0] = (int32_t)x0; out.rect[1] = (int32_t)y0; out.rect[2] = (int32_t)(m[2] - x0); out.rect[3] = (int32_t)(m[3] - y0);
+    }
+    return out;
 }
 
 }  // namespace pamd

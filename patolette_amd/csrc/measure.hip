@@ -13,12 +13,11 @@
 // result), wavefronts through four LDS cells as (w0 + w1) + (w2 + w3), and the tile's record leaves with a plain vector store.
 // k_measure_fold folds a frame's records: thread t adds records t, t + 256, ... in ascending order, then a halving tree.  No
 // floating-point atomic in this file: d_sum is a function of the arguments alone.
-// The ICtCp part is the byte route of k_frame_deltas<.., true, ..>: companding from a 256-entry table in LDS, dev_convert_linear with
-// the pow tables in LDS, the palette row read by index from LDS (from global memory beyond the chunk).
+// The ICtCp part is the lossy compare of the frame deltas (given_device.h, LossyLds), over kMeasureChunk rows.
 #include "measure.h"
 
 #define PAMD_POW_TABLES_IN_LDS
-#include "color_device.h"
+#include "given_device.h"
 
 namespace pamd {
 
@@ -30,27 +29,18 @@ __global__ __launch_bounds__(256) void k_measure(const ElemT *__restrict__ maps,
     constexpr int C = kMeasureChunk;
     __shared__ unsigned long long s_sse[C];
     __shared__ unsigned s_cnt[C], s_max[C], s_p8[C];
-    __shared__ double s_pal[WithD ? 3 : 1][WithD ? C : 1];
-    __shared__ double s_glut[WithD ? 256 : 1];
     __shared__ unsigned long long s_fsse;
     __shared__ unsigned s_fcnt, s_fmax;
     __shared__ double s_wsum[4], s_wmax[4];
     const unsigned tid = threadIdx.x, lane = tid & 63u;
     const bool resident = rows <= (unsigned)C;
-    if constexpr (WithD) {
-        pow_tables_to_lds();
-        __syncthreads();
-        s_glut[tid] = dc::gamma_decode((double)tid / 255.0);    // (256 threads) sRGB.c:70-89 of every byte value, as k_nn_map_u8 holds it
-    }
+    if constexpr (WithD) LossyLds<C>::fill(pal, rows);          // (the barrier below publishes it)
     // a row's cell exists 2^copies_log2 times (measure_copies_log2: as many as the chunk holds), a lane takes copy lane % copies: the
     // lanes of one LDS atomic that name one row -- most of a wavefront on a smooth image -- then queue at that many addresses, not one
     const unsigned copy = lane & ((1u << copies_log2) - 1u);
     if (resident) {
         for (unsigned j = tid; j < (rows << copies_log2); j += 256) { s_sse[j] = 0; s_cnt[j] = 0; s_max[j] = 0; }
-        for (unsigned j = tid; j < rows; j += 256) {
-            s_p8[j] = p8[j];
-            if constexpr (WithD) { s_pal[0][j] = pal[j]; s_pal[1][j] = pal[(size_t)rows + j]; s_pal[2][j] = pal[2 * (size_t)rows + j]; }
-        }
+        for (unsigned j = tid; j < rows; j += 256) s_p8[j] = p8[j];
     }
     if (tid == 0) { s_fsse = 0; s_fcnt = 0; s_fmax = 0; }
     __syncthreads();
@@ -66,7 +56,7 @@ __global__ __launch_bounds__(256) void k_measure(const ElemT *__restrict__ maps,
         if (skip_on && a == skip) continue;
         if (a >= rows) { bad = true; continue; }                 // (an element that is no row is never an address: `bad` fails the call)
         const unsigned char *q = px + (base + p) * (size_t)ch;
-        const unsigned b0 = q[0], b1 = q[1], b2 = q[2];
+        const unsigned b0 = q[0], b1 = q[1], b2 = q[2], b[3] = {b0, b1, b2};
         const unsigned row = resident ? s_p8[a] : p8[a];
         const int e0 = (int)b0 - (int)(row & 255u), e1 = (int)b1 - (int)((row >> 8) & 255u), e2 = (int)b2 - (int)((row >> 16) & 255u);
         const unsigned e = (unsigned)(e0 * e0 + e1 * e1 + e2 * e2);
@@ -83,13 +73,7 @@ __global__ __launch_bounds__(256) void k_measure(const ElemT *__restrict__ maps,
             atomicAdd(e_sse + cell, (unsigned long long)e);
         }
         if constexpr (WithD) {
-            double v[3] = {s_glut[b0], s_glut[b1], s_glut[b2]};
-            dev_convert_linear<PAMD_SRGB_TO_ICTCP>(v);
-            double q0, q1, q2;
-            if (resident) { q0 = s_pal[0][a]; q1 = s_pal[1][a]; q2 = s_pal[2][a]; }
-            else { q0 = pal[a]; q1 = pal[(size_t)rows + a]; q2 = pal[2 * (size_t)rows + a]; }
-            const double d0 = v[0] - q0, d1 = v[1] - q1, d2 = v[2] - q2;
-            const double d = (d0 * d0 + d1 * d1) + d2 * d2;
+            const double d = LossyLds<C>::dist2(a, b, pal, rows);
             ds += d;
             dm = d > dm ? d : dm;
         }

@@ -2677,6 +2677,26 @@ static void run_u8(Engine &E, size_t width, size_t height, const unsigned char *
     E.stats.ms_total += up + E.stats.ms_download;
 }
 
+// The frame around a run over pixels or maps the caller gives (the remaps, frame deltas, measure, gif_lzw): construction takes the
+// start time, points the workspace at the engine's streams and resets the statistics; lap() writes the named lap (the time since the
+// lap before it, or the start); done() the total.  Nothing happens on the way out: a run that throws leaves E.stats as far as it got.
+struct GivenRun {
+    Engine &E;
+    const double t_start;
+    double t_lap;
+    WsGuard wg;
+    explicit GivenRun(Engine &e) : E(e), t_start(now_ms()), t_lap(t_start), wg(&e.stream, &e.stream2) { E.stats = patolette_amd__Stats{}; }
+    void lap(double patolette_amd__Stats::*field) { const double t = now_ms(); E.stats.*field = t - t_lap; t_lap = t; }
+    void done() { E.stats.ms_total = now_ms() - t_start; }
+    // `count` words the kernels left at d, on the host once everything enqueued has run
+    std::vector<unsigned long long> words(const unsigned long long *d, size_t count) {
+        std::vector<unsigned long long> w(count);
+        HIP_CHECK(hipMemcpyAsync(w.data(), d, count * sizeof(unsigned long long), hipMemcpyDeviceToHost, E.stream));
+        E.sync();
+        return w;
+    }
+};
+
 // --------------------------------------------------------------------------------------------
 // remap: 8-bit pixels onto a palette the caller gives (include/patolette_amd.h, patolette_amd_remap_u8)
 // --------------------------------------------------------------------------------------------
@@ -2719,9 +2739,7 @@ static void run_remap(Engine &E, size_t frames, size_t width, size_t height, con
     const bool dither = mode == kRemapRiemersma, ordered = mode == kRemapOrdered;
     const size_t n = width * height, N = frames * n;
     hipStream_t s = E.stream;
-    const double t_start = now_ms();
-    WsGuard wg(&E.stream, &E.stream2);
-    E.stats = patolette_amd__Stats{};
+    GivenRun run(E);
     const int me = map_elem_for(K8);
     const bool lanes = dither && (frames > 1 ? dither_frames_lane_layout(frames, width, height, (int)k) : dither_lane_layout(width, height, (int)k));
     const bool fused = ordered || (!g_remap_two_pass.load(std::memory_order_relaxed) && (dither ? lanes : nn_map_u8_applies(N, (int)k)));
@@ -2737,9 +2755,8 @@ static void run_remap(Engine &E, size_t frames, size_t width, size_t height, con
         HIP_CHECK(hipStreamSynchronize(s));
         d_px = E.src8.p;
     }
-    E.stats.ms_upload = now_ms() - t_start;
+    run.lap(&patolette_amd__Stats::ms_upload);
     // the palette into the space its map compares in (patolette.c:268-299 for colour space sRGB, resp. :300-324)
-    double t0 = now_ms();
     palette_rows(pal, k, dither ? hm::color::srgb_to_rec2020 : hm::color::srgb_to_ictcp);
     E.map_palette = pal;
     if (want) {
@@ -2759,11 +2776,10 @@ static void run_remap(Engine &E, size_t frames, size_t width, size_t height, con
         }
         E.sync();
     }
-    E.stats.ms_map = now_ms() - t0;
-    t0 = now_ms();
+    run.lap(&patolette_amd__Stats::ms_map);
     if (want && map_touched(dither, width, height)) u8_outputs(E, d_map, N, p8.data(), K8, map_out, map_elem_out, quant_out, on_device);
-    E.stats.ms_download = now_ms() - t0;
-    E.stats.ms_total = now_ms() - t_start;
+    run.lap(&patolette_amd__Stats::ms_download);
+    run.done();
 }
 
 // --------------------------------------------------------------------------------------------
@@ -2799,9 +2815,7 @@ static void run_remap_rgba(Engine &E, size_t frames, size_t width, size_t height
     const bool dither = mode == kRemapRiemersma, ordered = mode == kRemapOrdered;
     const size_t n = width * height, N = frames * n, rows = off + k;
     hipStream_t s = E.stream;
-    const double t_start = now_ms();
-    WsGuard wg(&E.stream, &E.stream2);
-    E.stats = patolette_amd__Stats{};
+    GivenRun run(E);
     auto aligned = [](const void *p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; };
     if (on_device && ((map_out && !aligned(map_out, (size_t)map_elem_out)) || (quant_out && !aligned(quant_out, 4))))
         throw HipError("patolette_amd_remap_rgba_device: palette_map and quantized must be aligned to their element size");
@@ -2831,8 +2845,7 @@ static void run_remap_rgba(Engine &E, size_t frames, size_t width, size_t height
         HIP_CHECK(hipStreamSynchronize(s));
         d_px = E.src8.p;
     }
-    E.stats.ms_upload = now_ms() - t_start;
-    double t0 = now_ms();
+    run.lap(&patolette_amd__Stats::ms_upload);
     palette_rows(pal, k, dither ? hm::color::srgb_to_rec2020 : hm::color::srgb_to_ictcp);   // as run_remap takes its palette
     E.map_palette = pal;
     void *d_map = map_out ? (on_device ? map_out : (void *)E.rgba_map.p) : nullptr;
@@ -2893,14 +2906,13 @@ static void run_remap_rgba(Engine &E, size_t frames, size_t width, size_t height
         h_words[0] = 0;
     }
     E.sync();                                                         // (palw is the caller's local: the copy must have left the host)
-    E.stats.ms_map = now_ms() - t0;
-    t0 = now_ms();
+    run.lap(&patolette_amd__Stats::ms_map);
     if (h_words[0] & 1) throw HipError(kNoEntry);
     if (!on_device && map_out) HIP_CHECK(hipMemcpyAsync(map_out, d_map, N * (size_t)map_elem_out, hipMemcpyDeviceToHost, s));
     if (!on_device && quant_out) HIP_CHECK(hipMemcpyAsync(quant_out, d_q, 4 * N, hipMemcpyDeviceToHost, s));
     E.sync();
-    E.stats.ms_download = now_ms() - t0;
-    E.stats.ms_total = now_ms() - t_start;
+    run.lap(&patolette_amd__Stats::ms_download);
+    run.done();
 }
 
 // --------------------------------------------------------------------------------------------
@@ -2921,104 +2933,38 @@ static void stage_given(Engine &E, const void *maps, int eb, int me, size_t N, G
     HIP_CHECK(hipStreamSynchronize(s));
 }
 
+// The two flavours of the frame deltas: plain maps (patolette_amd_frame_deltas) and maps whose index 0 is the transparent entry
+// (patolette_amd_frame_deltas_rgba).  delta.h lays out the words the kernels leave.
+struct DeltaFlavour {
+    const char *bad_element;       // what a raised flag says
+    bool v_boxes;                  // per frame a second box, V (what vanishes in the next frame): 5 words a slot instead of 3, and a disposal
+    bool first_full;               // frame 0 is the full first map whatever the kernels counted
+    bool free_index;               // the caller's transparent index T, an index no entry uses, travels as given_transparent_on_device(T)
+};
+static const DeltaFlavour kPlainDeltas{"patolette_amd_frame_deltas: a map element is not below palette_rows, or names a dropped trailing (-1, -1, -1) row",
+                                       false, true, true};
+static const DeltaFlavour kRgbaDeltas{"patolette_amd_frame_deltas_rgba: a map element is not below palette_rows, or names a dropped trailing (-1, -1, -1) row",
+                                      true, false, false};
+
 // maps: frames x width x height elements of `eb` bytes; rows: what every element must stay below (lossy: the used rows of pal, planar
-// (rows,3) f64 sRGB; otherwise pal is empty and neither it nor the pixels are read).  `maps`, `pixels`, `delta_out`, `shown_out` are
-// device pointers when `on_device`; rects and changed are host memory.  Every output may be null; delta_out may be maps.
-static void run_frame_deltas(Engine &E, bool on_device, size_t frames, size_t width, size_t height, const void *maps, int eb, size_t rows, size_t T,
-                             const unsigned char *pixels, int channels, std::vector<double> pal, double tolerance, void *delta_out,
-                             void *shown_out, int32_t *rects, uint64_t *changed) {
+// (rows,3) f64 sRGB; otherwise pal is empty and neither it nor the pixels are read).  T (plain maps) and loop (RGBA maps): the
+// flavour's own argument.  `maps`, `pixels`, `delta_out`, `shown_out` are device pointers when `on_device`; rects, disposals (RGBA maps)
+// and changed are host memory.  Every output may be null; delta_out may be maps.
+static void run_frame_deltas(Engine &E, const DeltaFlavour &fl, bool on_device, size_t frames, size_t width, size_t height, const void *maps, int eb,
+                             size_t rows, size_t T, int loop, const unsigned char *pixels, int channels, std::vector<double> pal, double tolerance,
+                             void *delta_out, void *shown_out, int32_t *rects, int32_t *disposals, uint64_t *changed) {
     const bool lossy = tolerance > 0.0;
-    const size_t n = width * height, N = frames * n;
+    const size_t n = width * height, N = frames * n, cells = frames * (size_t)kDeltaSlots;
     hipStream_t s = E.stream;
-    const double t_start = now_ms();
-    WsGuard wg(&E.stream, &E.stream2);
-    E.stats = patolette_amd__Stats{};
+    GivenRun run(E);
     const int me = given_device_elem(eb, on_device);
     const unsigned Td = given_transparent_on_device(T);
     // the workspace, before anything is enqueued
-    const size_t words = frame_deltas_words(frames);
+    const size_t words = fl.v_boxes ? frame_deltas_rgba_words(frames) : frame_deltas_words(frames);
     E.dl_words.reserve(words);
-    E.dl_masks.reserve(frame_deltas_masks(frames, n));
+    if (!fl.v_boxes) E.dl_masks.reserve(frame_deltas_masks(frames, n));
     if (!on_device && shown_out) E.dl_shown.reserve(N * (size_t)me);
-    if (lossy) { E.dpal.reserve(3 * rows); E.h_pal.reserve(3 * rows); }
-    const void *d_maps = maps;
-    void *d_delta = delta_out, *d_shown = shown_out;
-    const unsigned char *d_px = pixels;
-    std::vector<unsigned> stage;
-    if (!on_device) {
-        stage_given(E, maps, eb, me, N, GivenSkip{}, 0, lossy ? pixels : nullptr, channels, stage);
-        if (lossy) d_px = E.src8.p;
-        d_maps = E.dl_maps.p;
-        d_delta = delta_out ? E.dl_maps.p : nullptr;                               // in place: the kernel allows it
-        d_shown = shown_out ? E.dl_shown.p : nullptr;
-    }
-    E.stats.ms_upload = now_ms() - t_start;
-    double t0 = now_ms();
-    if (lossy) {
-        palette_rows(pal, rows, hm::color::srgb_to_ictcp);                         // as run_remap's nearest map takes its palette
-        upload_palette(E, pal, rows);
-    }
-    launch_frame_deltas(d_maps, me, frames, width, height, rows, Td, lossy, d_px, channels, lossy ? E.dpal.p : nullptr, tolerance * tolerance,
-                        d_delta, d_shown, E.dl_masks.p, E.dl_words.p, s);
-    std::vector<unsigned long long> w(words);
-    HIP_CHECK(hipMemcpyAsync(w.data(), E.dl_words.p, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    E.sync();
-    E.stats.ms_map = now_ms() - t0;
-    t0 = now_ms();
-    if (w[words - 1] & 1)
-        throw HipError("patolette_amd_frame_deltas: a map element is not below palette_rows, or names a dropped trailing (-1, -1, -1) row");
-    const unsigned *box = reinterpret_cast<const unsigned *>(w.data());
-    const unsigned long long *cnt = w.data() + frames * (size_t)kDeltaSlots * 2;
-    for (size_t f = 0; f < frames; f++) {
-        unsigned m[4] = {0, 0, 0, 0};
-        unsigned long long count = 0;
-        for (int j = 0; j < kDeltaSlots; j++) {
-            const size_t cell = f * (size_t)kDeltaSlots + j;
-            for (int a = 0; a < 4; a++) m[a] = std::max(m[a], box[cell * 4 + a]);
-            count += cnt[cell];
-        }
-        if (f == 0) { m[0] = (unsigned)width; m[1] = (unsigned)height; m[2] = (unsigned)width; m[3] = (unsigned)height; count = n; }
-        if (changed) changed[f] = count;
-        if (rects) {
-            int32_t *r = rects + 4 * f;
-            if (count == 0) { r[0] = r[1] = r[2] = r[3] = 0; }
-            else {
-                r[0] = (int32_t)(width - m[0]); r[1] = (int32_t)(height - m[1]);
-                r[2] = (int32_t)(m[2] - (width - m[0])); r[3] = (int32_t)(m[3] - (height - m[1]));
-            }
-        }
-    }
-    if (!on_device) {
-        void *outs[2] = {delta_out, shown_out};
-        const void *from[2] = {d_delta, d_shown};
-        for (int o = 0; o < 2; o++) {
-            if (!outs[o]) continue;
-            if (eb == me) { HIP_CHECK(hipMemcpy(outs[o], from[o], N * (size_t)me, hipMemcpyDeviceToHost)); continue; }
-            HIP_CHECK(hipMemcpy(stage.data(), from[o], N * sizeof(unsigned), hipMemcpyDeviceToHost));   // (stage_given sized it; Td becomes T)
-            given_elems_out(stage.data(), me, outs[o], eb, 0, N, true, Td, T);
-        }
-    }
-    E.stats.ms_download = now_ms() - t0;
-    E.stats.ms_total = now_ms() - t_start;
-}
-
-// The same for maps whose index 0 is the transparent entry (include/patolette_amd.h, patolette_amd_frame_deltas_rgba): pointers and
-// palette as run_frame_deltas takes them (row 0 of pal is never read); disposals: host memory like rects.
-static void run_frame_deltas_rgba(Engine &E, bool on_device, size_t frames, size_t width, size_t height, const void *maps, int eb, size_t rows,
-                                  const unsigned char *pixels, int channels, std::vector<double> pal, double tolerance, int loop, void *delta_out,
-                                  void *shown_out, int32_t *rects, int32_t *disposals, uint64_t *changed) {
-    const bool lossy = tolerance > 0.0;
-    const size_t n = width * height, N = frames * n;
-    hipStream_t s = E.stream;
-    const double t_start = now_ms();
-    WsGuard wg(&E.stream, &E.stream2);
-    E.stats = patolette_amd__Stats{};
-    const int me = given_device_elem(eb, on_device);
-    // the workspace, before anything is enqueued
-    const size_t words = frame_deltas_rgba_words(frames);
-    E.dl_words.reserve(words);
-    if (!on_device && shown_out) E.dl_shown.reserve(N * (size_t)me);
-    else if (!shown_out) E.dl_shown.reserve(n * (size_t)me);                       // the canvas between the frames' launches
+    else if (fl.v_boxes && !shown_out) E.dl_shown.reserve(n * (size_t)me);         // the canvas between the frames' launches
     if (lossy) { E.dpal.reserve(3 * rows); E.h_pal.reserve(3 * rows); }
     const void *d_maps = maps;
     void *d_delta = delta_out, *d_shown = shown_out;
@@ -3031,42 +2977,30 @@ static void run_frame_deltas_rgba(Engine &E, bool on_device, size_t frames, size
         d_delta = delta_out ? E.dl_maps.p : nullptr;                               // in place: the kernels allow it
         d_shown = shown_out ? E.dl_shown.p : nullptr;
     }
-    E.stats.ms_upload = now_ms() - t_start;
-    double t0 = now_ms();
+    run.lap(&patolette_amd__Stats::ms_upload);
     if (lossy) {
-        palette_rows(pal, rows, hm::color::srgb_to_ictcp);
+        palette_rows(pal, rows, hm::color::srgb_to_ictcp);                         // as run_remap's nearest map takes its palette
         upload_palette(E, pal, rows);
     }
-    launch_frame_deltas_rgba(d_maps, me, frames, width, height, rows, loop, lossy, d_px, channels, lossy ? E.dpal.p : nullptr, tolerance * tolerance,
-                             d_delta, d_shown, d_shown ? nullptr : E.dl_shown.p, E.dl_words.p, s);
-    std::vector<unsigned long long> w(words);
-    HIP_CHECK(hipMemcpyAsync(w.data(), E.dl_words.p, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    E.sync();
-    E.stats.ms_map = now_ms() - t0;
-    t0 = now_ms();
-    if (w[words - 1] & 1)
-        throw HipError("patolette_amd_frame_deltas_rgba: a map element is not below palette_rows, or names a dropped trailing (-1, -1, -1) row");
-    const unsigned *box = reinterpret_cast<const unsigned *>(w.data());
-    const unsigned long long *cnt = w.data() + frames * (size_t)kDeltaSlots * 4;
+    const double *d_pal = lossy ? E.dpal.p : nullptr;
+    if (fl.v_boxes)
+        launch_frame_deltas_rgba(d_maps, me, frames, width, height, rows, loop, lossy, d_px, channels, d_pal, tolerance * tolerance, d_delta, d_shown,
+                                 d_shown ? nullptr : E.dl_shown.p, E.dl_words.p, s);
+    else
+        launch_frame_deltas(d_maps, me, frames, width, height, rows, Td, lossy, d_px, channels, d_pal, tolerance * tolerance, d_delta, d_shown,
+                            E.dl_masks.p, E.dl_words.p, s);
+    const std::vector<unsigned long long> w = run.words(E.dl_words.p, words);
+    run.lap(&patolette_amd__Stats::ms_map);
+    if (w[words - 1] & 1) throw HipError(fl.bad_element);
+    const unsigned *box = reinterpret_cast<const unsigned *>(w.data());             // C boxes, V boxes where the flavour has them, then the counts
+    const unsigned long long *cnt = w.data() + cells * (fl.v_boxes ? 4 : 2);
     for (size_t f = 0; f < frames; f++) {
-        unsigned m[4] = {0, 0, 0, 0}, vanish = 0;                                  // C[f] and V[f] united: the maxima of both
-        unsigned long long count = 0;
-        for (int j = 0; j < kDeltaSlots; j++) {
-            const size_t c_cell = f * (size_t)kDeltaSlots + j, v_cell = (frames + f) * (size_t)kDeltaSlots + j;
-            for (int a = 0; a < 4; a++) m[a] = std::max(m[a], std::max(box[c_cell * 4 + a], box[v_cell * 4 + a]));
-            vanish = std::max(vanish, box[v_cell * 4 + 2]);
-            count += cnt[c_cell];
-        }
-        if (changed) changed[f] = count;
-        if (disposals) disposals[f] = vanish ? 2 : 1;
-        if (rects) {
-            int32_t *r = rects + 4 * f;
-            if (m[2] == 0) { r[0] = r[1] = r[2] = r[3] = 0; }
-            else {
-                r[0] = (int32_t)(width - m[0]); r[1] = (int32_t)(height - m[1]);
-                r[2] = (int32_t)(m[2] - (width - m[0])); r[3] = (int32_t)(m[3] - (height - m[1]));
-            }
-        }
+        const size_t at = f * (size_t)kDeltaSlots;
+        const GivenFrameFold r = given_fold_frame(box + 4 * at, fl.v_boxes ? box + 4 * (cells + at) : nullptr, cnt + at, kDeltaSlots, width, height,
+                                                  fl.first_full && f == 0);
+        if (changed) changed[f] = r.count;
+        if (disposals) disposals[f] = r.vanish ? 2 : 1;
+        if (rects) std::memcpy(rects + 4 * f, r.rect, sizeof r.rect);
     }
     if (!on_device) {
         void *outs[2] = {delta_out, shown_out};
@@ -3074,12 +3008,12 @@ static void run_frame_deltas_rgba(Engine &E, bool on_device, size_t frames, size
         for (int o = 0; o < 2; o++) {
             if (!outs[o]) continue;
             if (eb == me) { HIP_CHECK(hipMemcpy(outs[o], from[o], N * (size_t)me, hipMemcpyDeviceToHost)); continue; }
-            HIP_CHECK(hipMemcpy(stage.data(), from[o], N * sizeof(unsigned), hipMemcpyDeviceToHost));   // (stage_given sized it)
-            given_elems_out(stage.data(), me, outs[o], eb, 0, N);
+            HIP_CHECK(hipMemcpy(stage.data(), from[o], N * sizeof(unsigned), hipMemcpyDeviceToHost));   // (stage_given sized it; Td becomes T)
+            given_elems_out(stage.data(), me, outs[o], eb, 0, N, fl.free_index, Td, T);
         }
     }
-    E.stats.ms_download = now_ms() - t0;
-    E.stats.ms_total = now_ms() - t_start;
+    run.lap(&patolette_amd__Stats::ms_download);
+    run.done();
 }
 
 // --------------------------------------------------------------------------------------------
@@ -3098,9 +3032,7 @@ static void run_measure(Engine &E, bool on_device, size_t frames, size_t width, 
                         long long skip, const MeasureOut &out) {
     const size_t n = width * height, N = frames * n;
     hipStream_t s = E.stream;
-    const double t_start = now_ms();
-    WsGuard wg(&E.stream, &E.stream2);
-    E.stats = patolette_amd__Stats{};
+    GivenRun run(E);
     const int me = given_device_elem(eb, on_device);
     const bool with_d = out.frame_d_sum || out.frame_d_max;
     const GivenSkip sk = given_skip_on_device(skip, eb, me, on_device);
@@ -3118,21 +3050,16 @@ static void run_measure(Engine &E, bool on_device, size_t frames, size_t width, 
         d_maps = E.dl_maps.p;
         d_px = E.src8.p;
     }
-    E.stats.ms_upload = now_ms() - t_start;
-    double t0 = now_ms();
-    std::vector<unsigned> rows8(k);
-    for (size_t i = 0; i < k; i++) rows8[i] = (unsigned)p8[3 * i] | (unsigned)p8[3 * i + 1] << 8 | (unsigned)p8[3 * i + 2] << 16;
+    run.lap(&patolette_amd__Stats::ms_upload);
+    const std::vector<unsigned> rows8 = given_row_words(p8, k);
     HIP_CHECK(hipMemcpyAsync(E.ms_p8.p, rows8.data(), k * sizeof(unsigned), hipMemcpyHostToDevice, s));
     if (with_d) {
         palette_rows(pal, k, hm::color::srgb_to_ictcp);                            // as run_remap's nearest map takes its palette
         upload_palette(E, pal, k);
     }
     launch_measure(d_maps, me, frames, n, d_px, channels, k, sk.on, sk.Sd, E.ms_p8.p, with_d ? E.dpal.p : nullptr, E.ms_words.p, E.ms_tiles.p, s);
-    std::vector<unsigned long long> w(words - from);
-    HIP_CHECK(hipMemcpyAsync(w.data(), E.ms_words.p + from, w.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    E.sync();
-    E.stats.ms_map = now_ms() - t0;
-    t0 = now_ms();
+    const std::vector<unsigned long long> w = run.words(E.ms_words.p + from, words - from);
+    run.lap(&patolette_amd__Stats::ms_map);
     if (w[0] & 1)
         throw HipError("patolette_amd_measure: a map element is neither skip_index nor below palette_rows, or names a dropped trailing (-1, -1, -1) row");
     const unsigned long long *er = w.data() + 1, *fr = er + 3 * k;
@@ -3148,8 +3075,8 @@ static void run_measure(Engine &E, bool on_device, size_t frames, size_t width, 
         if (out.frame_d_sum) std::memcpy(out.frame_d_sum + f, fr + 5 * f + 3, sizeof(double));
         if (out.frame_d_max) std::memcpy(out.frame_d_max + f, fr + 5 * f + 4, sizeof(double));
     }
-    E.stats.ms_download = now_ms() - t0;
-    E.stats.ms_total = now_ms() - t_start;
+    run.lap(&patolette_amd__Stats::ms_download);
+    run.done();
 }
 
 // --------------------------------------------------------------------------------------------
@@ -3162,9 +3089,7 @@ static void run_gif_lzw(Engine &E, bool on_device, size_t frames, size_t width, 
                         uint64_t *offsets) {
     const size_t n = width * height, N = frames * n, S = recs[frames].seg0;
     hipStream_t s = E.stream;
-    const double t_start = now_ms();
-    WsGuard wg(&E.stream, &E.stream2);
-    E.stats = patolette_amd__Stats{};
+    GivenRun run(E);
     // the workspace, before anything is enqueued
     const size_t stride = lzw_stage_words(std::min(seg, cap)), words = lzw_words(frames), out_words = bound / 4 + 1;
     E.lz_frames.reserve(frames + 1);
@@ -3179,16 +3104,12 @@ static void run_gif_lzw(Engine &E, bool on_device, size_t frames, size_t width, 
         stage_given(E, maps, 1, 1, N, GivenSkip{}, 0, nullptr, 0, none);
         d_maps = E.dl_maps.p;
     }
-    E.stats.ms_upload = now_ms() - t_start;
-    double t0 = now_ms();
+    run.lap(&patolette_amd__Stats::ms_upload);
     HIP_CHECK(hipMemcpyAsync(E.lz_frames.p, recs.data(), (frames + 1) * sizeof(LzwFrame), hipMemcpyHostToDevice, s));
     launch_lzw(d_maps, frames, n, width, E.lz_frames.p, S, seg, stride, m, E.lz_stage.p, E.lz_bits.p, E.lz_gbit.p, E.lz_words.p, E.lz_out.p,
                out_words, s);
-    std::vector<unsigned long long> w(words);
-    HIP_CHECK(hipMemcpyAsync(w.data(), E.lz_words.p, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    E.sync();
-    E.stats.ms_map = now_ms() - t0;
-    t0 = now_ms();
+    const std::vector<unsigned long long> w = run.words(E.lz_words.p, words);
+    run.lap(&patolette_amd__Stats::ms_map);
     if (w[0] & 1) throw HipError("patolette_amd_gif_lzw: a map element inside a rectangle is not below 2^min_code_size");
     for (size_t f = 0; f <= frames; f++) offsets[f] = w[1 + f];
     const size_t total = (size_t)w[1 + frames];
@@ -3196,8 +3117,8 @@ static void run_gif_lzw(Engine &E, bool on_device, size_t frames, size_t width, 
     if (total > capacity)
         throw HipError("patolette_amd_gif_lzw: capacity is too small: offsets[frames] holds the bytes needed, nothing was copied");
     HIP_CHECK(hipMemcpy(out, E.lz_out.p, total, hipMemcpyDeviceToHost));
-    E.stats.ms_download = now_ms() - t0;
-    E.stats.ms_total = now_ms() - t_start;
+    run.lap(&patolette_amd__Stats::ms_download);
+    run.done();
 }
 
 // The RGBA entry (include/patolette_amd.h, patolette_amd_rgba): the opaque pixels (alpha >= thr) are compacted in row-scan order and
@@ -3384,11 +3305,13 @@ struct ArgCheck {
     const char *name;
     int *exit_code;
     bool fail(int code, const char *text) const { fail_args(exit_code, code, (std::string(name) + ": " + text).c_str()); return false; }
-    // frames of width x height: validate()'s codes with nothing recorded, then at most `cap` pixels in all
-    bool shape(size_t frames, size_t width, size_t height, size_t cap, const char *beyond_cap) const {
+    // frames of width x height: validate()'s codes with nothing recorded, then the cap on the pixels in all -- validate()'s own for one
+    // image, or what the Riemersma walk of a remap numbers
+    bool shape(size_t frames, size_t width, size_t height, bool dither = false) const {
         *exit_code = frames == 0 ? -2 : validate(width, height, 1);
         if (*exit_code != 0) return false;
-        return frames > cap / (width * height) ? fail(-4, beyond_cap) : true;      // (n <= 1.6e9: no overflow before this)
+        if (frames <= (dither ? kDitherFramesMaxPixels : (size_t)40000 * 40000) / (width * height)) return true;   // (n <= 1.6e9: no overflow before this)
+        return fail(-4, dither ? "frames * width * height exceeds 2^31 pixels (the dither numbers pixels with 32 bits)" : "frames * width * height is too big");
     }
     bool map_elem_bytes(bool on_device, int eb) const {
         return (on_device ? (eb != 1 && eb != 4) : (eb != 1 && eb != 2 && eb != 4 && eb != 8))
@@ -3397,10 +3320,19 @@ struct ArgCheck {
     bool rows(size_t palette_rows, const char *text = "palette_rows must lie in [1, 2^31]") const {
         return palette_rows < 1 || palette_rows > ((size_t)1 << 31) ? fail(-1, text) : true;
     }
+    bool one_of(const double *palette, const unsigned char *palette_u8, const char *text = "pass exactly one of palette and palette_u8") const {
+        return (palette != nullptr) == (palette_u8 != nullptr) ? fail(-1, text) : true;
+    }
     bool palette(const double *palette, const unsigned char *palette_u8, size_t palette_rows, bool want_bytes, GivenPalette &out) const {
         const GivenPaletteError e = given_palette(palette, palette_u8, palette_rows, want_bytes, out);
         return e == kGivenPaletteAllFill ? fail(-1, "every palette row is the unused-row fill (-1, -1, -1)")
              : e == kGivenPaletteNotFinite ? fail(-1, "the palette holds a value that is not finite") : true;
+    }
+    // what the frame deltas' lossy mode reads, up to the palette's parse (the caller's: RGBA maps prepare row 0 first)
+    bool lossy(int channels, const unsigned char *pixels, const double *palette, const unsigned char *palette_u8) const {
+        if (channels != 3 && channels != 4) return fail(-1, "channels must be 3 or 4");
+        if (!pixels) return fail(-1, "a tolerance above 0 needs the frames' pixels");
+        return one_of(palette, palette_u8, "a tolerance above 0 needs exactly one of palette and palette_u8");
     }
 };
 
@@ -3607,10 +3539,8 @@ static void remap_entry(bool on_device, size_t frames, size_t width, size_t heig
     // mode: kRemapNearest, kRemapRiemersma, or kRemapOrdered with its `spread` (the ordered map counts pixels as the nearest one does)
     const bool dither = mode == kRemapRiemersma;
     const ArgCheck arg{"patolette_amd_remap", exit_code};
-    if (!arg.shape(frames, width, height, dither ? kDitherFramesMaxPixels : (size_t)40000 * 40000,
-                   dither ? "frames * width * height exceeds 2^31 pixels (the dither numbers pixels with 32 bits)"
-                          : "frames * width * height is too big")) return;
-    if ((palette != nullptr) == (palette_u8 != nullptr)) return (void)arg.fail(-1, "pass exactly one of palette and palette_u8");
+    if (!arg.shape(frames, width, height, dither)) return;
+    if (!arg.one_of(palette, palette_u8)) return;
     if (!arg.rows(palette_rows, "the palette needs at least one row")) return;
     if (validate_u8(palette_rows, channels, palette_map, map_elem_bytes) != 0)
         return (void)arg.fail(-1, "bad channels / map_elem_bytes (1, 2, 4 or 8, able to hold palette_rows - 1)");
@@ -3630,13 +3560,11 @@ static void remap_rgba_entry(bool on_device, size_t frames, size_t width, size_t
                              double spread, void *palette_map, int map_elem_bytes, unsigned char *quantized, int *exit_code) {
     const bool dither = mode == kRemapRiemersma;
     const ArgCheck arg{"patolette_amd_remap_rgba", exit_code};
-    if (!arg.shape(frames, width, height, dither ? kDitherFramesMaxPixels : (size_t)40000 * 40000,
-                   dither ? "frames * width * height exceeds 2^31 pixels (the dither numbers pixels with 32 bits)"
-                          : "frames * width * height is too big")) return;
+    if (!arg.shape(frames, width, height, dither)) return;
     if (mode != kRemapNearest && mode != kRemapRiemersma && mode != kRemapOrdered) return (void)arg.fail(-1, "mode must be 0 (nearest), 1 (Riemersma) or 2 (ordered)");
     if (alpha_threshold < 0 || alpha_threshold > 256) return (void)arg.fail(-1, "alpha_threshold must lie in [0, 256]");
     if (transparent_index != -1 && transparent_index != 0) return (void)arg.fail(-1, "transparent_index must be -1 (none) or 0 (row 0)");
-    if ((palette != nullptr) == (palette_u8 != nullptr)) return (void)arg.fail(-1, "pass exactly one of palette and palette_u8");
+    if (!arg.one_of(palette, palette_u8)) return;
     if (!arg.rows(palette_rows, "the palette needs at least one row")) return;
     if (validate_u8(palette_rows, 4, palette_map, map_elem_bytes) != 0)
         return (void)arg.fail(-1, "bad map_elem_bytes (1, 2, 4 or 8, able to hold palette_rows - 1)");
@@ -3650,8 +3578,7 @@ static void remap_rgba_entry(bool on_device, size_t frames, size_t width, size_t
     const size_t k = g.k - off;
     std::vector<double> pal(3 * k);
     for (int c = 0; c < 3; c++) for (size_t i = 0; i < k; i++) pal[(size_t)c * k + i] = g.pal[(size_t)c * g.k + off + i];
-    std::vector<unsigned> palw(g.k, 0u);
-    for (size_t i = off; i < g.k; i++) palw[i] = (unsigned)g.p8[3 * i] | (unsigned)g.p8[3 * i + 1] << 8 | (unsigned)g.p8[3 * i + 2] << 16 | 0xFF000000u;
+    const std::vector<unsigned> palw = given_row_words(g.p8, g.k, off, 0xFF000000u);
     *exit_code = guarded([&](Engine &E) {
         run_remap_rgba(E, frames, width, height, pixels, alpha_threshold, std::move(pal), k, palw, (unsigned)off, mode, spread, palette_map,
                        map_elem_bytes, quantized, on_device);
@@ -3664,7 +3591,7 @@ static void frame_deltas_entry(bool on_device, size_t frames, size_t width, size
                                const unsigned char *palette_u8, double tolerance, void *delta_maps, void *shown_maps, int32_t *rects,
                                uint64_t *changed, int *exit_code) {
     const ArgCheck arg{"patolette_amd_frame_deltas", exit_code};
-    if (!arg.shape(frames, width, height, (size_t)40000 * 40000, "frames * width * height is too big")) return;   // the nearest remap's cap
+    if (!arg.shape(frames, width, height)) return;
     const int eb = map_elem_bytes;
     if (!arg.map_elem_bytes(on_device, eb)) return;
     if (!palette_maps) return (void)arg.fail(-1, "no maps");
@@ -3677,24 +3604,22 @@ static void frame_deltas_entry(bool on_device, size_t frames, size_t width, size
     GivenPalette g;
     g.k = palette_rows;
     if (tolerance > 0.0) {                                                            // the lossy mode reads pixels and one palette
-        if (channels != 3 && channels != 4) return (void)arg.fail(-1, "channels must be 3 or 4");
-        if (!pixels) return (void)arg.fail(-1, "a tolerance above 0 needs the frames' pixels");
-        if ((palette != nullptr) == (palette_u8 != nullptr)) return (void)arg.fail(-1, "a tolerance above 0 needs exactly one of palette and palette_u8");
+        if (!arg.lossy(channels, pixels, palette, palette_u8)) return;
         if (!arg.palette(palette, palette_u8, palette_rows, false, g)) return;
     }
     *exit_code = guarded([&](Engine &E) {
-        run_frame_deltas(E, on_device, frames, width, height, palette_maps, eb, g.k, transparent_index, pixels, channels, std::move(g.pal), tolerance,
-                         delta_maps, shown_maps, rects, changed);
+        run_frame_deltas(E, kPlainDeltas, on_device, frames, width, height, palette_maps, eb, g.k, transparent_index, 0, pixels, channels,
+                         std::move(g.pal), tolerance, delta_maps, shown_maps, rects, nullptr, changed);
     });
 }
 
-// the deltas of maps whose index 0 is the transparent entry (include/patolette_amd.h): the arguments, then run_frame_deltas_rgba
+// the deltas of maps whose index 0 is the transparent entry (include/patolette_amd.h): the arguments, then run_frame_deltas
 static void frame_deltas_rgba_entry(bool on_device, size_t frames, size_t width, size_t height, const void *palette_maps, int map_elem_bytes,
                                     size_t palette_rows, const unsigned char *pixels, int channels, const double *palette,
                                     const unsigned char *palette_u8, double tolerance, int loop, void *delta_maps, void *shown_maps, int32_t *rects,
                                     int32_t *disposals, uint64_t *changed, int *exit_code) {
     const ArgCheck arg{"patolette_amd_frame_deltas_rgba", exit_code};
-    if (!arg.shape(frames, width, height, (size_t)40000 * 40000, "frames * width * height is too big")) return;   // the nearest remap's cap
+    if (!arg.shape(frames, width, height)) return;
     const int eb = map_elem_bytes;
     if (!arg.map_elem_bytes(on_device, eb)) return;
     if (!palette_maps) return (void)arg.fail(-1, "no maps");
@@ -3704,9 +3629,7 @@ static void frame_deltas_rgba_entry(bool on_device, size_t frames, size_t width,
     GivenPalette g;
     g.k = palette_rows;
     if (tolerance > 0.0) {                                                            // the lossy mode reads pixels and one palette
-        if (channels != 3 && channels != 4) return (void)arg.fail(-1, "channels must be 3 or 4");
-        if (!pixels) return (void)arg.fail(-1, "a tolerance above 0 needs the frames' pixels");
-        if ((palette != nullptr) == (palette_u8 != nullptr)) return (void)arg.fail(-1, "a tolerance above 0 needs exactly one of palette and palette_u8");
+        if (!arg.lossy(channels, pixels, palette, palette_u8)) return;
         std::vector<double> opaque;                                                   // row 0 is the transparent entry: its colour is never read
         if (palette) {
             opaque.assign(palette, palette + 3 * palette_rows);
@@ -3715,8 +3638,8 @@ static void frame_deltas_rgba_entry(bool on_device, size_t frames, size_t width,
         if (!arg.palette(palette ? opaque.data() : nullptr, palette_u8, palette_rows, false, g)) return;
     }
     *exit_code = guarded([&](Engine &E) {
-        run_frame_deltas_rgba(E, on_device, frames, width, height, palette_maps, eb, g.k, pixels, channels, std::move(g.pal), tolerance, loop,
-                              delta_maps, shown_maps, rects, disposals, changed);
+        run_frame_deltas(E, kRgbaDeltas, on_device, frames, width, height, palette_maps, eb, g.k, 0, loop, pixels, channels, std::move(g.pal), tolerance,
+                         delta_maps, shown_maps, rects, disposals, changed);
     });
 }
 
@@ -3725,13 +3648,13 @@ static void measure_entry(bool on_device, size_t frames, size_t width, size_t he
                           const void *palette_maps, int map_elem_bytes, const double *palette, const unsigned char *palette_u8, size_t palette_rows,
                           long long skip_index, const MeasureOut &out, int *exit_code) {
     const ArgCheck arg{"patolette_amd_measure", exit_code};
-    if (!arg.shape(frames, width, height, (size_t)40000 * 40000, "frames * width * height is too big")) return;   // the nearest remap's cap
+    if (!arg.shape(frames, width, height)) return;
     const int eb = map_elem_bytes;
     if (channels != 3 && channels != 4) return (void)arg.fail(-1, "channels must be 3 or 4");
     if (!arg.map_elem_bytes(on_device, eb)) return;
     if (!pixels) return (void)arg.fail(-1, "no pixels");
     if (!palette_maps) return (void)arg.fail(-1, "no maps");
-    if ((palette != nullptr) == (palette_u8 != nullptr)) return (void)arg.fail(-1, "pass exactly one of palette and palette_u8");
+    if (!arg.one_of(palette, palette_u8)) return;
     if (!arg.rows(palette_rows)) return;
     if (skip_index < -1) return (void)arg.fail(-1, "skip_index must be -1 (none) or an index");
     GivenPalette g;                                                        // with the bytes the integer part compares with
@@ -3745,7 +3668,7 @@ static void measure_entry(bool on_device, size_t frames, size_t width, size_t he
 static void gif_lzw_entry(bool on_device, size_t frames, size_t width, size_t height, const unsigned char *maps, const int32_t *rects,
                           int min_code_size, size_t segment, unsigned char *out, size_t capacity, uint64_t *offsets, int *exit_code) {
     const ArgCheck arg{"patolette_amd_gif_lzw", exit_code};
-    if (!arg.shape(frames, width, height, (size_t)40000 * 40000, "frames * width * height is too big")) return;   // the nearest remap's cap
+    if (!arg.shape(frames, width, height)) return;
     if (!maps) return (void)arg.fail(-1, "no maps");
     if (!offsets) return (void)arg.fail(-1, "no offsets");
     if (!out && capacity > 0) return (void)arg.fail(-1, "no out");

@@ -1,5 +1,6 @@
 // given_check.cpp -- the palette-given entries' host rules (csrc/given.h: the caller's palette, index elements in and out, the device's
-// values of the transparent and skip indices) against a per-element restatement of what the header documents.  Host code only:
+// values of the transparent and skip indices, the frame deltas' slots folded into rectangle, count and disposal) against a per-element
+// restatement of what the header documents.  Host code only:
 // test_given_host.py builds this with -fsanitize=address,undefined and runs it.  Every buffer is on the heap at exactly the size the ABI
 // documents, so a read or write past it is caught.  Exit status 0 and a line of counts: every case agreed, and every class occurred.
 #include <algorithm>
@@ -211,11 +212,78 @@ bool check_out_from(Counts &c) {
     }
     return check_out<S, u64>(0, 0, 0, false, 0, 0, c);
 }
+
+// ---- the frame deltas' words, folded ----------------------------------------------------------------------------------------------
+// The kernels' words as csrc/delta.h lays them out, restated: per frame and slot a box of four unsigned (two words), for RGBA maps a
+// second such box (V), then per frame and slot a count, then the flag word.
+constexpr int kSlots = 32;
+size_t words_plain(size_t frames) { return frames * kSlots * 3 + 1; }
+size_t words_rgba(size_t frames) { return frames * kSlots * 5 + 1; }
+
+struct Pos { unsigned x, y; int slot; };
+struct FrameCase { std::vector<Pos> changed, vanish; };
+
+// what include/patolette_amd.h says of a frame: the tight box of the changed and the vanishing positions as (x0, y0, w, h), (0, 0, 0, 0)
+// when there is none; their number; disposal 2 iff something vanishes; frame 0 of plain maps is the full frame with n changed
+bool check_fold(bool rgba, unsigned width, unsigned height, const std::vector<FrameCase> &frames, long &cases) {
+    const size_t F = frames.size(), cells = F * kSlots, words = rgba ? words_rgba(F) : words_plain(F);
+    std::unique_ptr<u64[]> w(new u64[words]);
+    std::fill(w.get(), w.get() + words, 0ull);
+    unsigned *box = reinterpret_cast<unsigned *>(w.get());
+    u64 *cnt = w.get() + cells * (rgba ? 4 : 2);
+    auto put = [&](size_t cell, const Pos &p) {                     // as the kernels keep a box: maxima over zero
+        unsigned *b = box + 4 * cell;
+        b[0] = std::max(b[0], width - p.x); b[1] = std::max(b[1], height - p.y); b[2] = std::max(b[2], p.x + 1); b[3] = std::max(b[3], p.y + 1);
+    };
+    for (size_t f = 0; f < F; f++) {
+        for (const Pos &p : frames[f].changed) { put(f * kSlots + p.slot, p); cnt[f * kSlots + p.slot]++; }
+        if (rgba) for (const Pos &p : frames[f].vanish) put(cells + f * kSlots + p.slot, p);
+    }
+    for (size_t f = 0; f < F; f++) {
+        const GivenFrameFold got = given_fold_frame(box + 4 * f * kSlots, rgba ? box + 4 * (cells + f * kSlots) : nullptr, cnt + f * kSlots, kSlots,
+                                                    width, height, !rgba && f == 0);
+        std::vector<Pos> all = frames[f].changed;
+        if (rgba) all.insert(all.end(), frames[f].vanish.begin(), frames[f].vanish.end());
+        int want[4] = {0, 0, 0, 0};
+        u64 count = frames[f].changed.size();
+        if (!rgba && f == 0) { want[2] = (int)width; want[3] = (int)height; count = (u64)width * height; }
+        else if (!all.empty()) {
+            unsigned x0 = width, y0 = height, x1 = 0, y1 = 0;
+            for (const Pos &p : all) { x0 = std::min(x0, p.x); y0 = std::min(y0, p.y); x1 = std::max(x1, p.x); y1 = std::max(y1, p.y); }
+            want[0] = (int)x0; want[1] = (int)y0; want[2] = (int)(x1 - x0 + 1); want[3] = (int)(y1 - y0 + 1);
+        }
+        for (int a = 0; a < 4; a++) if (got.rect[a] != want[a]) return fail("fold: rectangle", (long)f, a);
+        if (got.count != count) return fail("fold: count", (long)f, (long)got.count);
+        if (got.vanish != (rgba && !frames[f].vanish.empty())) return fail("fold: vanish", (long)f);
+        cases++;
+    }
+    return true;
+}
+
+bool check_folds(long &cases) {
+    const unsigned W = 7, H = 5;
+    const FrameCase empty{}, first{{{0, 0, 0}}, {}}, last{{{W - 1, H - 1, 31}}, {}};
+    // every maximum in a slot of its own: x0 from slot 3, y0 from 9, x1 from 17, y1 from 30; two positions share a slot
+    const FrameCase spread{{{1, 3, 3}, {4, 1, 9}, {5, 2, 17}, {2, 4, 30}, {3, 3, 30}}, {}};
+    const FrameCase disjoint{{{0, 0, 1}, {1, 1, 2}}, {{5, 3, 1}, {6, 4, 7}}};          // C top left, V bottom right: the union, disposal 2
+    const FrameCase only_v{{}, {{2, 2, 0}}};                                          // nothing changes, something vanishes: a rectangle still
+    for (bool rgba : {false, true}) {
+        // frame 0: the override for plain maps (whatever its cells hold), a frame like any other for RGBA maps
+        if (!check_fold(rgba, W, H, {empty, empty, first, last, spread}, cases)) return false;
+        if (!check_fold(rgba, W, H, {first, spread, empty}, cases)) return false;
+        if (!check_fold(rgba, W, H, {disjoint, only_v, disjoint, empty}, cases)) return false;
+        if (!check_fold(rgba, 1, 1, {first}, cases)) return false;                 // one frame of one pixel: cells of the last frame end at the counts
+    }
+    return true;
+}
 }  // namespace
 
 int main() {
     Counts c;
     if (!check_palettes(c) || !check_derivations(c) || !check_inbound(c) || !check_out_from<unsigned char>(c) || !check_out_from<unsigned int>(c)) return 1;
+    long folds = 0;
+    if (!check_folds(folds)) return 1;
+    printf("given_check: %ld frames folded from their slots agree\n", folds);
     long outs = 0;
     bool every_out = true;
     for (auto &row : c.out) for (long v : row) { outs += v; every_out = every_out && v > 0; }
