@@ -679,9 +679,43 @@ int patolette_amd_quantize_clusters(const double *colors, const double *weights,
                                     double *centers, size_t *n_clusters);
 
 /* patolette__PALETTE_get_refined_palette (palette/refine.c:165-221 -> patched faiss
- * kmeans_clustering).  centers_io planar (k,3) f64. */
+ * kmeans_clustering).  centers_io planar (k,3) f64.
+ *
+ * Two DEPARTURES, both where the reference does not return or is undefined; in each the centres come back as they went in
+ * (rounded to f32), as they do for n < k and for a NaN / Inf among the colours:
+ *
+ * 1. Empty clusters without a donor.  split_clusters (Clustering.cpp:216-263) gives an empty cluster half of a donor cj that it
+ *    accepts when a draw r in [0, 1) is below (h[cj] - 1) / (n - k), and walks round the clusters until one is accepted.  When
+ *    no cluster has a size h > 1 (weighted input whose cluster weight sums are <= 1, or NaN) no candidate can ever be accepted
+ *    and the reference spins.  Here, once no cluster with h > 1 is left, the remaining empty clusters of that iteration keep
+ *    what the update wrote (centre 0, size 0) and the iterations go on.  An acceptance probability that is small but positive
+ *    is the reference's behaviour and stays.  The same walk cannot end when n - k wraps: k > max(max_samples, 65536) makes
+ *    the subsample k * (max_samples / k) = 0 samples long.  KMeans is skipped when subsampling leaves fewer than k + 1 samples;
+ *    that includes a subsample of exactly k samples (max_samples / 2 < k <= max_samples, n > k), where the reference does
+ *    return -- with the first k samples of the image as centres, which refines nothing.
+ *
+ * 2. The finite domain.  With |x| > ~1.8e19 the f32 norm |x|^2 is +inf, every candidate distance is NaN and the reference's
+ *    nearest-centre index is -1, with which it indexes its arrays; the same follows once all centres are NaN, after a sum
+ *    overflowed or 1 / h met a subnormal h.  KMeans is skipped unless every f32 intermediate of an iteration is finite by
+ *    these bounds, taken from the f32 inputs:  B = max(1, largest |colour value|, largest |initial centre value|), both finite;
+ *    m = min(samples used, 2^25);  weights (if any) finite, >= 0 and the smallest positive one, wmin, a normal f32 (>= 2^-126);
+ *    Cb bounds every centre of every iteration: 8 B + 8 without weights; with them 4 min(exp(n / 2^23), 4 m wmax / wmin) B + 8
+ *    for n samples used (wmax = max(1, largest weight): the first from the rounding of the two chains a centre is the quotient
+ *    of, the second from h >= wmin);  required:  16 Cb^2 <= FLT_MAX  and  4 m wmax B <= FLT_MAX.  Without weights that is
+ *    B <= 5.7e17; with them, for values up to 255, any weights up to 2.7e8 samples (exp(n / 2^23) B <= 1.1e18), beyond that a
+ *    weight ratio of 3.4e7 -- the bound is a proven one, not a sharp one; an image beyond it is not
+ *    refined.  Weights without a positive one put no condition on wmin.  The full paths (patolette_amd,
+ *    patolette_amd_device, the batch and slice entries) apply the same rule: the pass that takes the largest weight also takes
+ *    the smallest positive one and notes a negative or non-finite one, over all GPUs of a sliced image. */
 int patolette_amd_kmeans_refine(const double *colors, const double *weights, size_t n,
                                 double *centers_io, size_t k, int niter, size_t max_samples);
+/* TESTS ONLY: what the last KMeans of the calling thread's engine ran, as a bit mask; 0 = it did not iterate (skipped, n == k, or
+ * niter 0).  1 list path (block-local sorts, one block per centroid collects its members) | 2 full scan | 4 the form beyond 4096
+ * centroids (counters and cursors in memory) | 8 pruned by the 32^3 table | 16 by the 64^3 table | 32 the 64^3 table read through
+ * the four-candidate table in LDS (one byte per assignment) | second half of the stable sort: 64 from int assignments, 128 from
+ * bytes, 256 from bytes with paired records, 512 through LDS in batches of 4096 | 1024 the block-parallel chain is on for clusters
+ * of PAMD_KM_LONG_MIN (8192) members | 2048 the order-free sums (patolette_amd_set_kmeans_update(1)): no sort, no chain. */
+int patolette_amd_debug_km_route(void);
 
 /* patolette__PALETTE_fill_palette_map_nearest (palette/nearest.c:150-209) */
 int patolette_amd_nn_map(const double *colors, size_t n, const double *palette, size_t k, size_t *map);

@@ -142,6 +142,7 @@ SYMBOLS = {
     "patolette_amd_quantize_clusters": (C.c_int, [dp, dp, C.c_size_t, C.c_size_t, dp, zp]),
     "patolette_amd_kmeans_refine": (C.c_int, [dp, dp, C.c_size_t, dp, C.c_size_t, C.c_int, C.c_size_t]),
     "patolette_amd_nn_map": (C.c_int, [dp, C.c_size_t, dp, C.c_size_t, zp]),
+    "patolette_amd_debug_km_route": (C.c_int, []),
     "patolette_amd_debug_nn_route": (C.c_int, [C.c_int]),
     "patolette_amd_debug_nn_map_elem": (C.c_int, [dp, C.c_size_t, dp, C.c_size_t, C.c_int, C.c_int, C.c_void_p]),
     "patolette_amd_set_global_quantiser": (C.c_int, [C.c_int]),

@@ -110,12 +110,23 @@ __global__ __launch_bounds__(256) void k_convert(SRC src, double *__restrict__ d
 }
 
 __global__ __launch_bounds__(256) void k_weight_stats(const double *__restrict__ w, size_t n, ConvertStats *stats) {
-    double mx = 0.0;
+    double mx = 0.0, mn = INFINITY;                        // mn: the smallest positive weight as KMeans will see it (f32)
+    bool bad = false;                                      // (float)weight negative, NaN or Inf
     const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) mx = fmax(mx, fabs(w[i]));
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const double v = w[i];
+        mx = fmax(mx, fabs(v));
+        const float f = (float)v;
+        if (!(f >= 0.f) || f == INFINITY) bad = true;
+        else if (f > 0.f) mn = fmin(mn, (double)f);
+    }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_down(mx, o, 64));
-    if ((threadIdx.x & 63) == 0) atomicMax(&stats->wmaxkey[blockIdx.x & (kStatSlots - 1)], f64_key(mx));
+    for (int o = 32; o > 0; o >>= 1) { mx = fmax(mx, __shfl_down(mx, o, 64)); mn = fmin(mn, __shfl_down(mn, o, 64)); }
+    if ((threadIdx.x & 63) == 0) {
+        atomicMax(&stats->wmaxkey[blockIdx.x & (kStatSlots - 1)], f64_key(mx));
+        atomicMin(&stats->wminkey[blockIdx.x & (kStatSlots - 1)], f64_key(mn));
+    }
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&stats->bad_weight, 1u);
 }
 
 __global__ void k_init_stats(ConvertStats *s) {
@@ -123,8 +134,9 @@ __global__ void k_init_stats(ConvertStats *s) {
         for (int p = 0; p < 3; p++) { s->minkey[threadIdx.x][p] = ~0ULL; s->maxkey[threadIdx.x][p] = 0ULL; s->sum[threadIdx.x][p][0] = 0.0; s->sum[threadIdx.x][p][1] = 0.0; }
         for (int q = 0; q < 6; q++) { s->mom[threadIdx.x][q][0] = 0.0; s->mom[threadIdx.x][q][1] = 0.0; }
         s->wmaxkey[threadIdx.x] = f64_key(0.0);
+        s->wminkey[threadIdx.x] = f64_key(INFINITY);
     }
-    if (threadIdx.x == 0) s->nonfinite_f32 = 0u;
+    if (threadIdx.x == 0) { s->nonfinite_f32 = 0u; s->bad_weight = 0u; }
 }
 
 __global__ __launch_bounds__(256) void k_fill_uniform(double *out, size_t n, unsigned long long seed) {

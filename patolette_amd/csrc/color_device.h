@@ -14,9 +14,11 @@ constexpr int PAMD_COPY = 100;       // internal: no conversion (colour space sR
 constexpr int kStatSlots = 32;       // same-address atomics serialise in L2: blocks spread over slots
 struct ConvertStats {                // filled by k_convert / k_weight_stats (ordered-key min/max per slot)
     unsigned long long minkey[kStatSlots][3], maxkey[kStatSlots][3], wmaxkey[kStatSlots];
+    unsigned long long wminkey[kStatSlots];   // the smallest positive weight as f32 (+inf: none) -- the finite domain of KMeans (patolette_amd.h)
     double sum[kStatSlots][3][2];    // binned column sums of the converted image (the root mean of the global quantiser)
     double mom[kStatSlots][6][2];    // binned raw second moments xx, yx, zx, yy, zy, zz (the root covariance)
     unsigned int nonfinite_f32;      // some converted value is NaN / Inf once cast to float (faiss Clustering.cpp:295-304 scans for that)
+    unsigned int bad_weight;         // some weight is negative, NaN or Inf once cast to float
 };
 
 // pow(x, y) for the conversions: x >= 0 (anything else returns what libm returns: NaN for x < 0 with a non-integer y, the signed

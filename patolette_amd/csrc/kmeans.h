@@ -27,7 +27,15 @@ struct KMeansWork {
     DevBuf<unsigned int> mid;                 // 32^3 table of four-candidate entries (held in LDS by k_km_assign_mid)
     DevBuf<unsigned int> bkeys;
     DevBuf<unsigned long long> fsum;          // order-free update (KmSums): per centroid 4 fixed-point sums (x, y, z, weight or count)
+    int route = 0;                            // KmRoute bits of the last kmeans_iterate (patolette_amd_debug_km_route); 0 = none ran
     void reserve(size_t nx, int k);
+};
+
+// what kmeans_iterate decided, for the tests (patolette_amd.h: patolette_amd_debug_km_route)
+enum KmRoute {
+    KM_ROUTE_LIST = 1 << 0, KM_ROUTE_SCAN = 1 << 1, KM_ROUTE_BIGK = 1 << 2, KM_ROUTE_G32 = 1 << 3, KM_ROUTE_G64 = 1 << 4,
+    KM_ROUTE_MID = 1 << 5, KM_ROUTE_SCATTER_INT = 1 << 6, KM_ROUTE_SCATTER_BYTE = 1 << 7, KM_ROUTE_SCATTER_PAIR = 1 << 8,
+    KM_ROUTE_SCATTER_LDS = 1 << 9, KM_ROUTE_COOP = 1 << 10, KM_ROUTE_SUMS = 1 << 11
 };
 
 void kmeans_gather(const double *d_planar, size_t N, bool weighted, const int *d_perm, size_t nx, KMeansWork &w, hipStream_t s);

@@ -1234,14 +1234,22 @@ __device__ __forceinline__ void km_split_clusters_wave(float *cent, float *hassi
                                                        unsigned *s_mt, float *s_h_, const int lane, unsigned int *flags = nullptr) {
     const KmSizes<HMEM> s_h{s_h_};
     for (int i = lane; i < 624; i += 64) s_mt[i] = seeded->mt[i];
-    for (int j = lane; j < k; j += 64) s_h.put(j, hassign[j]);
+    // DEPARTURE (patolette_amd.h, patolette_amd_kmeans_refine): the reference's walk does not end when no candidate can be
+    // accepted.  p = (h - 1) / (n - k) > 0 takes h > 1 (a NaN size compares false) with n > k; `donors` counts such clusters,
+    // wavefront-wide at the start and kept up to date as sizes are halved.  At 0 the remaining empty clusters stay as the
+    // update wrote them (centre 0, size 0).
+    int mine_donors = 0;
+    for (int j = lane; j < k; j += 64) { const float hj = hassign[j]; s_h.put(j, hj); mine_donors += hj > 1.f ? 1 : 0; }
     if constexpr (HMEM) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     int idx = 624;                                                          // nothing generated yet (DevMT::seed)
     const float denom = (float)(n - (unsigned long long)k);
+    int donors = n > (unsigned long long)k ? (int)wave_sum_u32((unsigned)mine_donors) : 0;
+    donors = __shfl(donors, 0, 64);
     for (int ci = 0; ci < k; ci++) {
         if (s_h.get(ci) != 0.f) continue;                                   // wave-uniform (one LDS word)
+        if (donors == 0) break;                                             // wave-uniform: no walk could end
         int cj0 = 0, cj = 0;
         for (;;) {
             if (idx >= 624) {
@@ -1273,6 +1281,9 @@ __device__ __forceinline__ void km_split_clusters_wave(float *cent, float *hassi
             if (m) { const int t = __ffsll((long long)m) - 1; idx += t + 1; cj = (cj0 + t) % k; break; }
             idx += navail; cj0 = (cj0 + navail) % k;
         }
+        const float hcj = s_h.get(cj);                                      // wave-uniform; a donor: hcj > 1
+        const float hi = hcj / 2, hj = hcj - hi;
+        donors += (hi > 1.f ? 1 : 0) + (hj > 1.f ? 1 : 0) - 1;
         if (lane == 0) {
             for (int j = 0; j < 3; j++) cent[ci * 3 + j] = cent[cj * 3 + j];
             for (int j = 0; j < 3; j++) {
@@ -1284,8 +1295,6 @@ __device__ __forceinline__ void km_split_clusters_wave(float *cent, float *hassi
                     cent[cj * 3 + j] = (float)((double)cent[cj * 3 + j] * (1 + (1 / 1024.)));
                 }
             }
-            const float hcj = s_h.get(cj);
-            const float hi = hcj / 2, hj = hcj - hi;
             s_h.put(ci, hi); s_h.put(cj, hj);
             hassign[ci] = hi; hassign[cj] = hj;
             if (flags) { flags[1 + ci] = 1u; flags[1 + cj] = 1u; }          // their next update must not be skipped
@@ -2244,8 +2253,10 @@ void kmeans_iterate(KMeansWork &w, size_t nx, int k, bool weighted, int niter, h
     if (use_mid) w.mid.reserve(32 * 32 * 32);
     // clusters of at least this many samples take the block-parallel exact chain (km_chain_coop)
     const unsigned long long long_min = getenv("PAMD_KM_LONG_MIN") ? (unsigned long long)atoll(getenv("PAMD_KM_LONG_MIN")) : 8192ULL;
+    int route = 0;                                            // KmRoute bits, set where the kernels are launched (patolette_amd_debug_km_route)
     for (int it = 0; it < niter; it++) {
         if (use_direct) {
+            route |= KM_ROUTE_LIST;
             unsigned short *offs = (unsigned short *)w.table.p;              // 257 x blocks x 2 bytes
             const int sblocks = (int)ceil_div(nx, (size_t)kKmSortBlock);
             {
@@ -2265,6 +2276,7 @@ void kmeans_iterate(KMeansWork &w, size_t nx, int k, bool weighted, int niter, h
             continue;
         }
         if (use_lut) {
+            route |= G == 64 ? KM_ROUTE_G64 : KM_ROUTE_G32;
             {
                 KTIME("k_km_lut_build", s, 16.0 * G * G * G);
                 const int ncoarse = G * G * G / 64;
@@ -2274,6 +2286,7 @@ void kmeans_iterate(KMeansWork &w, size_t nx, int k, bool weighted, int niter, h
                                    (const double *)cn2, w.lut.p, use_mid ? w.mid.p : (unsigned int *)nullptr);
             }
             if (use_mid) {
+                route |= KM_ROUTE_MID;
                 const int nmid = 32 * 32 * 32;
                 const size_t lds_mid = ((size_t)nmid + 4 * 256 + 16 * 256) * 4 + (size_t)16 * kKmQueue * 16;
                 static PerDeviceOnce attr3;
@@ -2290,19 +2303,21 @@ void kmeans_iterate(KMeansWork &w, size_t nx, int k, bool weighted, int niter, h
                                (const KmGridDev *)w.grid.p, G, w.lut.p);
             }
         } else {
+            route |= KM_ROUTE_SCAN | (bigk ? KM_ROUTE_BIGK : 0);
             KTIME("k_km_assign", s, 16.0 * nx);
             if (bigk) {
                 HIP_CHECK(hipMemsetAsync(w.table.p, 0, (size_t)k * nchunks * sizeof(unsigned int), s));
                 hipLaunchKernelGGL(k_km_assign_count<true>, cblocks, 256, 0, s, ks, nx, w.c4.p, k, nbits, chunk_len, nchunks, w.assign.p, w.table.p);
             } else hipLaunchKernelGGL(k_km_assign_count<false>, cblocks, 256, lds_cnt, s, ks, nx, w.c4.p, k, nbits, chunk_len, nchunks, w.assign.p, w.table.p);
         }
-        if (sums) { update_sums(use_lut && use_mid); continue; }
+        if (sums) { route |= KM_ROUTE_SUMS; update_sums(use_lut && use_mid); continue; }
         if (bigk) {
             // palettes beyond kKMeansMaxK entries (the reference has no limit, refine.c:77-89): the same stable counting sort and the
             // same chains, with the sort's per-centroid cursors in memory instead of LDS
             { KTIME("k_km_rowscan", s, 8.0 * k * nchunks); hipLaunchKernelGGL(k_km_rowscan, k, 256, 0, s, w.table.p, nchunks, w.rowtot.p); }
             hipLaunchKernelGGL(k_km_rowbase, 1, 256, 0, s, (const unsigned int *)w.rowtot.p, k, w.rowbase.p);
             {
+                route |= KM_ROUTE_SCATTER_INT;
                 KTIME("k_km_scatter", s, (weighted ? 36.0 : 32.0) * nx);
                 if (weighted) hipLaunchKernelGGL(k_km_scatter_big<true>, cblocks, 256, 0, s, ks, (const int *)w.assign.p, nx, nbits, chunk_len, nchunks, w.table.p, (const unsigned int *)w.rowbase.p, w.sorted.p);
                 else hipLaunchKernelGGL(k_km_scatter_big<false>, cblocks, 256, 0, s, ks, (const int *)w.assign.p, nx, nbits, chunk_len, nchunks, w.table.p, (const unsigned int *)w.rowbase.p, w.sorted.p);
@@ -2310,6 +2325,7 @@ void kmeans_iterate(KMeansWork &w, size_t nx, int k, bool weighted, int niter, h
             {
                 KTIME("k_km_update", s, 16.0 * nx);
                 const bool coop_on = nx >= long_min;
+                if (coop_on) route |= KM_ROUTE_COOP;
                 const size_t lds_up = coop_on ? (size_t)4 * 4096 * sizeof(float) : 0;
                 const unsigned long long lm = coop_on ? long_min : ~0ULL;
                 static PerDeviceOnce attr6;
@@ -2327,6 +2343,7 @@ void kmeans_iterate(KMeansWork &w, size_t nx, int k, bool weighted, int niter, h
             KTIME("k_km_scatter", s, (weighted ? 36.0 : 32.0) * nx - (use_mid ? 3.0 : 0.0) * nx);
             const unsigned char *a8 = (const unsigned char *)w.assign.p;               // k_km_assign_mid leaves one byte per sample
             if (use_mid && chunk_len >= 4096 && k <= 256) {
+                route |= KM_ROUTE_SCATTER_LDS;
                 constexpr size_t lds_ls = (size_t)(512 + 1024 + 4096 / 4 + 4 * 4096) * sizeof(unsigned int);
                 static PerDeviceOnce attr5;
                 attr5.once([&] {
@@ -2336,6 +2353,7 @@ void kmeans_iterate(KMeansWork &w, size_t nx, int k, bool weighted, int niter, h
                 if (weighted) hipLaunchKernelGGL(k_km_scatter_lds<true>, nchunks, 256, lds_ls, s, ks, a8, nx, k, chunk_len, nchunks, w.table.p, w.rowtot.p, w.sorted.p);
                 else hipLaunchKernelGGL(k_km_scatter_lds<false>, nchunks, 256, lds_ls, s, ks, a8, nx, k, chunk_len, nchunks, w.table.p, w.rowtot.p, w.sorted.p);
             } else if (use_mid && chunk_len >= 2 * k) {
+                route |= KM_ROUTE_SCATTER_PAIR;
                 static PerDeviceOnce attr3;
                 attr3.once([&] {
                     HIP_CHECK(hipFuncSetAttribute((const void *)k_km_scatter<true, unsigned char, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 9 * 256 * 4 + 4 * (256 + 64) * 16));
@@ -2344,9 +2362,11 @@ void kmeans_iterate(KMeansWork &w, size_t nx, int k, bool weighted, int niter, h
                 if (weighted) hipLaunchKernelGGL((k_km_scatter<true, unsigned char, true>), cblocks, 256, lds_sct_pair, s, ks, a8, nx, k, nbits, chunk_len, nchunks, w.table.p, w.rowtot.p, w.sorted.p);
                 else hipLaunchKernelGGL((k_km_scatter<false, unsigned char, true>), cblocks, 256, lds_sct_pair, s, ks, a8, nx, k, nbits, chunk_len, nchunks, w.table.p, w.rowtot.p, w.sorted.p);
             } else if (use_mid) {
+                route |= KM_ROUTE_SCATTER_BYTE;
                 if (weighted) hipLaunchKernelGGL((k_km_scatter<true, unsigned char>), cblocks, 256, lds_sct, s, ks, a8, nx, k, nbits, chunk_len, nchunks, w.table.p, w.rowtot.p, w.sorted.p);
                 else hipLaunchKernelGGL((k_km_scatter<false, unsigned char>), cblocks, 256, lds_sct, s, ks, a8, nx, k, nbits, chunk_len, nchunks, w.table.p, w.rowtot.p, w.sorted.p);
             } else {
+                route |= KM_ROUTE_SCATTER_INT;
                 if (weighted) hipLaunchKernelGGL((k_km_scatter<true, int>), cblocks, 256, lds_sct, s, ks, (const int *)w.assign.p, nx, k, nbits, chunk_len, nchunks, w.table.p, w.rowtot.p, w.sorted.p);
                 else hipLaunchKernelGGL((k_km_scatter<false, int>), cblocks, 256, lds_sct, s, ks, (const int *)w.assign.p, nx, k, nbits, chunk_len, nchunks, w.table.p, w.rowtot.p, w.sorted.p);
             }
@@ -2355,12 +2375,14 @@ void kmeans_iterate(KMeansWork &w, size_t nx, int k, bool weighted, int niter, h
             KTIME("k_km_update", s, 16.0 * nx);
             // the shared 64 KB buffer of the block-parallel chain is only asked for when clusters of that length can exist
             const bool coop_on = nx >= long_min;
+            if (coop_on) route |= KM_ROUTE_COOP;
             const size_t lds_up = coop_on ? (size_t)4 * 4096 * sizeof(float) : 0;
             const unsigned long long lm = coop_on ? long_min : ~0ULL;
             if (weighted) hipLaunchKernelGGL((k_km_update<true, false>), k, 256, lds_up, s, w.sorted.p, w.rowtot.p, k, (unsigned long long)nx, w.cent.p, w.hassign.p, w.c4.p, w.ticket.p, w.mt.p, lm, (float *)nullptr);
             else hipLaunchKernelGGL((k_km_update<false, false>), k, 256, lds_up, s, w.sorted.p, w.rowtot.p, k, (unsigned long long)nx, w.cent.p, w.hassign.p, w.c4.p, w.ticket.p, w.mt.p, lm, (float *)nullptr);
         }
     }
+    if (niter > 0) w.route = route;
     HIP_CHECK(hipGetLastError());
 }
 

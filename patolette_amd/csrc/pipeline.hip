@@ -941,6 +941,7 @@ struct Bounds {
     bool have_mom = false;                                   // ... and the raw second moments with them: both as exact (hi, lo) pairs
     double sum2[3][2] = {{0, 0}, {0, 0}, {0, 0}}, mom2[6][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}};
     bool nonfinite = false;                                  // a converted value is NaN / Inf as f32 (KMeans then leaves the centres alone)
+    double wmin = 0; bool bad_w = false;                     // the smallest positive weight as f32 (0: none), a negative / NaN / Inf weight
 };
 
 static int exp_bound(double v) {                 // smallest E with 2^E > v (v > 0)
@@ -2101,10 +2102,35 @@ static bool km_update_order_free() {
     const int v = g_km_update.load(std::memory_order_relaxed);
     return v < 0 ? env : v != 0;
 }
+// The domain in which every f32 intermediate of an iteration stays finite (patolette_amd.h, patolette_amd_kmeans_refine states the
+// rule).  Outside it an assignment kernel can return index -1 (every candidate distance NaN: |x|^2 = +inf, or every centre NaN after
+// a sum overflowed or 1 / h met a subnormal h), which then indexes counters and the sorted copy.
+//   B = max(1, |x|, |initial centre|); m = min(nx, 2^25): a chain of non-negative addends <= T stops growing at 2^25 T, and below
+//   that its roundings add at most a factor e^2.  A weighted centre is acc / h with |acc| <= (1 + e)^n sum w |x| and
+//   h >= (1 - e)^n sum w (e = 2^-24, recursive summation of non-negative terms): |centre| <= exp(n 2^-23) B whatever the weights;
+//   also h >= the smallest positive weight, so |centre| <= 4 m (wmax / wmin) B.  Cb = 4 x the smaller of the two (the +-1/1024
+//   nudges of split_clusters, at most one per halving of a size: < 1.14; the rounding of 1 / h and of the product);
+//   unweighted the count is exact or stuck at 2^24: Cb = 8 B.  A distance is at most |x|^2 + |y|^2 + 2 |x.y| <= 12 Cb^2.
+// min_w: the smallest positive weight as f32, 0 = there is none (every cluster is empty: centres 0)
+static bool km_domain_ok(const double bound_x, const double bound_c, const bool weighted, const double bound_w, const double min_w, const size_t nx) {
+    const double fmax = 3.4028234663852886e38, fmin = 1.1754943508222875e-38;
+    const double B = std::max(1.0, std::max(bound_x, bound_c)), m = (double)std::min<size_t>(nx, (size_t)1 << 25);
+    if (!(B < fmax) || !(bound_w < fmax)) return false;
+    double Cb = 8.0 * B;
+    if (weighted) {
+        if (min_w > 0 && min_w < fmin) return false;                              // 1 / h overflows from a subnormal h
+        const double by_n = std::exp(std::min((double)nx * 0x1p-23, 700.0)) * B;
+        Cb = 4.0 * (min_w > 0 ? std::min(by_n, 4.0 * m * (std::max(bound_w, min_w) / min_w) * B) : by_n);
+    }
+    Cb += 8.0;                                                                     // products w x that underflow: <= m 2^-149 / 2^-126
+    return 16.0 * Cb * Cb <= fmax && 4.0 * m * std::max(bound_w, 1.0) * B <= fmax;
+}
 // bound_x / bound_w: upper bounds of |colour value| and of the weights over the image (the order-free update scales by them)
+// min_w: the smallest positive weight as f32, 0 = none; bad_w: a weight is negative or not finite as f32
 static void kmeans_refine(Engine &E, size_t N, bool weighted, std::vector<double> &centers, size_t k, int niter, size_t max_samples,
-                          bool nonfinite, unsigned long long largest_cluster, double bound_x, double bound_w) {
+                          bool nonfinite, unsigned long long largest_cluster, double bound_x, double bound_w, double min_w = 0, bool bad_w = false) {
     hipStream_t s = E.stream;
+    E.km.route = 0;
     const KmSums sums_v{bound_x, bound_w};
     const KmSums *sums = km_update_order_free() ? &sums_v : nullptr;
     std::vector<float> cent(3 * k);
@@ -2117,12 +2143,21 @@ static void kmeans_refine(Engine &E, size_t N, bool weighted, std::vector<double
     const Shard *sh = E.shard;                                                     // sliced image: N is this GPU's part, the sample set is the whole image's
     const size_t Nt = sh ? sh->total : N;
     auto expect_longest = [&](size_t nx_) { return (size_t)((double)largest_cluster / (double)(Nt ? Nt : 1) * (double)nx_); };
-    bool ok = Nt >= k && !nonfinite;
+    bool ok = Nt >= k && !nonfinite && !bad_w;
     size_t nx = Nt;
     E.stats.kmeans_samples = 0;
+    const bool sub = ok && Nt > k * (size_t)mppc;                                  // Clustering.cpp:311-319
+    if (sub) nx = k * (size_t)mppc;
+    // DEPARTURES (patolette_amd.h): a subsample of fewer than k + 1 samples (k > max_samples: 0 of them) -- the reference's
+    // split_clusters then walks for ever with n - k wrapped; and input outside the finite domain
+    if (ok && sub && nx < k + 1) ok = false;
+    if (ok && nx != k) {
+        double bound_c = 0;
+        for (size_t i = 0; i < 3 * k; i++) bound_c = std::max(bound_c, std::fabs((double)cent[i]));
+        for (size_t i = 0; i < 3 * k && ok; i++) ok = std::isfinite(cent[i]);
+        ok = ok && km_domain_ok(bound_x, bound_c, weighted, bound_w, min_w, nx);
+    }
     if (ok) {
-        const bool sub = Nt > k * (size_t)mppc;                                    // Clustering.cpp:311-319
-        if (sub) nx = k * (size_t)mppc;
         E.km.reserve(nx, (int)k);
         const int *dperm = nullptr;
         if (sub) dperm = subsample_list(E, Nt, nx, s);                            // faiss draws the subsample from rand_perm(N, seed 1234)
@@ -2202,14 +2237,15 @@ static Bounds read_bounds(Engine &E, bool weighted, const std::function<void()> 
         parts[p][0] = 0; parts[p][1] = 0;                      // slot partials are exact multiples of the bin grids
         for (int t = 0; t < kStatSlots; t++) { parts[p][0] += cs.sum[t][p][0]; parts[p][1] += cs.sum[t][p][1]; }
     }
-    for (int t = 0; t < kStatSlots; t++) kw = std::max(kw, cs.wmaxkey[t]);
+    unsigned long long kwmin = ~0ULL, bad_w = weighted && cs.bad_weight != 0u ? 1ULL : 0ULL;
+    for (int t = 0; t < kStatSlots; t++) { kw = std::max(kw, cs.wmaxkey[t]); kwmin = std::min(kwmin, cs.wminkey[t]); }
     if (E.shard) {                                             // one image over several GPUs: the bounds and sums of ALL its pixels
-        const unsigned long long mine[8] = {kmin[0], kmin[1], kmin[2], kmax[0], kmax[1], kmax[2], kw, nonfinite};
-        const std::vector<unsigned long long> all = comm_gather_u64(E, mine, 8);
+        const unsigned long long mine[10] = {kmin[0], kmin[1], kmin[2], kmax[0], kmax[1], kmax[2], kw, nonfinite, kwmin, bad_w};
+        const std::vector<unsigned long long> all = comm_gather_u64(E, mine, 10);
         for (int r = 0; r < E.shard->comm.size; r++) {
-            const unsigned long long *row = all.data() + (size_t)r * 8;
+            const unsigned long long *row = all.data() + (size_t)r * 10;
             for (int p = 0; p < 3; p++) { kmin[p] = std::min(kmin[p], row[p]); kmax[p] = std::max(kmax[p], row[3 + p]); }
-            kw = std::max(kw, row[6]); nonfinite |= row[7];
+            kw = std::max(kw, row[6]); nonfinite |= row[7]; kwmin = std::min(kwmin, row[8]); bad_w |= row[9];
         }
         comm_sum_host(E, &parts[0][0], 6, 0);
     }
@@ -2222,6 +2258,8 @@ static Bounds read_bounds(Engine &E, bool weighted, const std::function<void()> 
         b.range = std::max(b.range, mx - mn);
     }
     b.wmax = weighted ? std::max(1.0, key_f64(kw)) : 1.0;
+    b.wmin = weighted && std::isfinite(key_f64(kwmin)) ? key_f64(kwmin) : 0.0;
+    b.bad_w = bad_w != 0ULL;
     const double lin = b.wmax * std::max(b.cmax, 1.0);
     const double quad = 3.0 * b.wmax * std::max(std::max(b.range, b.cmax), 1e-300) * std::max(std::max(b.range, b.cmax), 1e-300);
     b.e_lin = exp_bound(lin);
@@ -2327,7 +2365,7 @@ static void run_device(Engine &E, size_t width, size_t height, Pixels px, const 
     t0 = now_ms();
     if (opt->kmeans_niter > 0) {
         if (opt->verbose) printf("patolette ======== KMeans refinement\n");                // patolette.c:249-251
-        kmeans_refine(E, N, weighted, pal, len, opt->kmeans_niter, opt->kmeans_max_samples, bnd.nonfinite, largest_cluster, bnd.cmax, bnd.wmax);
+        kmeans_refine(E, N, weighted, pal, len, opt->kmeans_niter, opt->kmeans_max_samples, bnd.nonfinite, largest_cluster, bnd.cmax, bnd.wmax, bnd.wmin, bnd.bad_w);
     }
     E.stats.ms_kmeans = now_ms() - t0;
 
@@ -4068,17 +4106,22 @@ int patolette_amd_kmeans_refine(const double *colors, const double *weights, siz
         if (weighted) HIP_CHECK(hipMemcpy(E.cvt.p + 3 * n, weights, n * sizeof(double), hipMemcpyHostToDevice));
         std::vector<double> pal(centers_io, centers_io + 3 * k);
         bool nonfinite = false;                                     // Clustering.cpp:295-304 over every colour value as f32
-        for (size_t i = 0; i < 3 * n && !nonfinite; i++) nonfinite = !(std::fabs(colors[i]) < 0x1.ffffffp127);
-        double bx = 0, bw = 1;
-        if (!nonfinite && km_update_order_free()) {
-            for (size_t i = 0; i < 3 * n; i++) bx = std::max(bx, std::fabs(colors[i]));
-            if (weighted) for (size_t i = 0; i < n; i++) bw = std::max(bw, std::fabs(weights[i]));
+        double bx = 0, bw = 1, min_w = 0;
+        for (size_t i = 0; i < 3 * n && !nonfinite; i++) { nonfinite = !(std::fabs(colors[i]) < 0x1.ffffffp127); bx = std::max(bx, std::fabs(colors[i])); }
+        bool bad_w = false;                                         // as f32: the finite domain of kmeans_refine
+        if (!nonfinite && weighted) for (size_t i = 0; i < n; i++) {
+            const float wf = (float)weights[i];
+            bw = std::max(bw, std::fabs(weights[i]));
+            if (!(wf >= 0.f) || !std::isfinite(wf)) bad_w = true;
+            else if (wf > 0.f && (min_w == 0 || (double)wf < min_w)) min_w = (double)wf;
         }
-        kmeans_refine(E, n, weighted, pal, k, niter, max_samples, nonfinite, 0, bx, bw);
+        kmeans_refine(E, n, weighted, pal, k, niter, max_samples, nonfinite, 0, bx, bw, min_w, bad_w);
         std::memcpy(centers_io, pal.data(), 3 * k * sizeof(double));
         return 0;
     });
 }
+
+int patolette_amd_debug_km_route(void) { return holder().e ? holder().e->km.route : 0; }
 
 int patolette_amd_debug_nn_route(int route) { return nn_debug_route(route); }
 
