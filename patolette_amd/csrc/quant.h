@@ -11,6 +11,8 @@ namespace pamd {
 constexpr int kMaxChildren = 16;       // GQ makes <= 12 base clusters (global.c:19), LQ splits in 2
 constexpr int kTileA = 8192;           // pixels per block for streaming reductions (minmax / hist / cov)
 constexpr int kTileP = 2048;           // pixels per block for the stable partition (256 threads x 8 rounds)
+constexpr size_t kInfinityCacheBytes = (size_t)256 << 20;   // MI355X: the die-level last-level cache.  launch_partition holds ONE call's
+                                       // two buffers against it; images quantised side by side (the batch entry) share it: not measured
 
 // quantities accumulated per bucket by k_hist (two binned parts each)
 //   LQ : 0..2 = sum c*w, 3 = sum w

@@ -102,6 +102,13 @@ __device__ __forceinline__ double project(double x, double y, double z, const do
     return (x * a0 + y * a1) + z * a2;
 }
 
+// A load of a line that the split loop does not read again before it is overwritten (k_scatter_bin: the source pixels and
+// the bucket ids).  NT: non-temporal, so that the line does not push one out of the caches that the next sweep would have found there
+template <bool NT, typename T>
+__device__ __forceinline__ T load_last_use(const T *p) {
+    if constexpr (NT) return __builtin_nontemporal_load(p); else return *p;
+}
+
 __device__ __forceinline__ int tile_node(const int *t0, int nr, int t) {   // largest r with t0[r] <= t
     int lo = 0, hi = nr;
     while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (t0[mid] <= t) lo = mid; else hi = mid; }
@@ -821,7 +828,14 @@ __global__ __launch_bounds__(256, 5) void k_scatter(QuantBuffers qb, const Tile 
 // INV: every product is split onto the exact grids before it is added, so the children's moments no longer depend on where
 // the tile boundaries fall -- the same bits for any tiling, hence for any way of dealing an image out over several GPUs
 // (patolette_amd_slice).
-template <bool W, bool INV>
+// NT: what the kernel reads it reads for the last time, and says so (load_last_use).  An image whose two buffers do not fit in the
+// Infinity Cache together (launch_partition) then leaves this sweep with more of the lines it WROTE still cached, which the next
+// sweep, k_minmax, starts on.  Measured on the 4096^2 benchmark image, parent and this form alternated on three GPUs
+// (profiles/sweeps_ab.txt): the kernel's median time is lower on all three, beyond the parent's own run-to-run spread on one; on
+// the other two the parent is bimodal and its fast runs are as fast as this form, which stays at one time.  A smaller image is
+// served from the caches, where 8-byte non-temporal loads are the slower ones (1920x1080: the whole call 1 to 3 % slower), and
+// keeps plain loads.  Not measured: several images in flight at once (the batch entry), which share the Infinity Cache.
+template <bool W, bool INV, bool NT>
 __global__ __launch_bounds__(256, (W || INV) ? 2 : 3) void k_scatter_bin(QuantBuffers qb, const Tile *__restrict__ tiles, int ntiles, NodeDev *nodes,
                                                                         const NodeDev *__restrict__ nodes_ro,
                                                                         const unsigned long long *__restrict__ tileoff, const int from_end,
@@ -853,7 +867,7 @@ __global__ __launch_bounds__(256, (W || INV) ? 2 : 3) void k_scatter_bin(QuantBu
     auto fetch_buckets = [&](const Tile &tt, const int ti, unsigned (&b)[R], unsigned long long &toff) {
         const unsigned last = tt.count - 1u;
 #pragma unroll
-        for (int r = 0; r < R; r++) b[r] = qb.bkt[tt.start + min((unsigned)(r * 256) + threadIdx.x, last)];
+        for (int r = 0; r < R; r++) b[r] = load_last_use<NT>(qb.bkt + tt.start + min((unsigned)(r * 256) + threadIdx.x, last));
         toff = tileoff[(size_t)ti * kMaxChildren + (lane >> 5)];
     };
     // ranks: child of each pixel (k_cut's table is bucket > split), position among the wavefront's pixels of that child;
@@ -896,9 +910,9 @@ __global__ __launch_bounds__(256, (W || INV) ? 2 : 3) void k_scatter_bin(QuantBu
 #pragma unroll
             for (int r = 0; r < R; r++) {
                 const size_t src = t.start + min((unsigned)(r * 256) + threadIdx.x, last);
-                x[r] = sx[src]; y[r] = sy[src]; z[r] = sz[src];
+                x[r] = load_last_use<NT>(sx + src); y[r] = load_last_use<NT>(sy + src); z[r] = load_last_use<NT>(sz + src);
                 w[r] = 1.0;
-                if constexpr (W) w[r] = sw[src];
+                if constexpr (W) w[r] = load_last_use<NT>(sw + src);
             }
         }
         // 2. behind them, the next tile's buckets and offsets (straight-line: after the last tile the same tile is fetched
@@ -1234,11 +1248,16 @@ void launch_partition(const QuantBuffers &qb, const Tile *d_ptiles, int nptiles,
         KTIME_DYN(fuse_cov ? "k_scatter_cov" : "k_scatter", s, (qb.weighted ? 66.0 : 50.0), px, px_src);
         if (fuse_cov) {
             const int gb = std::min(nptiles, 256 * ((invariant || qb.weighted) ? 2 : 3));
+            // last-use loads where source and destination planes together exceed the Infinity Cache (k_scatter_bin)
+            const bool nt = 2 * (size_t)(qb.weighted ? 4 : 3) * qb.N * sizeof(double) > kInfinityCacheBytes;
+            auto go = [&](auto kernel) {
+                hipLaunchKernelGGL(kernel, gb, 256, 0, s, qb, d_ptiles, nptiles, d_nodes, (const NodeDev *)d_nodes, d_tileoff, fe, dyn);
+            };
             if (invariant) {
-                if (qb.weighted) hipLaunchKernelGGL((k_scatter_bin<true, true>), gb, 256, 0, s, qb, d_ptiles, nptiles, d_nodes, (const NodeDev *)d_nodes, d_tileoff, fe, dyn);
-                else hipLaunchKernelGGL((k_scatter_bin<false, true>), gb, 256, 0, s, qb, d_ptiles, nptiles, d_nodes, (const NodeDev *)d_nodes, d_tileoff, fe, dyn);
-            } else if (qb.weighted) hipLaunchKernelGGL((k_scatter_bin<true, false>), gb, 256, 0, s, qb, d_ptiles, nptiles, d_nodes, (const NodeDev *)d_nodes, d_tileoff, fe, dyn);
-            else hipLaunchKernelGGL((k_scatter_bin<false, false>), gb, 256, 0, s, qb, d_ptiles, nptiles, d_nodes, (const NodeDev *)d_nodes, d_tileoff, fe, dyn);
+                if (qb.weighted) { if (nt) go(k_scatter_bin<true, true, true>); else go(k_scatter_bin<true, true, false>); }
+                else { if (nt) go(k_scatter_bin<false, true, true>); else go(k_scatter_bin<false, true, false>); }
+            } else if (qb.weighted) { if (nt) go(k_scatter_bin<true, false, true>); else go(k_scatter_bin<true, false, false>); }
+            else { if (nt) go(k_scatter_bin<false, false, true>); else go(k_scatter_bin<false, false, false>); }
             if (gated) {
                 HIP_CHECK(hipGetLastError());
                 const int fg = (from_end ? 1 : 0) | 4;
