@@ -529,6 +529,72 @@ void patolette_amd_remap_rgba_u8_device(size_t frames, size_t width, size_t heig
  * way.  Process-wide; returns the previous mode. */
 int patolette_amd_debug_rgba_stamp_quad(int mode);
 
+/* ---- ColorHistogram: one palette for pixels that arrive in chunks ------------------------------
+ * Every palette-making entry above takes all its pixels in one array.  Here an exact histogram of the colours is kept in HBM, filled
+ * over as many calls as the caller likes (the frames of a clip a few at a time, the images of a directory), and the palette is made
+ * from it at the end.  8-bit input has at most 2^24 distinct colours, so the table has a fixed size, and the quantisers already take
+ * per-colour weights.
+ *   The table.  The caller owns it as device memory: patolette_amd_malloc(patolette_amd_hist_bytes(weighted)) bytes -- a 64-byte
+ *       header plus 2^24 64-bit counts (128 MB), plus 2^24 64-bit unit sums in a weighted table (256 MB) -- made usable by
+ *       patolette_amd_hist_clear and passed to every call with the same `weighted` (0 or 1) it was cleared with; a call on memory
+ *       that is not a cleared table of that mode fails with -1.  No handle, no registry; one table is used by one thread at a time.
+ *   Key.  A pixel's key is R << 16 | G << 8 | B.  A fourth channel does not enter the key.
+ *   Skipping by alpha.  With 4-channel pixels and an alpha_threshold in [0, 255], a pixel with alpha < alpha_threshold enters nothing
+ *       (opaque means alpha >= threshold, as for patolette_amd_rgba).  alpha_threshold -1: every pixel enters.
+ *   Unweighted (weighted == 0).  Per key a 64-bit count of pixels.
+ *   Weighted (weighted == 1, fixed when the table is cleared).  Per key also a second 64-bit integer: the sum of the pixels' weights
+ *       in units of 2^-32.  Each weight is converted on its own as rint(w * 2^32) -- the scaling is exact, ties go to even -- and then
+ *       integers are added.  A weight must be finite and satisfy 0 <= w <= 2^20 (the saliency weights derived here, 1 + sal^2 *
+ *       width * height / tile_size^2 with sal in [0, 1], stay far below that for any usual tile size; one beyond it is refused like
+ *       a given one).
+ *   Exact and order-free.  Both tables hold exact integers: the result of any sequence of adds and merges does not depend on order,
+ *       chunking, grid shape or timing.  A clip added whole, frame by frame, row by row or backwards gives the same bits.
+ *   Overflow.  Counts cannot overflow.  A weight sum that would pass 2^64 units is detected wherever partial sums are formed and
+ *       does not pass silently: the call fails with -1 and a text "<entry>: overflow: ...", the table is marked, and every later call
+ *       on it except patolette_amd_hist_clear fails the same way (what the table holds is then not defined).
+ *   A refused add leaves the table exactly as it was: bad arguments, a weight out of range or not finite (validated and converted
+ *       in a pass of their own before anything is accumulated), a saliency failure (-5, -6, -7; the weights of all frames of the
+ *       call are derived first).  Only overflow marks the table.
+ *
+ * patolette_amd_hist_add_u8: pixels as patolette_amd_frames_u8 takes them (`frames` images of width x height, `channels` 3 or 4).
+ *   A weighted table needs `weights` (frames * width * height values in frame order), or tile_size > 0: every frame then gets the
+ *   saliency weights patolette_amd_frames_u8 derives for it as an image of its own.  An unweighted table refuses both.  The *_device
+ *   flavour takes device pointers for pixels (any alignment) and weights: nothing crosses PCIe.
+ * patolette_amd_hist_merge: d_hist += d_other, bin by bin; both of the mode `weighted`; overflow as above (d_hist is marked).
+ * patolette_amd_hist_totals: *pixels = the sum of the counts, *colors = the number of keys with count > 0.
+ * patolette_amd_hist_export: every key with count > 0, ascending by key, into host buffers of `capacity` rows (at least *colors of
+ *   patolette_amd_hist_totals, else -1): colors (M,3) bytes, counts (M) uint64, weights (M) f64 -- equal to the count in an
+ *   unweighted table, units / 2^32 in a weighted one, rounded once.  Each may be NULL.
+ * patolette_amd_hist_palette: take the exported colours whose weight is > 0; M' of them.  M' == 0: -1.  M' <= palette_size: the
+ *   palette is those colours themselves in key order -- palette_u8 their bytes, palette bytes / 255.0, unused rows -1 resp. 0 as
+ *   patolette_amd_u8 fills them; no quantiser runs.  M' > palette_size: bit for bit what patolette_amd_u8 returns as palette and
+ *   palette_u8 for those M' colours as a 1 x M' image (width M', height 1) with those weights, tile_size 0, `options` with dither
+ *   and palette_only off, and neither map nor quantized image wanted (the same internal path, fed from HBM).  palette:
+ *   (palette_size,3) column-major f64; palette_u8: palette_size x 3; host memory, each may be NULL.
+ * Exit codes: 0; -2 frames == 0 or an empty image; -3 palette_size == 0; -4 more than 40000^2 pixels in one add; -5, -6, -7 from the
+ *   saliency stage; -1 with a text in patolette_amd_last_error that begins with the entry's name ("patolette_amd_hist_add:" for both
+ *   flavours of the add): no table or pixels, bad channels, an alpha_threshold outside [-1, 255] or one with 3 channels, the weights
+ *   rule above, a bad weight, memory that is not a cleared table of this mode, a capacity that is too small, no colour for a
+ *   palette, or "... overflow: ...".  The int-returning entries return these codes.  A failed call leaves the thread's engine usable.
+ * Statistics (patolette_amd_last_stats): the ms_* fields as for a remap -- ms_upload the pixels and weights of a host add, ms_saliency
+ *   the derived weights, ms_map the kernels and their flags (export and palette: the compaction), ms_download the rows on their way
+ *   out -- every other field 0.  A palette that runs the quantiser (M' > palette_size) leaves that call's statistics instead, as
+ *   patolette_amd_u8_device leaves them, without the compaction ahead of it.
+ * Kernels (hist.hip): k_hist_units (weights -> units and their check), k_hist_add (64-bit integer atomics, relaxed, agent scope,
+ *   behind a merge of equal keys in registers and in an LDS table), k_hist_merge, k_hist_totals; the export is compact.h over the bins. */
+size_t patolette_amd_hist_bytes(int weighted);
+int patolette_amd_hist_clear(void *d_hist, int weighted);
+void patolette_amd_hist_add_u8(void *d_hist, int weighted, size_t frames, size_t width, size_t height, const unsigned char *pixels,
+                               int channels, int alpha_threshold, const double *weights, double tile_size, int *exit_code);
+void patolette_amd_hist_add_u8_device(void *d_hist, int weighted, size_t frames, size_t width, size_t height, const unsigned char *d_pixels,
+                                      int channels, int alpha_threshold, const double *d_weights, double tile_size, int *exit_code);
+int patolette_amd_hist_merge(void *d_hist, const void *d_other, int weighted);
+void patolette_amd_hist_totals(const void *d_hist, int weighted, uint64_t *pixels, uint64_t *colors, int *exit_code);
+void patolette_amd_hist_export(const void *d_hist, int weighted, size_t capacity, unsigned char *colors, uint64_t *counts, double *weights,
+                               int *exit_code);
+void patolette_amd_hist_palette(const void *d_hist, int weighted, size_t palette_size, const patolette__QuantizationOptions *options,
+                                double *palette, unsigned char *palette_u8, int *exit_code);
+
 /* ---- batch of independent images (SURVEY.md 8(b) "Batch extension") -----------------------
  * count images of identical width x height; data[i] / weights[i] (weights may be NULL or hold
  * NULL entries) / tile_size / palettes[i] / palette_maps[i] / exit_codes[i] as for

@@ -22,7 +22,10 @@ and, for animations with transparency, `remap_rgba` (RGBA images or frames onto 
 entry) and `quantize_rgba_frames` (one shared palette and one transparent index for all frames, composed from `quantize_rgba`'s
 palette stage and `remap_rgba`) and `frame_deltas_rgba` (the deltas of such maps: 0 means "leave the canvas", every frame gets its
 own disposal, and the rectangle also covers what the next frame makes transparent);
-and `gif_lzw`, which LZW-compresses maps or deltas on the device, with `write_gif`, the GIF89a container around it.
+and `gif_lzw`, which LZW-compresses maps or deltas on the device, with `write_gif`, the GIF89a container around it;
+and `ColorHistogram`, for pixels that arrive in chunks (a long clip, a directory of images): an exact colour histogram kept on the
+GPU and filled by any number of `add` calls, whose `palette()` is the one shared palette that `remap` then maps every chunk onto --
+with `colors` ("how many colours does this have?") and an input of no more than K colours getting exactly those colours back.
 """
 import ctypes as C
 import types
@@ -1109,8 +1112,218 @@ def quantize_u8_batch(images, palette_size, weights=None, dither=True, palette_o
     return [_u8_result(codes[i], pal8[i], maps[i], quants[i], pals[i]) for i in range(count)]
 
 
+def _current_device_index():
+    """The HIP device the calling thread is on: torch's, where torch has initialised its runtime in this process, else 0 -- also
+    when the thread has selected another device by other means, which nothing here can see."""
+    import sys
+    torch = sys.modules.get("torch")
+    if torch is not None and torch.cuda.is_available() and torch.cuda.is_initialized():
+        return int(torch.cuda.current_device())
+    return 0
+
+
+class ColorHistogram:
+    """One palette for pixels that arrive in chunks (additive; include/patolette_amd.h, "ColorHistogram"): an exact histogram of
+    8-bit colours kept on the GPU, filled by as many `add` calls as the caller likes -- the frames of a clip a few at a time, the
+    images of a directory, what a decoder hands out -- and the palette made from it at the end:
+
+        h = ColorHistogram()
+        for chunk in chunks:                      # (F, H, W, 3) uint8 each, any F
+            h.add(chunk)
+        ok, palette_u8, palette, msg = h.palette(256)
+        maps = [remap(chunk, palette, dither="ordered")[1] for chunk in chunks]
+
+      * The key of a pixel is R << 16 | G << 8 | B; per key the table holds a 64-bit count and, with weighted=True (fixed at
+        construction), the sum of the pixels' weights as integers in units of 2^-32 (each weight rint(w * 2^32); 0 <= w <= 2^20).
+      * Exact and order-free: the same pixels added whole, frame by frame, row by row or backwards give the same bits.
+      * A refused add (a ValueError) leaves the histogram as it was.  A weight sum beyond 2^64 units raises OverflowError; after it
+        every method but `clear()` raises OverflowError too.
+      * The table (128 MB, weighted 256 MB) is allocated and cleared on the current device at construction and freed by `close()`,
+        by leaving the `with` block, or with the object.  The device is recorded as torch's current one where torch has already
+        initialised CUDA in the process, otherwise as device 0: a histogram made before the first torch CUDA call counts as
+        device 0's, whatever device the thread is on.
+    One histogram is used by one thread at a time; several histograms may be filled by several threads and merged."""
+
+    def __init__(self, weighted=False):
+        self._ptr = None
+        self._weighted = bool(weighted)
+        self._device = _current_device_index()
+        L = _native.lib()
+        ptr = L.patolette_amd_malloc(L.patolette_amd_hist_bytes(int(self._weighted)))
+        if not ptr:
+            raise MemoryError("ColorHistogram: no device memory for the table (%s)" % _native.last_error())
+        self._ptr = C.c_void_p(ptr)
+        try:
+            self.clear()
+        except Exception:
+            self.close()
+            raise
+
+    # -- lifetime
+    def close(self):
+        """Free the table.  Every later use raises ValueError; closing twice is fine."""
+        ptr, self._ptr = self._ptr, None
+        if ptr is not None:
+            _native.lib().patolette_amd_free(ptr)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _alive(self):
+        if self._ptr is None:
+            raise ValueError("this ColorHistogram has been closed")
+
+    def _there(self):
+        """A context in which the histogram's device is the current one (torch's, where torch runs in this process)."""
+        import contextlib
+        import sys
+        torch = sys.modules.get("torch")
+        if torch is not None and torch.cuda.is_available() and torch.cuda.is_initialized():
+            return torch.cuda.device(self._device)
+        return contextlib.nullcontext()
+
+    @staticmethod
+    def _raise(code):
+        """Nothing for 0; the saliency stage's exceptions; OverflowError / ValueError for the histogram's own refusals."""
+        if code == 0:
+            return
+        message = _message(code) if -7 <= code <= 0 else "exit code %d" % code
+        _raise_saliency(code, message)
+        if code == -1:
+            err = _native.last_error()
+            if err.startswith("patolette_amd_hist") and ": overflow:" in err:
+                raise OverflowError(err)
+            if err.startswith("patolette_amd_hist"):
+                raise ValueError(err)
+            raise RuntimeError(err or message)
+        raise ValueError(message)
+
+    # -- filling
+    @property
+    def weighted(self):
+        return self._weighted
+
+    def clear(self):
+        """Empty the histogram (also after an overflow).  Returns self."""
+        self._alive()
+        with self._there():
+            self._raise(_native.lib().patolette_amd_hist_clear(self._ptr, int(self._weighted)))
+        return self
+
+    def add(self, image, weights=None, tile_size=0, alpha_threshold=None):
+        """Add the pixels of an (H, W, 3|4) image or of (F, H, W, 3|4) frames, uint8 sRGB, a numpy array or a torch CUDA tensor on
+        the histogram's device (then nothing crosses PCIe).  A 4th channel does not enter the key; with alpha_threshold (0..255) a
+        pixel whose alpha is below it enters nothing.  A weighted histogram needs `weights` (one per pixel, finite, in [0, 2^20]) or
+        tile_size > 0 (every frame gets the saliency weights `quantize_frames` derives for it); an unweighted one takes neither.
+        Returns self."""
+        self._alive()
+        px, shape, dev = _u8_pixels(image, (3, 4), (3, 4), "image must be an (H, W, 3|4) or (F, H, W, 3|4) uint8 %s")
+        if len(shape) == 3:
+            shape = (1,) + shape
+        count, height, width, channels = shape
+        if dev is not None and (self._device if dev.index is None else dev.index) != self._device:
+            raise ValueError("the tensor lives on %s, the histogram on device %d" % (dev, self._device))
+        if not isinstance(tile_size, (int, float, np.integer, np.floating)) or not tile_size >= 0:
+            raise ValueError(bad_tile_size)
+        if not self._weighted and (weights is not None or tile_size > 0):
+            raise ValueError("an unweighted ColorHistogram takes neither weights nor a tile_size above 0")
+        if self._weighted and weights is None and not tile_size > 0:
+            raise ValueError("a weighted ColorHistogram needs weights, or a tile_size above 0 to derive them")
+        thr = -1
+        if alpha_threshold is not None:
+            if channels != 4:
+                raise ValueError("alpha_threshold needs pixels of 4 channels")
+            thr = _alpha_threshold(alpha_threshold)
+            if thr > 255:
+                raise ValueError("alpha_threshold must lie in [0, 255]")
+        w = _weights(weights, count * height * width, dev, "frames*height*width")
+        code = C.c_int(0)
+        with self._there():
+            _call("patolette_amd_hist_add_u8", dev, self._ptr, int(self._weighted), count, width, height, _vp(px), channels, thr, _vp(w),
+                  float(tile_size), C.byref(code))
+        self._raise(code.value)
+        return self
+
+    def merge(self, other):
+        """Add another histogram of the same mode and device into this one, bin by bin (`other` is unchanged).  Returns self."""
+        self._alive()
+        if not isinstance(other, ColorHistogram) or other is self:
+            raise ValueError("merge takes another ColorHistogram")
+        other._alive()
+        if other._weighted != self._weighted or other._device != self._device:
+            raise ValueError("merge needs two histograms of the same mode (weighted or not) on the same device")
+        with self._there():
+            self._raise(_native.lib().patolette_amd_hist_merge(self._ptr, other._ptr, int(self._weighted)))
+        return self
+
+    # -- reading
+    def _totals(self):
+        self._alive()
+        px, colors, code = C.c_uint64(0), C.c_uint64(0), C.c_int(0)
+        with self._there():
+            _native.lib().patolette_amd_hist_totals(self._ptr, int(self._weighted), C.byref(px), C.byref(colors), C.byref(code))
+        self._raise(code.value)
+        return int(px.value), int(colors.value)
+
+    @property
+    def pixels(self):
+        """How many pixels have entered."""
+        return self._totals()[0]
+
+    @property
+    def colors(self):
+        """How many distinct colours have entered."""
+        return self._totals()[1]
+
+    def export(self):
+        """Every colour with a count above 0, ascending by key: (colors (M, 3) uint8, counts (M,) int64, weights (M,) float64 -- the
+        counts again for an unweighted histogram, the summed weights (units / 2^32, rounded once) for a weighted one).  numpy."""
+        m = self._totals()[1]
+        colors, counts, weights = np.zeros((m, 3), dtype=np.uint8), np.zeros(m, dtype=np.uint64), np.zeros(m, dtype=np.float64)
+        code = C.c_int(0)
+        with self._there():
+            _native.lib().patolette_amd_hist_export(self._ptr, int(self._weighted), m, _vp(colors),
+                                                    counts.ctypes.data_as(C.POINTER(C.c_uint64)), _dp(weights), C.byref(code))
+        self._raise(code.value)
+        return colors, counts.astype(np.int64), weights
+
+    def palette(self, palette_size, color_space=ColorSpace_ICtCp, kmeans_niter=32, kmeans_max_samples=512 ** 2):
+        """The palette of `palette_size` rows for everything added so far.  Of the colours with a weight above 0 (a ValueError if
+        there is none): no more than palette_size of them are returned as they are, in key order, and no quantiser runs; more are
+        quantised with their counts (or summed weights) as weights -- bit for bit
+        `quantize_u8(colors[None], palette_size, dither=False, tile_size=0, weights=w, want_quantized=False)` on the exported list.
+        Returns (success, palette_u8 (K, 3) uint8, palette (K, 3) float64 as `quantize` returns it, message); both palettes go
+        straight into `remap`, `frame_deltas` and `write_gif`."""
+        self._alive()
+        palette_size = int(palette_size)
+        palette = np.zeros((max(palette_size, 0), 3), dtype=np.float64, order='F')
+        palette_u8 = np.zeros((max(palette_size, 0), 3), dtype=np.uint8)
+        opts = _options(False, False, color_space, kmeans_niter, kmeans_max_samples)
+        code = C.c_int(0)
+        with self._there():
+            _native.lib().patolette_amd_hist_palette(self._ptr, int(self._weighted), max(palette_size, 0), C.byref(opts), _vp(palette),
+                                                     _vp(palette_u8), C.byref(code))
+        if code.value in (-1, -5, -6, -7):
+            self._raise(code.value)
+        message = _message(code.value)
+        if code.value != 0:
+            return (False, None, None, message)
+        return (True, palette_u8, palette, message)
+
+
 __all__ = [
     "__doc__",
+    "ColorHistogram",
     "__version__",
     "quantize",
     "quantize_batch",

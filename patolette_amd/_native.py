@@ -130,6 +130,16 @@ SYMBOLS = {
     **_pair("patolette_amd_rgba", None, [C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_size_t,
                                          C.POINTER(QuantizationOptions), dp, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                          C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    # ColorHistogram: the table is device memory the caller owns (void*)
+    "patolette_amd_hist_bytes": (C.c_size_t, [C.c_int]),
+    "patolette_amd_hist_clear": (C.c_int, [C.c_void_p, C.c_int]),
+    **_pair("patolette_amd_hist_add_u8", None, [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_int,
+                                                C.c_void_p, C.c_double, C.POINTER(C.c_int)]),
+    "patolette_amd_hist_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "patolette_amd_hist_totals": (None, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+    "patolette_amd_hist_export": (None, [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint64), dp, C.POINTER(C.c_int)]),
+    "patolette_amd_hist_palette": (None, [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(QuantizationOptions), dp, C.c_void_p,
+                                          C.POINTER(C.c_int)]),
     "patolette_amd_batch": (None, [C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(dp), C.POINTER(dp), C.c_double, C.c_size_t,
                                    C.POINTER(QuantizationOptions), C.POINTER(dp), C.POINTER(zp), C.POINTER(C.c_int)]),
     "patolette_amd_batch_rows": (None, [C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(dp), C.POINTER(dp), C.c_double, C.c_size_t,

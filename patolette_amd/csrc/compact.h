@@ -3,8 +3,9 @@
 // Three launches: k_compact_count (one count per tile of 4096 items: a __ballot + __popcll per wave and item), k_compact_scan (the
 // tile counts into exclusive offsets, one block), k_compact_write (each item's rank = its tile's offset + the items before it in
 // the tile: per-wave ballots, a 64-entry scan in LDS).  The item order inside a tile is item j of thread t = j * 256 + t, so the
-// loads of one step are consecutive and the ranks follow the item index.  Used by the RGBA entry (rgba.hip: opaque pixels) and by
-// the masked dither (map.hip: opaque pixels in curve order).
+// loads of one step are consecutive and the ranks follow the item index.  Used by the RGBA entry (rgba.hip: opaque pixels), by
+// the masked dither (map.hip: opaque pixels in curve order) and by the colour histogram's export (hist.hip: the bins with a count;
+// its V is two 64-bit words, sixteen of which a thread of k_compact_write holds: 73 VGPRs unweighted, 105 weighted).
 //
 // An operation OP supplies:  using V = ...;  V load(size_t i);  bool keep(V);  void put(size_t i, V, bool keep, unsigned rank).
 // put is called for every item of [0, n) (rank is only meaningful when keep).

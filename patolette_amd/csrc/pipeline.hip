@@ -26,6 +26,7 @@
 #include "delta.h"
 #include "measure.h"
 #include "lzw.h"
+#include "hist.h"
 #include "saliency.h"
 #include "quant.h"
 #include "rgba.h"
@@ -999,6 +1000,12 @@ struct Engine {
     // the remap with alpha (run_remap_rgba): the stamp's flag and, behind it, every frame's opaque count; their pinned landing place
     DevBuf<unsigned> rr_words;
     PinBuf<unsigned> h_rr_words;
+    // the colour histogram (hist.h): the weights as units; the weights' flag, the totals and the export's count; the export's tile
+    // offsets; the exported rows (bytes, counts, weights)
+    DevBuf<unsigned long long> hs_units, hs_words, hs_counts;
+    DevBuf<unsigned> hs_tiles;
+    DevBuf<unsigned char> hs_rgb;
+    DevBuf<double> hs_w;
     DevBuf<ConvertStats> cstats;
     PinBuf<NodeIn> h_stage_in;
     PinBuf<NodeOut> h_stage_out;
@@ -3279,6 +3286,165 @@ static void run_rgba(Engine &E, size_t width, size_t height, const unsigned char
     E.stats.ms_total += up + E.stats.ms_download;
 }
 
+// --------------------------------------------------------------------------------------------
+// ColorHistogram: an exact colour histogram in memory the caller owns (include/patolette_amd.h; the table: hist.h)
+// --------------------------------------------------------------------------------------------
+using HistWord = unsigned long long;
+
+// `bytes` of device memory on the host, once everything enqueued has run
+static void hist_read(Engine &E, void *dst, const void *d_src, size_t bytes) {
+    HIP_CHECK(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, E.stream));
+    E.sync();
+}
+static HipError hist_error(const char *name, const char *text) { return HipError(std::string(name) + ": " + text); }
+static const char *const kHistOverflow = "overflow: a weight sum passed 2^64 units; only a clear makes the histogram usable again";
+
+// what every call but clear asks first: the table is a cleared one of this mode, and no sum in it has overflowed
+static void hist_check(Engine &E, const char *name, const HistWord *d_hist, bool weighted) {
+    HistWord h[2] = {0, 0};
+    hist_read(E, h, d_hist, sizeof h);
+    if (h[1] != kHistMagic + (weighted ? 1u : 0u)) throw hist_error(name, "the memory is not a cleared histogram of this mode");
+    if (h[0] & 1) throw hist_error(name, kHistOverflow);
+}
+
+static void run_hist_clear(Engine &E, HistWord *d_hist, bool weighted) {
+    const HistWord head[2] = {0, kHistMagic + (weighted ? 1u : 0u)};
+    HIP_CHECK(hipMemsetAsync(d_hist, 0, hist_words(weighted) * sizeof(HistWord), E.stream));
+    HIP_CHECK(hipMemcpyAsync(d_hist, head, sizeof head, hipMemcpyHostToDevice, E.stream));
+    E.sync();                                                         // (head is a local: the copy must have left the host)
+}
+
+// pixels: frames x width x height x channels bytes; thr: -1, or the alpha below which a pixel enters nothing; weights: frames x
+// width x height values or null -- then, in a weighted table, every frame's saliency weights.  `pixels` and `weights` are device
+// pointers when `on_device`.  Everything that can refuse the add runs before k_hist_add is enqueued.
+static void run_hist_add(Engine &E, const char *name, bool on_device, HistWord *d_hist, bool weighted, size_t frames, size_t width, size_t height,
+                         const unsigned char *pixels, int channels, int thr, const double *weights, double tile_size) {
+    const size_t N = frames * width * height;
+    hipStream_t s = E.stream;
+    GivenRun run(E);
+    const bool derive = weighted && !weights;
+    // the workspace, before anything is enqueued
+    E.hs_words.reserve(4);
+    if (weighted) E.hs_units.reserve(N);
+    if (derive) { E.wsal.reserve(N); saliency_reserve(E.sal, width, height); }
+    if (!on_device) { E.src8.reserve(N * (size_t)channels); if (weights) E.wsrc.reserve(N); }
+    hist_check(E, name, d_hist, weighted);
+    const unsigned char *d_px = pixels;
+    const double *d_w = weights;
+    if (!on_device) {
+        HIP_CHECK(hipMemcpyAsync(E.src8.p, pixels, N * (size_t)channels, hipMemcpyHostToDevice, s));
+        d_px = E.src8.p;
+        if (weights) { HIP_CHECK(hipMemcpyAsync(E.wsrc.p, weights, N * sizeof(double), hipMemcpyHostToDevice, s)); d_w = E.wsrc.p; }
+        HIP_CHECK(hipStreamSynchronize(s));
+    }
+    run.lap(&patolette_amd__Stats::ms_upload);
+    E.ms_saliency = 0.0;
+    if (derive) d_w = derive_weights(E, nullptr, d_px, channels, width, height, tile_size, frames);   // (all frames first; -5, -6, -7)
+    E.stats.ms_saliency = E.ms_saliency;
+    if (weighted) {
+        HIP_CHECK(hipMemsetAsync(E.hs_words.p, 0, sizeof(HistWord), s));
+        launch_hist_units(d_w, N, E.hs_units.p, reinterpret_cast<unsigned *>(E.hs_words.p), s);
+        HistWord bad = 0;
+        hist_read(E, &bad, E.hs_words.p, sizeof bad);
+        if (bad & 1) throw hist_error(name, "a weight is not finite or lies outside [0, 2^20]; nothing was added");
+    }
+    launch_hist_add(d_hist, weighted, d_px, channels, thr, N, weighted ? E.hs_units.p : nullptr, s);
+    HistWord flags = 0;
+    hist_read(E, &flags, d_hist, sizeof flags);
+    run.lap(&patolette_amd__Stats::ms_map);
+    if (flags & 1) throw hist_error(name, kHistOverflow);
+    run.done();
+}
+
+static void run_hist_merge(Engine &E, HistWord *d_hist, const HistWord *d_other, bool weighted) {
+    static const char *const name = "patolette_amd_hist_merge";
+    GivenRun run(E);
+    hist_check(E, name, d_hist, weighted);
+    hist_check(E, name, d_other, weighted);
+    launch_hist_merge(d_hist, d_other, weighted, E.stream);
+    HistWord flags = 0;
+    hist_read(E, &flags, d_hist, sizeof flags);
+    run.lap(&patolette_amd__Stats::ms_map);
+    if (flags & 1) throw hist_error(name, kHistOverflow);
+    run.done();
+}
+
+static void run_hist_totals(Engine &E, const HistWord *d_hist, bool weighted, uint64_t *pixels, uint64_t *colors) {
+    GivenRun run(E);
+    E.hs_words.reserve(4);
+    hist_check(E, "patolette_amd_hist_totals", d_hist, weighted);
+    launch_hist_totals(d_hist, E.hs_words.p + 1, E.stream);
+    HistWord t[2] = {0, 0};
+    hist_read(E, t, E.hs_words.p + 1, sizeof t);
+    if (pixels) *pixels = t[0];
+    if (colors) *colors = t[1];
+    run.lap(&patolette_amd__Stats::ms_map);
+    run.done();
+}
+
+// The bins with count > 0 (`positive`: and weight > 0) compacted in key order into E.hs_rgb, E.hs_w and -- with want_counts --
+// E.hs_counts; returns their number.  Nothing is enqueued when it returns.
+static size_t hist_compact(Engine &E, const HistWord *d_hist, bool weighted, bool positive, bool want_counts, size_t capacity, const char *name) {
+    hipStream_t s = E.stream;
+    const size_t nt = compact_tiles(kHistBins);
+    E.hs_tiles.reserve(nt + 1);
+    launch_hist_export_count(d_hist, weighted, positive, E.hs_tiles.p, E.hs_tiles.p + nt, s);
+    unsigned total = 0;
+    hist_read(E, &total, E.hs_tiles.p + nt, sizeof total);
+    const size_t M = total;
+    if (M > capacity) throw hist_error(name, "capacity is smaller than the number of colours (patolette_amd_hist_totals tells it)");
+    if (M == 0) return 0;
+    E.hs_rgb.reserve(3 * M); E.hs_w.reserve(M);
+    if (want_counts) E.hs_counts.reserve(M);
+    launch_hist_export_write(d_hist, weighted, positive, E.hs_tiles.p, E.hs_rgb.p, want_counts ? E.hs_counts.p : nullptr, E.hs_w.p, s);
+    E.sync();
+    return M;
+}
+
+static void run_hist_export(Engine &E, const HistWord *d_hist, bool weighted, size_t capacity, unsigned char *colors, uint64_t *counts,
+                            double *weights) {
+    static const char *const name = "patolette_amd_hist_export";
+    GivenRun run(E);
+    hist_check(E, name, d_hist, weighted);
+    const size_t M = hist_compact(E, d_hist, weighted, false, counts != nullptr, capacity, name);
+    run.lap(&patolette_amd__Stats::ms_map);
+    if (M && colors) HIP_CHECK(hipMemcpy(colors, E.hs_rgb.p, 3 * M, hipMemcpyDeviceToHost));
+    if (M && counts) HIP_CHECK(hipMemcpy(counts, E.hs_counts.p, M * sizeof(HistWord), hipMemcpyDeviceToHost));
+    if (M && weights) HIP_CHECK(hipMemcpy(weights, E.hs_w.p, M * sizeof(double), hipMemcpyDeviceToHost));
+    run.lap(&patolette_amd__Stats::ms_download);
+    run.done();
+}
+
+// The palette of K rows from the colours with a weight above 0 (M' of them): the colours themselves while M' <= K, else what
+// patolette_amd_u8_device returns for them as a 1 x M' image with those weights -- run_u8 itself, on the rows where they lie in HBM.
+static void run_hist_palette(Engine &E, const HistWord *d_hist, bool weighted, size_t K, const patolette__QuantizationOptions *opt,
+                             double *palette, unsigned char *palette_u8) {
+    static const char *const name = "patolette_amd_hist_palette";
+    GivenRun run(E);
+    hist_check(E, name, d_hist, weighted);
+    const size_t M = hist_compact(E, d_hist, weighted, true, false, kHistBins, name);
+    run.lap(&patolette_amd__Stats::ms_map);
+    if (M == 0) throw hist_error(name, "the histogram holds no colour with a weight above 0");
+    if (M > K) {                                                       // (the statistics are then run_u8's own: it resets them)
+        patolette__QuantizationOptions o = *opt;
+        o.dither = false; o.palette_only = false;
+        run_u8(E, M, 1, E.hs_rgb.p, 3, E.hs_w.p, 0.0, K, &o, palette, palette_u8, nullptr, 1, nullptr, true, false, nullptr);
+        return;
+    }
+    std::vector<unsigned char> rows(3 * M);
+    HIP_CHECK(hipMemcpy(rows.data(), E.hs_rgb.p, 3 * M, hipMemcpyDeviceToHost));
+    if (palette) {
+        for (size_t j = 0; j < 3 * K; j++) palette[j] = -1.0;                                     // unused rows as run_device fills them
+        for (int c = 0; c < 3; c++) for (size_t i = 0; i < M; i++) palette[K * (size_t)c + i] = (double)rows[3 * i + c] / 255.0;
+    }
+    if (palette_u8) {
+        std::memset(palette_u8, 0, 3 * K);
+        std::memcpy(palette_u8, rows.data(), 3 * M);
+    }
+    run.lap(&patolette_amd__Stats::ms_download);
+    run.done();
+}
+
 static int validate_u8(size_t K, int channels, const void *map_out, int map_elem) {
     if (channels != 3 && channels != 4) return -1;
     if (map_out) {
@@ -3899,6 +4065,72 @@ void patolette_amd_u8_device(size_t width, size_t height, const unsigned char *d
                              int *exit_code) {
     frames_entry(true, 1, width, height, d_pixels, channels, d_weights, tile_size, palette_size, options, palette, palette_u8,
                  d_palette_map, map_elem_bytes, d_quantized, kBadU8Args, exit_code);
+}
+
+// ---- ColorHistogram (include/patolette_amd.h): the arguments, then the run_hist_* above
+size_t patolette_amd_hist_bytes(int weighted) { return hist_words(weighted != 0) * sizeof(HistWord); }
+
+int patolette_amd_hist_clear(void *d_hist, int weighted) {
+    int code = 0;
+    if (!d_hist) { ArgCheck{"patolette_amd_hist_clear", &code}.fail(-1, "no histogram"); return code; }
+    return guarded([&](Engine &E) { run_hist_clear(E, (HistWord *)d_hist, weighted != 0); });
+}
+
+static void hist_add_entry(bool on_device, void *d_hist, int weighted, size_t frames, size_t width, size_t height, const unsigned char *pixels,
+                           int channels, int alpha_threshold, const double *weights, double tile_size, int *exit_code) {
+    static const char *const name = "patolette_amd_hist_add";
+    const ArgCheck arg{name, exit_code};
+    if (!arg.shape(frames, width, height)) return;
+    if (!d_hist) return (void)arg.fail(-1, "no histogram");
+    if (!pixels) return (void)arg.fail(-1, "no pixels");
+    if (channels != 3 && channels != 4) return (void)arg.fail(-1, "channels must be 3 or 4");
+    if (alpha_threshold < -1 || alpha_threshold > 255) return (void)arg.fail(-1, "alpha_threshold must be -1 (none) or lie in [0, 255]");
+    if (alpha_threshold >= 0 && channels != 4) return (void)arg.fail(-1, "an alpha_threshold needs pixels of 4 channels");
+    const bool derive = !weights && tile_size > 0.0;
+    if (weighted && !weights && !derive) return (void)arg.fail(-1, "a weighted histogram needs weights, or a tile_size above 0 to derive them");
+    if (!weighted && (weights || derive)) return (void)arg.fail(-1, "an unweighted histogram takes neither weights nor a tile_size above 0");
+    *exit_code = guarded([&](Engine &E) {
+        run_hist_add(E, name, on_device, (HistWord *)d_hist, weighted != 0, frames, width, height, pixels, channels, alpha_threshold, weights, tile_size);
+    });
+}
+
+void patolette_amd_hist_add_u8(void *d_hist, int weighted, size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels,
+                               int alpha_threshold, const double *weights, double tile_size, int *exit_code) {
+    hist_add_entry(false, d_hist, weighted, frames, width, height, pixels, channels, alpha_threshold, weights, tile_size, exit_code);
+}
+
+void patolette_amd_hist_add_u8_device(void *d_hist, int weighted, size_t frames, size_t width, size_t height, const unsigned char *d_pixels,
+                                      int channels, int alpha_threshold, const double *d_weights, double tile_size, int *exit_code) {
+    hist_add_entry(true, d_hist, weighted, frames, width, height, d_pixels, channels, alpha_threshold, d_weights, tile_size, exit_code);
+}
+
+int patolette_amd_hist_merge(void *d_hist, const void *d_other, int weighted) {
+    int code = 0;
+    const ArgCheck arg{"patolette_amd_hist_merge", &code};
+    if (!d_hist || !d_other) { arg.fail(-1, "no histogram"); return code; }
+    if (d_hist == d_other) { arg.fail(-1, "a histogram cannot be merged into itself"); return code; }
+    return guarded([&](Engine &E) { run_hist_merge(E, (HistWord *)d_hist, (const HistWord *)d_other, weighted != 0); });
+}
+
+void patolette_amd_hist_totals(const void *d_hist, int weighted, uint64_t *pixels, uint64_t *colors, int *exit_code) {
+    if (!d_hist) return (void)ArgCheck{"patolette_amd_hist_totals", exit_code}.fail(-1, "no histogram");
+    *exit_code = guarded([&](Engine &E) { run_hist_totals(E, (const HistWord *)d_hist, weighted != 0, pixels, colors); });
+}
+
+void patolette_amd_hist_export(const void *d_hist, int weighted, size_t capacity, unsigned char *colors, uint64_t *counts, double *weights,
+                               int *exit_code) {
+    if (!d_hist) return (void)ArgCheck{"patolette_amd_hist_export", exit_code}.fail(-1, "no histogram");
+    *exit_code = guarded([&](Engine &E) { run_hist_export(E, (const HistWord *)d_hist, weighted != 0, capacity, colors, counts, weights); });
+}
+
+void patolette_amd_hist_palette(const void *d_hist, int weighted, size_t palette_size, const patolette__QuantizationOptions *options,
+                                double *palette, unsigned char *palette_u8, int *exit_code) {
+    const ArgCheck arg{"patolette_amd_hist_palette", exit_code};
+    if (!d_hist) return (void)arg.fail(-1, "no histogram");
+    if (!options) return (void)arg.fail(-1, "no options");
+    *exit_code = validate(1, 1, palette_size);
+    if (*exit_code != 0) return;
+    *exit_code = guarded([&](Engine &E) { run_hist_palette(E, (const HistWord *)d_hist, weighted != 0, palette_size, options, palette, palette_u8); });
 }
 
 // Independent images: up to six are in flight at once, each on its own engine (HIP stream + workspace) driven by
