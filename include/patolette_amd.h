@@ -798,7 +798,12 @@ int patolette_amd_debug_nn_route(int route);
 int patolette_amd_debug_nn_map_elem(const double *colors, size_t n, const double *palette, size_t k, int map_elem_bytes, int misalign,
                                     void *map);
 
-/* patolette__DITHER_riemersma (dither/riemersma.c:437-459); colors/palette in linear Rec2020 */
+/* patolette__DITHER_riemersma (dither/riemersma.c:437-459); colors/palette in linear Rec2020.  Any double is taken for a PIXEL: one
+ * whose distances are all NaN or +Inf (a NaN, an infinite or a huge value in a plane) gets index 0, as do the pixels behind it
+ * while its error -- or a sum of errors that overflows -- is in the queue, and the chain goes on from there: the reference's
+ * behaviour, under both layouts.  The PALETTE is taken to be finite and below 2^1000 in magnitude: with a larger entry the error
+ * sums of the wavefront layout may overflow where no pixel announced it, and the map then differs from the reference's to the end of
+ * that run. */
 int patolette_amd_dither(const double *colors, size_t width, size_t height, const double *palette,
                          size_t k, size_t *map);
 
@@ -822,6 +827,13 @@ int patolette_amd_dither_layout_in_use(size_t width, size_t height, size_t palet
 /* Where the dither cuts the curve (host-side copy of the kernel's function, runs without a GPU): *d = first curve position of the
  * aligned 64-position block that holds in-image pixel number t (curve order, 0-based), *c = in-image pixels before that block. */
 void patolette_amd_debug_dither_locate(size_t width, size_t height, unsigned long long t, unsigned long long *d, unsigned long long *c);
+/* TESTS ONLY: what the lane layout's search read in the calling thread's last dither, copied to the host.  geom30: for each of the
+ * three grids (over the weighted palette's box +- 1/2 extent, +- 1 1/2 extents, +- 4 extents) ten doubles {lo[3], hi[3], inv[3], G};
+ * amb3: the margins of the f32 first pass {amb, amb_p, amb_x}; tables (NULL: geometry only): the 16-byte records, G^3 first records
+ * {count, entries 0..14} then G^3 second records {entries 15..29, one byte unused} for each grid in turn, 32 (G0^3 + G1^3 + G2^3) bytes, `capacity`
+ * the room there.  0; -1 where that dither did not take the lane layout (or a nearest map has used the workspace since) or the room
+ * is too small.  No kernel and no product path reads what this entry keeps. */
+int patolette_amd_debug_dither_lane_tables(double *geom30, float *amb3, unsigned char *tables, size_t capacity);
 
 /* ---- statistics of the last full-path call on this thread -------------------------------- */
 typedef struct patolette_amd__Stats {

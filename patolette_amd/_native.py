@@ -164,6 +164,7 @@ SYMBOLS = {
     "patolette_amd_dither_layout_in_use": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t]),
     "patolette_amd_debug_dither_locate": (None, [C.c_size_t, C.c_size_t, C.c_ulonglong, C.POINTER(C.c_ulonglong),
                                                  C.POINTER(C.c_ulonglong)]),
+    "patolette_amd_debug_dither_lane_tables": (C.c_int, [dp, C.POINTER(C.c_float), C.c_void_p, C.c_size_t]),
     "patolette_amd_last_stats": (None, [C.POINTER(Stats)]),
     "patolette_amd_last_map_palette": (C.c_size_t, [dp, C.c_size_t]),
     "patolette_amd_last_split_trace": (C.c_size_t, [C.POINTER(SplitTrace), C.POINTER(SplitRecord), C.c_size_t]),

@@ -29,6 +29,10 @@ struct NNWork {                        // scratch of the pruned NN map
     hipStream_t side_stream = nullptr, side_stream2 = nullptr;   // lane-per-run dither: the record grids are built here while the pixels are gathered
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr;
     int side_dev = -1;
+    // tests (dither_lane_tables): what the last dither's lane layout gave its kernels -- the three grids (first, 1.5 extents, 4 extents)
+    // and the margins of the f32 first pass; the record tables themselves are still in `lut`.  valid: the last dither or nearest map
+    // on this workspace was a lane-layout dither that finished
+    struct LaneTables { bool valid = false; double lo[3][3], hi[3][3], inv[3][3]; int G[3]; float amb, amb_p, amb_x; } lane_tables;
     NNWork() = default;
     NNWork(const NNWork &) = delete;
     NNWork &operator=(const NNWork &) = delete;
@@ -90,6 +94,9 @@ void dither_layout(int lanes);
 // returns the previous value
 int dither_solo_cap(int cap);
 int dither_stall_passes(int n);
+// tests: the lane layout's tables of the last dither on this workspace, read back (patolette_amd_debug_dither_lane_tables in
+// patolette_amd.h says what goes where).  0, or -1 where that dither did not take the lane layout or `capacity` is too small.
+int dither_lane_tables(NNWork &w, double *geom30, float *amb3, unsigned char *tables, size_t capacity, hipStream_t s);
 // keep the curve order of an image size on the device between calls (default) or make it again in every call
 void dither_order_cache(bool on);
 

@@ -939,6 +939,7 @@ static void launch_nn_mid_u8(const unsigned char *d_px, int channels, size_t n, 
 void launch_nn_map_u8(const unsigned char *d_px, int channels, size_t n, const double *d_pal, int k, void *d_out, int elem_bytes, NNWork &w, hipStream_t s) {
     if (!nn_map_u8_applies(n, k)) throw HipError("patolette_amd: the byte-source map kernel takes 2^22 .. 2^32 pixels and 8 .. 256 palette rows");
     if (channels != 3 && channels != 4) throw HipError("patolette_amd: 8-bit pixels have 3 or 4 channels");
+    w.lane_tables.valid = false;
     if (elem_bytes == 1) launch_nn_mid_u8<unsigned char>(d_px, channels, n, d_pal, k, (unsigned char *)d_out, w, s);
     else if (elem_bytes == 4) launch_nn_mid_u8<unsigned int>(d_px, channels, n, d_pal, k, (unsigned int *)d_out, w, s);
     else throw HipError("patolette_amd: the byte-source map kernel writes 1- or 4-byte elements");
@@ -949,6 +950,7 @@ void launch_nn_map_u8(const unsigned char *d_px, int channels, size_t n, const d
 void launch_nn_map(const double *d_colors, size_t plane_stride, size_t n, const double *d_pal, int k, void *d_out, int elem_bytes,
                    const double *lo, const double *hi, NNWork &w, hipStream_t s) {
     if (elem_bytes != 1 && elem_bytes != 4 && elem_bytes != 8) throw HipError("patolette_amd: map element size must be 1, 4 or 8");
+    w.lane_tables.valid = false;                                    // (w.lut may be written below)
     const int cls = nn_size_class(n);
     bool use_lut = cls >= 1 && k >= 8 && k <= 4096;
     double blo[3] = {0, 0, 0}, bhi[3] = {0, 0, 0};
@@ -1074,7 +1076,12 @@ __device__ __forceinline__ int wave_argmin_nonneg_f64(double v) {
 // stand behind an s_nop each, and the three compare / select pairs behind theirs; interleaved, each fills the other's gaps:
 // 14 issue slots instead of 21 on a chain whose cost is its instruction count.  Returns the row minima (every lane its row's).
 // (The wait states inside these two blocks are counted by hand for the CDNA3 / CDNA4 issue rules -- the hazard recogniser does not
-// look inside inline asm -- and the K = 100 / 128 / 130 / 256 dither parity tests are their check after every toolchain change.)
+// look inside inline asm.  Their check after every toolchain change: tests/test_gpu_dither_edges.py, whose "ties-*-grouped" images make
+// two, four and eight distances of one lane EQUAL at every pair of places -- the one case the compare / select chain exists for --
+// next to the K = 100 / 128 / 130 / 256 dither parity tests on noise, which never do.)
+// The compares that keep an earlier entry are ORDERED (v_cmp_lg, not v_cmp_neq): for a query that is NaN every distance and bd are
+// NaN, nothing is "less or greater", and e falls through to entry 0 -- the reference's strict '<' from +Inf never leaves index 0 --
+// where the unordered form kept the lane's last entry.  Same instruction class, same wait states.
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__) && !defined(__gfx942__)
 #error "map.hip: the hand-scheduled DPP blocks of the dither are written for gfx950 (MI355X); see the Makefile's ARCH"
 #endif
@@ -1085,12 +1092,12 @@ __device__ __forceinline__ unsigned dither_rows4(const double d0, const double d
                  "s_nop 0\n\t"
                  "v_min_u32_dpp %[t], %[hi], %[hi] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
                  "v_cndmask_b32_e64 %[e], 3, 2, vcc\n\t"                   // entry 2 if it attains the minimum, else 3
-                 "v_cmp_neq_f64_e32 vcc, %[d1], %[bd]\n\t"
+                 "v_cmp_lg_f64_e32 vcc, %[d1], %[bd]\n\t"
                  "v_min_u32_dpp %[t], %[t], %[t] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
                  "s_nop 0\n\t"
                  "v_cndmask_b32_e32 %[e], 1, %[e], vcc\n\t"               // entry 1 if it does
                  "v_min_u32_dpp %[t], %[t], %[t] row_ror:4 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_cmp_neq_f64_e32 vcc, %[d0], %[bd]\n\t"
+                 "v_cmp_lg_f64_e32 vcc, %[d0], %[bd]\n\t"
                  "s_nop 0\n\t"
                  "v_min_u32_dpp %[t], %[t], %[t] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
                  "v_cndmask_b32_e32 %[e], 0, %[e], vcc"                     // entry 0 if it does
@@ -1106,7 +1113,7 @@ __device__ __forceinline__ unsigned dither_rows4(const double d0, const double d
 __device__ __forceinline__ unsigned dither_rows2(const double d0, const double bd, int &e) {
     const unsigned hi = (unsigned)__double2hiint(bd);
     unsigned t; int ee;
-    asm volatile("v_cmp_neq_f64_e32 vcc, %[d0], %[bd]\n\t"
+    asm volatile("v_cmp_lg_f64_e32 vcc, %[d0], %[bd]\n\t"
                  "s_nop 0\n\t"
                  "v_min_u32_dpp %[t], %[hi], %[hi] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
                  "v_cndmask_b32_e64 %[e], 0, 1, vcc\n\t"                   // entry 0 if it attains the minimum, else 1
@@ -1253,7 +1260,7 @@ __global__ __launch_bounds__(64) void k_dither(const double *__restrict__ img, s
         double bd = INFINITY; int bj = 0;
         if constexpr (PER > 0) {
             // the lane's smallest distance first (v_min_f64), the entry that attains it afterwards: the FIRST of the lane's
-            // entries equal to the minimum = ascending index with strict '<' (distances are never NaN here)
+            // entries equal to the minimum = ascending index with strict '<' (a NaN query: every distance is NaN, entry 0 of lane 0)
             double dd[PER];
 #pragma unroll
             for (int m = 0; m < PER; m++) {
@@ -1333,7 +1340,15 @@ __global__ __launch_bounds__(64) void k_dither(const double *__restrict__ img, s
     unsigned met = 0;                                                // ... for this many groups of sixteen in a row
     const unsigned need = (MODE == 1 && sg.through) ? (unsigned)(npix / sg.S / 16) + 3u : 1u;
     // up to sixteen pending pixels, in order; `limit` < 16 only for the very last group
-    auto group = [&](const int limit, const bool warmup) {
+    // SAFE (a std::bool_constant): the sums restart by selection instead of the multiplication by keep = 0, which keeps a NaN or an
+    // infinity for ever (NaN * 0) where the reference's queue drops it after sixteen steps.  Same bits for finite sums, three
+    // instructions more per step: only the wavefronts that have loaded a pixel that is NaN or not below kDitherTame = 2^1000 in some
+    // plane take it (`unsafe`).  With every pixel below that -- and a palette below it, which the entry points' callers hand over --
+    // an error is below 2^1001 and a sum of sixteen below 2^1004: no sum overflows on the fused path.  (Two finite pixels of 1e308 in
+    // a row do overflow the reference's sum; they are above the limit and take SAFE.)
+    constexpr double kDitherTame = 0x1.0p1000;
+    bool unsafe = false;
+    auto group = [&](const int limit, const bool warmup, auto SAFE) {
         double pcs[16];
 #pragma unroll
         for (int j = 0; j < 16; j++) pcs[j] = rpx[ch * kRing + ((head + (unsigned)j) & (kRing - 1))];
@@ -1349,7 +1364,8 @@ __global__ __launch_bounds__(64) void k_dither(const double *__restrict__ img, s
                 const double err = pcs[j] - prw[bi];                 // original pixel - chosen colour (riemersma.c:333-340)
                 // lane (c, j) starts the sum of step + 16 with term 0: acc * keep + t with keep = 0 there, 1 elsewhere -- the product is
                 // exact, so the fused form rounds exactly like (keep ? acc : 0) + t, in two instructions instead of four
-                acc = __builtin_fma(acc, keep[j], err * wl[j]);
+                if constexpr (decltype(SAFE)::value) acc = (dph == j ? 0.0 : acc) + err * wl[j];
+                else acc = __builtin_fma(acc, keep[j], err * wl[j]);
             }
         }
         if constexpr (MODE == 0) {
@@ -1373,6 +1389,7 @@ __global__ __launch_bounds__(64) void k_dither(const double *__restrict__ img, s
     const bool needs_skip = width < (1u << L) || height < (1u << L);
     // decode the block of 64 positions at d0 and append its in-image pixels to the ring; false = an empty aligned square was skipped
     auto load_block = [&](unsigned long long &d0) -> bool {
+        bool fin = true;                                             // this lane's pixel is tame: no NaN, below kDitherTame (or the lane loads none)
         if constexpr (MASKED) {                                      // 64 ranks of the table: every one below mcount is visited
             const unsigned long long r = d0 + (unsigned long long)lane;
             const bool inb = r < mcount;
@@ -1380,9 +1397,12 @@ __global__ __launch_bounds__(64) void k_dither(const double *__restrict__ img, s
             if (inb) {
                 const unsigned p = mpos[r];
                 const unsigned slot = (count + (unsigned)lane) & (kRing - 1);   // (d0 is a multiple of 64: the lanes below are in too)
-                rpx[slot] = pr[p]; rpx[kRing + slot] = pg[p]; rpx[2 * kRing + slot] = pb[p];
+                const double v0 = pr[p], v1 = pg[p], v2 = pb[p];
+                rpx[slot] = v0; rpx[kRing + slot] = v1; rpx[2 * kRing + slot] = v2;
                 rpos[slot] = p;
+                fin = fabs(v0) < kDitherTame && fabs(v1) < kDitherTame && fabs(v2) < kDitherTame;
             }
+            if (__any(!fin)) unsafe = true;
             count += (unsigned)__popcll(mask);
             __builtin_amdgcn_wave_barrier();
             d0 += 64;
@@ -1430,9 +1450,12 @@ __global__ __launch_bounds__(64) void k_dither(const double *__restrict__ img, s
         if (inb) {                                                   // append to the ring in curve order
             const size_t p = (size_t)y * width + x;
             const unsigned slot = (count + (unsigned)__popcll(mask & ((1ULL << lane) - 1ULL))) & (kRing - 1);
-            rpx[slot] = pr[p]; rpx[kRing + slot] = pg[p]; rpx[2 * kRing + slot] = pb[p];
+            const double v0 = pr[p], v1 = pg[p], v2 = pb[p];
+            rpx[slot] = v0; rpx[kRing + slot] = v1; rpx[2 * kRing + slot] = v2;
             rpos[slot] = (unsigned)p;
+            fin = fabs(v0) < kDitherTame && fabs(v1) < kDitherTame && fabs(v2) < kDitherTame;
         }
+        if (__any(!fin)) unsafe = true;
         count += (unsigned)__popcll(mask);
         __builtin_amdgcn_wave_barrier();
         d0 += 64;
@@ -1455,7 +1478,7 @@ __global__ __launch_bounds__(64) void k_dither(const double *__restrict__ img, s
 #pragma unroll
         for (int j = 0; j < 16; j++) {
             const double e = __shfl(ev, (lane & 48) | j, 64);
-            acc = __builtin_fma(acc, keep[j], e * wl[j]);
+            acc = (dph == j ? 0.0 : acc) + e * wl[j];                // (by selection: an error that is not finite must not outlive its restart)
         }
         head = count = 16;
         __builtin_amdgcn_wave_barrier();
@@ -1463,9 +1486,13 @@ __global__ __launch_bounds__(64) void k_dither(const double *__restrict__ img, s
     while (d0 < d_end && !done) {
         const bool warmup = d0 < d_start;
         if (!load_block(d0)) continue;
-        while ((int)(count - head) >= 16 && !done) group(16, warmup);
+        while ((int)(count - head) >= 16 && !done) {
+            if (unsafe) group(16, warmup, std::true_type{}); else group(16, warmup, std::false_type{});
+        }
     }
-    if (count != head && !done) group((int)(count - head), false);
+    if (count != head && !done) {
+        if (unsafe) group((int)(count - head), false, std::true_type{}); else group((int)(count - head), false, std::false_type{});
+    }
 }
 
 // --------------------------------------------------------------------------------------------
@@ -2112,6 +2139,15 @@ __global__ __launch_bounds__(64) void k_dither_lane_repair(DitherLanes a, const 
     auto requeue = [&](const unsigned c16) {
         const double ev = rpx[ch * kRing + ((head - 16u + (unsigned)dph) & (kRing - 1))] - prw[c16];
         acc = 0.0;
+        if (__any(!(fabs(ev) < 0x1.0p1000))) {                       // by selection: an error that is not finite, or so large that a sum
+                                                                     // of sixteen may overflow, must not outlive its restart
+#pragma unroll
+            for (int j = 0; j < 16; j++) {
+                const double e = __shfl(ev, (lane & 48) | j, 64);
+                acc = (dph == j ? 0.0 : acc) + e * wl[j];
+            }
+            return;
+        }
 #pragma unroll
         for (int j = 0; j < 16; j++) {
             const double e = __shfl(ev, (lane & 48) | j, 64);
@@ -2244,6 +2280,10 @@ __global__ __launch_bounds__(64) void k_dither_lane_repair(DitherLanes a, const 
             bool jumped = false;
             while ((int)(count - head) >= 16 && !done && !jumped) {
                 group(16);
+                // A sum that is not finite (a NaN, an infinite or a huge pixel within the last 32 steps): the restart by multiplication
+                // keeps it for ever (NaN * 0) where the reference's queue drops an error after sixteen steps.  Within a group no lane is
+                // read after its own restart, so the group's choices are the chain's; the queue is rebuilt before the next one.
+                if (__any(!__builtin_isfinite(acc))) requeue((unsigned)__shfl((int)tail, dph, 64));
                 // every 64 steps of a stretch: has the chain come round?
                 if (!done && T - flat_from >= 48u && ((T - flat_from) & 63u) < 16u) {
                     const unsigned P = find_period();
@@ -2335,6 +2375,7 @@ static bool launch_dither_lanes(const double *d_img, size_t plane_stride, int wh
     // src8 (launch_dither_u8; no mask): the pixels as interleaved 8-bit sRGB, `channels` bytes each, in place of d_img / which
     const size_t nframe = width * height;
     const size_t npix = mpos ? mcount : frames * nframe;
+    w.lane_tables.valid = false;
     DitherLanes a{};
     // runs: eight wavefronts of 64 per CU (two per SIMD), none shorter than 256 pixels unless asked for
     size_t S = cfg.segments > 0 ? (size_t)cfg.segments : std::min<size_t>((size_t)num_cus() * 8 * 64, npix / 256);
@@ -2545,7 +2586,35 @@ static bool launch_dither_lanes(const double *d_img, size_t plane_stride, int wh
 #undef PAMD_DITHER_UNPERMUTE
     }
     HIP_CHECK(hipGetLastError());
+    {
+        NNWork::LaneTables &t = w.lane_tables;                          // (tests: dither_lane_tables)
+        for (int lv = 0; lv < 3; lv++) {
+            const NNGrid &gg = lv == 0 ? a.g : a.wide[lv - 1].g;
+            const double *hh = lv == 0 ? a.hi : a.wide[lv - 1].hi;
+            for (int c = 0; c < 3; c++) { t.lo[lv][c] = gg.lo[c]; t.hi[lv][c] = hh[c]; t.inv[lv][c] = gg.inv[c]; }
+            t.G[lv] = gg.G;
+        }
+        t.amb = a.amb; t.amb_p = a.amb_p; t.amb_x = a.amb_x;
+        t.valid = true;
+    }
     return true;
+}
+
+int dither_lane_tables(NNWork &w, double *geom30, float *amb3, unsigned char *tables, size_t capacity, hipStream_t s) {
+    const NNWork::LaneTables &t = w.lane_tables;
+    if (!t.valid) return -1;
+    size_t bytes = 0;
+    for (int lv = 0; lv < 3; lv++) {
+        for (int c = 0; c < 3; c++) { geom30[10 * lv + c] = t.lo[lv][c]; geom30[10 * lv + 3 + c] = t.hi[lv][c]; geom30[10 * lv + 6 + c] = t.inv[lv][c]; }
+        geom30[10 * lv + 9] = (double)t.G[lv];
+        bytes += (size_t)t.G[lv] * t.G[lv] * t.G[lv] * 32;
+    }
+    amb3[0] = t.amb; amb3[1] = t.amb_p; amb3[2] = t.amb_x;
+    if (tables == nullptr) return 0;
+    if (capacity < bytes || w.lut.cap < bytes) return -1;
+    HIP_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(hipMemcpy(tables, w.lut.p, bytes, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 // the pixels into linear Rec2020 in image order (what the wavefront layout reads), for the fall-back out of the lane layout
@@ -2757,6 +2826,7 @@ void launch_dither_masked(const double *d_img, size_t plane_stride, int which, s
 static void launch_dither_waves(const double *d_img, size_t plane_stride, size_t width, size_t height, const double *d_pal, int k,
                                 void *d_out, int elem_bytes, NNWork &w, hipStream_t s, const unsigned *mpos, size_t mcount) {
     size_t lds = ((size_t)6 * k + 3 * 128) * sizeof(double) + 128 * sizeof(unsigned int);      // palette (raw + weighted) + the ring of pending pixels
+    w.lane_tables.valid = false;
     double *gtab = nullptr;
     if (lds > 150 * 1024) {                                      // K > 3200: the tables in global memory (workspace kept with the engine)
         w.dtab.reserve((size_t)6 * k);

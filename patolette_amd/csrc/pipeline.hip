@@ -1380,6 +1380,9 @@ static void ws_prepare(Engine &E, size_t N, size_t K, bool weighted, bool verbos
     E.stage_in.reserve(nput); E.stage_out.reserve(nput); E.ids.reserve(nput); E.h_stage_in.reserve(nput); E.h_stage_out.reserve(nput);
     E.h_ids.reserve(nput); E.h_ids_get.reserve(nput);
     E.h_cent.reserve(3 * K);                                       // KMeans: the centroids' pinned copy
+    // the map stage's palette (at most K rows) on the device and pinned: an engine that met a smaller K first would otherwise grow
+    // them in the map stage, where the second stream may still hold work of this call
+    E.dpal.reserve(3 * K); E.h_pal.reserve(3 * K);
     if (lq_dev) { E.lqctl.reserve(1); E.h_lqhead.reserve(1); E.h_lqrec.reserve(kLqNodeCap); E.h_lqcen.reserve(kLqNodeCap); }
 }
 
@@ -4411,6 +4414,9 @@ void patolette_amd_dither_layout(int lanes) { dither_layout(lanes); }
 int patolette_amd_debug_dither_solo_cap(int cap) { return dither_solo_cap(cap); }
 int patolette_amd_debug_dither_stall_passes(int n) { return dither_stall_passes(n); }
 int patolette_amd_dither_layout_in_use(size_t width, size_t height, size_t k) { return dither_lane_layout(width, height, (int)k) ? 1 : 0; }
+int patolette_amd_debug_dither_lane_tables(double *geom30, float *amb3, unsigned char *tables, size_t capacity) {
+    return guarded([&](Engine &E) -> int { return dither_lane_tables(E.nn, geom30, amb3, tables, capacity, E.stream); });
+}
 void patolette_amd_last_stats(patolette_amd__Stats *out) { *out = engine().stats; }
 size_t patolette_amd_last_split_trace(patolette_amd__SplitTrace *hdr, patolette_amd__SplitRecord *recs, size_t capacity) {
     Engine &E = engine();

@@ -82,3 +82,16 @@ def constant_mean_image(rows, cols, seed, values=(0.25, 0.5, 0.75)):
     rng = np.random.default_rng(seed)
     order = np.argsort(rng.random((rows, cols, 3)), axis=2)
     return np.asarray(values, dtype=np.float64)[order]
+
+
+def dither_locate(native, width, height):
+    """t -> the in-image pixels before the aligned 64-position block of the curve that holds in-image pixel t: where the wavefront
+    layout starts a run that is cut at t (patolette_amd_debug_dither_locate, host code: no GPU)"""
+    import ctypes as C
+    L = native.lib()
+
+    def locate(t):
+        d, c = C.c_ulonglong(0), C.c_ulonglong(0)
+        L.patolette_amd_debug_dither_locate(width, height, int(t), C.byref(d), C.byref(c))
+        return int(c.value)
+    return locate
