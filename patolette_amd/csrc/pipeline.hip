@@ -2319,11 +2319,27 @@ static ConvertPlan convert_plan(const Engine &E, const patolette__QuantizationOp
     }
     return p;
 }
+// Stage S1's launch for a device image as `px` describes it, into E.cvt / E.cstats on stream s: the whole image, or the pixels
+// [lo, hi) of it (upload_image's pieces; `first`: the launch that initialises the statistics)
+static void convert_pixels(Engine &E, const ConvertPlan &cp, const Pixels &px, size_t N, hipStream_t s, size_t lo = 0, size_t hi = ~(size_t)0,
+                           bool first = true) {
+    if (px.u8) launch_convert_u8(cp.which, px.u8, px.channels, E.cvt.p, N, E.cstats.p, s, cp.sumk, cp.momk, lo, hi, first);
+    else if (px.rows) launch_convert_rows(cp.which, px.f64, E.cvt.p, N, E.cstats.p, s, cp.sumk, cp.momk, lo, hi, first);
+    else launch_convert(cp.which, px.f64, E.cvt.p, N, E.cstats.p, s, cp.sumk, cp.momk, lo, hi, first);
+}
 
-// the dither launchers' counters of their last walk, into the call's statistics
-static void copy_dither_stats(Engine &E) {
-    E.stats.dither_segments = E.nn.dither_segments; E.stats.dither_repairs = E.nn.dither_repairs; E.stats.dither_rounds = E.nn.dither_rounds;
-    E.stats.dither_through = E.nn.dither_through; E.stats.dither_jumps = E.nn.dither_jumps; E.stats.dither_solo = E.nn.dither_solo;
+// A palette's write-out (patolette.c:327-336): K rows, planar -- `off` rows of zeros (the RGBA entry's transparent row), the `rows`
+// rows of `pal` (planar with that stride), -1 for the unused ones
+static void write_palette(double *out, size_t K, size_t off, const std::vector<double> &pal, size_t rows) {
+    for (size_t j = 0; j < K * 3; j++) out[j] = j % K < off ? 0.0 : -1.0;
+    for (int j = 0; j < 3; j++) for (size_t i = 0; i < rows; i++) out[K * (size_t)j + off + i] = pal[(size_t)j * rows + i];
+}
+
+// the dither launchers' counters of their last walk, added to the call's statistics (which start at zero: a call of one walk gets
+// that walk's counters, run_remap_rgba's frame-by-frame walks their sums)
+static void add_dither_stats(Engine &E) {
+    E.stats.dither_segments += E.nn.dither_segments; E.stats.dither_repairs += E.nn.dither_repairs; E.stats.dither_rounds += E.nn.dither_rounds;
+    E.stats.dither_through += E.nn.dither_through; E.stats.dither_jumps += E.nn.dither_jumps; E.stats.dither_solo += E.nn.dither_solo;
 }
 // whether the map stage writes the map at all: a 1x1 dither visits nothing (riemersma.c:452-456)
 static bool map_touched(bool dither, size_t width, size_t height) { return !(dither && std::max(width, height) <= 1); }
@@ -2342,26 +2358,19 @@ static void run_device(Engine &E, size_t width, size_t height, Pixels px, const 
     ws_prepare(E, N, K, weighted, opt->verbose);
     if (opt->kmeans_niter > 0) subsample_start(E, E.shard ? E.shard->total : N, K, opt->kmeans_max_samples);
     // S1: colour conversion into the working image (x|y|z|w planar), patolette.c:201-207
-    double t0 = now_ms();
-    E.cvt.reserve((weighted ? 4 : 3) * N);
-    E.cstats.reserve(1);
+    double t0 = now_ms();                                        // (E.cvt and E.cstats: ws_prepare)
     if (E.shard && opt->dither && !opt->palette_only)
         throw HipError("patolette_amd: dithering walks the whole image along one curve; it is not available per slice");
     const ConvertPlan cp = convert_plan(E, opt, N);
-    const int which = cp.which;
-    const BinK sumk = cp.sumk, momk = cp.momk;
-    if (px.converted) { /* upload_image has converted the image chunk by chunk behind its upload */ }
-    else if (px.u8) launch_convert_u8(which, px.u8, px.channels, E.cvt.p, N, E.cstats.p, s, sumk, momk);
-    else if (px.rows) launch_convert_rows(which, px.f64, E.cvt.p, N, E.cstats.p, s, sumk, momk);
-    else launch_convert(which, px.f64, E.cvt.p, N, E.cstats.p, s, sumk, momk);
+    if (!px.converted) convert_pixels(E, cp, px, N, s);          // (else upload_image has converted the image chunk by chunk behind its upload)
     if (weighted) {
         HIP_CHECK(hipMemcpyAsync(E.cvt.p + 3 * N, d_weights, N * sizeof(double), hipMemcpyDeviceToDevice, s));
         launch_weight_stats(d_weights, N, E.cstats.p, s);
     }
     // the quantiser's size-only preparations go behind the statistics' download: they run while the host derives the bounds
     Bounds bnd = read_bounds(E, weighted, [&] { gq_prepare(E, N, weighted); });
-    bnd.have_sum = sumk.M0 != 0.0;
-    bnd.have_mom = momk.M0 != 0.0;
+    bnd.have_sum = cp.sumk.M0 != 0.0;
+    bnd.have_mom = cp.momk.M0 != 0.0;
     E.stats.ms_convert = now_ms() - t0;
 
     // S2 + S3: global + local quantiser (progress lines as patolette.c:209-229 prints them when verbose)
@@ -2411,7 +2420,7 @@ static void run_device(Engine &E, size_t width, size_t height, Pixels px, const 
                     launch_convert(pix, E.cvt.p, E.aux.p, N, nullptr, s);      // plane stride of cvt is N for x,y,z
                     dither(E.aux.p, PAMD_COPY, 0);
                 }
-                copy_dither_stats(E);
+                add_dither_stats(E);
             }
             palette_rows(pal, len, hm::color::rec2020_to_srgb);
         } else {                                                               // patolette.c:300-324
@@ -2442,9 +2451,8 @@ static void run_device(Engine &E, size_t width, size_t height, Pixels px, const 
         E.sync();
     }
     E.stats.ms_map = now_ms() - t0;
-    // S6: palette write-out, unused rows = -1 (patolette.c:327-336)
-    for (size_t j = 0; j < K * 3; j++) palette[j] = -1.0;
-    for (int j = 0; j < 3; j++) for (size_t i = 0; i < len; i++) palette[K * (size_t)j + i] = pal[(size_t)j * len + i];
+    // S6: palette write-out, unused rows = -1
+    write_palette(palette, K, 0, pal, len);
     E.stats.ms_total = now_ms() - t_start;
 }
 
@@ -2543,29 +2551,29 @@ static void download_map_widened(Engine &E, const void *d_map, int me, size_t N,
 }
 
 // A host image up into E.src (f64: planar, or (N,3) row-major when `rows`) or E.src8 (interleaved 8-bit pixels of 3 or 4 channels), which
-// the caller has reserved; `host` describes it as Pixels describes a device image.  Nothing is waited for.
+// the caller has reserved as it has E.cvt (with the weights' plane if the call has weights: run_device must not move what is converted
+// here) and E.cstats -- ws_prepare; `host` describes it as Pixels describes a device image.  Nothing is waited for.
 // Large images go up in pieces and what a piece completes is converted (on a second stream) while the next one is on the link:
 // the conversion (0.5 ms of a 4096^2 image's 7 ms upload) disappears behind the copy.  Its statistics are exact sums and keyed
 // extrema, so the chunking changes no bit.  With derived weights too: the saliency stage reads the sRGB source, which stays where it is.
-// weight_plane: the call will have weights (E.cvt gets their plane now: run_device must not move what is converted here).
-// Returns whether E.cvt / E.cstats hold the converted image.
-static bool upload_image(Engine &E, const Pixels &host, size_t N, bool weight_plane, const patolette__QuantizationOptions *opt) {
+// Returns the image as it now lies on the device, `converted` set where E.cvt / E.cstats hold the converted image.
+static Pixels upload_image(Engine &E, const Pixels &host, size_t N, const patolette__QuantizationOptions *opt) {
     hipStream_t s = E.stream;
+    Pixels dev = host;
+    if (host.u8) dev.u8 = E.src8.p; else dev.f64 = E.src.p;
     unsigned char *dst = host.u8 ? E.src8.p : (unsigned char *)E.src.p;
     const unsigned char *from = host.u8 ? host.u8 : (const unsigned char *)host.f64;
     const size_t px_bytes = host.u8 ? (size_t)host.channels : 3 * sizeof(double);
     const size_t chunk_min = getenv("PAMD_UPLOAD_CHUNK_MIN") ? (size_t)atoll(getenv("PAMD_UPLOAD_CHUNK_MIN")) : ((size_t)1 << 21);   // (read per call: tests lower it)
     if (!(N >= chunk_min && !E.shard)) {
         HIP_CHECK(hipMemcpyAsync(dst, from, N * px_bytes, hipMemcpyHostToDevice, s));
-        return false;
+        return dev;
     }
     if (!E.stream2) {
         HIP_CHECK(hipStreamCreateWithFlags(&E.stream2, hipStreamNonBlocking));
         for (hipEvent_t *e : {&E.ev_up[0], &E.ev_up[1], &E.ev_join}) HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
     const ConvertPlan cp = convert_plan(E, opt, N);
-    E.cvt.reserve((weight_plane ? 4 : 3) * N);
-    E.cstats.reserve(1);
     HIP_CHECK(hipEventRecord(E.ev_join, s));                     // whatever the engine's stream still holds comes first
     HIP_CHECK(hipStreamWaitEvent(E.stream2, E.ev_join, 0));
     // planar source: the first two planes go up whole (every copy call has a fixed cost: 24 pieces made the upload 0.44 ms
@@ -2581,9 +2589,7 @@ static bool upload_image(Engine &E, const Pixels &host, size_t N, bool weight_pl
         HIP_CHECK(hipMemcpyAsync(dst + head + lo * step, from + head + lo * step, cnt * step, hipMemcpyHostToDevice, s));
         HIP_CHECK(hipEventRecord(E.ev_up[c & 1], s));
         HIP_CHECK(hipStreamWaitEvent(E.stream2, E.ev_up[c & 1], 0));
-        if (host.u8) launch_convert_u8(cp.which, E.src8.p, host.channels, E.cvt.p, N, E.cstats.p, E.stream2, cp.sumk, cp.momk, lo, lo + cnt, c == 0);
-        else if (host.rows) launch_convert_rows(cp.which, E.src.p, E.cvt.p, N, E.cstats.p, E.stream2, cp.sumk, cp.momk, lo, lo + cnt, c == 0);
-        else launch_convert(cp.which, E.src.p, E.cvt.p, N, E.cstats.p, E.stream2, cp.sumk, cp.momk, lo, lo + cnt, c == 0);
+        convert_pixels(E, cp, dev, N, E.stream2, lo, lo + cnt, c == 0);
     }
     HIP_CHECK(hipEventRecord(E.ev_join, E.stream2));
     HIP_CHECK(hipStreamWaitEvent(s, E.ev_join, 0));
@@ -2591,7 +2597,52 @@ static bool upload_image(Engine &E, const Pixels &host, size_t N, bool weight_pl
     // hipStreamSynchronize on it has returned; a record behind the wait makes the stream's state readable again (the late-growth
     // count of patolette_amd_debug_workspace asks exactly that question).  Both pieces' waits on ev_up[0] are enqueued by now.
     HIP_CHECK(hipEventRecord(E.ev_up[0], s));
-    return true;
+    dev.converted = true;
+    return dev;
+}
+
+// The front half of the quantising drivers (run_host, run_u8, run_rgba): what run_device takes -- the image on the device and its
+// weights there (given, derived, or null) -- and the time from t_start until the upload's wait was over.
+// src: frames x width x height pixels as the caller gives them, host memory unless `on_device`; `weights` likewise.  stage: the
+// pixels go into the workspace -- a host image always (upload_image); a device image where the kernels cannot read it in place
+// (run_rgba's unaligned pixels).  The caller has reserved what its output half takes and has enqueued nothing: this reserves the rest,
+// uploads, waits for what came from the host, and derives the weights the binding derives when tile_size > 0 (each frame as an image
+// of its own).  counted (run_rgba's opaque count): enqueued behind the upload; it waits for the stream itself -- one wait for the
+// upload and its own download -- and says whether anything is left to quantise: only then are weights derived.
+struct QuantInput { Pixels px; const double *d_w; double ms_upload; };
+static QuantInput quant_input(Engine &E, double t_start, const Pixels &src, bool on_device, bool stage, size_t frames, size_t width, size_t height,
+                              const double *weights, double tile_size, size_t K, const patolette__QuantizationOptions *opt,
+                              const std::function<bool(const unsigned char *)> &counted = nullptr) {
+    const size_t N = frames * width * height;
+    const bool derive = !weights && tile_size > 0.0, weighted = weights || derive;
+    if (stage) { if (src.u8) E.src8.reserve(N * (size_t)src.channels); else E.src.reserve(3 * N); }
+    if (weights && !on_device) E.wsrc.reserve(N);
+    if (derive) { E.wsal.reserve(N); saliency_reserve(E.sal, width, height); }
+    ws_prepare(E, N, K, weighted, opt->verbose);   // (the workspace as run_device will want it: nothing is queued yet)
+    QuantInput in{src, weights, 0.0};
+    if (!on_device) in.px = upload_image(E, src, N, opt);
+    else if (stage) {
+        HIP_CHECK(hipMemcpyAsync(E.src8.p, src.u8, N * (size_t)src.channels, hipMemcpyDeviceToDevice, E.stream));
+        in.px.u8 = E.src8.p;
+    }
+    if (weights && !on_device) {
+        HIP_CHECK(hipMemcpyAsync(E.wsrc.p, weights, N * sizeof(double), hipMemcpyHostToDevice, E.stream));
+        in.d_w = E.wsrc.p;
+    }
+    bool any = true;
+    if (counted) any = counted(in.px.u8);
+    else if (!on_device) HIP_CHECK(hipStreamSynchronize(E.stream));
+    in.ms_upload = now_ms() - t_start;
+    E.ms_saliency = 0.0;
+    if (derive && any) in.d_w = derive_weights(E, in.px.f64, in.px.u8, in.px.rows ? -3 : in.px.channels, width, height, tile_size, frames);
+    return in;
+}
+// ... and their epilogue, behind the output half that began at t_out: run_device has written its own stages' times and their total
+static void quant_stats(Engine &E, const QuantInput &in, double t_out) {
+    E.stats.ms_saliency = E.ms_saliency;
+    E.stats.ms_upload = in.ms_upload;
+    E.stats.ms_download = now_ms() - t_out;
+    E.stats.ms_total += E.ms_saliency + in.ms_upload + E.stats.ms_download;
 }
 
 // host-buffer entry: upload, run, download + widen
@@ -2600,33 +2651,17 @@ static void run_host(Engine &E, size_t width, size_t height, const double *data,
                      void *d_map_out = nullptr) {
     // d_map_out: leave the narrow index map (u8 for K <= 256, else u32) in HBM there instead of widening it into palette_map
     const size_t N = width * height;
-    double t0 = now_ms();
+    const double t_start = now_ms();
     WsGuard wg(&E.stream, &E.stream2);
-    const bool derive = !weights && tile_size > 0.0, weighted = weights || derive;
-    E.src.reserve(3 * N);
-    if (weights) E.wsrc.reserve(N);
-    else if (derive) { E.wsal.reserve(N); saliency_reserve(E.sal, width, height); }
-    ws_prepare(E, N, K, weighted, opt->verbose);   // (the workspace as run_device will want it: nothing is queued yet)
-    Pixels px{E.src.p, nullptr, 3, rows};
-    px.converted = upload_image(E, Pixels{data, nullptr, 3, rows}, N, weighted, opt);
-    if (weights) HIP_CHECK(hipMemcpyAsync(E.wsrc.p, weights, N * sizeof(double), hipMemcpyHostToDevice, E.stream));
-    HIP_CHECK(hipStreamSynchronize(E.stream));
-    const double up = now_ms() - t0;
-    const double *d_w = weights ? E.wsrc.p : nullptr;
-    E.ms_saliency = 0.0;
-    if (derive) d_w = derive_weights(E, E.src.p, nullptr, rows ? -3 : 3, width, height, tile_size);
     const int me = map_elem_for(K);
     if (!opt->palette_only && !d_map_out) E.dmap.reserve(N * (size_t)me);
+    const QuantInput in = quant_input(E, t_start, Pixels{data, nullptr, 3, rows}, false, true, 1, width, height, weights, tile_size, K, opt);
     std::vector<double> pal(3 * K);
-    run_device(E, width, height, px, d_w, K, opt, pal.data(), d_map_out ? d_map_out : (void *)E.dmap.p, me);
-    E.stats.ms_saliency = E.ms_saliency;
-    E.stats.ms_total += E.ms_saliency;
-    t0 = now_ms();
+    run_device(E, width, height, in.px, in.d_w, K, opt, pal.data(), d_map_out ? d_map_out : (void *)E.dmap.p, me);
+    const double t_out = now_ms();
     if (!opt->palette_only && !d_map_out && map_touched(opt->dither, width, height)) download_map_widened(E, E.dmap.p, me, N, palette_map);
     std::memcpy(palette, pal.data(), 3 * K * sizeof(double));
-    E.stats.ms_upload = up;
-    E.stats.ms_download = now_ms() - t0;
-    E.stats.ms_total += up + E.stats.ms_download;
+    quant_stats(E, in, t_out);
 }
 
 // the device's index map (elements of me: 1 or 4 bytes) into a host buffer with elements of map_elem_out (1, 2, 4 or 8)
@@ -2637,6 +2672,7 @@ static void download_map(const void *d_map, int me, size_t N, void *map_out, int
     given_elems_out(tmp.data(), me, map_out, map_elem_out, 0, N);
 }
 
+static HipError named_error(const char *name, const char *text) { return HipError(std::string(name) + ": " + text); }
 static const char *const kBadDeviceMapElem = "patolette_amd: device map_elem_bytes must be 1 for K <= 256, else 4";
 
 // Where the 8-bit entries' index map (elements of map_elem_for(K8) bytes) lands: in the caller's buffer when that is device memory, else
@@ -2671,6 +2707,31 @@ static void u8_outputs(Engine &E, const void *d_map, size_t N, const unsigned ch
     E.sync();
 }
 
+// The RGBA entries' counterpart (run_rgba, run_remap_rgba): where the kernel that writes the caller's map elements and RGBA words puts
+// them -- the caller's buffers when those are device memory, else E.rgba_map and E.quant8 -- and whether the N pixels must be staged.
+// Checks what the kernels ask of device buffers (`entry`: the caller's C entry, for the message) and reserves these places, with
+// E.src8 for staged pixels: the caller has enqueued nothing yet.  want: a map-derived output is made at all.
+struct RgbaOut { bool stage_px; void *d_map; unsigned char *d_q; };
+static RgbaOut rgba_out_place(Engine &E, const char *entry, size_t N, bool on_device, const unsigned char *pixels, bool want, void *map_out,
+                              int map_elem_out, unsigned char *quant_out) {
+    auto aligned = [](const void *p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; };
+    if (on_device && ((map_out && !aligned(map_out, (size_t)map_elem_out)) || (quant_out && !aligned(quant_out, 4))))
+        throw named_error(entry, "palette_map and quantized must be aligned to their element size");
+    RgbaOut o{!on_device || !aligned(pixels, 4), nullptr, nullptr};   // the kernels read one 32-bit word per pixel
+    if (o.stage_px) E.src8.reserve(4 * N);
+    if (want && !on_device && map_out) E.rgba_map.reserve(N * (size_t)map_elem_out);
+    if (want && !on_device && quant_out) E.quant8.reserve(4 * N);
+    if (want && map_out) o.d_map = on_device ? map_out : (void *)E.rgba_map.p;
+    if (want && quant_out) o.d_q = on_device ? quant_out : E.quant8.p;
+    return o;
+}
+// ... and from there into the caller's buffers where those are host memory, behind one wait for everything the call has enqueued
+static void rgba_copy_out(Engine &E, const RgbaOut &o, size_t N, void *map_out, int map_elem_out, unsigned char *quant_out) {
+    if (o.d_map && o.d_map != map_out) HIP_CHECK(hipMemcpyAsync(map_out, o.d_map, N * (size_t)map_elem_out, hipMemcpyDeviceToHost, E.stream));
+    if (o.d_q && o.d_q != quant_out) HIP_CHECK(hipMemcpyAsync(quant_out, o.d_q, 4 * N, hipMemcpyDeviceToHost, E.stream));
+    E.sync();
+}
+
 // 8-bit adaptor around the path: interleaved u8 in; f64 palette, u8 palette, index map and
 // reconstructed u8 image out.  `pixels`, `d_map_out`, `d_quant_out` are device pointers when `on_device`.
 static void run_u8(Engine &E, size_t width, size_t height, const unsigned char *pixels, int channels, const double *weights,
@@ -2681,48 +2742,22 @@ static void run_u8(Engine &E, size_t width, size_t height, const unsigned char *
     // download and reconstruction serve it as they serve one image
     const size_t N = width * height;
     const size_t fcount = frames ? frames->count : 1, fheight = frames ? frames->height : height;   // one image: a stack of one
-    hipStream_t s = E.stream;
-    double t0 = now_ms();
+    const double t_start = now_ms();
     WsGuard wg(&E.stream, &E.stream2);
-    const bool derive = !weights && tile_size > 0.0, weighted = weights || derive;
-    if (derive) { E.wsal.reserve(N); saliency_reserve(E.sal, width, fheight); }
-    ws_prepare(E, N, K, weighted, opt->verbose);   // (as run_host)
-    // what the stages below take of the workspace, before anything is enqueued (their own reservations are then no-ops)
-    E.cvt.reserve((weighted ? 4 : 3) * N); E.cstats.reserve(1);
+    // what the output stage takes of the workspace, before anything is enqueued (its own reservations are then no-ops)
     void *d_map = u8_map_place(E, N, K, !opt->palette_only && (map_out || quant_out), map_out, map_elem_out, on_device || map_on_device,
                                quant_out, on_device);
-    const unsigned char *d_px = pixels;
-    const double *d_w = weights;
-    bool converted = false;
-    if (!on_device) {
-        E.src8.reserve(N * (size_t)channels);
-        if (weights) E.wsrc.reserve(N);
-        d_px = E.src8.p;
-        converted = upload_image(E, Pixels{nullptr, pixels, channels}, N, weighted, opt);
-        if (weights) {
-            HIP_CHECK(hipMemcpyAsync(E.wsrc.p, weights, N * sizeof(double), hipMemcpyHostToDevice, s));
-            d_w = E.wsrc.p;
-        }
-        HIP_CHECK(hipStreamSynchronize(s));
-    }
-    const double up = now_ms() - t0;
-    E.ms_saliency = 0.0;
-    if (derive) d_w = derive_weights(E, nullptr, d_px, channels, width, fheight, tile_size, fcount);   // (each frame as an image of its own)
+    const QuantInput in = quant_input(E, t_start, Pixels{nullptr, pixels, channels}, on_device, !on_device, fcount, width, fheight, weights,
+                                      tile_size, K, opt);
     std::vector<double> pal(3 * K);
-    Pixels px8{nullptr, d_px, channels};
-    px8.converted = converted;
-    run_device(E, width, height, px8, d_w, K, opt, pal.data(), d_map, map_elem_for(K), nullptr, frames);
-    E.stats.ms_saliency = E.ms_saliency;
-    E.stats.ms_total += E.ms_saliency;
-    t0 = now_ms();
+    run_device(E, width, height, in.px, in.d_w, K, opt, pal.data(), d_map, map_elem_for(K), nullptr, frames);
+    const double t_out = now_ms();
     std::vector<unsigned char> p8(3 * K);
     palette_to_u8(pal.data(), K, p8.data());
     if (palette) std::memcpy(palette, pal.data(), 3 * K * sizeof(double));
     if (palette_u8) std::memcpy(palette_u8, p8.data(), 3 * K);
     if (d_map && map_touched(opt->dither, width, fheight)) u8_outputs(E, d_map, N, p8.data(), K, map_out, map_elem_out, quant_out, on_device);
-    E.stats.ms_upload = up;
-    E.stats.ms_download = now_ms() - t0;
-    E.stats.ms_total += up + E.stats.ms_download;
+    quant_stats(E, in, t_out);
 }
 
 // The frame around a run over pixels or maps the caller gives (the remaps, frame deltas, measure, gif_lzw): construction takes the
@@ -2759,6 +2794,12 @@ static std::atomic<int> g_remap_two_pass{0};
 // bytes along the curve and converts them there; no f64 image is written.
 // Ordered (mode kRemapOrdered, `spread`): launch_ordered_map shifts, converts and searches in one kernel; palette in ICtCp, no f64 image.
 enum { kRemapNearest = 0, kRemapRiemersma = 1, kRemapOrdered = 2 };
+// The remaps' 8-bit pixels into E.src8 (reserved), from the host or -- `on_device` -- from where the kernels cannot read them; waited for
+static const unsigned char *remap_stage_pixels(Engine &E, const unsigned char *pixels, size_t bytes, bool on_device) {
+    HIP_CHECK(hipMemcpyAsync(E.src8.p, pixels, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, E.stream));
+    HIP_CHECK(hipStreamSynchronize(E.stream));
+    return E.src8.p;
+}
 // The remaps' Riemersma walk over `frames` frames of 8-bit pixels (N in all) with the Rec2020 palette in E.dpal and in `pal`: fused, or
 // through the planes in E.cvt, which the caller has reserved (3 * N) unless `fused`
 static void remap_dither(Engine &E, const unsigned char *d_px, int channels, size_t frames, size_t width, size_t height, const std::vector<double> &pal,
@@ -2781,46 +2822,60 @@ static void remap_dither(Engine &E, const unsigned char *d_px, int channels, siz
     }
 }
 
+// Which way a remap of N pixels onto k rows goes.  walk_frames: the frames a Riemersma walk takes together (run_remap: all of them,
+// hence the frames' layout rule; run_remap_rgba walks frame by frame: 1).  lanes: the walk's lane layout runs; fused: no f64 image is
+// written -- otherwise the caller reserves remap_planes, what such a route takes of the workspace besides the palette and the map.
+struct RemapRoute { bool lanes, fused; };
+static RemapRoute remap_route(int mode, size_t walk_frames, size_t width, size_t height, size_t N, size_t k) {
+    const bool dither = mode == kRemapRiemersma;
+    const bool lanes = dither && (walk_frames > 1 ? dither_frames_lane_layout(walk_frames, width, height, (int)k) : dither_lane_layout(width, height, (int)k));
+    return {lanes, mode == kRemapOrdered || (!g_remap_two_pass.load(std::memory_order_relaxed) && (dither ? lanes : nn_map_u8_applies(N, (int)k)))};
+}
+static void remap_planes(Engine &E, size_t N) { E.cvt.reserve(3 * N); E.cstats.reserve(1); E.h_cstats.reserve(1); }
+
+// The remaps' maps without a walk, over `frames` frames of 8-bit pixels (N in all) with the ICtCp palette's k rows on their way into
+// E.dpal: ordered; nearest, fused; or nearest through the planes in E.cvt (remap_planes)
+static void remap_flat(Engine &E, const unsigned char *d_px, int channels, size_t frames, size_t width, size_t height, bool ordered, double spread,
+                       bool fused, size_t k, void *d_map, int me) {
+    const size_t N = frames * width * height;
+    hipStream_t s = E.stream;
+    if (ordered) {
+        launch_ordered_map(d_px, channels, frames, width, height, spread, E.dpal.p, (int)k, d_map, me, s);
+    } else if (fused) {
+        HIP_CHECK(hipStreamSynchronize(s));                                       // (the map kernels' tables are reserved on an idle stream)
+        launch_nn_map_u8(d_px, channels, N, E.dpal.p, (int)k, d_map, me, E.nn, s);
+    } else {
+        launch_convert_u8(PAMD_SRGB_TO_ICTCP, d_px, channels, E.cvt.p, N, E.cstats.p, s);
+        const Bounds b = read_bounds(E, false);                                   // (waits: the map kernels' tables are reserved on an idle stream)
+        launch_nn_map(E.cvt.p, N, N, E.dpal.p, (int)k, d_map, me, b.lo, b.hi, E.nn, s);
+    }
+}
+
 static void run_remap(Engine &E, size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels, std::vector<double> pal,
                       size_t k, const std::vector<unsigned char> &p8, size_t K8, int mode, double spread, void *map_out, int map_elem_out,
                       unsigned char *quant_out, bool on_device) {
-    const bool dither = mode == kRemapRiemersma, ordered = mode == kRemapOrdered;
-    const size_t n = width * height, N = frames * n;
-    hipStream_t s = E.stream;
+    const bool dither = mode == kRemapRiemersma;
+    const size_t N = frames * width * height;
     GivenRun run(E);
     const int me = map_elem_for(K8);
-    const bool lanes = dither && (frames > 1 ? dither_frames_lane_layout(frames, width, height, (int)k) : dither_lane_layout(width, height, (int)k));
-    const bool fused = ordered || (!g_remap_two_pass.load(std::memory_order_relaxed) && (dither ? lanes : nn_map_u8_applies(N, (int)k)));
+    const RemapRoute route = remap_route(mode, frames, width, height, N, k);
     // the workspace, before anything is enqueued
     if (!on_device) E.src8.reserve(N * (size_t)channels);
     E.dpal.reserve(3 * k); E.h_pal.reserve(3 * k);
     void *d_map = u8_map_place(E, N, K8, map_out || quant_out, map_out, map_elem_out, on_device, quant_out, on_device);
     const bool want = d_map != nullptr;
-    if (want && !fused) { E.cvt.reserve(3 * N); E.cstats.reserve(1); E.h_cstats.reserve(1); }
-    const unsigned char *d_px = pixels;
-    if (!on_device) {
-        HIP_CHECK(hipMemcpyAsync(E.src8.p, pixels, N * (size_t)channels, hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        d_px = E.src8.p;
-    }
+    if (want && !route.fused) remap_planes(E, N);
+    const unsigned char *d_px = on_device ? pixels : remap_stage_pixels(E, pixels, N * (size_t)channels, false);
     run.lap(&patolette_amd__Stats::ms_upload);
     // the palette into the space its map compares in (patolette.c:268-299 for colour space sRGB, resp. :300-324)
     palette_rows(pal, k, dither ? hm::color::srgb_to_rec2020 : hm::color::srgb_to_ictcp);
     E.map_palette = pal;
     if (want) {
         upload_palette(E, pal, k);
-        if (ordered) {
-            launch_ordered_map(d_px, channels, frames, width, height, spread, E.dpal.p, (int)k, d_map, me, s);
-        } else if (!dither && fused) {
-            HIP_CHECK(hipStreamSynchronize(s));                                       // (the map kernels' tables are reserved on an idle stream)
-            launch_nn_map_u8(d_px, channels, N, E.dpal.p, (int)k, d_map, me, E.nn, s);
-        } else if (!dither) {
-            launch_convert_u8(PAMD_SRGB_TO_ICTCP, d_px, channels, E.cvt.p, N, E.cstats.p, s);
-            const Bounds b = read_bounds(E, false);                                   // (waits: the map kernels' tables are reserved on an idle stream)
-            launch_nn_map(E.cvt.p, N, N, E.dpal.p, (int)k, d_map, me, b.lo, b.hi, E.nn, s);
-        } else {
-            remap_dither(E, d_px, channels, frames, width, height, pal, k, d_map, me, fused, lanes);
-            copy_dither_stats(E);
+        if (!dither) remap_flat(E, d_px, channels, frames, width, height, mode == kRemapOrdered, spread, route.fused, k, d_map, me);
+        else {
+            remap_dither(E, d_px, channels, frames, width, height, pal, k, d_map, me, route.fused, route.lanes);
+            add_dither_stats(E);
         }
         E.sync();
     }
@@ -2860,44 +2915,29 @@ static void rgba_masked_frame(Engine &E, const unsigned char *d_px, size_t width
 static void run_remap_rgba(Engine &E, size_t frames, size_t width, size_t height, const unsigned char *pixels, int thr, std::vector<double> pal, size_t k,
                            const std::vector<unsigned> &palw, unsigned off, int mode, double spread, void *map_out, int map_elem_out,
                            unsigned char *quant_out, bool on_device) {
-    const bool dither = mode == kRemapRiemersma, ordered = mode == kRemapOrdered;
+    const bool dither = mode == kRemapRiemersma;
     const size_t n = width * height, N = frames * n, rows = off + k;
     hipStream_t s = E.stream;
     GivenRun run(E);
-    auto aligned = [](const void *p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; };
-    if (on_device && ((map_out && !aligned(map_out, (size_t)map_elem_out)) || (quant_out && !aligned(quant_out, 4))))
-        throw HipError("patolette_amd_remap_rgba_device: palette_map and quantized must be aligned to their element size");
-    const bool stage_px = !on_device || !aligned(pixels, 4);         // the kernels read one 32-bit word per pixel
     const int me = map_elem_for(k);                                   // the mappers' elements: choices among the opaque rows
     const bool want = map_out || quant_out;
-    const bool lanes = dither && dither_lane_layout(width, height, (int)k);
-    const bool two_pass = g_remap_two_pass.load(std::memory_order_relaxed) != 0;
-    const bool fused = ordered || (!two_pass && (dither ? lanes : nn_map_u8_applies(N, (int)k)));
+    const RemapRoute route = remap_route(mode, 1, width, height, N, k);
     const size_t tiles = compact_tiles(n);
     // the workspace, before anything is enqueued
-    if (stage_px) E.src8.reserve(4 * N);
+    const RgbaOut out = rgba_out_place(E, "patolette_amd_remap_rgba_device", N, on_device, pixels, want, map_out, map_elem_out, quant_out);
     E.dpal.reserve(3 * k); E.h_pal.reserve(3 * k);
     E.pal8.reserve(4 * rows);
     E.rr_words.reserve(1 + frames); E.h_rr_words.reserve(1 + frames);
     if (want) {
         E.dmap.reserve((dither ? n : N) * (size_t)me);
-        if (!on_device && map_out) E.rgba_map.reserve(N * (size_t)map_elem_out);
-        if (!on_device && quant_out) E.quant8.reserve(4 * N);
         if (dither) { E.cvt.reserve(3 * n); E.rgba_cpos.reserve(n); E.rgba_rgb.reserve(3 * n); dither_mask_reserve(E.nn, n); }
-        else if (!fused) { E.cvt.reserve(3 * N); E.cstats.reserve(1); E.h_cstats.reserve(1); }
+        else if (!route.fused) remap_planes(E, N);
     }
     if (dither) E.rgba_cnt.reserve(frames * tiles);
-    const unsigned char *d_px = pixels;
-    if (stage_px) {
-        HIP_CHECK(hipMemcpyAsync(E.src8.p, pixels, 4 * N, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        d_px = E.src8.p;
-    }
+    const unsigned char *d_px = out.stage_px ? remap_stage_pixels(E, pixels, 4 * N, on_device) : pixels;
     run.lap(&patolette_amd__Stats::ms_upload);
     palette_rows(pal, k, dither ? hm::color::srgb_to_rec2020 : hm::color::srgb_to_ictcp);   // as run_remap takes its palette
     E.map_palette = pal;
-    void *d_map = map_out ? (on_device ? map_out : (void *)E.rgba_map.p) : nullptr;
-    unsigned char *d_q = quant_out ? (on_device ? quant_out : E.quant8.p) : nullptr;
     unsigned *d_flag = E.rr_words.p, *h_words = E.h_rr_words.p;
     HIP_CHECK(hipMemsetAsync(d_flag, 0, sizeof(unsigned), s));
     HIP_CHECK(hipMemcpyAsync(E.pal8.p, palw.data(), 4 * rows, hipMemcpyHostToDevice, s));
@@ -2906,18 +2946,9 @@ static void run_remap_rgba(Engine &E, size_t frames, size_t width, size_t height
     if (!dither) {
         if (want) {
             upload_palette(E, pal, k);
-            if (ordered) {
-                launch_ordered_map(d_px, 4, frames, width, height, spread, E.dpal.p, (int)k, E.dmap.p, me, s);
-            } else if (fused) {
-                HIP_CHECK(hipStreamSynchronize(s));                                   // (the map kernels' tables are reserved on an idle stream)
-                launch_nn_map_u8(d_px, 4, N, E.dpal.p, (int)k, E.dmap.p, me, E.nn, s);
-            } else {
-                launch_convert_u8(PAMD_SRGB_TO_ICTCP, d_px, 4, E.cvt.p, N, E.cstats.p, s);
-                const Bounds b = read_bounds(E, false);                               // (waits, as in run_remap)
-                launch_nn_map(E.cvt.p, N, N, E.dpal.p, (int)k, E.dmap.p, me, b.lo, b.hi, E.nn, s);
-            }
+            remap_flat(E, d_px, 4, frames, width, height, mode == kRemapOrdered, spread, route.fused, k, E.dmap.p, me);
         }
-        launch_rgba_stamp(d_px, want ? E.dmap.p : nullptr, me, N, thr, off, E.pal8.p, rows, d_map, map_elem_out, d_q, d_flag, s);
+        launch_rgba_stamp(d_px, want ? E.dmap.p : nullptr, me, N, thr, off, E.pal8.p, rows, out.d_map, map_elem_out, out.d_q, d_flag, s);
         HIP_CHECK(hipMemcpyAsync(h_words, d_flag, sizeof(unsigned), hipMemcpyDeviceToHost, s));
     } else {
         for (size_t f = 0; f < frames; f++)
@@ -2931,24 +2962,20 @@ static void run_remap_rgba(Engine &E, size_t frames, size_t width, size_t height
             for (size_t f = 0; f < frames; f++) {
                 const size_t M = h_words[1 + f];
                 const unsigned char *px_f = d_px + 4 * n * f;
-                void *map_f = d_map ? (void *)((unsigned char *)d_map + n * f * mb) : nullptr;
-                unsigned char *q_f = d_q ? d_q + 4 * n * f : nullptr;
+                void *map_f = out.d_map ? (void *)((unsigned char *)out.d_map + n * f * mb) : nullptr;
+                unsigned char *q_f = out.d_q ? out.d_q + 4 * n * f : nullptr;
                 if (M == 0) {                                          // nothing to walk: element 0 and (0, 0, 0, 0) throughout
                     if (map_f) HIP_CHECK(hipMemsetAsync(map_f, 0, n * mb, s));
                     if (q_f) HIP_CHECK(hipMemsetAsync(q_f, 0, 4 * n, s));
                 } else if (M == n) {                                   // no transparent pixel: the plain walk of run_remap
-                    if (map_touched(true, width, height)) remap_dither(E, px_f, 4, 1, width, height, pal, k, E.dmap.p, me, fused, lanes);
+                    if (map_touched(true, width, height)) remap_dither(E, px_f, 4, 1, width, height, pal, k, E.dmap.p, me, route.fused, route.lanes);
                     else HIP_CHECK(hipMemsetAsync(E.dmap.p, 0, n * (size_t)me, s));       // (a 1x1 dither writes nothing: entry 0)
                     launch_rgba_expand(E.dmap.p, me, nullptr, n, n, off, E.pal8.p, (int)rows, map_f, map_elem_out, q_f, s);
                 } else {
                     rgba_masked_frame(E, px_f, width, height, thr, M, E.rgba_cnt.p + f * tiles, pal, k, off, E.pal8.p, rows, me, map_f, map_elem_out,
                                       q_f);
                 }
-                if (M > 0 && map_touched(true, width, height)) {      // the walks' counters, summed over the frames
-                    E.stats.dither_segments += E.nn.dither_segments; E.stats.dither_repairs += E.nn.dither_repairs;
-                    E.stats.dither_rounds += E.nn.dither_rounds; E.stats.dither_through += E.nn.dither_through;
-                    E.stats.dither_jumps += E.nn.dither_jumps; E.stats.dither_solo += E.nn.dither_solo;
-                }
+                if (M > 0 && map_touched(true, width, height)) add_dither_stats(E);   // the walks' counters, summed over the frames
             }
         }
         h_words[0] = 0;
@@ -2956,9 +2983,7 @@ static void run_remap_rgba(Engine &E, size_t frames, size_t width, size_t height
     E.sync();                                                         // (palw is the caller's local: the copy must have left the host)
     run.lap(&patolette_amd__Stats::ms_map);
     if (h_words[0] & 1) throw HipError(kNoEntry);
-    if (!on_device && map_out) HIP_CHECK(hipMemcpyAsync(map_out, d_map, N * (size_t)map_elem_out, hipMemcpyDeviceToHost, s));
-    if (!on_device && quant_out) HIP_CHECK(hipMemcpyAsync(quant_out, d_q, 4 * N, hipMemcpyDeviceToHost, s));
-    E.sync();
+    rgba_copy_out(E, out, N, map_out, map_elem_out, quant_out);
     run.lap(&patolette_amd__Stats::ms_download);
     run.done();
 }
@@ -3178,21 +3203,14 @@ static void run_rgba(Engine &E, size_t width, size_t height, const unsigned char
                      int map_elem_out, unsigned char *quant_out, int *transparent_index, bool on_device) {
     const size_t N = width * height;
     hipStream_t s = E.stream;
-    double t0 = now_ms();
+    const double t_start = now_ms();
     WsGuard wg(&E.stream, &E.stream2);
-    const bool derive = !weights && tile_size > 0.0;
-    const bool weighted = weights || derive;
+    const bool weighted = weights || tile_size > 0.0;
     const bool want_map = !opt->palette_only && (map_out || quant_out);
     const int me = map_elem_for(K);                                  // the compact map (choices < K - 1 when masked)
-    auto aligned = [](const void *p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; };
-    if (on_device && ((map_out && !aligned(map_out, (size_t)map_elem_out)) || (quant_out && !aligned(quant_out, 4))))
-        throw HipError("patolette_amd_rgba_device: palette_map and quantized must be aligned to their element size");
-    const bool stage_px = !on_device || !aligned(pixels, 4);         // the kernels read one 32-bit word per pixel
     // everything the call can take of the workspace, before anything is enqueued (run_device's own preparation at M <= N pixels
     // is then a no-op, save for what it reserves behind a synchronisation)
-    if (derive) { E.wsal.reserve(N); saliency_reserve(E.sal, width, height); }
-    ws_prepare(E, N, K, weighted, opt->verbose);
-    E.cvt.reserve((weighted ? 4 : 3) * N); E.cstats.reserve(1);
+    const RgbaOut out = rgba_out_place(E, "patolette_amd_rgba_device", N, on_device, pixels, want_map, map_out, map_elem_out, quant_out);
     E.rgba_cnt.reserve(compact_tiles(N) + 1); E.h_rgba_m.reserve(1);
     E.rgba_cpos.reserve(N); E.rgba_rgb.reserve(3 * N);
     if (weighted) E.rgba_w.reserve(N);
@@ -3201,62 +3219,45 @@ static void run_rgba(Engine &E, size_t width, size_t height, const unsigned char
         E.dmap.reserve(N * (size_t)me);
         if (opt->dither) { E.aux.reserve(3 * N); dither_mask_reserve(E.nn, N); }
         else if (opt->color_space == patolette__CIELuv) E.aux.reserve(3 * N);
-        if (!on_device && map_out) E.rgba_map.reserve(N * (size_t)map_elem_out);
-        if (!on_device && quant_out) E.quant8.reserve(4 * N);
     }
-    if (stage_px) E.src8.reserve(4 * N);
-    if (weights && !on_device) E.wsrc.reserve(N);
 
-    // upload (host images: converted behind the upload, as run_u8 -- kept if every pixel turns out opaque)
-    const unsigned char *d_px = pixels;
-    const double *d_w = weights;
-    bool converted = false;
-    if (!on_device) converted = upload_image(E, Pixels{nullptr, pixels, 4}, N, weighted, opt);
-    else if (stage_px) HIP_CHECK(hipMemcpyAsync(E.src8.p, pixels, 4 * N, hipMemcpyDeviceToDevice, s));
-    if (stage_px) d_px = E.src8.p;
-    if (weights && !on_device) {
-        HIP_CHECK(hipMemcpyAsync(E.wsrc.p, weights, N * sizeof(double), hipMemcpyHostToDevice, s));
-        d_w = E.wsrc.p;
-    }
-    // count the opaque pixels (one small synchronisation)
-    unsigned *d_m = E.rgba_cnt.p + compact_tiles(N);
-    launch_alpha_count(d_px, N, thr, E.rgba_cnt.p, d_m, s);
-    HIP_CHECK(hipMemcpyAsync(E.h_rgba_m.p, d_m, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    const size_t M = E.h_rgba_m.p[0];
-    const double up = now_ms() - t0;
+    // upload (host images: converted behind the upload, as run_u8 -- kept if every pixel turns out opaque); behind it the count of the
+    // opaque pixels (one small synchronisation); then the weights the binding derives (tile_size > 0): over the full image's RGB, as
+    // run_u8 -- restricted to the opaque pixels below
+    size_t M = 0;
+    const QuantInput in = quant_input(E, t_start, Pixels{nullptr, pixels, 4}, on_device, out.stage_px, 1, width, height, weights, tile_size, K,
+                                      opt, [&](const unsigned char *d_px) {
+        unsigned *d_m = E.rgba_cnt.p + compact_tiles(N);
+        launch_alpha_count(d_px, N, thr, E.rgba_cnt.p, d_m, s);
+        HIP_CHECK(hipMemcpyAsync(E.h_rgba_m.p, d_m, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        M = E.h_rgba_m.p[0];
+        if (M < N && M > 0 && K < 2) throw CodeError(-3, "Palette size should be greater than 0.");
+        return M > 0;
+    });
     const bool masked = M < N;
-    if (masked && M > 0 && K < 2) throw CodeError(-3, "Palette size should be greater than 0.");
     if (transparent_index) *transparent_index = masked ? 0 : -1;
 
-    E.ms_saliency = 0.0;
     const size_t Kq = masked ? K - 1 : K;                            // rows the path makes
     std::vector<double> pal(3 * std::max<size_t>(Kq, 1), -1.0);
     size_t len = 0;
     void *d_cmap = want_map ? (void *)E.dmap.p : nullptr;
-    // weights the binding derives (tile_size > 0): over the full image's RGB, as run_u8 -- then restricted to the opaque pixels
-    if (M > 0 && derive) d_w = derive_weights(E, nullptr, d_px, 4, width, height, tile_size);
     if (masked) {
-        launch_alpha_compact(d_px, N, M, thr, E.rgba_cnt.p, d_w, E.rgba_cpos.p, E.rgba_rgb.p, d_w ? E.rgba_w.p : nullptr, s);
+        launch_alpha_compact(in.px.u8, N, M, thr, E.rgba_cnt.p, in.d_w, E.rgba_cpos.p, E.rgba_rgb.p, in.d_w ? E.rgba_w.p : nullptr, s);
         HIP_CHECK(hipStreamSynchronize(s));                           // (run_device sizes its workspace before it enqueues)
     }
     if (M > 0) {
         if (!masked) {
-            Pixels px8{nullptr, d_px, 4};
-            px8.converted = converted;
-            run_device(E, width, height, px8, d_w, K, opt, pal.data(), d_cmap, me);
+            run_device(E, width, height, in.px, in.d_w, K, opt, pal.data(), d_cmap, me);
         } else {
             const DitherMask mask{width, height, E.rgba_cpos.p};
-            Pixels px8{nullptr, E.rgba_rgb.p, 3};
-            run_device(E, M, 1, px8, d_w ? E.rgba_w.p : nullptr, Kq, opt, pal.data(), d_cmap, me, &mask);
+            run_device(E, M, 1, Pixels{nullptr, E.rgba_rgb.p, 3}, in.d_w ? E.rgba_w.p : nullptr, Kq, opt, pal.data(), d_cmap, me, &mask);
         }
         len = E.stats.n_clusters;
     } else {
         E.stats = patolette_amd__Stats{};
     }
-    E.stats.ms_saliency = E.ms_saliency;
-    E.stats.ms_total += E.ms_saliency;
-    t0 = now_ms();
+    const double t_out = now_ms();
 
     // palettes: row 0 the transparent entry when masked; unused rows -1 / (0, 0, 0, 0)
     const size_t off = masked ? 1 : 0;
@@ -3266,27 +3267,17 @@ static void run_rgba(Engine &E, size_t width, size_t height, const unsigned char
         for (int c = 0; c < 3; c++) prgba[4 * (off + i) + c] = p8[3 * i + c];
         prgba[4 * (off + i) + 3] = 255;
     }
-    if (palette) {
-        for (size_t j = 0; j < 3 * K; j++) palette[j] = -1.0;
-        if (masked) for (int c = 0; c < 3; c++) palette[K * (size_t)c] = 0.0;
-        for (int c = 0; c < 3; c++) for (size_t i = 0; i < Kq; i++) palette[K * (size_t)c + off + i] = pal[Kq * (size_t)c + i];
-    }
+    if (palette) write_palette(palette, K, off, pal, Kq);
     if (palette_rgba) std::memcpy(palette_rgba, prgba.data(), 4 * K);
 
     if (want_map) {
         if (!masked && !map_touched(opt->dither, width, height))
             HIP_CHECK(hipMemsetAsync(E.dmap.p, 0, N * (size_t)me, s));        // (a 1x1 dither wrote nothing: entry 0)
         HIP_CHECK(hipMemcpyAsync(E.pal8.p, prgba.data(), 4 * K, hipMemcpyHostToDevice, s));
-        void *d_map = map_out ? (on_device ? map_out : (void *)E.rgba_map.p) : nullptr;
-        unsigned char *d_q = quant_out ? (on_device ? quant_out : E.quant8.p) : nullptr;
-        launch_rgba_expand(d_cmap, me, masked ? E.rgba_cpos.p : nullptr, N, M, (unsigned)off, E.pal8.p, (int)K, d_map, map_elem_out, d_q, s);
-        if (!on_device && map_out) HIP_CHECK(hipMemcpyAsync(map_out, d_map, N * (size_t)map_elem_out, hipMemcpyDeviceToHost, s));
-        if (!on_device && quant_out) HIP_CHECK(hipMemcpyAsync(quant_out, d_q, 4 * N, hipMemcpyDeviceToHost, s));
-        E.sync();                                                     // (prgba is a local: the copy must have left the host)
+        launch_rgba_expand(d_cmap, me, masked ? E.rgba_cpos.p : nullptr, N, M, (unsigned)off, E.pal8.p, (int)K, out.d_map, map_elem_out, out.d_q, s);
+        rgba_copy_out(E, out, N, map_out, map_elem_out, quant_out);   // (prgba is a local: the copy must have left the host)
     }
-    E.stats.ms_upload = up;
-    E.stats.ms_download = now_ms() - t0;
-    E.stats.ms_total += up + E.stats.ms_download;
+    quant_stats(E, in, t_out);
 }
 
 // --------------------------------------------------------------------------------------------
@@ -3299,15 +3290,14 @@ static void hist_read(Engine &E, void *dst, const void *d_src, size_t bytes) {
     HIP_CHECK(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, E.stream));
     E.sync();
 }
-static HipError hist_error(const char *name, const char *text) { return HipError(std::string(name) + ": " + text); }
 static const char *const kHistOverflow = "overflow: a weight sum passed 2^64 units; only a clear makes the histogram usable again";
 
 // what every call but clear asks first: the table is a cleared one of this mode, and no sum in it has overflowed
 static void hist_check(Engine &E, const char *name, const HistWord *d_hist, bool weighted) {
     HistWord h[2] = {0, 0};
     hist_read(E, h, d_hist, sizeof h);
-    if (h[1] != kHistMagic + (weighted ? 1u : 0u)) throw hist_error(name, "the memory is not a cleared histogram of this mode");
-    if (h[0] & 1) throw hist_error(name, kHistOverflow);
+    if (h[1] != kHistMagic + (weighted ? 1u : 0u)) throw named_error(name, "the memory is not a cleared histogram of this mode");
+    if (h[0] & 1) throw named_error(name, kHistOverflow);
 }
 
 static void run_hist_clear(Engine &E, HistWord *d_hist, bool weighted) {
@@ -3349,13 +3339,13 @@ static void run_hist_add(Engine &E, const char *name, bool on_device, HistWord *
         launch_hist_units(d_w, N, E.hs_units.p, reinterpret_cast<unsigned *>(E.hs_words.p), s);
         HistWord bad = 0;
         hist_read(E, &bad, E.hs_words.p, sizeof bad);
-        if (bad & 1) throw hist_error(name, "a weight is not finite or lies outside [0, 2^20]; nothing was added");
+        if (bad & 1) throw named_error(name, "a weight is not finite or lies outside [0, 2^20]; nothing was added");
     }
     launch_hist_add(d_hist, weighted, d_px, channels, thr, N, weighted ? E.hs_units.p : nullptr, s);
     HistWord flags = 0;
     hist_read(E, &flags, d_hist, sizeof flags);
     run.lap(&patolette_amd__Stats::ms_map);
-    if (flags & 1) throw hist_error(name, kHistOverflow);
+    if (flags & 1) throw named_error(name, kHistOverflow);
     run.done();
 }
 
@@ -3368,7 +3358,7 @@ static void run_hist_merge(Engine &E, HistWord *d_hist, const HistWord *d_other,
     HistWord flags = 0;
     hist_read(E, &flags, d_hist, sizeof flags);
     run.lap(&patolette_amd__Stats::ms_map);
-    if (flags & 1) throw hist_error(name, kHistOverflow);
+    if (flags & 1) throw named_error(name, kHistOverflow);
     run.done();
 }
 
@@ -3395,7 +3385,7 @@ static size_t hist_compact(Engine &E, const HistWord *d_hist, bool weighted, boo
     unsigned total = 0;
     hist_read(E, &total, E.hs_tiles.p + nt, sizeof total);
     const size_t M = total;
-    if (M > capacity) throw hist_error(name, "capacity is smaller than the number of colours (patolette_amd_hist_totals tells it)");
+    if (M > capacity) throw named_error(name, "capacity is smaller than the number of colours (patolette_amd_hist_totals tells it)");
     if (M == 0) return 0;
     E.hs_rgb.reserve(3 * M); E.hs_w.reserve(M);
     if (want_counts) E.hs_counts.reserve(M);
@@ -3427,7 +3417,7 @@ static void run_hist_palette(Engine &E, const HistWord *d_hist, bool weighted, s
     hist_check(E, name, d_hist, weighted);
     const size_t M = hist_compact(E, d_hist, weighted, true, false, kHistBins, name);
     run.lap(&patolette_amd__Stats::ms_map);
-    if (M == 0) throw hist_error(name, "the histogram holds no colour with a weight above 0");
+    if (M == 0) throw named_error(name, "the histogram holds no colour with a weight above 0");
     if (M > K) {                                                       // (the statistics are then run_u8's own: it resets them)
         patolette__QuantizationOptions o = *opt;
         o.dither = false; o.palette_only = false;
@@ -3563,29 +3553,38 @@ static void slice_entry(size_t total_pixels, size_t slice_begin, const patolette
     if (Ep) Ep->shard = nullptr;
 }
 
+// one f64 image in host memory, planar or (`rows`) row-major: validate()'s codes, then run_host
+static void host_entry(bool rows, size_t width, size_t height, const double *data, const double *weights, double tile_size, size_t palette_size,
+                       const patolette__QuantizationOptions *options, double *palette, size_t *palette_map, int *exit_code) {
+    *exit_code = validate(width, height, palette_size);
+    if (*exit_code != 0) return;
+    *exit_code = guarded([&](Engine &E) { run_host(E, width, height, data, weights, tile_size, palette_size, options, palette, palette_map, rows); });
+}
+// run_device for an entry whose image is device memory: the caller's palette is written only when the run has succeeded
+static void device_entry_run(Engine &E, size_t width, size_t height, const double *d_data, const double *d_weights, size_t palette_size,
+                             const patolette__QuantizationOptions *options, double *palette, void *d_map, int map_elem_bytes) {
+    std::vector<double> pal(3 * palette_size);
+    run_device(E, width, height, Pixels{d_data, nullptr, 3}, d_weights, palette_size, options, pal.data(), d_map, map_elem_bytes);
+    std::memcpy(palette, pal.data(), 3 * palette_size * sizeof(double));
+}
+
 extern "C" {
 
 void patolette(size_t width, size_t height, const double *data, const double *weights, size_t palette_size,
                const patolette__QuantizationOptions *options, double *palette, size_t *palette_map, int *exit_code) {
-    *exit_code = validate(width, height, palette_size);
-    if (*exit_code != 0) return;
-    *exit_code = guarded([&](Engine &E) { run_host(E, width, height, data, weights, 0.0, palette_size, options, palette, palette_map); });
+    host_entry(false, width, height, data, weights, 0.0, palette_size, options, palette, palette_map, exit_code);
 }
 
 void patolette_amd_quantize(size_t width, size_t height, const double *data, const double *weights, double tile_size,
                             size_t palette_size, const patolette__QuantizationOptions *options, double *palette,
                             size_t *palette_map, int *exit_code) {
-    *exit_code = validate(width, height, palette_size);
-    if (*exit_code != 0) return;
-    *exit_code = guarded([&](Engine &E) { run_host(E, width, height, data, weights, tile_size, palette_size, options, palette, palette_map); });
+    host_entry(false, width, height, data, weights, tile_size, palette_size, options, palette, palette_map, exit_code);
 }
 
 void patolette_amd_quantize_rows(size_t width, size_t height, const double *rows, const double *weights, double tile_size,
                                  size_t palette_size, const patolette__QuantizationOptions *options, double *palette,
                                  size_t *palette_map, int *exit_code) {
-    *exit_code = validate(width, height, palette_size);
-    if (*exit_code != 0) return;
-    *exit_code = guarded([&](Engine &E) { run_host(E, width, height, rows, weights, tile_size, palette_size, options, palette, palette_map, true); });
+    host_entry(true, width, height, rows, weights, tile_size, palette_size, options, palette, palette_map, exit_code);
 }
 
 void patolette_amd_slice(size_t total_pixels, size_t slice_begin, size_t slice_pixels, const double *slice_data,
@@ -3609,10 +3608,7 @@ void patolette_amd_slice_device(size_t total_pixels, size_t slice_begin, size_t 
     if (!comm_ok(comm)) { *exit_code = -1; return; }
     slice_entry(total_pixels, slice_begin, comm, slice_args_ok(total_pixels, slice_begin, slice_pixels, d_slice_data, options, d_slice_map),
                 exit_code, [&](Engine &E) {
-        std::vector<double> pal(3 * palette_size);
-        run_device(E, slice_pixels, 1, Pixels{d_slice_data, nullptr, 3}, d_slice_weights, palette_size, options, pal.data(), d_slice_map,
-                   map_elem_bytes);
-        std::memcpy(palette, pal.data(), 3 * palette_size * sizeof(double));
+        device_entry_run(E, slice_pixels, 1, d_slice_data, d_slice_weights, palette_size, options, palette, d_slice_map, map_elem_bytes);
     });
 }
 
@@ -3711,10 +3707,7 @@ void patolette_amd_device(size_t width, size_t height, const double *d_data, con
     *exit_code = validate(width, height, palette_size);
     if (*exit_code != 0) return;
     *exit_code = guarded([&](Engine &E) {
-        std::vector<double> pal(3 * palette_size);
-        run_device(E, width, height, Pixels{d_data, nullptr, 3}, d_weights, palette_size, options, pal.data(), d_palette_map,
-                   map_elem_bytes);
-        std::memcpy(palette, pal.data(), 3 * palette_size * sizeof(double));
+        device_entry_run(E, width, height, d_data, d_weights, palette_size, options, palette, d_palette_map, map_elem_bytes);
     });
 }
 
@@ -4397,7 +4390,8 @@ int patolette_amd_dither(const double *colors, size_t width, size_t height, cons
         HIP_CHECK(hipMemcpy(E.src.p, colors, 3 * n * sizeof(double), hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(E.dpal.p, palette, 3 * k * sizeof(double), hipMemcpyHostToDevice));
         launch_dither(E.src.p, n, PAMD_COPY, width, height, E.dpal.p, palette, (int)k, E.dmap.p, 4, E.nn, E.stream);
-        copy_dither_stats(E);
+        E.stats = patolette_amd__Stats{};                           // (a call of its own: nothing of the one before it stays)
+        add_dither_stats(E);
         E.sync();
         if (map_touched(true, width, height)) download_map(E.dmap.p, 4, n, map, 8);
         return 0;
