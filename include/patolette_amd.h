@@ -443,6 +443,65 @@ void patolette_amd_gif_lzw_device(size_t frames, size_t width, size_t height, co
                                   int min_code_size, size_t segment, unsigned char *out, size_t capacity, uint64_t *offsets,
                                   int *exit_code);
 
+/* ---- gif_lzw_lossy: the same streams, shorter, where a nearly equal colour may continue a match ---
+ * The lossy LZW coder of the GIF tools: when the next symbol would end the current dictionary match, the coder may continue the match
+ * with a NEARLY EQUAL colour instead.  Ordered-dithered maps, whose pattern breaks every long match of the exact coder, gain most.
+ * Everything of patolette_amd_gif_lzw stays -- maps, rects, min_code_size m, segment, out, capacity, offsets, the segments, the opening
+ * Clear, the width rule, the closing code, the Clear of a full dictionary, frames from byte boundaries, the capacity bound (still at
+ * most one code per symbol) -- but the step.  With the current prefix P and the next symbol s (never the first symbol of a segment,
+ * which is taken as it is):
+ *     for c in [s] + near[s][1 .. near[s][0]], in this order:
+ *         if (P, c) is in the dictionary: P = its code; the step has coded c; next symbol
+ *     no candidate is in the dictionary -- exactly the old miss: emit P; enter (P, s) if free < 4096 (the width step as before), else
+ *         emit Clear and reset; P = s; the step has coded s.
+ * Greedy, one step of look-ahead, deterministic: the exact symbol wins over any candidate, an earlier candidate over a later one, and
+ * a miss enters the TRUE symbol.  tests/lzw_lossy_ref.py states the same in Python; the device's bytes and coded maps equal its own.
+ *   near: host memory in both flavours, 4096 bytes, uint8[256][16].  near[s][0] is the count, in [0, 15]; near[s][1 .. count] are the
+ *       candidates in order of preference; the rest of a row is not read, nor is any row at or above 2^m.  Checked before anything is
+ *       enqueued: every count read must be <= 15 and every candidate read below 2^m, else -1.  Duplicates and a candidate equal to s are
+ *       allowed and harmless.  NULL is a -1.  patolette_amd_gif_neighbours makes the table of a palette; any table of this layout serves.
+ *   coded: NULL, or frames x width x height bytes that do not overlap maps (-1 if they do): inside every rectangle, at the position
+ *       each symbol came from, the symbol its step coded.  Positions outside the rectangles are not written.  Host memory; the
+ *       *_device flavour takes device pointers for maps and coded.
+ * What follows from the rule:
+ *   (a) frame f's stream decodes to coded[f] inside its rectangle;
+ *   (b) the stream of `maps` under `near` is bit for bit the EXACT coder's stream of `coded` (by induction over the steps: the exact
+ *       coder on the coded symbols hits where this one hit and misses where it missed, with the same dictionary): patolette_amd_gif_lzw
+ *       on `coded` returns the same bytes;
+ *   (c) every coded element is the map's element or one of its row's candidates;
+ *   (d) a symbol with an empty row that appears in no row -- a transparent index -- is never replaced and never replaces: transparency
+ *       is never lossy;
+ *   (e) with every count 0 the bytes are patolette_amd_gif_lzw's;
+ *   (f) the first symbol of every segment is exact.
+ * With the table of patolette_amd_gif_neighbours at tolerance t, a coded entry lies within t (ICtCp) of the MAP's entry, not of the
+ * source pixel.  Behind patolette_amd_frame_deltas(tolerance t1) every pixel a viewer shows lies within t1 + t of its frame's source
+ * or within t of the frame's own choice; nothing accumulates over the frames, because every drawn pixel is coded from that frame's own
+ * entry.  patolette_amd_measure on the composited coded maps gives the true cost.
+ * Flag, capacity, exit codes and statistics: as patolette_amd_gif_lzw, the text starting "patolette_amd_gif_lzw_lossy:"; -1 also for
+ *   no near, a bad table, and coded overlapping maps.  What coded holds after a failed call is not defined.
+ * Three kernels, one launch each: k_lzw_lossy_segments (lane j < 16 of the segment's wavefront probes the dictionary for candidate j in
+ *   the same step; a ballot's lowest hit wins), then k_lzw_offsets and k_lzw_pack as they are. */
+void patolette_amd_gif_lzw_lossy(size_t frames, size_t width, size_t height, const unsigned char *maps, const int32_t *rects,
+                                 int min_code_size, size_t segment, const unsigned char *near, unsigned char *coded, unsigned char *out,
+                                 size_t capacity, uint64_t *offsets, int *exit_code);
+void patolette_amd_gif_lzw_lossy_device(size_t frames, size_t width, size_t height, const unsigned char *d_maps, const int32_t *rects,
+                                        int min_code_size, size_t segment, const unsigned char *near, unsigned char *d_coded,
+                                        unsigned char *out, size_t capacity, uint64_t *offsets, int *exit_code);
+
+/* The lossy coder's table for a palette.  Host code only: it never touches the device and works without one.
+ *   palette / palette_u8, palette_rows: exactly one of the two, as patolette_amd_remap_u8 takes them (trailing (-1, -1, -1) rows of an
+ *       f64 palette are dropped); palette_rows in [1, 256].
+ *   Every used row goes through the sRGB -> ICtCp conversion exactly as patolette_amd_frame_deltas prepares its palette, and
+ *   D = (d0*d0 + d1*d1) + d2*d2 in f64, no FMA, between two rows is the D of that contract.
+ *   near_out: 4096 bytes, all written.  Row s lists the OTHER used rows e with D <= tolerance^2, by (D ascending, e ascending), cut to
+ *       max_neighbours in [0, 15].  transparent_index (-1: none, else in [0, 255]) is left out both as s and as e.  Dropped rows and
+ *       rows >= palette_rows have count 0 and appear nowhere.  At tolerance 0 only identical rows are neighbours.
+ * Exit codes: 0; -1 with a "patolette_amd_gif_neighbours:" text for both or neither palette, palette_rows, transparent_index or
+ *   max_neighbours out of range, a tolerance that is negative or not finite, a palette value that is not finite, every row the
+ *   unused-row fill, or no near_out. */
+void patolette_amd_gif_neighbours(const double *palette, const unsigned char *palette_u8, size_t palette_rows, int transparent_index,
+                                  double tolerance, int max_neighbours, unsigned char *near_out, int *exit_code);
+
 /* ---- RGBA images: a transparent palette slot, an alpha-aware dither ---------------------------
  * pixels: width*height interleaved 8-bit RGBA.  Pixel i is TRANSPARENT iff alpha_i < alpha_threshold (an integer in [0, 256]);
  * every other pixel is OPAQUE.  M = number of opaque pixels, N = width*height.

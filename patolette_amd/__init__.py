@@ -22,7 +22,8 @@ and, for animations with transparency, `remap_rgba` (RGBA images or frames onto 
 entry) and `quantize_rgba_frames` (one shared palette and one transparent index for all frames, composed from `quantize_rgba`'s
 palette stage and `remap_rgba`) and `frame_deltas_rgba` (the deltas of such maps: 0 means "leave the canvas", every frame gets its
 own disposal, and the rectangle also covers what the next frame makes transparent);
-and `gif_lzw`, which LZW-compresses maps or deltas on the device, with `write_gif`, the GIF89a container around it;
+and `gif_lzw`, which LZW-compresses maps or deltas on the device, with `write_gif`, the GIF89a container around it, and `gif_lzw_lossy`
+with `gif_neighbours`, the lossy coder that lets a nearly equal colour continue a dictionary match;
 and `ColorHistogram`, for pixels that arrive in chunks (a long clip, a directory of images): an exact colour histogram kept on the
 GPU and filled by any number of `add` calls, whose `palette()` is the one shared palette that `remap` then maps every chunk onto --
 with `colors` ("how many colours does this have?") and an input of no more than K colours getting exactly those colours back.
@@ -731,6 +732,32 @@ def gif_lzw_bound(rects, segment=None):
     return int(np.sum((12 * (area + 2 * nseg + area // 3000 + 2) + 7) // 8))
 
 
+def _gif_lzw_args(maps, rects, min_code_size, segment):
+    """What `gif_lzw` and `gif_lzw_lossy` check alike, before any library call -> (maps, (F, H, W), torch device or None, m, the C
+    entry's segment, (F, 4) int32 rectangles)."""
+    m, shape, dev = _gif_maps(maps)
+    count, height, width = shape
+    if isinstance(min_code_size, (bool, np.bool_)) or not isinstance(min_code_size, (int, np.integer)) or not 2 <= int(min_code_size) <= 8:
+        raise ValueError("min_code_size must be an integer in [2, 8]")
+    return m, shape, dev, int(min_code_size), _gif_segment(segment), _gif_rects(rects, count, height, width)
+
+
+def _gif_lzw_run(name, m, shape, dev, mcs, seg, segment, r, extra):
+    """The C entry `name` (patolette_amd_gif_lzw or its lossy twin, whose `extra` arguments stand ahead of `out`) -> what `gif_lzw` returns."""
+    count, height, width = shape
+    out = np.empty(gif_lzw_bound(r, segment), dtype=np.uint8)
+    offsets = np.zeros(count + 1, dtype=np.uint64)
+    code = C.c_int(0)
+    _call(name, dev, count, width, height, _vp(m), r.ctypes.data_as(C.POINTER(C.c_int32)) if count else None,
+          mcs, seg, *extra, out.ctypes.data_as(C.c_void_p), out.size, offsets.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(code))
+    if code.value == -1 and _native.last_error().startswith(name + ":"):
+        raise ValueError(_native.last_error())
+    message = _message(code.value)
+    if code.value != 0:
+        return (False, None, None, message)
+    return (True, out[:int(offsets[count])], offsets.astype(np.int64), message)
+
+
 def gif_lzw(maps, rects=None, min_code_size=8, segment=None):
     """Index maps LZW-compressed as a GIF's image data, on the device (additive; include/patolette_amd.h: patolette_amd_gif_lzw).
 
@@ -744,26 +771,95 @@ def gif_lzw(maps, rects=None, min_code_size=8, segment=None):
 
     Returns (success, data uint8 numpy array, offsets (F + 1,) int64, message): frame f's raw LZW stream -- not yet cut into
     sub-blocks -- is data[offsets[f]:offsets[f + 1]].  The result is always numpy.  `write_gif` wraps it in the container."""
-    m, shape, dev = _gif_maps(maps)
-    count, height, width = shape
-    if isinstance(min_code_size, (bool, np.bool_)) or not isinstance(min_code_size, (int, np.integer)) or not 2 <= int(min_code_size) <= 8:
-        raise ValueError("min_code_size must be an integer in [2, 8]")
-    seg = _gif_segment(segment)
-    r = _gif_rects(rects, count, height, width)
-    out = np.empty(gif_lzw_bound(r, segment), dtype=np.uint8)
-    offsets = np.zeros(count + 1, dtype=np.uint64)
+    m, shape, dev, mcs, seg, r = _gif_lzw_args(maps, rects, min_code_size, segment)
+    return _gif_lzw_run("patolette_amd_gif_lzw", m, shape, dev, mcs, seg, segment, r, ())
+
+
+def _gif_near(near, mcs):
+    """`near` as the contiguous (256, 16) uint8 table of the lossy coder, checked as the library checks it at minimum code size `mcs`."""
+    t = np.asarray(near.detach().cpu().numpy() if hasattr(near, "detach") else near)
+    if t.shape != (256, 16) or t.dtype != np.uint8:
+        raise ValueError("near must be a (256, 16) uint8 array: per symbol the count, then up to 15 candidates (`gif_neighbours` makes one)")
+    t = np.ascontiguousarray(t)
+    rows = t[:1 << mcs]
+    if np.any(rows[:, 0] > 15):
+        raise ValueError("near: a row below 2 ** min_code_size has a count above 15")
+    if np.any((rows[:, 1:] >= (1 << mcs)) & (np.arange(1, 16)[None, :] <= rows[:, :1])):
+        raise ValueError("near: a candidate of a row below 2 ** min_code_size is not below 2 ** min_code_size")
+    return t
+
+
+def gif_neighbours(palette, tolerance, transparent_index=None, max_neighbours=15):
+    """The table `gif_lzw_lossy` and `write_gif(near=...)` take, for a palette (include/patolette_amd.h: patolette_amd_gif_neighbours).
+    Host code: no GPU is needed.
+
+      * palette: as `remap` takes it, (K, 3) uint8 or float64 with K <= 256 (trailing (-1, -1, -1) rows of a float palette are unused).
+      * tolerance: an ICtCp distance, the unit of `frame_deltas` and `measure`: row s lists the OTHER used rows within `tolerance` of it,
+        nearest first (ties by index), at most `max_neighbours` (0 .. 15) of them.  0 lists identical rows only.
+      * transparent_index: None, or an index in [0, 255] that neither gets candidates nor is one: transparency is never lossy.
+
+    What the tolerance means: a coded entry lies within `tolerance` of the MAP's entry, not of the source pixel.  Behind
+    `frame_deltas(tolerance=t1)` every pixel a viewer shows lies within t1 + tolerance of its frame's source, or within `tolerance`
+    of the frame's own choice; nothing accumulates over the frames, because every drawn pixel is coded from that frame's own entry.
+    `measure` on the composited `coded` maps of `gif_lzw_lossy` gives the true cost.
+
+    Returns (success, near (256, 16) uint8, message)."""
+    pal8, palf = _remap_palette(palette)
+    rows = (pal8 if pal8 is not None else palf).shape[0]
+    if rows > 256:
+        raise ValueError("a GIF colour table holds at most 256 rows")
+    if isinstance(tolerance, (bool, np.bool_)) or not isinstance(tolerance, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(tolerance) or tolerance < 0:
+        raise ValueError("tolerance must be a finite number that is not negative")
+    if transparent_index is not None and (isinstance(transparent_index, (bool, np.bool_)) or not isinstance(transparent_index, (int, np.integer))
+                                          or not 0 <= int(transparent_index) <= 255):
+        raise ValueError("transparent_index must be None or an index in [0, 255]")
+    if isinstance(max_neighbours, (bool, np.bool_)) or not isinstance(max_neighbours, (int, np.integer)) or not 0 <= int(max_neighbours) <= 15:
+        raise ValueError("max_neighbours must be an integer in [0, 15]")
+    if palf is not None and not np.all(np.isfinite(palf)):
+        raise ValueError("the palette holds a value that is not finite")
+    near = np.zeros((256, 16), dtype=np.uint8)
     code = C.c_int(0)
-    _call("patolette_amd_gif_lzw", dev, count, width, height, _vp(m), r.ctypes.data_as(C.POINTER(C.c_int32)) if count else None,
-          int(min_code_size), seg, out.ctypes.data_as(C.c_void_p), out.size, offsets.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(code))
-    if code.value == -1 and _native.last_error().startswith("patolette_amd_gif_lzw:"):
+    _native.lib().patolette_amd_gif_neighbours(_vp(palf), _vp(pal8), rows, -1 if transparent_index is None else int(transparent_index),
+                                               float(tolerance), int(max_neighbours), near.ctypes.data_as(C.c_void_p), C.byref(code))
+    if code.value == -1 and _native.last_error().startswith("patolette_amd_gif_neighbours:"):
         raise ValueError(_native.last_error())
-    message = _message(code.value)
     if code.value != 0:
-        return (False, None, None, message)
-    return (True, out[:int(offsets[count])], offsets.astype(np.int64), message)
+        return (False, None, _message(code.value))
+    return (True, near, _message(code.value))
 
 
-def write_gif(file, maps, palette_u8, rects=None, transparent_index=None, delay=0.04, loop=0, disposal=1, segment=None):
+def gif_lzw_lossy(maps, near, rects=None, min_code_size=8, segment=None, want_coded=False):
+    """`gif_lzw` by the lossy coder (additive; include/patolette_amd.h: patolette_amd_gif_lzw_lossy): where the next symbol would end the
+    current dictionary match, one of its candidates in `near` that continues the match is coded in its place -- the exact symbol
+    first, then the row's order.  Ordered-dithered maps, which break every long match of the exact coder, gain most.
+
+      * maps, rects, min_code_size, segment: as `gif_lzw` takes them.
+      * near: (256, 16) uint8, per symbol the count (0 .. 15) and then the candidates in order of preference, all below
+        2 ** min_code_size; `gif_neighbours(palette, tolerance, transparent_index)` makes it.  A symbol with an empty row that appears
+        in no row -- the transparent index -- is never replaced and never replaces.  An all-zero table gives `gif_lzw`'s bytes.
+      * want_coded: also return what the streams decode to: a copy of `maps` overwritten inside the rectangles (numpy), or a cloned
+        tensor that stays on the GPU (a CUDA tensor in).  `gif_lzw(coded, ...)` returns the same bytes as this call.
+
+    What the tolerance of the table means: a coded entry lies within it of the MAP's entry, not of the source pixel.  Behind
+    `frame_deltas(tolerance=t1)` and a table at t2 every pixel a viewer shows lies within t1 + t2 of its frame's source, or within t2
+    of the frame's own choice; nothing accumulates, because every drawn pixel is coded from that frame's own entry.  `measure` on the
+    composited `coded` maps gives the true cost.
+
+    Returns (success, data, offsets, coded or None, message), data and offsets as `gif_lzw` returns them."""
+    m, shape, dev, mcs, seg, r = _gif_lzw_args(maps, rects, min_code_size, segment)
+    table = _gif_near(near, mcs)
+    coded = None
+    if want_coded:
+        coded = m.clone() if dev is not None else m.copy()
+    ok, data, offsets, message = _gif_lzw_run("patolette_amd_gif_lzw_lossy", m, shape, dev, mcs, seg, segment, r,
+                                              (table.ctypes.data_as(C.c_void_p), _vp(coded)))
+    if not ok:
+        return (False, None, None, None, message)
+    return (True, data, offsets, coded.reshape(tuple(maps.shape)) if want_coded else None, message)
+
+
+def write_gif(file, maps, palette_u8, rects=None, transparent_index=None, delay=0.04, loop=0, disposal=1, segment=None, near=None):
     """Write an animation's maps as a GIF89a file: a small pure-Python container around `gif_lzw`, so that
     `quantize_frames(frames, 255, dither="ordered")` -> `frame_deltas` -> `write_gif` yields a file any viewer opens.
 
@@ -775,6 +871,10 @@ def write_gif(file, maps, palette_u8, rects=None, transparent_index=None, delay=
         None for no loop block; disposal: every frame's disposal method (1: leave in place, what `frame_deltas`' deltas need), or a
         sequence of F of them, one per frame: `frame_deltas_rgba` returns the ones its deltas need --
         `write_gif(file, deltas, palette_rgba[:, :3], rects, transparent_index=0, disposal=disposals)`.
+      * near: None for the exact coder, or the table of `gif_neighbours(palette_u8, tolerance, transparent_index)`: the streams come from
+        `gif_lzw_lossy` and the file is smaller.  A shown entry then lies within that tolerance (ICtCp) of the MAP's entry, not of the
+        source pixel: behind `frame_deltas(tolerance=t1)` within t1 + tolerance of its frame's source; nothing accumulates over the
+        frames.  `measure` on the composited `coded` maps of `gif_lzw_lossy` gives the true cost.
     Out of scope: local colour tables, interlace, APNG."""
     import os
     m, shape, dev = _gif_maps(maps)
@@ -812,7 +912,10 @@ def write_gif(file, maps, palette_u8, rects=None, transparent_index=None, delay=
             raise ValueError("disposal must be 0, 1, 2 or 3")
         disposals = [int(disposal)] * count
     _gif_segment(segment)
-    ok, data, offsets, message = gif_lzw(m, r, mcs, segment)
+    if near is None:
+        ok, data, offsets, message = gif_lzw(m, r, mcs, segment)
+    else:
+        ok, data, offsets, _, message = gif_lzw_lossy(m, _gif_near(near, mcs), r, mcs, segment)
     if not ok:
         raise RuntimeError(message)
     table = np.zeros((1 << bits, 3), dtype=np.uint8)
@@ -1341,6 +1444,8 @@ __all__ = [
     "psnr",
     "gif_lzw",
     "gif_lzw_bound",
+    "gif_lzw_lossy",
+    "gif_neighbours",
     "write_gif",
     "saliency_weights",
     "ColorSpace_sRGB",

@@ -34,4 +34,14 @@ void launch_lzw(const unsigned char *d_maps, size_t frames, size_t n, size_t wid
                 size_t stride, int m, unsigned *d_stage, unsigned *d_bits, unsigned long long *d_gbit, unsigned long long *d_words,
                 unsigned *d_out, size_t out_words, hipStream_t s);
 
+// bytes of the lossy coder's table: 256 rows of 16 -- the count, then up to 15 candidates in order of preference
+constexpr size_t kLzwNearBytes = 4096;
+
+// The lossy LZW of include/patolette_amd.h (patolette_amd_gif_lzw_lossy): launch_lzw with k_lzw_lossy_segments in the place of
+// k_lzw_segments.  d_near: the table, of which the rows below 2^m are read (the host has checked their counts and candidates);
+// 16-byte aligned.  d_coded: null, or frames x n bytes that do not overlap d_maps: the symbol each step coded, inside the rectangles.
+void launch_lzw_lossy(const unsigned char *d_maps, size_t frames, size_t n, size_t width, const LzwFrame *d_frames, size_t S, size_t seg_len,
+                      size_t stride, int m, const unsigned char *d_near, unsigned char *d_coded, unsigned *d_stage, unsigned *d_bits,
+                      unsigned long long *d_gbit, unsigned long long *d_words, unsigned *d_out, size_t out_words, hipStream_t s);
+
 }  // namespace pamd

@@ -26,6 +26,7 @@
 #include "delta.h"
 #include "measure.h"
 #include "lzw.h"
+#include "lzw_near.h"
 #include "hist.h"
 #include "saliency.h"
 #include "quant.h"
@@ -990,6 +991,7 @@ struct Engine {
     DevBuf<LzwFrame> lz_frames;                  // gif_lzw: the frames' rectangles and first segments (lzw.h)
     DevBuf<unsigned> lz_stage, lz_bits, lz_out;  // ... the segments' staging areas and bit lengths; the packed streams
     DevBuf<unsigned long long> lz_gbit, lz_words;   // ... every segment's first bit in the output; the flag and the frames' offsets
+    DevBuf<unsigned char> lz_near;               // gif_lzw_lossy: the table of near colours (lzw_near.h)
     // the RGBA entry (run_rgba): tile counts / offsets + the opaque count, each pixel's compact number, the opaque pixels' RGB and
     // weights, the full index map on its way to the host, the count's pinned landing place
     DevBuf<unsigned> rgba_cnt;
@@ -3157,12 +3159,16 @@ static void run_measure(Engine &E, bool on_device, size_t frames, size_t width, 
 // --------------------------------------------------------------------------------------------
 // maps: frames x width x height one-byte elements, a device pointer when `on_device`; recs: the frames' rectangles with their first
 // segments, frames + 1 records (lzw.h); seg: a segment's pixels; cap: the largest rectangle's area.  out, offsets: host memory.
-static void run_gif_lzw(Engine &E, bool on_device, size_t frames, size_t width, size_t height, const unsigned char *maps,
-                        const std::vector<LzwFrame> &recs, size_t seg, size_t cap, size_t bound, int m, unsigned char *out, size_t capacity,
-                        uint64_t *offsets) {
+// name: the entry's, ahead of what a failure says.  lossy: null for the exact coder (patolette_amd_gif_lzw), else the lossy one's table
+// (host memory, checked) and `coded` -- null, or where the coded symbols go inside the rectangles: a device pointer when `on_device`.
+struct LzwLossy { const unsigned char *near; unsigned char *coded; };
+static void run_gif_lzw(Engine &E, const char *name, bool on_device, size_t frames, size_t width, size_t height, const unsigned char *maps,
+                        const std::vector<LzwFrame> &recs, size_t seg, size_t cap, size_t bound, int m, const LzwLossy *lossy, unsigned char *out,
+                        size_t capacity, uint64_t *offsets) {
     const size_t n = width * height, N = frames * n, S = recs[frames].seg0;
     hipStream_t s = E.stream;
     GivenRun run(E);
+    const std::string who = std::string(name) + ": ";
     // the workspace, before anything is enqueued
     const size_t stride = lzw_stage_words(std::min(seg, cap)), words = lzw_words(frames), out_words = bound / 4 + 1;
     E.lz_frames.reserve(frames + 1);
@@ -3171,6 +3177,12 @@ static void run_gif_lzw(Engine &E, bool on_device, size_t frames, size_t width, 
     E.lz_gbit.reserve(S + 1);
     E.lz_words.reserve(words);
     E.lz_out.reserve(out_words);
+    unsigned char *d_coded = lossy ? lossy->coded : nullptr;
+    std::vector<unsigned char> h_coded;                                    // host maps: the coded maps on their way to the rectangles
+    if (lossy) {
+        E.lz_near.reserve(kLzwNearBytes);
+        if (!on_device && lossy->coded) { E.dl_shown.reserve(N); d_coded = E.dl_shown.p; h_coded.resize(N); }
+    }
     const unsigned char *d_maps = maps;
     if (!on_device) {
         std::vector<unsigned> none;
@@ -3179,17 +3191,33 @@ static void run_gif_lzw(Engine &E, bool on_device, size_t frames, size_t width, 
     }
     run.lap(&patolette_amd__Stats::ms_upload);
     HIP_CHECK(hipMemcpyAsync(E.lz_frames.p, recs.data(), (frames + 1) * sizeof(LzwFrame), hipMemcpyHostToDevice, s));
-    launch_lzw(d_maps, frames, n, width, E.lz_frames.p, S, seg, stride, m, E.lz_stage.p, E.lz_bits.p, E.lz_gbit.p, E.lz_words.p, E.lz_out.p,
-               out_words, s);
+    if (lossy) {
+        HIP_CHECK(hipMemcpyAsync(E.lz_near.p, lossy->near, kNearRow << m, hipMemcpyHostToDevice, s));   // the rows that are read
+        launch_lzw_lossy(d_maps, frames, n, width, E.lz_frames.p, S, seg, stride, m, E.lz_near.p, d_coded, E.lz_stage.p, E.lz_bits.p, E.lz_gbit.p,
+                         E.lz_words.p, E.lz_out.p, out_words, s);
+    } else {
+        launch_lzw(d_maps, frames, n, width, E.lz_frames.p, S, seg, stride, m, E.lz_stage.p, E.lz_bits.p, E.lz_gbit.p, E.lz_words.p, E.lz_out.p,
+                   out_words, s);
+    }
     const std::vector<unsigned long long> w = run.words(E.lz_words.p, words);
     run.lap(&patolette_amd__Stats::ms_map);
-    if (w[0] & 1) throw HipError("patolette_amd_gif_lzw: a map element inside a rectangle is not below 2^min_code_size");
+    if (w[0] & 1) throw HipError(who + "a map element inside a rectangle is not below 2^min_code_size");
     for (size_t f = 0; f <= frames; f++) offsets[f] = w[1 + f];
     const size_t total = (size_t)w[1 + frames];
-    if (total > bound) throw HipError("patolette_amd_gif_lzw: the streams exceed the stated bound (internal error)");
+    if (total > bound) throw HipError(who + "the streams exceed the stated bound (internal error)");
     if (total > capacity)
-        throw HipError("patolette_amd_gif_lzw: capacity is too small: offsets[frames] holds the bytes needed, nothing was copied");
+        throw HipError(who + "capacity is too small: offsets[frames] holds the bytes needed, nothing was copied");
     HIP_CHECK(hipMemcpy(out, E.lz_out.p, total, hipMemcpyDeviceToHost));
+    if (!h_coded.empty()) {                                                // the rectangles' rows; nothing outside them is written
+        HIP_CHECK(hipMemcpy(h_coded.data(), d_coded, N, hipMemcpyDeviceToHost));
+        for (size_t f = 0; f < frames; f++) {
+            const LzwFrame &F = recs[f];
+            for (size_t y = 0; y < F.area / F.w; y++) {
+                const size_t at = f * n + (F.y0 + y) * width + F.x0;
+                std::memcpy(lossy->coded + at, h_coded.data() + at, F.w);
+            }
+        }
+    }
     run.lap(&patolette_amd__Stats::ms_download);
     run.done();
 }
@@ -3864,16 +3892,26 @@ static void measure_entry(bool on_device, size_t frames, size_t width, size_t he
     });
 }
 
-// index maps LZW-compressed (include/patolette_amd.h): the arguments, then run_gif_lzw
-static void gif_lzw_entry(bool on_device, size_t frames, size_t width, size_t height, const unsigned char *maps, const int32_t *rects,
-                          int min_code_size, size_t segment, unsigned char *out, size_t capacity, uint64_t *offsets, int *exit_code) {
-    const ArgCheck arg{"patolette_amd_gif_lzw", exit_code};
+// index maps LZW-compressed (include/patolette_amd.h), by the exact coder or -- `lossy` -- the lossy one: the arguments, then run_gif_lzw
+static void gif_lzw_entry(const char *name, bool on_device, size_t frames, size_t width, size_t height, const unsigned char *maps,
+                          const int32_t *rects, int min_code_size, size_t segment, const LzwLossy *lossy, unsigned char *out, size_t capacity,
+                          uint64_t *offsets, int *exit_code) {
+    const ArgCheck arg{name, exit_code};
     if (!arg.shape(frames, width, height)) return;
     if (!maps) return (void)arg.fail(-1, "no maps");
     if (!offsets) return (void)arg.fail(-1, "no offsets");
     if (!out && capacity > 0) return (void)arg.fail(-1, "no out");
     if (min_code_size < 2 || min_code_size > 8) return (void)arg.fail(-1, "min_code_size must lie in [2, 8]");
     if (segment > kLzwSegmentMax) return (void)arg.fail(-1, "segment must be 0 (the default) or lie in [1, 2^24]");
+    if (lossy) {
+        if (!lossy->near) return (void)arg.fail(-1, "no near: the table of patolette_amd_gif_neighbours, or any 4096 bytes of its layout");
+        const NearError e = near_check(lossy->near, min_code_size);
+        if (e == kNearCount) return (void)arg.fail(-1, "near: a row below 2^min_code_size has a count above 15");
+        if (e == kNearCandidate) return (void)arg.fail(-1, "near: a candidate of a row below 2^min_code_size is not below 2^min_code_size");
+        const size_t N = frames * width * height;
+        const uintptr_t a = (uintptr_t)maps, b = (uintptr_t)lossy->coded;
+        if (lossy->coded && a < b + N && b < a + N) return (void)arg.fail(-1, "coded must not overlap maps");
+    }
     const size_t seg = segment ? segment : kLzwSegment;
     std::vector<LzwFrame> recs;
     try { recs.resize(frames + 1); } catch (const std::bad_alloc &) { return (void)arg.fail(-1, "no memory for the frames' table"); }
@@ -3891,8 +3929,26 @@ static void gif_lzw_entry(bool on_device, size_t frames, size_t width, size_t he
     }
     recs[frames] = LzwFrame{0, 0, 0, 0, (unsigned)S};
     *exit_code = guarded([&](Engine &E) {
-        run_gif_lzw(E, on_device, frames, width, height, maps, recs, seg, cap, bound, min_code_size, out, capacity, offsets);
+        run_gif_lzw(E, name, on_device, frames, width, height, maps, recs, seg, cap, bound, min_code_size, lossy, out, capacity, offsets);
     });
+}
+
+// the lossy coder's table for a palette (include/patolette_amd.h): host code from end to end -- no engine, no device
+static void gif_neighbours_entry(const double *palette, const unsigned char *palette_u8, size_t palette_rows, int transparent_index, double tolerance,
+                                 int max_neighbours, unsigned char *near_out, int *exit_code) {
+    const ArgCheck arg{"patolette_amd_gif_neighbours", exit_code};
+    if (!arg.one_of(palette, palette_u8)) return;
+    if (palette_rows < 1 || palette_rows > kNearRows) return (void)arg.fail(-1, "palette_rows must lie in [1, 256]");
+    if (transparent_index < -1 || transparent_index > 255) return (void)arg.fail(-1, "transparent_index must be -1 (none) or lie in [0, 255]");
+    if (!(std::isfinite(tolerance) && tolerance >= 0.0)) return (void)arg.fail(-1, "tolerance must be finite and not negative");
+    if (max_neighbours < 0 || max_neighbours > (int)kNearMost) return (void)arg.fail(-1, "max_neighbours must lie in [0, 15]");
+    if (!near_out) return (void)arg.fail(-1, "no near_out");
+    try {
+        GivenPalette g;
+        if (!arg.palette(palette, palette_u8, palette_rows, false, g)) return;
+        near_build(std::move(g.pal), g.k, transparent_index, tolerance, (size_t)max_neighbours, near_out);
+        *exit_code = 0;
+    } catch (const std::bad_alloc &) { arg.fail(-1, "no memory for the palette"); }
 }
 
 static void rgba_entry(bool on_device, size_t width, size_t height, const unsigned char *pixels, int alpha_threshold, const double *weights,
@@ -4025,12 +4081,33 @@ void patolette_amd_measure_device(size_t frames, size_t width, size_t height, co
 
 void patolette_amd_gif_lzw(size_t frames, size_t width, size_t height, const unsigned char *maps, const int32_t *rects, int min_code_size,
                            size_t segment, unsigned char *out, size_t capacity, uint64_t *offsets, int *exit_code) {
-    gif_lzw_entry(false, frames, width, height, maps, rects, min_code_size, segment, out, capacity, offsets, exit_code);
+    gif_lzw_entry("patolette_amd_gif_lzw", false, frames, width, height, maps, rects, min_code_size, segment, nullptr, out, capacity, offsets, exit_code);
 }
 
 void patolette_amd_gif_lzw_device(size_t frames, size_t width, size_t height, const unsigned char *d_maps, const int32_t *rects, int min_code_size,
                                   size_t segment, unsigned char *out, size_t capacity, uint64_t *offsets, int *exit_code) {
-    gif_lzw_entry(true, frames, width, height, d_maps, rects, min_code_size, segment, out, capacity, offsets, exit_code);
+    gif_lzw_entry("patolette_amd_gif_lzw", true, frames, width, height, d_maps, rects, min_code_size, segment, nullptr, out, capacity, offsets, exit_code);
+}
+
+void patolette_amd_gif_lzw_lossy(size_t frames, size_t width, size_t height, const unsigned char *maps, const int32_t *rects, int min_code_size,
+                                 size_t segment, const unsigned char *near, unsigned char *coded, unsigned char *out, size_t capacity,
+                                 uint64_t *offsets, int *exit_code) {
+    const LzwLossy lossy{near, coded};
+    gif_lzw_entry("patolette_amd_gif_lzw_lossy", false, frames, width, height, maps, rects, min_code_size, segment, &lossy, out, capacity, offsets,
+                  exit_code);
+}
+
+void patolette_amd_gif_lzw_lossy_device(size_t frames, size_t width, size_t height, const unsigned char *d_maps, const int32_t *rects,
+                                        int min_code_size, size_t segment, const unsigned char *near, unsigned char *d_coded, unsigned char *out,
+                                        size_t capacity, uint64_t *offsets, int *exit_code) {
+    const LzwLossy lossy{near, d_coded};
+    gif_lzw_entry("patolette_amd_gif_lzw_lossy", true, frames, width, height, d_maps, rects, min_code_size, segment, &lossy, out, capacity, offsets,
+                  exit_code);
+}
+
+void patolette_amd_gif_neighbours(const double *palette, const unsigned char *palette_u8, size_t palette_rows, int transparent_index,
+                                  double tolerance, int max_neighbours, unsigned char *near_out, int *exit_code) {
+    gif_neighbours_entry(palette, palette_u8, palette_rows, transparent_index, tolerance, max_neighbours, near_out, exit_code);
 }
 
 void patolette_amd_frames_u8(size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels, const double *weights,
