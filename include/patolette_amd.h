@@ -781,6 +781,23 @@ int patolette_amd_principal_axis(const double cov6[6], double axis[3]);
 /* the same solver as the DEVICE runs it inside the split loop's control kernel (one problem per lane): `count` column-major 3x3
  * matrices in, w (3 per problem), z (9 per problem) and LAPACK's info out; host buffers.  Returns 0, or -1 on a HIP error. */
 int patolette_amd_eigen_sym3_device(const double *a_colmajor, size_t count, double *w, double *z, int *info);
+/* The global quantiser (global.c:189-377) from a 512-bucket moment table the caller gives, for tests: what it decides, on the
+ * route asked for, from the production code itself on scratch buffers.
+ *   table        host, the engine's own layout: quantity q, part p, bucket b at (q * 2 + p) * 512 + b; quantities 0..2 sum c,
+ *                3 sum |c|^2, 4..9 sum c_r c_s ((r,s) = 00,01,11,02,12,22); when weighted also 10..12 sum w c, 13 sum w
+ *   counts       512 pixel counts
+ *   palette_size passed straight through (quantize() takes the device route above 12 only; here either route runs at any size)
+ *   route        0 the host's turn (the DP kernels, then the host's decisions), 1 the control kernel
+ * Out: *kbase base clusters (0 when *error, the eigen-solver's failure), cuts[14] (q_0 = 0 .. q_kbase = 512), bucket_table[512]
+ * (bucket -> base cluster), per base cluster begin[12], n[12], sw[12], mean[12][3].  Optional (NULL to skip):
+ *   prefix_w0[2][513], prefix[14][513]   the inclusive prefixes, 1-based, as the termination test reads them: row 0 of prefix_w0,
+ *                rows 0..9 of prefix (w1[0..2], w2, the six wrs).  Route 0 adds the DP kernels' own chains: row 1 of prefix_w0,
+ *                rows 10..13 (w1[0..2], w2); route 1 leaves those zero
+ *   cut_table[13][513]   the DP's L[k][n] as the route left it
+ * Returns 0, or -1 on bad arguments or a HIP error. */
+int patolette_amd_debug_gq_table(const double *table, const uint32_t *counts, int weighted, size_t palette_size, int route, int *kbase, int *error,
+                                 int *cuts, unsigned char *bucket_table, uint64_t *begin, uint64_t *n, double *sw, double *mean,
+                                 uint64_t *prefix_w0, double *prefix, int *cut_table);
 /* out[i] = pow(x[i], y) as the colour conversions evaluate it on the device (x >= 0; <= 0.52 ulp) */
 int patolette_amd_pow(const double *x, double y, double *out, size_t n);
 

@@ -90,6 +90,8 @@ SYMBOLS = {
     "patolette_amd_eigen_sym3": (C.c_int, [dp, dp, dp]),
     "patolette_amd_principal_axis": (C.c_int, [dp, dp]),
     "patolette_amd_eigen_sym3_device": (C.c_int, [dp, C.c_size_t, dp, dp, C.POINTER(C.c_int)]),
+    "patolette_amd_debug_gq_table": (C.c_int, [dp, C.c_void_p, C.c_int, C.c_size_t, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, dp, dp, C.c_void_p, dp, C.c_void_p]),
     "patolette_amd_fill_image": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64]),
     "patolette_amd_fill_weights": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64]),
     "patolette_amd_device": (None, [C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -226,6 +228,39 @@ def last_split_trace():
                 splits=[dict(row=r.row, new_row=r.new_row, split=r.split, degenerate=r.degenerate, n=r.n, n_left=r.n_left,
                              n_right=r.n_right, sw=r.sw, axis=[float(v) for v in r.axis], cov6=[float(v) for v in r.cov6],
                              dist=r.dist, dist_left=r.dist_left, dist_right=r.dist_right, benefit=r.benefit) for r in recs[:n]])
+
+
+def debug_gq_table(table, counts, weighted, palette_size, route, details=True):
+    """The global quantiser from a given moment table (patolette_amd_debug_gq_table; tests only).  `table`: (10 or 14, 2, 512) f64 in the
+    engine's layout, `counts`: 512 uint32, `route`: 0 the host's turn, 1 the control kernel.  Returns a dict: kbase, error, cuts
+    (kbase + 1), bucket_table (512,), begin / n / sw (kbase,), mean (kbase, 3) and, with `details`, prefix_w0 (2, 513),
+    prefix (14, 513) and cut_table (13, 513)."""
+    import numpy as np
+    nq = 14 if weighted else 10
+    t = np.ascontiguousarray(table, dtype=np.float64).reshape(-1)
+    c = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+    if t.size != nq * 2 * 512 or c.size != 512:
+        raise ValueError("debug_gq_table: table must hold %d x 2 x 512 doubles and counts 512 entries" % nq)
+    kbase, error = C.c_int(0), C.c_int(0)
+    cuts = np.zeros(14, dtype=np.int32)
+    lut = np.zeros(512, dtype=np.uint8)
+    begin, n = np.zeros(12, dtype=np.uint64), np.zeros(12, dtype=np.uint64)
+    sw, mean = np.zeros(12), np.zeros((12, 3))
+    pw0 = np.zeros((2, 513), dtype=np.uint64) if details else None
+    pre = np.zeros((14, 513)) if details else None
+    ctab = np.zeros((13, 513), dtype=np.int32) if details else None
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None      # noqa: E731
+    rc = lib().patolette_amd_debug_gq_table(t.ctypes.data_as(dp), vp(c), 1 if weighted else 0, int(palette_size), int(route), C.byref(kbase),
+                                            C.byref(error), vp(cuts), vp(lut), vp(begin), vp(n), sw.ctypes.data_as(dp), mean.ctypes.data_as(dp),
+                                            vp(pw0), pre.ctypes.data_as(dp) if details else None, vp(ctab))
+    if rc != 0:
+        raise RuntimeError("patolette_amd_debug_gq_table: %d (%s)" % (rc, last_error()))
+    k = kbase.value
+    out = dict(kbase=k, error=error.value, cuts=[int(v) for v in cuts[:k + 1]] if k else [], bucket_table=lut, begin=begin[:k].copy(),
+               n=n[:k].copy(), sw=sw[:k].copy(), mean=mean[:k].copy())
+    if details:
+        out.update(prefix_w0=pw0, prefix=pre, cut_table=ctab)
+    return out
 
 
 def last_cluster_centers():

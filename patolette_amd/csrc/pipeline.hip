@@ -653,6 +653,9 @@ struct GqTab {                                          // LDS: inclusive prefix
     }
 };
 
+// the inclusive prefixes, 1-based, as a test reads them back (patolette_amd_debug_gq_table): w0, then w1[0..2], w2, wrs[0..5]
+struct GqPrefixes { unsigned long long w0[kBuckets + 1]; double t[10][kBuckets + 1]; };
+
 // entry (k, n) of the DP by ONE wavefront (k_gq_dp's block, quant.hip): E_k[n] and L[k][n] from Ep = E_{k-1}
 __device__ __forceinline__ void gq_dp_entry(const GqTab &c, const double *Ep, const int k, const int n, const int lane, double &e_out, int &cut_out) {
     double best = INFINITY; int bt = -1;
@@ -672,7 +675,7 @@ __device__ __forceinline__ void gq_dp_entry(const GqTab &c, const double *Ep, co
 
 __global__ __launch_bounds__(1024) void k_gq_control(const double *__restrict__ hist, const unsigned int *__restrict__ hcount, GqDpDev *g,
                                                      const int palette_size, const int weighted, NodeDev *nodes, const int base0,
-                                                     unsigned char *lut, GqOut *out, GqOut *out_host) {
+                                                     unsigned char *lut, GqOut *out, GqOut *out_host, GqPrefixes *dbg_prefixes) {
     __shared__ GqTab c;
     __shared__ double E[2][kBuckets + 1];
     __shared__ int s_q[16], s_nq, s_stop, s_err, s_top;
@@ -728,6 +731,10 @@ __global__ __launch_bounds__(1024) void k_gq_control(const double *__restrict__ 
         for (int u = 0; u < 8; u++) c.w0[1 + lane * 8 + u] = before + v[u];
     }
     __syncthreads();
+    if (dbg_prefixes) {                                              // tests only (patolette_amd_debug_gq_table): the prefixes as the search reads them
+        for (int i = tid; i <= kBuckets; i += 1024) dbg_prefixes->w0[i] = c.w0[i];
+        for (int i = tid; i < 10 * (kBuckets + 1); i += 1024) { const int q = i / (kBuckets + 1), n = i - q * (kBuckets + 1); dbg_prefixes->t[q][n] = c.t[q][n]; }
+    }
     if (tid == 0) s_ticks[1] = wall_clock64();
     // ---- 2. the axis of everything, E_1; L as the reference starts it (zero, L[i][i] = i: global.c:236-238)
     for (int i = tid; i < (kGqMaxK + 1) * (kBuckets + 1); i += 1024) { const int r = i / (kBuckets + 1), n = i - r * (kBuckets + 1); g->cut[r][n] = r == n ? r : 0; }
@@ -1678,7 +1685,7 @@ static int gq_device_turn(QuantCall &C) {
     {
         KTIME("k_gq_control", s, (double)C.hs * 8);
         hipLaunchKernelGGL(k_gq_control, 1, 1024, 0, s, (const double *)E.hist.p, (const unsigned int *)E.hcount.p, E.gq.p, (int)std::min<size_t>(C.K, (size_t)1 << 30),
-                           C.weighted ? 1 : 0, E.nodes.p, 1, E.lut.p, E.gqout.p, E.h_gqout.p);
+                           C.weighted ? 1 : 0, E.nodes.p, 1, E.lut.p, E.gqout.p, E.h_gqout.p, (GqPrefixes *)nullptr);
         HIP_CHECK(hipGetLastError());
     }
     launch_partition(C.qroot, E.tilesP.p, C.ntP0, C.N, E.round_nodes.p, E.node_tile0.p, 1, E.nodes.p, E.lut.p, E.tilecnt.p, E.tileoff.p, true, s, C.inv_sums,
@@ -1704,6 +1711,69 @@ static int gq_device_turn(QuantCall &C) {
     return kHostLoop;
 }
 
+// What the host's turn decides from the downloaded table (`hh`: quantity q, part p, bucket b at (q * 2 + p) * 512 + b; `hc`: the
+// buckets' counts) and the device's cut table: the cuts, the bucket -> base cluster table and the base clusters' records.
+// gq_host_turn and the table-level test entry (patolette_amd_debug_gq_table) both come here.
+struct GqDecision {
+    std::vector<size_t> cuts;
+    int kbase = 0;
+    std::vector<unsigned char> lut;
+    struct Base { unsigned long long begin, n; double sw, mean[3]; } base[kGqMaxK];
+};
+static bool gq_host_decide(const double *hh, const unsigned int *hc, const bool weighted, const size_t K, const int (*cut)[kBuckets + 1], GqDecision &D,
+                           hm::CellMoments *prefixes = nullptr) {
+    auto H = [&](int q, int b) { return hh[(size_t)(q * 2 + 0) * kBuckets + b] + hh[(size_t)(q * 2 + 1) * kBuckets + b]; };
+
+    auto cm = std::make_unique<hm::CellMoments>();
+    std::memset(cm.get(), 0, sizeof(hm::CellMoments));
+    for (int b = 0; b < kBuckets; b++) {
+        cm->w0[b + 1] = hc[b];
+        for (int r = 0; r < 3; r++) cm->w1[r][b + 1] = H(r, b);
+        cm->w2[b + 1] = H(3, b);
+        for (int q = 0; q < 6; q++) cm->wrs[q][b + 1] = H(4 + q, b);
+    }
+    for (int i = 1; i <= kBuckets; i++) {                       // cells.c:114-136 sequential prefix
+        cm->w0[i] += cm->w0[i - 1]; cm->w2[i] += cm->w2[i - 1];
+        for (int r = 0; r < 3; r++) cm->w1[r][i] += cm->w1[r][i - 1];
+        for (int q = 0; q < 6; q++) cm->wrs[q][i] += cm->wrs[q][i - 1];
+    }
+    if (prefixes) *prefixes = *cm;
+    D.cuts = hm::gq_principal_quantizer(K, *cm, cut);
+    const std::vector<size_t> &cuts = D.cuts;
+    if (cuts.size() < 2) return false;
+    const int kbase = D.kbase = (int)cuts.size() - 1;
+
+    // base clusters: bucket b belongs to the first cell j with b+1 <= q[j+1] (global.c:328-335)
+    std::vector<unsigned char> &lut = D.lut;
+    lut.assign(kBuckets, 0);
+    for (int b = 0; b < kBuckets; b++) {
+        int j = 0;
+        while (j < kbase - 1 && !((size_t)(b + 1) <= cuts[j + 1])) j++;
+        lut[b] = (unsigned char)j;
+    }
+    unsigned long long pos = 0;
+    for (int j = 0; j < kbase; j++) {
+        GqDecision::Base &c = D.base[j];
+        c.begin = pos;
+        unsigned long long cnt = 0;
+        double s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0};          // exact: parts lie on the bin grids
+        for (int b = 0; b < kBuckets; b++) if (lut[b] == j) {
+            cnt += hc[b];
+            for (int q = 0; q < (weighted ? 4 : 3); q++) {
+                int qi = weighted ? 10 + q : q;
+                s0[q] += hh[(size_t)(qi * 2 + 0) * kBuckets + b];
+                s1[q] += hh[(size_t)(qi * 2 + 1) * kBuckets + b];
+            }
+        }
+        c.n = cnt;
+        c.sw = weighted ? (s0[3] + s1[3]) : (double)cnt;
+        const double inv = 1 / c.sw;
+        for (int q = 0; q < 3; q++) c.mean[q] = (s0[q] + s1[q]) * inv;
+        pos += cnt;
+    }
+    return true;
+}
+
 // The host's turn of the global quantiser: the cell moments come down, hm::gq_principal_quantizer decides, the bucket table and the
 // base clusters' records go up, the partition follows
 static int gq_host_turn(QuantCall &C) {
@@ -1724,60 +1794,25 @@ static int gq_host_turn(QuantCall &C) {
     E.sync();
     std::memcpy(hh.data(), E.h_dbl.p, hs * sizeof(double));
     std::memcpy(hc.data(), E.h_round.p, kBuckets * sizeof(unsigned int));
-    auto H = [&](int q, int b) { return hh[(size_t)(q * 2 + 0) * kBuckets + b] + hh[(size_t)(q * 2 + 1) * kBuckets + b]; };
-
-    auto cm = std::make_unique<hm::CellMoments>();
-    std::memset(cm.get(), 0, sizeof(hm::CellMoments));
-    for (int b = 0; b < kBuckets; b++) {
-        cm->w0[b + 1] = hc[b];
-        for (int r = 0; r < 3; r++) cm->w1[r][b + 1] = H(r, b);
-        cm->w2[b + 1] = H(3, b);
-        for (int q = 0; q < 6; q++) cm->wrs[q][b + 1] = H(4 + q, b);
-    }
-    for (int i = 1; i <= kBuckets; i++) {                       // cells.c:114-136 sequential prefix
-        cm->w0[i] += cm->w0[i - 1]; cm->w2[i] += cm->w2[i - 1];
-        for (int r = 0; r < 3; r++) cm->w1[r][i] += cm->w1[r][i - 1];
-        for (int q = 0; q < 6; q++) cm->wrs[q][i] += cm->wrs[q][i - 1];
-    }
-    std::vector<size_t> cuts = hm::gq_principal_quantizer(K, *cm, E.h_gq.p->cut);
-    if (cuts.size() < 2) return -1;
-    const int kbase = C.kbase = (int)cuts.size() - 1;
+    GqDecision D;
+    if (!gq_host_decide(hh.data(), hc.data(), weighted, K, E.h_gq.p->cut, D)) return -1;
+    const std::vector<size_t> &cuts = D.cuts;
+    const std::vector<unsigned char> &lut = D.lut;
+    const int kbase = C.kbase = D.kbase;
     E.trace_hdr.n_base = kbase;
     for (int j = 0; j <= kbase && j < 14; j++) E.trace_hdr.gq_cuts[j] = cuts[j];
-
-    // base clusters: bucket b belongs to the first cell j with b+1 <= q[j+1] (global.c:328-335)
-    std::vector<unsigned char> lut(kBuckets);
-    for (int b = 0; b < kBuckets; b++) {
-        int j = 0;
-        while (j < kbase - 1 && !((size_t)(b + 1) <= cuts[j + 1])) j++;
-        lut[b] = (unsigned char)j;
-    }
     // Two base clusters (what noise and most photographs give): the partition is a binary split like the local quantiser's, so
     // it takes the same pipelined kernel and the children's centred moments ride along instead of costing a sweep of their own
     const bool gq_binary = kbase == 2;
     std::vector<int> &base_ids = C.base_ids;
-    {
-        unsigned long long pos = 0;
-        for (int j = 0; j < kbase; j++) {
-            HNode c; c.buf = 1; c.begin = pos;
-            unsigned long long cnt = 0;
-            double s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0};      // exact: parts lie on the bin grids
-            for (int b = 0; b < kBuckets; b++) if (lut[b] == j) {
-                cnt += hc[b];
-                for (int q = 0; q < (weighted ? 4 : 3); q++) {
-                    int qi = weighted ? 10 + q : q;
-                    s0[q] += hh[(size_t)(qi * 2 + 0) * kBuckets + b];
-                    s1[q] += hh[(size_t)(qi * 2 + 1) * kBuckets + b];
-                }
-            }
-            c.n = cnt; c.gn = cnt;                                   // sliced image: the segment on this GPU follows from the partition
-            c.sw = weighted ? (s0[3] + s1[3]) : (double)cnt;
-            const double inv = 1 / c.sw;
-            for (int q = 0; q < 3; q++) c.mean[q] = (s0[q] + s1[q]) * inv;
-            pos += cnt;
-            base_ids.push_back((int)hn.size());
-            hn.push_back(c);
-        }
+    for (int j = 0; j < kbase; j++) {
+        const GqDecision::Base &b = D.base[j];
+        HNode c; c.buf = 1; c.begin = b.begin;
+        c.n = b.n; c.gn = b.n;                                       // sliced image: the segment on this GPU follows from the partition
+        c.sw = b.sw;
+        for (int q = 0; q < 3; q++) c.mean[q] = b.mean[q];
+        base_ids.push_back((int)hn.size());
+        hn.push_back(c);
     }
     {
         NodeIn d = make_nodedev(hn[0], C.bnd);
@@ -4337,6 +4372,84 @@ int patolette_amd_eigen_sym3_device(const double *a_colmajor, size_t count, doub
         HIP_CHECK(hipMemcpy(info, di.p, count * sizeof(int), hipMemcpyDeviceToHost));
         return 0;
     } catch (const std::exception &e) { engine().last_error = e.what(); return -1; }
+}
+// The global quantiser from a moment table the caller gives, on either route (tests only).  Scratch buffers throughout; the DP state
+// starts as 0xFF bytes, so that an entry a route reads without having written it cannot pass for the reference's initial value.
+int patolette_amd_debug_gq_table(const double *table, const uint32_t *counts, int weighted, size_t palette_size, int route, int *kbase, int *error,
+                                 int *cuts, unsigned char *bucket_table, uint64_t *begin, uint64_t *n, double *sw, double *mean,
+                                 uint64_t *prefix_w0, double *prefix, int *cut_table) {
+    if (!table || !counts || !kbase || !error || !cuts || !bucket_table || !begin || !n || !sw || !mean || palette_size < 1 || (route != 0 && route != 1))
+        return -1;
+    return guarded([&](Engine &E) -> int {
+        hipStream_t s = E.stream;
+        const size_t hs = (size_t)(weighted ? 14 : 10) * 2 * kBuckets;
+        DevBuf<double> d_hist; DevBuf<unsigned int> d_hcount; DevBuf<GqDpDev> d_g;
+        d_hist.reserve(hs); d_hcount.reserve(kBuckets); d_g.reserve(1);
+        HIP_CHECK(hipMemcpyAsync(d_hist.p, table, hs * sizeof(double), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(d_hcount.p, counts, kBuckets * sizeof(unsigned int), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemsetAsync(d_g.p, 0xFF, sizeof(GqDpDev), s));
+        auto h_g = std::make_unique<GqDpDev>();
+        *kbase = 0; *error = 0;
+        for (int j = 0; j < 14; j++) cuts[j] = 0;
+        for (int j = 0; j < kGqMaxK; j++) { begin[j] = 0; n[j] = 0; sw[j] = 0; for (int q = 0; q < 3; q++) mean[3 * j + q] = 0; }
+        std::memset(bucket_table, 0, kBuckets);
+        if (prefix_w0) std::memset(prefix_w0, 0, 2 * (kBuckets + 1) * sizeof(uint64_t));
+        if (prefix) std::memset(prefix, 0, 14 * (kBuckets + 1) * sizeof(double));
+        if (route == 0) {
+            launch_gq_dp(d_hist.p, d_hcount.p, (int)std::min<size_t>(palette_size, kGqMaxK), d_g.p, s);
+            HIP_CHECK(hipMemcpyAsync(h_g.get(), d_g.p, sizeof(GqDpDev), hipMemcpyDeviceToHost, s));
+            E.sync();
+            GqDecision D;
+            auto cm = std::make_unique<hm::CellMoments>();
+            const bool ok = gq_host_decide(table, counts, weighted != 0, palette_size, h_g->cut, D, cm.get());
+            if (prefix_w0) for (int i = 0; i <= kBuckets; i++) { prefix_w0[i] = cm->w0[i]; prefix_w0[kBuckets + 1 + i] = h_g->w0[i]; }
+            if (prefix) {                                            // rows 0..9 the host's own chains, 10..13 k_gq_prefix's (what the DP read)
+                for (int r = 0; r < 3; r++) std::memcpy(prefix + (size_t)r * (kBuckets + 1), cm->w1[r], sizeof(cm->w1[r]));
+                std::memcpy(prefix + (size_t)3 * (kBuckets + 1), cm->w2, sizeof(cm->w2));
+                for (int q = 0; q < 6; q++) std::memcpy(prefix + (size_t)(4 + q) * (kBuckets + 1), cm->wrs[q], sizeof(cm->wrs[q]));
+                for (int r = 0; r < 3; r++) std::memcpy(prefix + (size_t)(10 + r) * (kBuckets + 1), h_g->w1[r], sizeof(h_g->w1[r]));
+                std::memcpy(prefix + (size_t)13 * (kBuckets + 1), h_g->w2, sizeof(h_g->w2));
+            }
+            if (cut_table) std::memcpy(cut_table, h_g->cut, sizeof(h_g->cut));
+            if (!ok) { *error = 1; return 0; }
+            *kbase = D.kbase;
+            for (int j = 0; j <= D.kbase && j < 14; j++) cuts[j] = (int)D.cuts[j];
+            std::memcpy(bucket_table, D.lut.data(), kBuckets);
+            for (int j = 0; j < D.kbase; j++) {
+                begin[j] = D.base[j].begin; n[j] = D.base[j].n; sw[j] = D.base[j].sw;
+                for (int q = 0; q < 3; q++) mean[3 * j + q] = D.base[j].mean[q];
+            }
+            return 0;
+        }
+        DevBuf<NodeDev> d_nodes; DevBuf<unsigned char> d_lut; DevBuf<GqOut> d_out; DevBuf<GqPrefixes> d_pre;
+        d_nodes.reserve(1 + kGqMaxK); d_lut.reserve(kBuckets); d_out.reserve(2); d_pre.reserve(1);
+        HIP_CHECK(hipMemsetAsync(d_nodes.p, 0, (1 + kGqMaxK) * sizeof(NodeDev), s));
+        HIP_CHECK(hipMemsetAsync(d_out.p, 0, 2 * sizeof(GqOut), s));
+        hipLaunchKernelGGL(k_gq_control, 1, 1024, 0, s, (const double *)d_hist.p, (const unsigned int *)d_hcount.p, d_g.p, (int)std::min<size_t>(palette_size, (size_t)1 << 30),
+                           weighted ? 1 : 0, d_nodes.p, 1, d_lut.p, d_out.p, d_out.p + 1, (prefix_w0 || prefix) ? d_pre.p : (GqPrefixes *)nullptr);
+        HIP_CHECK(hipGetLastError());
+        GqOut o;
+        std::vector<NodeDev> h_nodes(1 + kGqMaxK);
+        auto h_pre = std::make_unique<GqPrefixes>();
+        HIP_CHECK(hipMemcpyAsync(&o, d_out.p, sizeof(GqOut), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(h_nodes.data(), d_nodes.p, (1 + kGqMaxK) * sizeof(NodeDev), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(bucket_table, d_lut.p, kBuckets, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(h_g.get(), d_g.p, sizeof(GqDpDev), hipMemcpyDeviceToHost, s));
+        if (prefix_w0 || prefix) HIP_CHECK(hipMemcpyAsync(h_pre.get(), d_pre.p, sizeof(GqPrefixes), hipMemcpyDeviceToHost, s));
+        E.sync();
+        if (prefix_w0) std::memcpy(prefix_w0, h_pre->w0, sizeof(h_pre->w0));
+        if (prefix) std::memcpy(prefix, h_pre->t, sizeof(h_pre->t));
+        if (cut_table) std::memcpy(cut_table, h_g->cut, sizeof(h_g->cut));
+        if (o.error) { *error = 1; std::memset(bucket_table, 0, kBuckets); return 0; }
+        *kbase = o.kbase;
+        for (int j = 0; j <= o.kbase && j < 14; j++) cuts[j] = o.cuts[j];
+        for (int j = 0; j < o.kbase; j++) {
+            const NodeDev &c = h_nodes[1 + j];
+            begin[j] = c.begin; n[j] = c.n; sw[j] = c.sw;
+            for (int q = 0; q < 3; q++) mean[3 * j + q] = c.mean[q];
+        }
+        return 0;
+    });
 }
 int patolette_amd_eigen_sym3(const double a_colmajor[9], double w[3], double z[9]) {
     std::memcpy(z, a_colmajor, 9 * sizeof(double));

@@ -1162,6 +1162,12 @@ __device__ __forceinline__ double gq_distortion(const GqDpDev *g, int a, int b) 
 __global__ void k_gq_init(GqDpDev *g) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i <= kBuckets) g->E[0][i] = i >= 1 ? gq_distortion(g, 0, i) : 0.0;
+    // L as the reference starts it (zero, L[r][r] = r: global.c:236-238).  k_gq_dp writes only n >= k + 1, and the backtrack reads
+    // the diagonal whenever a cut lands on t = k - 1
+    for (int e = i; e < (kGqMaxK + 1) * (kBuckets + 1); e += (int)(gridDim.x * blockDim.x)) {
+        const int r = e / (kBuckets + 1), n = e - r * (kBuckets + 1);
+        g->cut[r][n] = r == n ? r : 0;
+    }
 }
 // step k: reads E[(k & 1)], writes E[(k & 1) ^ 1] and cut[k][n]
 __global__ __launch_bounds__(256) void k_gq_dp(GqDpDev *g, int k) {

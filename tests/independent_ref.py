@@ -140,6 +140,36 @@ def should_terminate(q, axis, cells):
     return bias < 0.1                                             # bias_threshold, global.c:20
 
 
+def l_chain(L, k):
+    """l_chain, global.c:72-97: the cuts [0 = q0 .. qk = 512] that the cut table L holds for k cells."""
+    N = BUCKETS
+    ch = [0] * (k + 1)
+    t = N
+    for j in range(k - 1, 0, -1):
+        t = L[(j + 1, t)]
+        ch[j] = t
+    ch[k] = N
+    return ch
+
+
+def dp_step(k, E, L, cells):
+    """global.c:252-272 for one k: returns E_k from E = E_{k-1} and writes L[(k, n)] for n = k+1 .. 512.  Entries n <= k keep
+    E_{k-1}[n] (the copy), and L there is never written."""
+    N = BUCKETS
+    E_ = E
+    E = E.copy()
+    for n in range(k + 1, N + 1):
+        # global.c:252-272: cut = n-1, e = E_[n-1]; then t = n-2 down to k-1: `if (c < e)` takes it.  A strict '<' scanned
+        # downwards keeps the FIRST minimum of (E_[n-1], c(n-2), c(n-3), ...), which is what argmin returns; the candidates
+        # are evaluated element-wise with the same expression as Cells.distortion (no reassociation).
+        ts = np.arange(n - 2, k - 2, -1)
+        cand = np.concatenate(([E_[n - 1]], E_[ts] + cells.distortion_to(ts, n)))
+        j = int(np.argmin(cand))
+        L[(k, n)] = n - 1 if j == 0 else int(ts[j - 1])
+        E[n] = cand[j]
+    return E
+
+
 def principal_quantizer(K, cells):
     """quantize/global.c:189-298: DP over the 512 buckets, k = 2..min(12, K), with the termination test BEFORE each k."""
     N = BUCKETS
@@ -150,30 +180,12 @@ def principal_quantizer(K, cells):
     for i in range(1, N + 1):
         E[i] = cells.distortion(0, i)
     L = {(i, i): i for i in range(1, K + 1)}                     # global.c:236-238
-
-    def chain(k):                                                 # l_chain, global.c:72-97
-        ch = [0] * (k + 1)
-        t = N
-        for j in range(k - 1, 0, -1):
-            t = L[(j + 1, t)]
-            ch[j] = t
-        ch[k] = N
-        return ch
-    result = chain(1)
+    result = l_chain(L, 1)
     for k in range(2, min(12, K) + 1):
         if should_terminate(result, axis, cells):
             break
-        E_ = E.copy()
-        for n in range(k + 1, N + 1):
-            # global.c:252-272: cut = n-1, e = E_[n-1]; then t = n-2 down to k-1: `if (c < e)` takes it.  A strict '<' scanned
-            # downwards keeps the FIRST minimum of (E_[n-1], c(n-2), c(n-3), ...), which is what argmin returns; the candidates
-            # are evaluated element-wise with the same expression as Cells.distortion (no reassociation).
-            ts = np.arange(n - 2, k - 2, -1)
-            cand = np.concatenate(([E_[n - 1]], E_[ts] + cells.distortion_to(ts, n)))
-            j = int(np.argmin(cand))
-            L[(k, n)] = n - 1 if j == 0 else int(ts[j - 1])
-            E[n] = cand[j]
-        result = chain(k)
+        E = dp_step(k, E, L, cells)
+        result = l_chain(L, k)
     return result
 
 

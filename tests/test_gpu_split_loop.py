@@ -6,6 +6,7 @@ evaluated candidate nodes may differ (the device's selection rule is exact-safe,
 import numpy as np
 import pytest
 
+from tests import tie_prover as tp
 from tests.test_tie_prover import content
 
 pytestmark = pytest.mark.gpu
@@ -157,7 +158,12 @@ def test_global_quantiser_on_the_device_equals_the_hosts_turn(gpu, native, ob, l
         assert np.array_equal(cen_h, cen_d) and np.array_equal(pal_h, pal_d) and np.array_equal(map_h, map_d), desc
         ec, pal_o, map_o = ob.patolette(w, h, ob.planar(colors), wts, K, dither=False, color_space=cs, kmeans_niter=0)
         assert ec == 0, desc
-        if kind in (0, 1, 2) or np.allclose(pal_d, pal_o, rtol=0, atol=1e-9):
+        if kind == 3 and not (np.allclose(pal_d, pal_o, rtol=0, atol=1e-9) and np.array_equal(map_d, map_o)):
+            # noise / posterised / gradient: the oracle's own decisions can be ties.  No escape: the tie referee proves every decision
+            # of both traces and replays the oracle from the HIP path's centres, or raises (the last call above was this result's)
+            why = tp.explain_divergence(ob, native, gpu, w, h, ob.planar(colors), wts, K, cs, False, 0, 512 ** 2, pal_d, map_d)
+            print("proven tie:", desc, why["first"])
+        else:
             assert np.allclose(pal_d, pal_o, rtol=0, atol=1e-9) and np.array_equal(map_d, map_o), desc
         seen.append(st_d["n_base_clusters"])
     print("seed %d: base clusters per case %s" % (seed, seen))
