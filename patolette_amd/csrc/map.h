@@ -55,35 +55,47 @@ int nn_debug_route(int route);
 // elements of 1 or 4 bytes.
 bool nn_map_u8_applies(size_t n, int k);
 void launch_nn_map_u8(const unsigned char *d_px, int channels, size_t n, const double *d_pal, int k, void *d_out, int elem_bytes, NNWork &w, hipStream_t s);
-// which: the conversion the pixels still need on their way into linear Rec2020 (PAMD_COPY: none) -- only the lane-per-run layout
-// (dither_lane_layout) converts on the fly; h_pal: the same palette on the host if the caller has it (else it is read back)
-bool dither_lane_layout(size_t width, size_t height, int k);
-void launch_dither(const double *d_img, size_t plane_stride, int which, size_t width, size_t height, const double *d_pal, const double *h_pal, int k,
-                   void *d_out, int elem_bytes, NNWork &w, hipStream_t s, int layout = -1);   // layout: 1 lanes, 0 wavefronts, -1 decide here
 
-// `frames` images of width x height one after another (frame f's pixels at offset f * width * height of every plane and of d_out), one
-// palette: every frame is dithered along its own curve from the empty error queue, exactly as launch_dither would dither it alone.
-// Where dither_frames_lane_layout holds, all frames are walked side by side in one set of launches; otherwise frame after frame
-// through the wavefront layout, which takes linear Rec2020 pixels (which == PAMD_COPY).  At most kDitherFramesMaxPixels in all.
+// ---- the Riemersma dither ----
+// One dither call: what is walked, onto which palette, into which map.  Every frame is dithered along its own width x height curve
+// from the empty error queue.
+struct DitherJob {
+    // the pixels, one of two forms.  Planes: f64, plane p at planes + p * plane_stride, frame f at offset f * width * height of every
+    // plane; `which`: the conversion they still need on their way into linear Rec2020 (PAMD_COPY: none) -- only the lane layout
+    // converts on the fly.  Bytes: interleaved 8-bit sRGB, `channels` (3 or 4) each, frame after frame; the conversion rides on the
+    // lane layout's gather and no f64 image exists, so the caller has checked that the lane layout applies (dither_lane_layout, resp.
+    // dither_frames_lane_layout for frames > 1).
+    const double *planes = nullptr;
+    size_t plane_stride = 0;
+    int which = -1;
+    const unsigned char *bytes = nullptr;
+    int channels = 3;
+    // A single image has up to 2^32 - 1 pixels; more frames than one, and bytes, kDitherFramesMaxPixels in all.
+    size_t frames = 1, width = 0, height = 0;
+    // Masked (the RGBA entries; planes, one frame): only some pixels are visited.  cpos[pixel] = the pixel's number among the `opaque`
+    // ones (row-scan order), or -1 for a transparent pixel, which the walk skips exactly like a position outside the image.  The planes
+    // are then the opaque pixels' compact ones (plane_stride >= opaque), the map `opaque` choices in compact order, and the layout is
+    // decided on `opaque`.  mpos: the launcher's own (the table it makes of cpos, in dither_mask_reserve's part of the workspace).
+    const int *cpos = nullptr;
+    size_t opaque = 0;
+    const unsigned *mpos = nullptr;
+    // the palette, planar (k,3) in linear Rec2020: on the device and, if the caller has it, on the host (else it is read back)
+    const double *d_pal = nullptr, *h_pal = nullptr;
+    int k = 0;
+    // the map: frame f's choices at element f * width * height; elements of 1, 4 or 8 bytes
+    void *out = nullptr;
+    int elem_bytes = 0;
+    int layout = -1;                   // 1 lanes, 0 wavefronts, -1 decided by the launcher (what the caller decided when it chose the pixels' form)
+};
 constexpr size_t kDitherFramesMaxPixels = (size_t)1 << 31;
+// Which layout walks the runs when the job does not say: one lane per run (all frames side by side in one set of launches) where these
+// hold, else one wavefront per run, frame after frame, which takes planes in linear Rec2020 (which == PAMD_COPY).
+bool dither_lane_layout(size_t width, size_t height, int k);
 bool dither_frames_lane_layout(size_t frames, size_t width, size_t height, int k);
-void launch_dither_frames(const double *d_img, size_t plane_stride, int which, size_t frames, size_t width, size_t height, const double *d_pal,
-                          const double *h_pal, int k, void *d_out, int elem_bytes, NNWork &w, hipStream_t s, int layout = -1);
-
-// The lane layout straight from interleaved 8-bit sRGB pixels (the remap entry): `frames` images of width x height, `channels` (3 or 4)
-// bytes per pixel, palette in linear Rec2020; the conversion rides on the gather and no f64 image exists.  Only where the lane layout
-// applies (dither_lane_layout, resp. dither_frames_lane_layout for frames > 1).  Returns false when the walk's verification stalled
-// for good: the caller then converts the image and calls launch_dither / launch_dither_frames.
-bool launch_dither_u8(const unsigned char *d_px, int channels, size_t frames, size_t width, size_t height, const double *d_pal, const double *h_pal,
-                      int k, void *d_out, int elem_bytes, NNWork &w, hipStream_t s);
-
-// The same chain over a width x height image of which only some pixels are visited (the RGBA entry): d_cpos[pixel] = the pixel's
-// number among the m opaque ones (row-scan order), or -1 for a transparent pixel, which the walk skips exactly like a position
-// outside the image.  d_img: the opaque pixels' compact planes (plane_stride >= m), d_out: m choices in compact order.  The layout
-// is decided on m (dither_lane_layout(m, 1, k)) unless the caller passes it.
-void launch_dither_masked(const double *d_img, size_t plane_stride, int which, size_t width, size_t height, const int *d_cpos, size_t m,
-                          const double *d_pal, const double *h_pal, int k, void *d_out, int elem_bytes, NNWork &w, hipStream_t s, int layout = -1);
-// what launch_dither_masked takes of the workspace for an image of npix pixels, reserved before anything is enqueued
+// Returns false only for bytes, when the lane walk's verification stalled for good and nothing usable was written: the caller then
+// converts the image and sends the planes with layout 0.  Planes that stall are converted and walked by the wavefront layout here.
+bool launch_dither(const DitherJob &job, NNWork &w, hipStream_t s);
+// what a masked job takes of the workspace for an image of npix pixels, for callers that reserve before anything is enqueued
 void dither_mask_reserve(NNWork &w, size_t npix);
 
 // test / tuning knob: runs the curve is cut into (0 = chosen from the image size) and in-image pixels of warm-up (< 0 = default)

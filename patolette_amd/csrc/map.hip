@@ -17,6 +17,7 @@
 // wavefront each (DitherSeg), or ~130 000 runs of one LANE each on large images (DitherLanes).
 #include "map.h"
 #include "compact.h"
+#include "dither_host.h"
 #include "dither_slots.h"
 
 #include <algorithm>
@@ -63,11 +64,6 @@ __global__ __launch_bounds__(256) void k_nn_map(const double *__restrict__ c, si
 // fall back to the full scan.  (32^3 grid -> ~3 candidates per pixel.)
 // --------------------------------------------------------------------------------------------
 constexpr int kLutMax = 30;                  // candidates kept per cell: 15 in the primary record, 15 in the secondary
-
-struct NNGrid {
-    double lo[3], cw[3], inv[3];             // cell (i,j,k) spans lo + i*cw .. lo + (i+1)*cw
-    int G;
-};
 
 // Coarse pass of the LUT build: a (G/4)^3 grid whose cells each cover 4x4x4 cells of the final grid.  The entries that
 // survive the pruning rule on a coarse cell are a superset of the survivors on every cell inside it (a larger box has a
@@ -1012,10 +1008,6 @@ __host__ __device__ __forceinline__ void hilbert_d2xy(int L, unsigned long long 
     xo = x; yo = y;
 }
 
-struct DitherWeights { double w[16]; };
-
-constexpr double kRw = 0.51254268114958, kGw = 0.8234075540095561, kBw = 0.2435159132377184;   // riemersma.c:38-42
-
 // ---- wave-level helpers for the serial chain (DPP: a few cycles per step, vs ~100 for ds_bpermute) ----
 template <int CTRL>
 __device__ __forceinline__ double dpp_f64(double v) {
@@ -1570,7 +1562,7 @@ __global__ __launch_bounds__(64) void k_dither_order(unsigned width, unsigned he
 // pixels).  Write side: eight consecutive runs = 64 bytes.
 // WHICH: the conversion into linear Rec2020 the pixels still need (patolette.c:268-299; PAMD_COPY = none), done on the way -- the
 // same device routine k_convert applies, so the same bits, without a pass of its own over the image
-// FRAMES (launch_dither_frames): the image is a stack of frames of n pixels each, `fruns` runs per frame, and spos is the table of
+// FRAMES (a DitherJob with frames > 1): the image is a stack of frames of n pixels each, `fruns` runs per frame, and spos is the table of
 // ONE frame: run b lies in frame b / fruns, whose ranks start at t(b / fruns * fruns) = frame * n, which is also where its pixels start
 // (a body shared by two kernels, not a flag on one: k_dither_streams keeps its argument list, so its code is what it was)
 // U8 (the remap entry): the pixels are interleaved 8-bit sRGB (px8, ch bytes each) instead of f64 planes, WHICH is
@@ -1649,7 +1641,7 @@ __global__ __launch_bounds__(256) void k_dither_streams_frames(const double *__r
     dither_streams_tile<WHICH, true>(img, plane_stride, spos, R, sx, sy, sz, fruns);
 }
 
-// the same from interleaved 8-bit sRGB pixels (launch_dither_u8)
+// the same from interleaved 8-bit sRGB pixels (a DitherJob's bytes)
 __global__ __launch_bounds__(256) void k_dither_streams_u8(const unsigned char *__restrict__ px8, int ch, const unsigned *__restrict__ spos, DitherRuns R,
                                                           double *__restrict__ sx, double *__restrict__ sy, double *__restrict__ sz) {
     dither_streams_tile<PAMD_SRGB_TO_REC2020, false, true>(nullptr, 0, spos, R, sx, sy, sz, 0u, px8, ch);
@@ -2324,7 +2316,7 @@ __global__ __launch_bounds__(64) void k_dither_lane_repair(DitherLanes a, const 
     }
 }
 
-struct DitherConfig { int segments = 0, warm = -1, lanes = -1; };    // 0 / -1 = chosen by launch_dither
+// ---- the dither's host side: the arithmetic is dither_host.h's, what follows enqueues ----
 // process-wide knobs, set from any thread while batch workers read them: atomics (a reader takes ONE snapshot per call)
 static std::atomic<int> g_dither_segments{0}, g_dither_warm{-1}, g_dither_lanes{-1};
 static std::atomic<int> g_dither_solo_cap{4096};                     // patolette_amd_debug_dither_solo_cap: solo passes before the lane layout gives up
@@ -2335,17 +2327,42 @@ int dither_solo_cap(int cap) { return g_dither_solo_cap.exchange(cap < 0 ? 4096 
 static std::atomic<int> g_dither_stall_passes{2};                    // passes without progress before one wavefront goes alone (tests: 0 = at once)
 int dither_stall_passes(int n) { return g_dither_stall_passes.exchange(n < 0 ? 2 : n); }
 
-// the sixteen weights of the error queue (riemersma.c: a geometric ramp from 1/16 to 1)
-static DitherWeights dither_weights() {
-    DitherWeights wts;
-    const double m = std::exp(std::log(16.0) / (16.0 - 1));
-    double v = 1;
-    for (int i = 0; i < 16; i++) { wts.w[i] = v / 16.0; v *= m; }
-    return wts;
+bool dither_lane_layout(size_t width, size_t height, int k) { return dither_lane_rule(dither_cfg_snapshot(), width * height, k); }
+// What the frame-batched lane walk needs besides dither_lane_layout on all the pixels: a run of 64 pixels at least in every frame,
+// and one tile row per 8 runs (grid.y)
+bool dither_frames_lane_layout(size_t frames, size_t width, size_t height, int k) {
+    const size_t n = width * height;
+    return dither_lanes_possible(frames, n, k) && dither_lane_layout(frames * n, 1, k);
 }
-// what the lane walk itself can take, whatever the knobs say: a run of 64 pixels in every frame, one tile row per 8 runs (grid.y),
-// the pruned search's palette sizes
-static bool dither_lanes_possible(size_t frames, size_t n, int k) { return frames > 0 && n >= 64 && frames <= (size_t)8 * 65535 && k >= 8 && k <= 256; }
+
+// A run-time value into a compile-time one: each calls the generic lambda `f` with a tag that carries the value in its type.  Every
+// helper names only values its callers' kernels exist for: no instantiation comes into being through a combination nobody launches.
+template <int V> using int_c = std::integral_constant<int, V>;
+template <class T> struct type_c { using type = T; };
+template <class F> static void with_bool(bool b, F &&f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+// the map's element type from its size (the route has checked it: 1, 4 or 8)
+template <class F> static void with_elem(int elem_bytes, F &&f) {
+    if (elem_bytes == 1) f(type_c<unsigned char>{});
+    else if (elem_bytes == 4) f(type_c<unsigned int>{});
+    else f(type_c<unsigned long long>{});
+}
+// the conversion the pixels still need on their way into linear Rec2020
+template <class F> static void with_which(int which, F &&f) {
+    switch (which) {
+        case PAMD_COPY: f(int_c<PAMD_COPY>{}); break;
+        case PAMD_SRGB_TO_REC2020: f(int_c<PAMD_SRGB_TO_REC2020>{}); break;
+        case PAMD_CIELUV_TO_REC2020: f(int_c<PAMD_CIELUV_TO_REC2020>{}); break;
+        case PAMD_ICTCP_TO_REC2020: f(int_c<PAMD_ICTCP_TO_REC2020>{}); break;
+        default: throw HipError("patolette_amd: the dither takes its pixels as linear Rec2020, sRGB, CIELuv or ICtCp");
+    }
+}
+// PER, the palette entries a lane keeps, from k: 1, 2 or 4 -- and with GENERIC (the wavefront layout's kernel) 0, the loop, above 256
+template <bool GENERIC, class F> static void with_per(int k, F &&f) {
+    if (k <= 64) f(int_c<1>{});
+    else if (k <= 128) f(int_c<2>{});
+    else if (!GENERIC || k <= 256) f(int_c<4>{});
+    else if constexpr (GENERIC) f(int_c<0>{});
+}
 
 static int current_device() { int d = -1; (void)hipGetDevice(&d); return d; }
 static std::atomic<bool> g_dither_order_cache{true};
@@ -2362,184 +2379,153 @@ static void dither_order(NNWork &w, size_t width, size_t height, hipStream_t s) 
     w.order_w = width; w.order_h = height; w.order_dev = current_device();
 }
 
-// One lane per run (k_dither_lanes): K in [8, 256], images of 2^16 pixels and more.  h_pal: the palette on the host, planar (k,3).
-// Returns false when the verification stalls (a long flat stretch whose colour is not a palette entry: launch_dither_waves' comment):
-// the caller then takes the wavefront layout, which can walk one run through its successors.
-// mpos: the masked table (mcount opaque pixels, compact numbers in curve order: launch_dither_masked) in place of the cached curve order
-// frames > 1 (launch_dither_frames; no mask): d_img / d_out hold that many width x height frames one after another, each walked along
-// its own curve from the empty queue -- one cut with the same number of runs in every frame, so that run boundaries fall on the
-// frame starts (t(f S / frames) = f width height exactly), one table of width * height ranks, one set of launches
-static bool launch_dither_lanes(const double *d_img, size_t plane_stride, int which, size_t width, size_t height, const double *d_pal, const double *h_pal,
-                                int k, void *d_out, int elem_bytes, NNWork &w, const DitherConfig &cfg, const DitherWeights &wts, hipStream_t s,
-                                const unsigned *mpos, size_t mcount, size_t frames = 1, const unsigned char *src8 = nullptr, int channels = 3) {
-    // src8 (launch_dither_u8; no mask): the pixels as interleaved 8-bit sRGB, `channels` bytes each, in place of d_img / which
-    const size_t nframe = width * height;
-    const size_t npix = mpos ? mcount : frames * nframe;
-    w.lane_tables.valid = false;
+static void dither_counters(NNWork &w, size_t segments) {
+    w.dither_segments = segments; w.dither_repairs = 0; w.dither_rounds = 0; w.dither_through = 0; w.dither_jumps = 0; w.dither_solo = 0;
+}
+
+// ---- one lane per run (k_dither_lanes): K in [8, 256], images of 2^16 pixels and more ----
+// What one lane walk is made of: the kernels' argument and, on the host, the cut and the geometry it was filled from.
+// job.mpos: the masked table (job.opaque pixels, compact numbers in curve order: dither_mask_table) in place of the cached curve order.
+// job.frames > 1 (no mask): the planes / bytes / out hold that many width x height frames one after another, each walked along its own
+// curve from the empty queue -- one cut (dither_lane_cut), one table of width * height ranks, one set of launches.
+// job.bytes (no mask): the pixels as interleaved 8-bit sRGB in place of the planes and `which`.
+struct LaneWalk {
     DitherLanes a{};
-    // runs: eight wavefronts of 64 per CU (two per SIMD), none shorter than 256 pixels unless asked for
-    size_t S = cfg.segments > 0 ? (size_t)cfg.segments : std::min<size_t>((size_t)num_cus() * 8 * 64, npix / 256);
-    S = std::max<size_t>(1, std::min(std::min(S, npix / 64), (size_t)8 * 65535));    // (a tile row per 8 runs: grid.y)
-    if (frames > 1) {                                               // the same limits, per frame (dither_frames_lane_layout: they leave one run at least)
-        const size_t per = cfg.segments > 0 ? ceil_div((size_t)cfg.segments, frames) : std::min<size_t>((size_t)num_cus() * 8 * 64, npix / 256) / frames;
-        a.fruns = (unsigned)std::max<size_t>(1, std::min(std::min(per, nframe / 64), (size_t)8 * 65535 / frames));
-        S = frames * a.fruns;
-    }
-    a.R.N = npix; a.R.S = (unsigned)S; a.R.Lmax = (unsigned)ceil_div(npix, S);
-    // warm-up: 256 pixels.  With a repair pass that costs a tenth of a millisecond (one wavefront per listed run) the 2-6 % of the
-    // boundaries that 256 steps do not settle are cheaper than 256 more steps for every run (8192^2: noise 3.65 -> 3.28 ms,
-    // scene 6.0 -> 5.4, gradients + 2 % noise 5.36 -> 5.27; 384 lies between)
-    a.warm = (unsigned)std::min<size_t>(cfg.warm >= 0 ? (size_t)cfg.warm : 256, npix / S);     // (the warm-up of a run is the end of its predecessor)
-    const size_t nw = ceil_div(S, 64), cells = nw * a.R.Lmax * 64;
-    // the grid of the exact-pruning records: the weighted palette's bounding box, half its extent wider on every side -- error
-    // diffusion pushes queries beyond the palette's hull; what still falls outside takes the full scan
-    std::vector<double> wp(3 * (size_t)k);
-    const double fw[3] = {(double)(float)kRw, (double)(float)kGw, (double)(float)kBw};
-    NNGrid g, gw[2];
-    g.G = npix >= ((size_t)1 << 20) ? 64 : 32;
-    for (int c = 0; c < 3; c++) {
-        double lo = INFINITY, hi = -INFINITY;
-        for (int j = 0; j < k; j++) { const double v = h_pal[(size_t)c * k + j] * fw[c]; wp[(size_t)c * k + j] = v; lo = std::min(lo, v); hi = std::max(hi, v); }
-        double r = hi - lo;
-        if (!(r > 0) || !std::isfinite(r)) r = 0;
-        const double m = 0.5 * r + 1e-3;
-        g.lo[c] = lo - m;
-        const double Rg = r + 2 * m;
-        g.cw[c] = Rg / g.G;
-        g.inv[c] = g.G / Rg;
-        a.hi[c] = g.lo[c] + Rg;
-        // the wider grids: 1.5 extents around the palette's box with the first grid's number of cells, 4 extents with 32 across
-        for (int lv = 0; lv < 2; lv++) {
-            gw[lv].G = lv == 0 ? g.G : 32;
-            const double mo = (lv == 0 ? 1.5 : 4.0) * r + (lv == 0 ? 5e-3 : 1e-2), Ro = r + 2 * mo;
-            gw[lv].lo[c] = lo - mo;
-            gw[lv].cw[c] = Ro / gw[lv].G;
-            gw[lv].inv[c] = gw[lv].G / Ro;
-            a.wide[lv].hi[c] = gw[lv].lo[c] + Ro;
-        }
-    }
-    {
-        // margin of the f32 first pass (the table comment above k_nn_map_mid): 2.5 E, E = 2^-24 (9 max |p - lo|^2 + 5 |hi - lo|^2) (1 + 1e-3)
-        double wmax = 0.0, r2 = 0.0;
-        for (int j = 0; j < k; j++) {
-            double d = 0.0;
-            for (int c = 0; c < 3; c++) { const double t = wp[(size_t)c * k + j] - g.lo[c]; d += t * t; }
-            wmax = std::max(wmax, d);
-        }
-        for (int c = 0; c < 3; c++) { const double t = a.hi[c] - g.lo[c]; r2 += t * t; }
-        const double M = 2.5 * 1.001 * 0x1.0p-24 * (9.0 * wmax + 5.0 * r2);
-        a.amb = (float)M;
-        if ((double)a.amb < M) a.amb = std::nextafter(a.amb, INFINITY);
-        if (!(M < 3.0e38)) a.amb = INFINITY;
-        // outside the grid the query's own |x - lo|^2 stands where |hi - lo|^2 did (evaluated in f32: 1e-6 relative, inside the 1e-3)
-        const double Mp = 2.5 * 1.002 * 0x1.0p-24 * 9.0 * wmax, Mx = 2.5 * 1.002 * 0x1.0p-24 * 5.0;
-        a.amb_p = std::nextafter((float)Mp, INFINITY); a.amb_x = std::nextafter((float)Mx, INFINITY);
-        if (!(Mp < 3.0e38)) a.amb_p = INFINITY;
-    }
-    const int ncell = g.G * g.G * g.G, ncellw[2] = {gw[0].G * gw[0].G * gw[0].G, gw[1].G * gw[1].G * gw[1].G};
+    DitherLaneGeometry geo;
+    size_t npix, S, nw, cells;
+    int ncell, ncellw[2];
+    const unsigned *sp;                  // rank -> pixel number: the masked table or the cached curve order
+    dim3 tiles, tiles8;
+};
+
+// the workspace, the flags cleared, the weighted palette on the device; returns with the stream idle
+static void lanes_reserve(const DitherJob &job, NNWork &w, LaneWalk &L, hipStream_t s) {
+    const int k = job.k;
+    const NNGrid &g = L.geo.g, *gw = L.geo.gw;
+    L.ncell = g.G * g.G * g.G; L.ncellw[0] = gw[0].G * gw[0].G * gw[0].G; L.ncellw[1] = gw[1].G * gw[1].G * gw[1].G;
+    const int ncell = L.ncell, *ncellw = L.ncellw;
     w.dtab.reserve(3 * (size_t)k);
     w.lut.reserve(((size_t)ncell + ncellw[0] + ncellw[1]) * 32);
     w.clist.reserve((size_t)((ncell + ncellw[0] + ncellw[1]) / 64) * (1 + kCoarseMax) * 2);
-    w.dsort.reserve(3 * cells);
-    if (!mpos) {
+    w.dsort.reserve(3 * L.cells);
+    if (!job.mpos) {
+        const size_t nframe = job.width * job.height;
         if (w.dpos.cap < nframe) { w.order_w = 0; w.order_h = 0; }
         w.dpos.reserve(nframe);
     }
-    w.dsmap.reserve(cells + 32 * S + 128);
-    w.dside.reserve(S + 16);
-    w.dflag.reserve(S + 64);
-    HIP_CHECK(hipMemsetAsync(w.dflag.p, 0, S + 64, s));                 // (the check writes entries 1 .. S - 1; 0 and S stay 0)
+    w.dsmap.reserve(L.cells + 32 * L.S + 128);
+    w.dside.reserve(L.S + 16);
+    w.dflag.reserve(L.S + 64);
+    HIP_CHECK(hipMemsetAsync(w.dflag.p, 0, L.S + 64, s));               // (the check writes entries 1 .. S - 1; 0 and S stay 0)
     w.hrep.reserve(2);
-    HIP_CHECK(hipMemcpyAsync(w.dtab.p, wp.data(), wp.size() * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipStreamSynchronize(s));                               // (wp is a local: the copy must have left the host)
-    // the two record grids depend on the palette alone, the gather on the image alone: the grids are built on a side stream
-    // (forked off `s` here, joined before the first launch that reads them), a few hundred single-wavefront blocks under a
-    // bandwidth-bound kernel
-    if (w.side_stream == nullptr || w.side_dev != current_device()) {
-        if (w.ev_fork) { (void)hipEventDestroy(w.ev_fork); w.ev_fork = nullptr; }
-        if (w.ev_join) { (void)hipEventDestroy(w.ev_join); w.ev_join = nullptr; }
-        if (w.ev_join2) { (void)hipEventDestroy(w.ev_join2); w.ev_join2 = nullptr; }
-        if (w.side_stream) { (void)hipStreamDestroy(w.side_stream); w.side_stream = nullptr; }
-        if (w.side_stream2) { (void)hipStreamDestroy(w.side_stream2); w.side_stream2 = nullptr; }
-        HIP_CHECK(hipStreamCreateWithFlags(&w.side_stream, hipStreamNonBlocking));
-        HIP_CHECK(hipStreamCreateWithFlags(&w.side_stream2, hipStreamNonBlocking));
-        HIP_CHECK(hipEventCreateWithFlags(&w.ev_fork, hipEventDisableTiming));
-        HIP_CHECK(hipEventCreateWithFlags(&w.ev_join, hipEventDisableTiming));
-        HIP_CHECK(hipEventCreateWithFlags(&w.ev_join2, hipEventDisableTiming));
-        w.side_dev = current_device();
-    }
-    hipStream_t sb = w.side_stream, sc = w.side_stream2;            // the first grid on one, the two wider ones on the other
+    HIP_CHECK(hipMemcpyAsync(w.dtab.p, L.geo.wp.data(), L.geo.wp.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipStreamSynchronize(s));                               // (the copy has left the host, and `s` is idle where the side streams fork off it)
+}
+
+// the two side streams and their events, made once per device
+static void dither_side_streams(NNWork &w) {
+    if (w.side_stream != nullptr && w.side_dev == current_device()) return;
+    if (w.ev_fork) { (void)hipEventDestroy(w.ev_fork); w.ev_fork = nullptr; }
+    if (w.ev_join) { (void)hipEventDestroy(w.ev_join); w.ev_join = nullptr; }
+    if (w.ev_join2) { (void)hipEventDestroy(w.ev_join2); w.ev_join2 = nullptr; }
+    if (w.side_stream) { (void)hipStreamDestroy(w.side_stream); w.side_stream = nullptr; }
+    if (w.side_stream2) { (void)hipStreamDestroy(w.side_stream2); w.side_stream2 = nullptr; }
+    HIP_CHECK(hipStreamCreateWithFlags(&w.side_stream, hipStreamNonBlocking));
+    HIP_CHECK(hipStreamCreateWithFlags(&w.side_stream2, hipStreamNonBlocking));
+    HIP_CHECK(hipEventCreateWithFlags(&w.ev_fork, hipEventDisableTiming));
+    HIP_CHECK(hipEventCreateWithFlags(&w.ev_join, hipEventDisableTiming));
+    HIP_CHECK(hipEventCreateWithFlags(&w.ev_join2, hipEventDisableTiming));
+    w.side_dev = current_device();
+}
+
+// The three record grids depend on the palette alone, the gather on the image alone: the grids are built on side streams (forked
+// off `s` here, joined by lanes_join before the first launch that reads them), a few hundred single-wavefront blocks under a
+// bandwidth-bound kernel.  The first grid on one stream, the two wider ones on the other.
+static void lanes_build_grids(int k, NNWork &w, LaneWalk &L, hipStream_t s) {
+    DitherLanes &a = L.a;
+    const int ncell = L.ncell, *ncellw = L.ncellw;
+    hipStream_t sb = w.side_stream, sc = w.side_stream2;
     HIP_CHECK(hipEventRecord(w.ev_fork, s));
     HIP_CHECK(hipStreamWaitEvent(sb, w.ev_fork, 0));
     HIP_CHECK(hipStreamWaitEvent(sc, w.ev_fork, 0));
     unsigned char *l1 = w.lut.p, *l2 = w.lut.p + (size_t)ncell * 16;
     {
         KTIME("k_nn_lut_build", sb, 32.0 * ncell);
-        hipLaunchKernelGGL(k_nn_lut_coarse<unsigned char>, ncell / 64, 64, 0, sb, (const double *)w.dtab.p, k, g, w.clist.p, (float4 *)nullptr);
-        hipLaunchKernelGGL(k_nn_lut_build<unsigned char>, ncell / 64, 64, 0, sb, (const double *)w.dtab.p, k, g, l1, l2, (const unsigned char *)w.clist.p, (unsigned int *)nullptr);
+        hipLaunchKernelGGL(k_nn_lut_coarse<unsigned char>, ncell / 64, 64, 0, sb, (const double *)w.dtab.p, k, L.geo.g, w.clist.p, (float4 *)nullptr);
+        hipLaunchKernelGGL(k_nn_lut_build<unsigned char>, ncell / 64, 64, 0, sb, (const double *)w.dtab.p, k, L.geo.g, l1, l2, (const unsigned char *)w.clist.p, (unsigned int *)nullptr);
     }
     {
         unsigned char *tp = w.lut.p + (size_t)ncell * 32, *cp = (unsigned char *)w.clist.p + (size_t)(ncell / 64) * (1 + kCoarseMax);
         for (int lv = 0; lv < 2; lv++) {
+            const NNGrid &gw = L.geo.gw[lv];
             unsigned char *t1 = tp, *t2 = tp + (size_t)ncellw[lv] * 16;
             KTIME("k_nn_lut_build", sc, 32.0 * ncellw[lv]);
-            hipLaunchKernelGGL(k_nn_lut_coarse<unsigned char>, ncellw[lv] / 64, 64, 0, sc, (const double *)w.dtab.p, k, gw[lv], cp, (float4 *)nullptr);
-            hipLaunchKernelGGL(k_nn_lut_build<unsigned char>, ncellw[lv] / 64, 64, 0, sc, (const double *)w.dtab.p, k, gw[lv], t1, t2, (const unsigned char *)cp, (unsigned int *)nullptr);
-            a.wide[lv].g = gw[lv]; a.wide[lv].lut = t1; a.wide[lv].lut2 = t2;
+            hipLaunchKernelGGL(k_nn_lut_coarse<unsigned char>, ncellw[lv] / 64, 64, 0, sc, (const double *)w.dtab.p, k, gw, cp, (float4 *)nullptr);
+            hipLaunchKernelGGL(k_nn_lut_build<unsigned char>, ncellw[lv] / 64, 64, 0, sc, (const double *)w.dtab.p, k, gw, t1, t2, (const unsigned char *)cp, (unsigned int *)nullptr);
+            a.wide[lv].g = gw; a.wide[lv].lut = t1; a.wide[lv].lut2 = t2;
             tp += (size_t)ncellw[lv] * 32;
             cp += (size_t)(ncellw[lv] / 64) * (1 + kCoarseMax);
         }
     }
     HIP_CHECK(hipEventRecord(w.ev_join, sb));
     HIP_CHECK(hipEventRecord(w.ev_join2, sc));
-    double *sx = w.dsort.p, *sy = sx + cells, *sz = sy + cells;
-    const dim3 tiles((unsigned)ceil_div((size_t)a.R.Lmax, 64), (unsigned)nw), tiles8((unsigned)ceil_div((size_t)a.R.Lmax, 256), (unsigned)ceil_div(S, 8));
-    if (!mpos) dither_order(w, width, height, s);
-    const unsigned *sp = mpos ? mpos : (const unsigned *)w.dpos.p;
-    if (src8) {
-        KTIME("k_dither_gather_u8", s, (28.0 + channels) * npix);
-        if (a.fruns) hipLaunchKernelGGL(k_dither_streams_frames_u8, tiles8, 256, 0, s, src8, channels, sp, a.R, sx, sy, sz, a.fruns);
-        else hipLaunchKernelGGL(k_dither_streams_u8, tiles8, 256, 0, s, src8, channels, sp, a.R, sx, sy, sz);
+    a.lut = l1; a.lut2 = l2; a.g = L.geo.g;
+}
+
+// the pixels into the transposed layout, converted on the way
+static void lanes_gather(const DitherJob &job, NNWork &w, LaneWalk &L, hipStream_t s) {
+    DitherLanes &a = L.a;
+    double *sx = w.dsort.p, *sy = sx + L.cells, *sz = sy + L.cells;
+    if (!job.mpos) dither_order(w, job.width, job.height, s);
+    const unsigned *sp = L.sp = job.mpos ? job.mpos : (const unsigned *)w.dpos.p;
+    if (job.bytes) {
+        KTIME("k_dither_gather_u8", s, (28.0 + job.channels) * L.npix);
+        if (a.fruns) hipLaunchKernelGGL(k_dither_streams_frames_u8, L.tiles8, 256, 0, s, job.bytes, job.channels, sp, a.R, sx, sy, sz, a.fruns);
+        else hipLaunchKernelGGL(k_dither_streams_u8, L.tiles8, 256, 0, s, job.bytes, job.channels, sp, a.R, sx, sy, sz);
     } else {
-        KTIME("k_dither_gather", s, 52.0 * npix);
-#define PAMD_DITHER_STREAMS(WHICH)                                                                                              \
-        do {                                                                                                                   \
-            if (a.fruns) hipLaunchKernelGGL(k_dither_streams_frames<WHICH>, tiles8, 256, 0, s, d_img, plane_stride, sp, a.R, sx, sy, sz, a.fruns); \
-            else hipLaunchKernelGGL(k_dither_streams<WHICH>, tiles8, 256, 0, s, d_img, plane_stride, sp, a.R, sx, sy, sz); \
-        } while (0)
-        switch (which) {
-            case PAMD_COPY: PAMD_DITHER_STREAMS(PAMD_COPY); break;
-            case PAMD_SRGB_TO_REC2020: PAMD_DITHER_STREAMS(PAMD_SRGB_TO_REC2020); break;
-            case PAMD_CIELUV_TO_REC2020: PAMD_DITHER_STREAMS(PAMD_CIELUV_TO_REC2020); break;
-            case PAMD_ICTCP_TO_REC2020: PAMD_DITHER_STREAMS(PAMD_ICTCP_TO_REC2020); break;
-            default: throw HipError("patolette_amd: the dither takes its pixels as linear Rec2020, sRGB, CIELuv or ICtCp");
-        }
-#undef PAMD_DITHER_STREAMS
+        KTIME("k_dither_gather", s, 52.0 * L.npix);
+        with_which(job.which, [&](auto W) {
+            constexpr int WHICH = decltype(W)::value;
+            if (a.fruns) hipLaunchKernelGGL(k_dither_streams_frames<WHICH>, L.tiles8, 256, 0, s, job.planes, job.plane_stride, sp, a.R, sx, sy, sz, a.fruns);
+            else hipLaunchKernelGGL(k_dither_streams<WHICH>, L.tiles8, 256, 0, s, job.planes, job.plane_stride, sp, a.R, sx, sy, sz);
+        });
     }
+    a.sx = sx; a.sy = sy; a.sz = sz;
+}
+
+// every run from its speculative warm-up, once the record grids are there
+static void lanes_walk(const DitherJob &job, NNWork &w, LaneWalk &L, const DitherWeights &wts, hipStream_t s) {
+    DitherLanes &a = L.a;
     HIP_CHECK(hipStreamWaitEvent(s, w.ev_join, 0));
     HIP_CHECK(hipStreamWaitEvent(s, w.ev_join2, 0));
-    a.sx = sx; a.sy = sy; a.sz = sz;
-    a.smap = w.dsmap.p; a.side = reinterpret_cast<unsigned short *>(w.dsmap.p + ((cells + 63) & ~(size_t)63));
+    a.smap = w.dsmap.p; a.side = reinterpret_cast<unsigned short *>(w.dsmap.p + ((L.cells + 63) & ~(size_t)63));
     a.list = w.dside.p + 2;                                          // [0] jumps taken, [1] failing boundaries, then their list
     a.flag = w.dflag.p;
-    a.lut = l1; a.lut2 = l2; a.g = g;
-    const size_t lds = (size_t)6 * k * sizeof(double) + (size_t)k * sizeof(float4);
+    const size_t lds = (size_t)6 * job.k * sizeof(double) + (size_t)job.k * sizeof(float4);
     {
-        KTIME("k_dither", s, 25.0 * npix);
-        if (a.fruns) hipLaunchKernelGGL(k_dither_lanes<true>, (unsigned)ceil_div(S, 256), 256, lds, s, a, d_pal, k, wts);
-        else hipLaunchKernelGGL(k_dither_lanes<false>, (unsigned)ceil_div(S, 256), 256, lds, s, a, d_pal, k, wts);
+        KTIME("k_dither", s, 25.0 * L.npix);
+        with_bool(a.fruns != 0, [&](auto FR) {
+            hipLaunchKernelGGL(k_dither_lanes<decltype(FR)::value>, (unsigned)ceil_div(L.S, 256), 256, lds, s, a, job.d_pal, job.k, wts);
+        });
     }
     HIP_CHECK(hipGetLastError());
-    w.dither_segments = S; w.dither_repairs = 0; w.dither_rounds = 0; w.dither_through = 0; w.dither_jumps = 0; w.dither_solo = 0;
-    unsigned prev_nf = 0xFFFFFFFFu;
-    int stalled = 0;
+}
+
+// Check every boundary, walk the listed runs again, until a pass lists none.  false: the verification stalls (a long flat stretch
+// whose colour is not a palette entry: launch_dither_waves' comment) beyond the solo cap.
+static bool lanes_verify(const DitherJob &job, NNWork &w, LaneWalk &L, const DitherWeights &wts, hipStream_t s) {
+    DitherLanes &a = L.a;
+    const size_t S = L.S;
+    const int k = job.k;
+    DitherStall stall;
     HIP_CHECK(hipMemsetAsync(w.dside.p, 0, sizeof(unsigned), s));
     for (size_t round = 0; S > 1; round++) {
         HIP_CHECK(hipMemsetAsync(w.dside.p + 1, 0, sizeof(unsigned), s));
         {
             KTIME("k_dither_fix", s, 0.0);
-            if (a.fruns) hipLaunchKernelGGL(k_dither_lane_check<true>, (unsigned)ceil_div(S - 1, 256), 256, 0, s, a);
-            else hipLaunchKernelGGL(k_dither_lane_check<false>, (unsigned)ceil_div(S - 1, 256), 256, 0, s, a);
+            with_bool(a.fruns != 0, [&](auto FR) {
+                hipLaunchKernelGGL(k_dither_lane_check<decltype(FR)::value>, (unsigned)ceil_div(S - 1, 256), 256, 0, s, a);
+            });
         }
         HIP_CHECK(hipMemcpyAsync(w.hrep.p, w.dside.p, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
@@ -2549,54 +2535,82 @@ static bool launch_dither_lanes(const double *d_img, size_t plane_stride, int wh
         static const bool trace = getenv("PAMD_DITHER_TRACE") != nullptr;      // one line per verification pass on stderr
         if (trace) fprintf(stderr, "patolette_amd: dither, lane layout: pass %zu, %u of %zu boundaries fail\n", round + 1, nf, S - 1);
         if (nf == 0) break;
-        stalled = (prev_nf != 0xFFFFFFFFu && nf + std::max(1u, prev_nf / 8) >= prev_nf) ? stalled + 1 : 0;
-        prev_nf = nf;
-        const bool solo = stalled >= g_dither_stall_passes.load(std::memory_order_relaxed);   // no progress twice in a row: one wavefront alone, then the passes resume
+        const bool solo = stall.step(nf) >= g_dither_stall_passes.load(std::memory_order_relaxed);   // no progress twice in a row: one wavefront alone, then the passes resume
         if (solo) {
             w.dither_solo++;
             if (++w.dither_through > (size_t)g_dither_solo_cap.load(std::memory_order_relaxed)) return false;   // (never seen at 4096; the wavefront layout takes the image then)
-            stalled = 0; prev_nf = 0xFFFFFFFFu;
+            stall.reset();
         }
         a.solo = solo ? 1 : 0;
         w.dither_repairs += solo ? 1 : nf;
         KTIME("k_dither_fix", s, 0.0);
         const size_t lds_r = (size_t)6 * k * sizeof(double) + 3 * 128 * sizeof(double) + 128 * sizeof(unsigned) + 2048;   // + the history of choices
         const unsigned nblk = solo ? 1u : nf;
-#define PAMD_DITHER_REPAIR(PER)                                                                                                 \
-        do {                                                                                                                   \
-            if (a.fruns) hipLaunchKernelGGL((k_dither_lane_repair<PER, true>), nblk, 64, lds_r, s, a, d_pal, k, wts);          \
-            else hipLaunchKernelGGL((k_dither_lane_repair<PER, false>), nblk, 64, lds_r, s, a, d_pal, k, wts);                 \
-        } while (0)
-        if (k <= 64) PAMD_DITHER_REPAIR(1);
-        else if (k <= 128) PAMD_DITHER_REPAIR(2);
-        else PAMD_DITHER_REPAIR(4);
-#undef PAMD_DITHER_REPAIR
+        with_per<false>(k, [&](auto PER) {
+            with_bool(a.fruns != 0, [&](auto FR) {
+                hipLaunchKernelGGL((k_dither_lane_repair<decltype(PER)::value, decltype(FR)::value>), nblk, 64, lds_r, s, a, job.d_pal, k, wts);
+            });
+        });
         HIP_CHECK(hipGetLastError());
     }
+    return true;
+}
+
+// the choices out of the transposed layout into the caller's map
+static void lanes_unpermute(const DitherJob &job, LaneWalk &L, hipStream_t s) {
+    const DitherLanes &a = L.a;
     {
-        KTIME("k_dither_unpermute", s, (5.0 + elem_bytes) * npix);
-#define PAMD_DITHER_UNPERMUTE(T)                                                                                                \
-        do {                                                                                                                   \
-            if (a.fruns) hipLaunchKernelGGL(k_dither_unpermute_frames<T>, tiles, 256, 0, s, (const unsigned char *)a.smap, sp, a.R, (T *)d_out, a.fruns); \
-            else hipLaunchKernelGGL(k_dither_unpermute<T>, tiles, 256, 0, s, (const unsigned char *)a.smap, sp, a.R, (T *)d_out); \
-        } while (0)
-        if (elem_bytes == 1) PAMD_DITHER_UNPERMUTE(unsigned char);
-        else if (elem_bytes == 4) PAMD_DITHER_UNPERMUTE(unsigned int);
-        else PAMD_DITHER_UNPERMUTE(unsigned long long);
-#undef PAMD_DITHER_UNPERMUTE
+        KTIME("k_dither_unpermute", s, (5.0 + job.elem_bytes) * L.npix);
+        with_elem(job.elem_bytes, [&](auto E) {
+            using T = typename decltype(E)::type;
+            if (a.fruns) hipLaunchKernelGGL(k_dither_unpermute_frames<T>, L.tiles, 256, 0, s, (const unsigned char *)a.smap, L.sp, a.R, (T *)job.out, a.fruns);
+            else hipLaunchKernelGGL(k_dither_unpermute<T>, L.tiles, 256, 0, s, (const unsigned char *)a.smap, L.sp, a.R, (T *)job.out);
+        });
     }
     HIP_CHECK(hipGetLastError());
-    {
-        NNWork::LaneTables &t = w.lane_tables;                          // (tests: dither_lane_tables)
-        for (int lv = 0; lv < 3; lv++) {
-            const NNGrid &gg = lv == 0 ? a.g : a.wide[lv - 1].g;
-            const double *hh = lv == 0 ? a.hi : a.wide[lv - 1].hi;
-            for (int c = 0; c < 3; c++) { t.lo[lv][c] = gg.lo[c]; t.hi[lv][c] = hh[c]; t.inv[lv][c] = gg.inv[c]; }
-            t.G[lv] = gg.G;
-        }
-        t.amb = a.amb; t.amb_p = a.amb_p; t.amb_x = a.amb_x;
-        t.valid = true;
+}
+
+// what the walk gave its kernels, kept for the tests (dither_lane_tables)
+static void lanes_remember(NNWork &w, const DitherLanes &a) {
+    NNWork::LaneTables &t = w.lane_tables;
+    for (int lv = 0; lv < 3; lv++) {
+        const NNGrid &gg = lv == 0 ? a.g : a.wide[lv - 1].g;
+        const double *hh = lv == 0 ? a.hi : a.wide[lv - 1].hi;
+        for (int c = 0; c < 3; c++) { t.lo[lv][c] = gg.lo[c]; t.hi[lv][c] = hh[c]; t.inv[lv][c] = gg.inv[c]; }
+        t.G[lv] = gg.G;
     }
+    t.amb = a.amb; t.amb_p = a.amb_p; t.amb_x = a.amb_x;
+    t.valid = true;
+}
+
+// job.h_pal: the palette on the host, planar (k,3).  Returns false when the verification stalls for good: the caller then takes the
+// wavefront layout, which can walk one run through its successors.
+static bool launch_dither_lanes(const DitherJob &job, NNWork &w, const DitherConfig &cfg, hipStream_t s) {
+    const size_t nframe = job.width * job.height;
+    const DitherWeights wts = dither_weights();
+    w.lane_tables.valid = false;
+    LaneWalk L;
+    DitherLanes &a = L.a;
+    L.npix = job.mpos ? job.opaque : job.frames * nframe;
+    const DitherLaneCut cut = dither_lane_cut(cfg.segments, cfg.warm, num_cus(), L.npix, nframe, job.frames);
+    L.S = cut.S;
+    a.R.N = L.npix; a.R.S = (unsigned)cut.S; a.R.Lmax = cut.Lmax; a.fruns = cut.fruns; a.warm = cut.warm;
+    L.nw = ceil_div(L.S, 64); L.cells = L.nw * a.R.Lmax * 64;
+    L.tiles = dim3((unsigned)ceil_div((size_t)a.R.Lmax, 64), (unsigned)L.nw);
+    L.tiles8 = dim3((unsigned)ceil_div((size_t)a.R.Lmax, 256), (unsigned)ceil_div(L.S, 8));
+    L.geo = dither_lane_geometry(job.h_pal, job.k, L.npix);
+    for (int c = 0; c < 3; c++) { a.hi[c] = L.geo.hi[c]; a.wide[0].hi[c] = L.geo.whi[0][c]; a.wide[1].hi[c] = L.geo.whi[1][c]; }
+    a.amb = L.geo.amb; a.amb_p = L.geo.amb_p; a.amb_x = L.geo.amb_x;
+
+    lanes_reserve(job, w, L, s);
+    dither_side_streams(w);
+    lanes_build_grids(job.k, w, L, s);
+    lanes_gather(job, w, L, s);
+    lanes_walk(job, w, L, wts, s);
+    dither_counters(w, L.S);
+    if (!lanes_verify(job, w, L, wts, s)) return false;
+    lanes_unpermute(job, L, s);
+    lanes_remember(w, a);
     return true;
 }
 
@@ -2617,6 +2631,106 @@ int dither_lane_tables(NNWork &w, double *geom30, float *amb3, unsigned char *ta
     return 0;
 }
 
+// ---- one wavefront per run (k_dither): any K, any size; pixels in linear Rec2020, image order ----
+// Frame f of the job (its planes and its part of the map; a masked job has one frame and its table).
+static void launch_dither_waves(const DitherJob &job, size_t f, NNWork &w, const DitherConfig &cfg, hipStream_t s) {
+    const size_t width = job.width, height = job.height, nframe = width * height;
+    const int k = job.k, elem_bytes = job.elem_bytes;
+    const double *d_img = job.planes + f * nframe;
+    void *d_out = (unsigned char *)job.out + f * nframe * (size_t)elem_bytes;
+    const unsigned *mpos = job.mpos;
+    const size_t mcount = job.opaque;
+    size_t lds = ((size_t)6 * k + 3 * 128) * sizeof(double) + 128 * sizeof(unsigned int);      // palette (raw + weighted) + the ring of pending pixels
+    w.lane_tables.valid = false;
+    double *gtab = nullptr;
+    if (lds > 150 * 1024) {                                      // K > 3200: the tables in global memory (workspace kept with the engine)
+        w.dtab.reserve((size_t)6 * k);
+        gtab = w.dtab.p;
+        lds = (size_t)3 * 128 * sizeof(double) + 128 * sizeof(unsigned int);
+    }
+    const DitherWeights wts = dither_weights();
+    const size_t npix = mpos ? mcount : nframe;
+    const DitherWaveCut cut = dither_wave_cut(cfg, num_cus(), npix, width, height);
+    const size_t S = cut.S;
+    DitherSeg sg{};
+    sg.warm = cut.warm;
+    sg.S = (unsigned)S;
+    dither_counters(w, S);
+    if (S > 1) {
+        w.dside.reserve(16 * std::max(S, (size_t)num_cus() * 8) + 16);   // the default cap at once: no regrowth behind queued work
+        w.hrep.reserve(2);
+        sg.side = w.dside.p;
+        sg.repairs = w.dside.p + 16 * S;
+        sg.b0 = 1; sg.through = 0;
+    }
+    auto reset_counters = [&]() {                                // [0] = 0 repairs, [1] = no run yet (atomicMin)
+        w.hrep.p[0] = 0u; w.hrep.p[1] = 0xFFFFFFFFu;
+        HIP_CHECK(hipMemcpyAsync(sg.repairs, w.hrep.p, 2 * sizeof(unsigned), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipStreamSynchronize(s));                      // (the pinned words are read back into below)
+    };
+    if (S > 1) reset_counters();
+    // mode 0: every run from its warm-up; 1: the boundary checks and repairs
+    auto launch = [&](int mode, unsigned blocks) {
+        with_elem(elem_bytes, [&](auto E) {
+            using OutT = typename decltype(E)::type;
+            auto go = [&](auto PER, auto GT) {
+                with_bool(mode != 0, [&](auto M) {
+                    with_bool(mpos != nullptr, [&](auto MASKED) {
+                        constexpr int MODE = decltype(M)::value ? 1 : 0;
+                        HIP_CHECK(hipFuncSetAttribute((const void *)(k_dither<OutT, decltype(PER)::value, decltype(GT)::value, MODE, decltype(MASKED)::value>),
+                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                        hipLaunchKernelGGL((k_dither<OutT, decltype(PER)::value, decltype(GT)::value, MODE, decltype(MASKED)::value>), blocks, 64, lds, s, d_img,
+                                           job.plane_stride, (unsigned)width, (unsigned)height, job.d_pal, k, (OutT *)d_out, wts, gtab, sg, mpos,
+                                           (unsigned long long)mcount);
+                    });
+                });
+            };
+            if (gtab) go(int_c<0>{}, std::true_type{});
+            else with_per<true>(k, [&](auto PER) { go(PER, std::false_type{}); });
+        });
+        HIP_CHECK(hipGetLastError());
+    };
+    {
+        KTIME("k_dither", s, (24.0 + elem_bytes + (mpos ? 4.0 : 0.0)) * npix);
+        launch(0, (unsigned)S);
+    }
+    if (S == 1 || std::max(width, height) <= 1) return;
+    // verify every boundary, walk the runs whose starting state was not the true one again, until a pass finds nothing to do
+    // Where the image is FLAT over more than a warm-up and the flat colour is not a palette entry, the true chain is periodic (period
+    // 4 .. 14 measured) and a zero-queue chain settles into the same cycle at another phase: it never meets the true one, and a
+    // verification pass then fixes one run -- the lowest failing one, whose predecessor is final -- while its neighbours are rebuilt
+    // from tails that are about to change.  Two passes in a row that fix next to nothing are taken as that: the lowest failing run
+    // is walked THROUGH the runs behind it (one wavefront, the true chain) until it meets what is there -- the end of the flat
+    // stretch --, and the passes resume (runs it overwrote pass their next check in sixteen steps).
+    DitherStall stall;
+    for (size_t round = 0;; round++) {
+        if (round > 2 * S + 8) throw HipError("patolette_amd: the dither's boundary repairs did not settle");
+        {
+            KTIME("k_dither_fix", s, 0.0);
+            launch(1, (unsigned)S - 1);
+        }
+        HIP_CHECK(hipMemcpyAsync(w.hrep.p, sg.repairs, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        const unsigned r = w.hrep.p[0], lowest = w.hrep.p[1];
+        w.dither_rounds = round + 1;
+        if (r == 0) break;
+        w.dither_repairs += r;
+        const int stalled = stall.step(r);
+        reset_counters();
+        if (stalled >= 2 && (size_t)lowest + 1 < S) {
+            // the pass above has rebuilt run `lowest` from its final predecessor: it is final now, and the walk starts behind it
+            // (the record of that run is voided so that the kernel does not take its boundary for verified)
+            HIP_CHECK(hipMemsetAsync(sg.side + 16 * ((size_t)lowest + 1), 0xFF, 16 * sizeof(unsigned), s));
+            sg.b0 = lowest + 1; sg.through = 1;
+            { KTIME("k_dither_fix", s, 0.0); launch(1, 1u); }
+            sg.b0 = 1; sg.through = 0;
+            reset_counters();
+            w.dither_through++;
+            stall.reset();
+        }
+    }
+}
+
 // the pixels into linear Rec2020 in image order (what the wavefront layout reads), for the fall-back out of the lane layout
 template <int WHICH>
 __global__ __launch_bounds__(256) void k_dither_convert(const double *__restrict__ img, size_t plane_stride, size_t n, double *__restrict__ dst) {
@@ -2628,162 +2742,6 @@ __global__ __launch_bounds__(256) void k_dither_convert(const double *__restrict
         dev_convert<WHICH>(c);
         dst[i] = c[0]; dst[n + i] = c[1]; dst[2 * n + i] = c[2];
     }
-}
-
-template <typename OutT>
-static void launch_dither_t(int mode, unsigned blocks, const double *d_img, size_t plane_stride, size_t width, size_t height, const double *d_pal,
-                            int k, OutT *out, const DitherWeights &wts, size_t lds, double *gtab, const DitherSeg &sg, hipStream_t s,
-                            const unsigned *mpos, size_t mcount) {
-#define PAMD_DITHER2(PER, GT, MODE, MASKED)                                                                                    \
-    do {                                                                                                                       \
-        HIP_CHECK(hipFuncSetAttribute((const void *)(k_dither<OutT, PER, GT, MODE, MASKED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL((k_dither<OutT, PER, GT, MODE, MASKED>), blocks, 64, lds, s, d_img, plane_stride, (unsigned)width, (unsigned)height, d_pal, k, \
-                           out, wts, gtab, sg, mpos, (unsigned long long)mcount);                                             \
-    } while (0)
-#define PAMD_DITHER1(PER, GT, MODE)                                                                                            \
-    do { if (mpos) PAMD_DITHER2(PER, GT, MODE, true); else PAMD_DITHER2(PER, GT, MODE, false); } while (0)
-#define PAMD_DITHER(PER, GT)                                                                                                   \
-    do { if (mode == 0) PAMD_DITHER1(PER, GT, 0); else PAMD_DITHER1(PER, GT, 1); } while (0)
-    if (gtab) PAMD_DITHER(0, true);
-    else if (k <= 64) PAMD_DITHER(1, false);
-    else if (k <= 128) PAMD_DITHER(2, false);
-    else if (k <= 256) PAMD_DITHER(4, false);
-    else PAMD_DITHER(0, false);
-#undef PAMD_DITHER
-#undef PAMD_DITHER1
-#undef PAMD_DITHER2
-}
-
-// One lane per run where the pruned search applies (8 <= K <= 256) and the image is large: the lane layout needs ~10^5 runs of a few
-// hundred pixels to fill the GPU and pays a gather, an un-permute and a repair round of fixed cost -- 2048^2: 2.3 ms against 1.6 ms
-// for one wavefront per run, 4096^2: 2.7 ms, 8192^2: 4.8 against 15.6 ms.  dither_layout(1) asks for it from 65 536 pixels on.
-bool dither_lane_layout(size_t width, size_t height, int k) {
-    const DitherConfig cfg = dither_cfg_snapshot();
-    const size_t npix = width * height;
-    if (!(k >= 8 && k <= 256) || cfg.segments == 1 || cfg.lanes == 0) return false;
-    return cfg.lanes > 0 ? npix >= 65536 : npix >= ((size_t)1 << 23);
-}
-
-static void launch_dither_waves(const double *d_img, size_t plane_stride, size_t width, size_t height, const double *d_pal, int k,
-                                void *d_out, int elem_bytes, NNWork &w, hipStream_t s, const unsigned *mpos = nullptr, size_t mcount = 0);
-
-static void launch_dither_any(const double *d_img, size_t plane_stride, int which, size_t width, size_t height, const double *d_pal, const double *h_pal,
-                              int k, void *d_out, int elem_bytes, NNWork &w, hipStream_t s, int layout, const unsigned *mpos, size_t mcount) {
-    if (width * height >> 32) throw HipError("patolette_amd: the dither kernel numbers pixels with 32 bits");
-    if (elem_bytes != 1 && elem_bytes != 4 && elem_bytes != 8) throw HipError("patolette_amd: map element size must be 1, 4 or 8");
-    const size_t npix = mpos ? mcount : width * height;
-    {
-        const DitherConfig cfg = dither_cfg_snapshot();
-        // layout: what the caller decided when it chose the pixels' form (the knobs may change between its look and this one)
-        if (layout >= 0 ? layout != 0 : dither_lane_layout(npix, 1, k)) {
-            const DitherWeights wts = dither_weights();
-            std::vector<double> hp;
-            if (!h_pal) {
-                hp.resize(3 * (size_t)k);
-                HIP_CHECK(hipMemcpyAsync(hp.data(), d_pal, hp.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-                HIP_CHECK(hipStreamSynchronize(s));
-                h_pal = hp.data();
-            }
-            if (launch_dither_lanes(d_img, plane_stride, which, width, height, d_pal, h_pal, k, d_out, elem_bytes, w, cfg, wts, s, mpos, mcount)) return;
-            // stalled: the wavefront layout from scratch (it needs the pixels as linear Rec2020 in image order)
-            const size_t n = npix;
-            if (which != PAMD_COPY) {
-                w.dsort.reserve(3 * n);
-                const int gb = stream_blocks(n, 16);
-                switch (which) {
-                    case PAMD_SRGB_TO_REC2020: hipLaunchKernelGGL(k_dither_convert<PAMD_SRGB_TO_REC2020>, gb, 256, 0, s, d_img, plane_stride, n, w.dsort.p); break;
-                    case PAMD_CIELUV_TO_REC2020: hipLaunchKernelGGL(k_dither_convert<PAMD_CIELUV_TO_REC2020>, gb, 256, 0, s, d_img, plane_stride, n, w.dsort.p); break;
-                    default: hipLaunchKernelGGL(k_dither_convert<PAMD_ICTCP_TO_REC2020>, gb, 256, 0, s, d_img, plane_stride, n, w.dsort.p); break;
-                }
-                HIP_CHECK(hipGetLastError());
-                d_img = w.dsort.p; plane_stride = n; which = PAMD_COPY;
-            }
-            const size_t lane_passes = w.dither_rounds;
-            launch_dither_waves(d_img, plane_stride, width, height, d_pal, k, d_out, elem_bytes, w, s, mpos, mcount);
-            w.dither_rounds += lane_passes;
-            return;
-        }
-        if (which != PAMD_COPY) throw HipError("patolette_amd: the wavefront-per-run dither takes linear Rec2020 pixels");
-    }
-    launch_dither_waves(d_img, plane_stride, width, height, d_pal, k, d_out, elem_bytes, w, s, mpos, mcount);
-}
-
-void launch_dither(const double *d_img, size_t plane_stride, int which, size_t width, size_t height, const double *d_pal, const double *h_pal, int k,
-                   void *d_out, int elem_bytes, NNWork &w, hipStream_t s, int layout) {
-    launch_dither_any(d_img, plane_stride, which, width, height, d_pal, h_pal, k, d_out, elem_bytes, w, s, layout, nullptr, 0);
-}
-
-// The remap entry's dither from 8-bit sRGB pixels (frames images of width x height, channels bytes per pixel; palette in linear
-// Rec2020): the lane layout with the conversion on the gather, no f64 image.  The caller has checked that the lane layout applies
-// (dither_lane_layout / dither_frames_lane_layout).  false: the verification stalled for good (launch_dither_lanes) and nothing
-// usable was written -- the caller converts the image and takes launch_dither / launch_dither_frames.
-bool launch_dither_u8(const unsigned char *d_px, int channels, size_t frames, size_t width, size_t height, const double *d_pal, const double *h_pal,
-                      int k, void *d_out, int elem_bytes, NNWork &w, hipStream_t s) {
-    const size_t n = width * height, N = frames * n;
-    if (frames == 0 || n == 0 || N / n != frames || N > kDitherFramesMaxPixels) throw HipError("patolette_amd: the dither takes up to 2^31 pixels in all");
-    if (elem_bytes != 1 && elem_bytes != 4 && elem_bytes != 8) throw HipError("patolette_amd: map element size must be 1, 4 or 8");
-    if (channels != 3 && channels != 4) throw HipError("patolette_amd: 8-bit pixels have 3 or 4 channels");
-    if (!dither_lanes_possible(frames, n, k)) throw HipError("patolette_amd: this image cannot take the lane layout");
-    const DitherConfig cfg = dither_cfg_snapshot();
-    const DitherWeights wts = dither_weights();
-    return launch_dither_lanes(nullptr, 0, PAMD_SRGB_TO_REC2020, width, height, d_pal, h_pal, k, d_out, elem_bytes, w, cfg, wts, s, nullptr, 0, frames, d_px, channels);
-}
-
-// ---- frames of one size, one palette (patolette_amd_frames_u8) ----
-// What the frame-batched lane walk needs besides dither_lane_layout on all the pixels: a run of 64 pixels at least in every frame,
-// and one tile row per 8 runs (grid.y)
-bool dither_frames_lane_layout(size_t frames, size_t width, size_t height, int k) {
-    const size_t n = width * height;
-    return dither_lanes_possible(frames, n, k) && dither_lane_layout(frames * n, 1, k);
-}
-
-// Every frame dithered along its own curve from the empty queue.  The lane layout walks all frames side by side (launch_dither_lanes
-// with frames > 1).  Frame after frame through the single-image wavefront layout: whatever the lane layout does not take (a palette
-// outside 8 .. 256 rows, too few pixels, a knob that asks for wavefronts), and a batched walk whose verification stalled for good.
-void launch_dither_frames(const double *d_img, size_t plane_stride, int which, size_t frames, size_t width, size_t height, const double *d_pal,
-                          const double *h_pal, int k, void *d_out, int elem_bytes, NNWork &w, hipStream_t s, int layout) {
-    const size_t n = width * height, N = frames * n;
-    if (frames == 0 || n == 0 || N / n != frames || N > kDitherFramesMaxPixels) throw HipError("patolette_amd: the frame-batched dither takes up to 2^31 pixels in all");
-    if (elem_bytes != 1 && elem_bytes != 4 && elem_bytes != 8) throw HipError("patolette_amd: map element size must be 1, 4 or 8");
-    if (frames == 1) { launch_dither(d_img, plane_stride, which, width, height, d_pal, h_pal, k, d_out, elem_bytes, w, s, layout); return; }
-    size_t lane_passes = 0;
-    if (layout >= 0 ? layout != 0 : dither_frames_lane_layout(frames, width, height, k)) {
-        // (layout: what the caller decided when it chose the pixels' form; the knobs may have changed since, the hard limits have not)
-        if (!dither_lanes_possible(frames, n, k)) throw HipError("patolette_amd: these frames cannot take the lane layout");
-        const DitherConfig cfg = dither_cfg_snapshot();
-        const DitherWeights wts = dither_weights();
-        std::vector<double> hp;
-        if (!h_pal) {
-            hp.resize(3 * (size_t)k);
-            HIP_CHECK(hipMemcpyAsync(hp.data(), d_pal, hp.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-            HIP_CHECK(hipStreamSynchronize(s));
-            h_pal = hp.data();
-        }
-        if (launch_dither_lanes(d_img, plane_stride, which, width, height, d_pal, h_pal, k, d_out, elem_bytes, w, cfg, wts, s, nullptr, 0, frames)) return;
-        // stalled: the wavefront layout from scratch, frame by frame (it needs the pixels as linear Rec2020 in image order; w.dsort
-        // holds more than 3 N already)
-        if (which != PAMD_COPY) {
-            w.dsort.reserve(3 * N);
-            const int gb = stream_blocks(N, 16);
-            switch (which) {
-                case PAMD_SRGB_TO_REC2020: hipLaunchKernelGGL(k_dither_convert<PAMD_SRGB_TO_REC2020>, gb, 256, 0, s, d_img, plane_stride, N, w.dsort.p); break;
-                case PAMD_CIELUV_TO_REC2020: hipLaunchKernelGGL(k_dither_convert<PAMD_CIELUV_TO_REC2020>, gb, 256, 0, s, d_img, plane_stride, N, w.dsort.p); break;
-                default: hipLaunchKernelGGL(k_dither_convert<PAMD_ICTCP_TO_REC2020>, gb, 256, 0, s, d_img, plane_stride, N, w.dsort.p); break;
-            }
-            HIP_CHECK(hipGetLastError());
-            d_img = w.dsort.p; plane_stride = N; which = PAMD_COPY;
-        }
-        lane_passes = w.dither_rounds;
-    }
-    if (which != PAMD_COPY) throw HipError("patolette_amd: the wavefront-per-run dither takes linear Rec2020 pixels");
-    size_t segments = 0, repairs = 0, rounds = lane_passes, through = 0, jumps = 0, solo = 0;
-    for (size_t f = 0; f < frames; f++) {
-        launch_dither_waves(d_img + f * n, plane_stride, width, height, d_pal, k, (unsigned char *)d_out + f * n * (size_t)elem_bytes, elem_bytes, w, s);
-        segments += w.dither_segments; repairs += w.dither_repairs; rounds += w.dither_rounds; through += w.dither_through;
-        jumps += w.dither_jumps; solo += w.dither_solo;
-    }
-    w.dither_segments = segments; w.dither_repairs = repairs; w.dither_rounds = rounds; w.dither_through = through;
-    w.dither_jumps = jumps; w.dither_solo = solo;
 }
 
 // The masked table: which curve ranks hold an opaque pixel (cpos[pixel] >= 0), in curve order, as compact pixel numbers -- one
@@ -2807,106 +2765,81 @@ void dither_mask_reserve(NNWork &w, size_t npix) {
     w.dmcnt.reserve(compact_tiles(npix) + 1);
 }
 
-void launch_dither_masked(const double *d_img, size_t plane_stride, int which, size_t width, size_t height, const int *d_cpos, size_t m,
-                          const double *d_pal, const double *h_pal, int k, void *d_out, int elem_bytes, NNWork &w, hipStream_t s, int layout) {
-    const size_t npix = width * height;
-    if (npix >> 32) throw HipError("patolette_amd: the dither kernel numbers pixels with 32 bits");
-    if (m == 0 || m > npix) throw HipError("patolette_amd: masked dither with no opaque pixel");
+// the route's step for a job with cpos: the table into w.dmpos, and into the job
+static void dither_mask_table(DitherJob &job, NNWork &w, hipStream_t s) {
+    const size_t npix = job.width * job.height, m = job.opaque;
     dither_mask_reserve(w, npix);
-    dither_order(w, width, height, s);
-    const MaskTableOp op{(const unsigned *)w.dpos.p, d_cpos, w.dmpos.p};
+    dither_order(w, job.width, job.height, s);
+    const MaskTableOp op{(const unsigned *)w.dpos.p, job.cpos, w.dmpos.p};
     unsigned *total = w.dmcnt.p + compact_tiles(npix);
     launch_compact_count(op, npix, w.dmcnt.p, total, s, "k_dither_mask", 8.0 * npix);
     launch_compact_write(op, npix, w.dmcnt.p, s, "k_dither_mask", 12.0 * npix + 4.0 * m);
     HIP_CHECK(hipStreamSynchronize(s));          // (the launchers below size their workspace before they enqueue)
-    launch_dither_any(d_img, plane_stride, which, width, height, d_pal, h_pal, k, d_out, elem_bytes, w, s, layout, w.dmpos.p, m);
+    job.mpos = w.dmpos.p;
 }
 
-// mpos: the masked table (mcount opaque pixels, compact numbers in curve order) or nullptr
-static void launch_dither_waves(const double *d_img, size_t plane_stride, size_t width, size_t height, const double *d_pal, int k,
-                                void *d_out, int elem_bytes, NNWork &w, hipStream_t s, const unsigned *mpos, size_t mcount) {
-    size_t lds = ((size_t)6 * k + 3 * 128) * sizeof(double) + 128 * sizeof(unsigned int);      // palette (raw + weighted) + the ring of pending pixels
-    w.lane_tables.valid = false;
-    double *gtab = nullptr;
-    if (lds > 150 * 1024) {                                      // K > 3200: the tables in global memory (workspace kept with the engine)
-        w.dtab.reserve((size_t)6 * k);
-        gtab = w.dtab.p;
-        lds = (size_t)3 * 128 * sizeof(double) + 128 * sizeof(unsigned int);
+// what a job may be, entry by entry (map.h); the error texts are the entries' own
+static void dither_validate(const DitherJob &job) {
+    const size_t n = job.width * job.height, N = job.frames * n;
+    if (job.frames != 1 || job.bytes) {
+        if (job.frames == 0 || n == 0 || N / n != job.frames || N > kDitherFramesMaxPixels)
+            throw HipError(job.bytes ? "patolette_amd: the dither takes up to 2^31 pixels in all" : "patolette_amd: the frame-batched dither takes up to 2^31 pixels in all");
+    } else if (n >> 32) throw HipError("patolette_amd: the dither kernel numbers pixels with 32 bits");
+    if (job.cpos && (job.opaque == 0 || job.opaque > n)) throw HipError("patolette_amd: masked dither with no opaque pixel");
+    if (job.elem_bytes != 1 && job.elem_bytes != 4 && job.elem_bytes != 8) throw HipError("patolette_amd: map element size must be 1, 4 or 8");
+    if (job.bytes) {
+        if (job.channels != 3 && job.channels != 4) throw HipError("patolette_amd: 8-bit pixels have 3 or 4 channels");
+        if (!dither_lanes_possible(job.frames, n, job.k)) throw HipError("patolette_amd: this image cannot take the lane layout");
     }
-    const DitherWeights wts = dither_weights();
-    // Runs: two wavefronts per SIMD fill the issue slots of the chip (one chain alone uses ~2/3 of its SIMD's); never shorter than
-    // the warm-up -- below that the speculative steps outnumber the useful ones.
-    const size_t npix = mpos ? mcount : width * height;
+}
+
+// The one route.  The lane layout where the caller says so (job.layout: what it decided when it chose the pixels' form; the knobs may
+// have changed since, the hard limits have not) or the rule does; after a lane walk whose verification stalled for good, and for
+// whatever the lane layout does not take (a palette outside 8 .. 256 rows, too few pixels, a knob that asks for wavefronts), the
+// wavefront layout frame after frame, each frame along its own curve from the empty queue.
+bool launch_dither(const DitherJob &job_in, NNWork &w, hipStream_t s) {
+    DitherJob job = job_in;
+    dither_validate(job);
+    if (job.cpos) dither_mask_table(job, w, s);
+    const size_t n = job.width * job.height, npix = job.mpos ? job.opaque : job.frames * n;
     const DitherConfig cfg = dither_cfg_snapshot();
-    DitherSeg sg{};
-    sg.warm = cfg.warm >= 0 ? (unsigned)cfg.warm : 1024u;
-    size_t S = cfg.segments > 0 ? (size_t)cfg.segments : (size_t)num_cus() * 8;
-    if (cfg.segments <= 0) S = std::min(S, npix / std::max<size_t>(sg.warm, 256));
-    S = std::min(S, npix / 128);                                 // every run after the first has its sixteen predecessors
-    if (std::max(width, height) < 16) S = 1;
-    if (S < 1) S = 1;
-    sg.S = (unsigned)S;
-    w.dither_segments = S; w.dither_repairs = 0; w.dither_rounds = 0; w.dither_through = 0; w.dither_jumps = 0; w.dither_solo = 0;
-    if (S > 1) {
-        w.dside.reserve(16 * std::max(S, (size_t)num_cus() * 8) + 16);   // the default cap at once: no regrowth behind queued work
-        w.hrep.reserve(2);
-        sg.side = w.dside.p;
-        sg.repairs = w.dside.p + 16 * S;
-        sg.b0 = 1; sg.through = 0;
-    }
-    auto reset_counters = [&]() {                                // [0] = 0 repairs, [1] = no run yet (atomicMin)
-        w.hrep.p[0] = 0u; w.hrep.p[1] = 0xFFFFFFFFu;
-        HIP_CHECK(hipMemcpyAsync(sg.repairs, w.hrep.p, 2 * sizeof(unsigned), hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipStreamSynchronize(s));                      // (the pinned words are read back into below)
-    };
-    if (S > 1) reset_counters();
-    auto launch = [&](int mode, unsigned blocks) {
-        if (elem_bytes == 1) launch_dither_t<unsigned char>(mode, blocks, d_img, plane_stride, width, height, d_pal, k, (unsigned char *)d_out, wts, lds, gtab, sg, s, mpos, mcount);
-        else if (elem_bytes == 4) launch_dither_t<unsigned int>(mode, blocks, d_img, plane_stride, width, height, d_pal, k, (unsigned int *)d_out, wts, lds, gtab, sg, s, mpos, mcount);
-        else launch_dither_t<unsigned long long>(mode, blocks, d_img, plane_stride, width, height, d_pal, k, (unsigned long long *)d_out, wts, lds, gtab, sg, s, mpos, mcount);
-        HIP_CHECK(hipGetLastError());
-    };
-    {
-        KTIME("k_dither", s, (24.0 + elem_bytes + (mpos ? 4.0 : 0.0)) * npix);
-        launch(0, (unsigned)S);
-    }
-    if (S == 1 || std::max(width, height) <= 1) return;
-    // verify every boundary, walk the runs whose starting state was not the true one again, until a pass finds nothing to do
-    // Where the image is FLAT over more than a warm-up and the flat colour is not a palette entry, the true chain is periodic (period
-    // 4 .. 14 measured) and a zero-queue chain settles into the same cycle at another phase: it never meets the true one, and a
-    // verification pass then fixes one run -- the lowest failing one, whose predecessor is final -- while its neighbours are rebuilt
-    // from tails that are about to change.  Two passes in a row that fix next to nothing are taken as that: the lowest failing run
-    // is walked THROUGH the runs behind it (one wavefront, the true chain) until it meets what is there -- the end of the flat
-    // stretch --, and the passes resume (runs it overwrote pass their next check in sixteen steps).
-    unsigned prev_r = 0xFFFFFFFFu;
-    int stalled = 0;
-    for (size_t round = 0;; round++) {
-        if (round > 2 * S + 8) throw HipError("patolette_amd: the dither's boundary repairs did not settle");
-        {
-            KTIME("k_dither_fix", s, 0.0);
-            launch(1, (unsigned)S - 1);
+    const bool lanes = job.bytes || (job.layout >= 0 ? job.layout != 0
+                                                      : (job.frames == 1 || dither_lanes_possible(job.frames, n, job.k)) && dither_lane_rule(cfg, npix, job.k));
+    size_t lane_passes = 0;
+    if (lanes) {
+        if (job.frames > 1 && !dither_lanes_possible(job.frames, n, job.k)) throw HipError("patolette_amd: these frames cannot take the lane layout");
+        std::vector<double> hp;
+        if (!job.h_pal) {
+            hp.resize(3 * (size_t)job.k);
+            HIP_CHECK(hipMemcpyAsync(hp.data(), job.d_pal, hp.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+            job.h_pal = hp.data();
         }
-        HIP_CHECK(hipMemcpyAsync(w.hrep.p, sg.repairs, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        const unsigned r = w.hrep.p[0], lowest = w.hrep.p[1];
-        w.dither_rounds = round + 1;
-        if (r == 0) break;
-        w.dither_repairs += r;
-        stalled = (prev_r != 0xFFFFFFFFu && r + std::max(1u, prev_r / 8) >= prev_r) ? stalled + 1 : 0;
-        prev_r = r;
-        reset_counters();
-        if (stalled >= 2 && (size_t)lowest + 1 < S) {
-            // the pass above has rebuilt run `lowest` from its final predecessor: it is final now, and the walk starts behind it
-            // (the record of that run is voided so that the kernel does not take its boundary for verified)
-            HIP_CHECK(hipMemsetAsync(sg.side + 16 * ((size_t)lowest + 1), 0xFF, 16 * sizeof(unsigned), s));
-            sg.b0 = lowest + 1; sg.through = 1;
-            { KTIME("k_dither_fix", s, 0.0); launch(1, 1u); }
-            sg.b0 = 1; sg.through = 0;
-            reset_counters();
-            w.dither_through++;
-            stalled = 0; prev_r = 0xFFFFFFFFu;
+        if (launch_dither_lanes(job, w, cfg, s)) return true;
+        if (job.bytes) return false;                                 // (nothing usable was written; the planes are the caller's to make)
+        // stalled: the wavefront layout from scratch (it needs the pixels as linear Rec2020 in image order; w.dsort holds more than
+        // 3 npix already)
+        if (job.which != PAMD_COPY) {
+            w.dsort.reserve(3 * npix);
+            with_which(job.which, [&](auto W) {
+                if constexpr (decltype(W)::value != PAMD_COPY)
+                    hipLaunchKernelGGL(k_dither_convert<decltype(W)::value>, stream_blocks(npix, 16), 256, 0, s, job.planes, job.plane_stride, npix, w.dsort.p);
+            });
+            HIP_CHECK(hipGetLastError());
+            job.planes = w.dsort.p; job.plane_stride = npix; job.which = PAMD_COPY;
         }
+        lane_passes = w.dither_rounds;
     }
+    if (job.which != PAMD_COPY) throw HipError("patolette_amd: the wavefront-per-run dither takes linear Rec2020 pixels");
+    size_t segments = 0, repairs = 0, rounds = lane_passes, through = 0, jumps = 0, solo = 0;
+    for (size_t f = 0; f < job.frames; f++) {
+        launch_dither_waves(job, f, w, cfg, s);
+        segments += w.dither_segments; repairs += w.dither_repairs; rounds += w.dither_rounds; through += w.dither_through;
+        jumps += w.dither_jumps; solo += w.dither_solo;
+    }
+    w.dither_segments = segments; w.dither_repairs = repairs; w.dither_rounds = rounds; w.dither_through = through;
+    w.dither_jumps = jumps; w.dither_solo = solo;
+    return true;
 }
 
 }  // namespace pamd

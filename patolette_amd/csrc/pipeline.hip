@@ -2322,11 +2322,11 @@ static Bounds read_bounds(Engine &E, bool weighted, const std::function<void()> 
 // the full path, inputs resident in HBM
 // --------------------------------------------------------------------------------------------
 // The RGBA entry's compact image: the pipeline runs on the M opaque pixels as an M x 1 image, and the dither walks the width x height
-// curve over them (launch_dither_masked; cpos[pixel] = compact number or -1)
+// curve over them (DitherJob's cpos: cpos[pixel] = compact number or -1)
 struct DitherMask { size_t width, height; const int *cpos; };
 // The frames entry's stack: the pipeline runs on count * width * height pixels as ONE image of width x (count * height) -- the palette
 // stage sees a list of colours, the nearest map is position-independent -- and only the dither knows the frames: each is walked along
-// its own width x height curve from the empty queue (launch_dither_frames)
+// its own width x height curve from the empty queue (DitherJob's frames)
 struct Frames { size_t count, width, height; };
 
 struct Pixels {                      // device-resident input image: planar f64 sRGB, or interleaved 8-bit sRGB
@@ -2441,22 +2441,23 @@ static void run_device(Engine &E, size_t width, size_t height, Pixels px, const 
                 HIP_CHECK(hipMemcpyAsync(E.dpal.p, pal.data(), 3 * len * sizeof(double), hipMemcpyHostToDevice, s));
                 HIP_CHECK(hipStreamSynchronize(s));
                 // (masked: this image is the M x 1 list of opaque pixels, and the layout is decided on M as well)
-                auto dither = [&](const double *img, int which, int layout) {
-                    if (mask) launch_dither_masked(img, N, which, mask->width, mask->height, mask->cpos, N, E.dpal.p, pal.data(), (int)len, d_map,
-                                                   map_elem, E.nn, s, layout);
-                    else if (frames) launch_dither_frames(img, N, which, frames->count, frames->width, frames->height, E.dpal.p, pal.data(), (int)len,
-                                                          d_map, map_elem, E.nn, s, layout);
-                    else launch_dither(img, N, which, width, height, E.dpal.p, pal.data(), (int)len, d_map, map_elem, E.nn, s, layout);
-                };
+                DitherJob job;
+                job.width = width; job.height = height;
+                if (mask) { job.width = mask->width; job.height = mask->height; job.cpos = mask->cpos; job.opaque = N; }
+                else if (frames) { job.frames = frames->count; job.width = frames->width; job.height = frames->height; }
+                job.d_pal = E.dpal.p; job.h_pal = pal.data(); job.k = (int)len;
+                job.out = d_map; job.elem_bytes = map_elem;
+                job.plane_stride = N;                                          // plane stride of cvt is N for x,y,z
                 if (frames ? dither_frames_lane_layout(frames->count, frames->width, frames->height, (int)len)
                            : dither_lane_layout(width, height, (int)len)) {      // decided ONCE: launch_dither is told
                     // the pixels go into curve order anyway: their conversion to linear Rec2020 rides on that pass
-                    dither(E.cvt.p, pix, 1);
+                    job.planes = E.cvt.p; job.which = pix; job.layout = 1;
                 } else {
                     E.aux.reserve(3 * N);
-                    launch_convert(pix, E.cvt.p, E.aux.p, N, nullptr, s);      // plane stride of cvt is N for x,y,z
-                    dither(E.aux.p, PAMD_COPY, 0);
+                    launch_convert(pix, E.cvt.p, E.aux.p, N, nullptr, s);
+                    job.planes = E.aux.p; job.which = PAMD_COPY; job.layout = 0;
                 }
+                launch_dither(job, E.nn, s);
                 add_dither_stats(E);
             }
             palette_rows(pal, len, hm::color::rec2020_to_srgb);
@@ -2827,7 +2828,7 @@ static std::atomic<int> g_remap_two_pass{0};
 // given, dropped rows included).  `pixels`, `map_out`, `quant_out` are device pointers when `on_device`.
 // Nearest, two-pass: pixels -> ICtCp planes (k_convert_u8, whose statistics bound the grid) -> launch_nn_map.  Nearest, fused (where the
 // LDS-table kernel runs): launch_nn_map_u8 converts in registers.  Dither, two-pass: pixels -> linear
-// Rec2020 planes -> launch_dither / launch_dither_frames.  Dither, fused (where the lane layout runs): launch_dither_u8 gathers the
+// Rec2020 planes -> launch_dither.  Dither, fused (where the lane layout runs): launch_dither with the job's bytes gathers the
 // bytes along the curve and converts them there; no f64 image is written.
 // Ordered (mode kRemapOrdered, `spread`): launch_ordered_map shifts, converts and searches in one kernel; palette in ICtCp, no f64 image.
 enum { kRemapNearest = 0, kRemapRiemersma = 1, kRemapOrdered = 2 };
@@ -2843,19 +2844,25 @@ static void remap_dither(Engine &E, const unsigned char *d_px, int channels, siz
                          size_t k, void *d_map, int me, bool fused, bool lanes) {
     const size_t N = frames * width * height;
     hipStream_t s = E.stream;
+    DitherJob job;
+    job.frames = frames; job.width = width; job.height = height;
+    job.d_pal = E.dpal.p; job.h_pal = pal.data(); job.k = (int)k;
+    job.out = d_map; job.elem_bytes = me;
     bool done = false;
     if (fused) {
         HIP_CHECK(hipStreamSynchronize(s));
-        done = launch_dither_u8(d_px, channels, frames, width, height, E.dpal.p, pal.data(), (int)k, d_map, me, E.nn, s);
+        job.bytes = d_px; job.channels = channels;
+        done = launch_dither(job, E.nn, s);
         // the lane walk's verification stalled beyond patolette_amd_debug_dither_solo_cap: the planes after all, for the wavefront layout
         if (!done) { HIP_CHECK(hipStreamSynchronize(s)); E.cvt.reserve(3 * N); }
     }
     if (!done) {
-        const int layout = (lanes && !fused) ? 1 : 0;                         // (after a stalled lane walk: not the same walk again)
         launch_convert_u8(PAMD_SRGB_TO_REC2020, d_px, channels, E.cvt.p, N, nullptr, s);
         HIP_CHECK(hipStreamSynchronize(s));
-        if (frames > 1) launch_dither_frames(E.cvt.p, N, PAMD_COPY, frames, width, height, E.dpal.p, pal.data(), (int)k, d_map, me, E.nn, s, layout);
-        else launch_dither(E.cvt.p, N, PAMD_COPY, width, height, E.dpal.p, pal.data(), (int)k, d_map, me, E.nn, s, layout);
+        job.bytes = nullptr;
+        job.planes = E.cvt.p; job.plane_stride = N; job.which = PAMD_COPY;
+        job.layout = (lanes && !fused) ? 1 : 0;                               // (after a stalled lane walk: not the same walk again)
+        launch_dither(job, E.nn, s);
     }
 }
 
@@ -2939,7 +2946,12 @@ static void rgba_masked_frame(Engine &E, const unsigned char *d_px, size_t width
     launch_alpha_compact(d_px, n, M, thr, d_offsets, nullptr, E.rgba_cpos.p, E.rgba_rgb.p, nullptr, s);
     launch_convert_u8(PAMD_SRGB_TO_REC2020, E.rgba_rgb.p, 3, E.cvt.p, M, nullptr, s);
     HIP_CHECK(hipStreamSynchronize(s));                               // (the dither launchers size their workspace before they enqueue)
-    launch_dither_masked(E.cvt.p, M, PAMD_COPY, width, height, E.rgba_cpos.p, M, E.dpal.p, pal.data(), (int)k, E.dmap.p, me, E.nn, s);
+    DitherJob job;
+    job.planes = E.cvt.p; job.plane_stride = M; job.which = PAMD_COPY;
+    job.width = width; job.height = height; job.cpos = E.rgba_cpos.p; job.opaque = M;
+    job.d_pal = E.dpal.p; job.h_pal = pal.data(); job.k = (int)k;
+    job.out = E.dmap.p; job.elem_bytes = me;
+    launch_dither(job, E.nn, s);
     launch_rgba_expand(E.dmap.p, me, E.rgba_cpos.p, n, M, off, d_palw, (int)rows, d_map, map_elem, d_quant, s);
 }
 
@@ -4579,7 +4591,12 @@ int patolette_amd_dither(const double *colors, size_t width, size_t height, cons
         E.src.reserve(3 * n); E.dpal.reserve(3 * k); E.dmap.reserve(n * 4);
         HIP_CHECK(hipMemcpy(E.src.p, colors, 3 * n * sizeof(double), hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(E.dpal.p, palette, 3 * k * sizeof(double), hipMemcpyHostToDevice));
-        launch_dither(E.src.p, n, PAMD_COPY, width, height, E.dpal.p, palette, (int)k, E.dmap.p, 4, E.nn, E.stream);
+        DitherJob job;
+        job.planes = E.src.p; job.plane_stride = n; job.which = PAMD_COPY;
+        job.width = width; job.height = height;
+        job.d_pal = E.dpal.p; job.h_pal = palette; job.k = (int)k;
+        job.out = E.dmap.p; job.elem_bytes = 4;
+        launch_dither(job, E.nn, E.stream);
         E.stats = patolette_amd__Stats{};                           // (a call of its own: nothing of the one before it stays)
         add_dither_stats(E);
         E.sync();

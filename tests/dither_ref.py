@@ -136,9 +136,9 @@ def layout(probes, pal, order, width, height, ranks=None, fill=None, anchors=Non
     return Layout(image, seq, ranks[ok], np.nonzero(ok)[0], np.nonzero(~ok)[0], width, height, pal)
 
 
-# ---- the lane layout's host arithmetic (launch_dither_lanes), restated ----------------------------------------------------------------
+# ---- the lane layout's host arithmetic (csrc/dither_host.h), restated -----------------------------------------------------------------
 class Geometry:
-    """lo, hi, inv: (3 grids, 3 axes); G: (3,); amb, amb_p, amb_x: float32"""
+    """lo, hi, inv (and cw, the cell widths): (3 grids, 3 axes); G: (3,); amb, amb_p, amb_x: float32"""
 
     def __init__(self, lo, hi, inv, G, amb, amb_p, amb_x):
         self.lo, self.hi, self.inv, self.G, self.amb, self.amb_p, self.amb_x = lo, hi, inv, G, amb, amb_p, amb_x
@@ -153,24 +153,28 @@ def lane_geometry(pal, npix):
     margins of the f32 first pass, expression by expression as the host forms them"""
     wp = np.asarray(pal, dtype=np.float64) * FW
     G0 = 64 if npix >= 1 << 20 else 32
-    lo, hi = wp.min(axis=0), wp.max(axis=0)
-    r = hi - lo
+    # (the host folds with std::min / std::max from +-inf, which never take a NaN: fmin / fmax, not min / max)
+    lo, hi = np.fmin.reduce(np.vstack([np.full(3, np.inf), wp])), np.fmax.reduce(np.vstack([np.full(3, -np.inf), wp]))
+    with np.errstate(invalid="ignore"):
+        r = hi - lo
     r = np.where((r > 0) & np.isfinite(r), r, 0.0)
     glo, ghi, ginv, GG = np.zeros((3, 3)), np.zeros((3, 3)), np.zeros((3, 3)), np.array([G0, G0, 32])
     m = 0.5 * r + 1e-3
     glo[0] = lo - m
     Rg = r + 2 * m
     ginv[0] = G0 / Rg
+    gcw = np.zeros((3, 3))
+    gcw[0] = Rg / G0
     ghi[0] = glo[0] + Rg
     for lv in (0, 1):
         mo = (1.5 if lv == 0 else 4.0) * r + (5e-3 if lv == 0 else 1e-2)
         Ro = r + 2 * mo
         glo[lv + 1] = lo - mo
         ginv[lv + 1] = GG[lv + 1] / Ro
+        gcw[lv + 1] = Ro / GG[lv + 1]
         ghi[lv + 1] = glo[lv + 1] + Ro
     t = wp - glo[0]
-    wmax = float(np.max(((0.0 + t[:, 0] * t[:, 0]) + t[:, 1] * t[:, 1]) + t[:, 2] * t[:, 2]))
-    wmax = max(0.0, wmax)
+    wmax = float(np.fmax.reduce(np.concatenate([[0.0], ((0.0 + t[:, 0] * t[:, 0]) + t[:, 1] * t[:, 1]) + t[:, 2] * t[:, 2]])))
     t = ghi[0] - glo[0]
     r2 = float(((0.0 + t[0] * t[0]) + t[1] * t[1]) + t[2] * t[2])
     M = 2.5 * 1.001 * 2.0 ** -24 * (9.0 * wmax + 5.0 * r2)
@@ -183,7 +187,56 @@ def lane_geometry(pal, npix):
     amb_p, amb_x = _f32_up(Mp), _f32_up(Mx)
     if not Mp < 3.0e38:
         amb_p = np.float32(np.inf)
-    return Geometry(glo, ghi, ginv, GG, amb, amb_p, amb_x)
+    geo = Geometry(glo, ghi, ginv, GG, amb, amb_p, amb_x)
+    geo.cw = gcw
+    return geo
+
+
+# the two cuts, the layout rule and the stall rule (csrc/dither_host.h), restated from the kernels' limits: integers throughout
+def lanes_possible(frames, n, k):
+    """a run of 64 pixels in every frame, one tile row per 8 runs (grid.y <= 65535), the pruned search's palette sizes"""
+    return frames > 0 and n >= 64 and frames <= 8 * 65535 and 8 <= k <= 256
+
+
+def lane_rule(segments, lanes, npix, k):
+    """the lane layout: 8 <= k <= 256, not the single chain, not switched off; from 2^23 pixels, or from 2^16 when asked for"""
+    if not 8 <= k <= 256 or segments == 1 or lanes == 0:
+        return False
+    return npix >= (65536 if lanes > 0 else 1 << 23)
+
+
+def lane_cut(segments, warm, cus, npix, nframe, frames):
+    """(S, Lmax, fruns, warm) of the lane layout: 512 runs per CU, none shorter than 256 pixels unless asked for, never shorter than 64,
+    8 * 65535 at the most; a stack of frames: the same per frame, every frame the same number of runs"""
+    auto = min(cus * 512, npix // 256)
+    S = max(1, min(segments if segments > 0 else auto, npix // 64, 8 * 65535))
+    fruns = 0
+    if frames > 1:
+        per = -(-segments // frames) if segments > 0 else auto // frames
+        fruns = max(1, min(per, nframe // 64, 8 * 65535 // frames))
+        S = frames * fruns
+    return S, -(-npix // S), fruns, min(warm if warm >= 0 else 256, npix // S)
+
+
+def wave_cut(segments, warm, cus, npix, width, height):
+    """(S, warm) of the wavefront layout: 8 runs per CU, none shorter than the warm-up (256 at least) unless asked for, never shorter
+    than 128; one chain for an image under 16 pixels across"""
+    warm = warm if warm >= 0 else 1024
+    S = segments if segments > 0 else min(cus * 8, npix // max(warm, 256))
+    S = min(S, npix // 128)
+    if max(width, height) < 16:
+        S = 1
+    return max(S, 1), warm
+
+
+def stall_steps(counts):
+    """per verification pass: how many passes in a row left work that had not dropped by an eighth (one at least) of the pass before"""
+    out, prev, stalled = [], None, 0
+    for n in counts:
+        stalled = stalled + 1 if prev is not None and n + max(1, prev // 8) >= prev else 0
+        prev = n
+        out.append(stalled)
+    return out
 
 
 def nn_cell(q, lo, inv, G):

@@ -8,7 +8,12 @@ Entries: quantize (planar, row-major; given and derived weights), quantize_u8, q
 pixels transparent; a tensor view that is not 4-byte aligned), remap and remap_rgba in all three modes, quantize_rgba_frames,
 quantize_u8_batch -- the 8-bit ones from a numpy array and from a torch device tensor -- then the other routes through the knobs
 the tests use: the chunked upload (PAMD_UPLOAD_CHUNK_MIN), patolette_amd_debug_remap_two_pass, patolette_amd_dither_layout,
-patolette_amd_debug_nn_route.  `--large` adds the f64 images of up to 2048 x 2048 this tool began with.
+patolette_amd_debug_nn_route.  Those images (96 x 80) are below the 65 536 pixels from which patolette_amd_dither_layout(1) selects
+the lane layout, so the `route_` calls follow: quantize with dither in the three colour spaces on 256 x 256, quantize_frames on
+4 x 128 x 128, quantize_rgba and remap_rgba on 256 x 288 with 5 % of the pixels transparent, remap fused and two-pass -- each under
+the lane layout, the wavefront layout, the single chain (patolette_amd_dither_config(1, -1)) and the lane walk that gives up at its
+first stalled pass (warm-up 1, patolette_amd_debug_dither_stall_passes(0), patolette_amd_debug_dither_solo_cap(0)) -- and K = 300 on
+96 x 80, the wavefront layout's generic loop.  `--large` adds the f64 images of up to 2048 x 2048 this tool began with.
 
 A k_fill_weights launch goes ahead of every call, so a `rocprofv3 --kernel-trace --memory-copy-trace --output-format rocpd` of this
 script can be cut into calls:
@@ -17,7 +22,7 @@ script can be cut into calls:
 
 prints per call the kernels with their grids and the copies with direction and bytes in order of start, runs of one line folded;
 sorted instead for the calls whose work runs on more than one stream at once (the batch; the chunked uploads, whose conversions
-run beside the copies)."""
+run beside the copies; route_lanes_* and route_gives_up_*, whose lane walks build their record grids on two side streams)."""
 import glob
 import os
 import re
@@ -54,6 +59,7 @@ def large_cases():
 
 
 W, H, FW, FH, F, K = 96, 80, 40, 24, 3, 20
+RW, RH = 256, 288                                                # the dither-route cases: RW x RW, 4 frames of RW/2 x RW/2, RW x RH with alpha
 
 
 def image_u8(w, h, seed, frames=None):
@@ -89,6 +95,11 @@ def calls(large):
     kw = dict(kmeans_niter=2)
     # every input, and the remaps' palettes, before the first call: what making them enqueues belongs to no call
     arrays = {"img": img, "frames": frames}
+    # the route cases' images: 65 536 pixels and more, the RGBA one with 65 536 opaque pixels and transparent ones scattered inside it
+    rcolors = smooth(RW, RW) * 0.8 + 0.2 * rng.random((RW * RW, 3))
+    alpha = np.where(rng.random((RH, RW)) < 0.05, 0, 255).astype(np.uint8)
+    arrays.update(rimg=image_u8(RW, RW, 4), rframes=image_u8(RW // 2, RW // 2, 5, 4), rrgba=np.concatenate([image_u8(RW, RH, 6), alpha[..., None]], axis=-1))
+    assert int((alpha == 255).sum()) >= 65536
     for kind in ("none", "some", "all"):
         arrays["img_" + kind], arrays["frames_" + kind] = with_alpha(img, kind), with_alpha(frames, kind)
     tensors = {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in arrays.items()}
@@ -153,6 +164,9 @@ def calls(large):
     def reset():
         L.patolette_amd_debug_remap_two_pass(0)
         L.patolette_amd_dither_layout(-1)
+        L.patolette_amd_dither_config(0, -1)
+        L.patolette_amd_debug_dither_stall_passes(-1)
+        L.patolette_amd_debug_dither_solo_cap(-1)
         L.patolette_amd_debug_nn_route(0)
 
     def knobbed(set_knob, fn):
@@ -176,6 +190,44 @@ def calls(large):
             yield "remap_rgba_unaligned" + knob, knobbed(set_knob, u8(p.remap_rgba, odd, palrgba, dither=True))
             yield "u8_np_dither" + knob, knobbed(set_knob, u8(p.quantize_u8, img, K, dither=True, tile_size=0, **kw))
             yield "rgba_some_np_dither" + knob, knobbed(set_knob, u8(p.quantize_rgba, arrays["img_some"], K, dither=True, tile_size=0, **kw))
+
+    # the dither's routes at the size from which patolette_amd_dither_layout(1) selects the lane layout (65 536 pixels; the images
+    # above are far below it, so their _lanes cases walk wavefronts): every driver of a Riemersma walk under each layout, the single
+    # chain, and the lane walk that gives up at its first stalled pass and hands the image to the wavefront layout
+    def route_knobs(layout, segments, warm, stall, cap):
+        def set_knob():
+            L.patolette_amd_dither_layout(layout)
+            L.patolette_amd_dither_config(segments, warm)
+            L.patolette_amd_debug_dither_stall_passes(stall)
+            L.patolette_amd_debug_dither_solo_cap(cap)
+        return set_knob
+
+    def two_pass(fn):
+        def run():
+            L.patolette_amd_debug_remap_two_pass(1)
+            return fn()                                            # (knobbed's reset puts it back)
+        return run
+
+    def quantize_at(w, h, src, **k):
+        def run():
+            r = p.quantize(w, h, src, K, **k)
+            assert r[0], r[-1]
+            return dict(pal=r[1], map=r[2])
+        return run
+
+    for knob, set_knob in (("lanes", route_knobs(1, 0, -1, -1, -1)), ("wavefronts", route_knobs(0, 0, -1, -1, -1)),
+                           ("chain", route_knobs(-1, 1, -1, -1, -1)), ("gives_up", route_knobs(1, 0, 1, 0, 0))):
+        for cs in ("sRGB", "CIELuv", "ICtCp"):
+            yield "route_%s_quantize_%s" % (knob, cs), knobbed(set_knob, quantize_at(RW, RW, rcolors, dither=True, tile_size=0,
+                                                                                     color_space=getattr(p, "ColorSpace_" + cs), **kw))
+        for where, at in (("np", arrays), ("torch", tensors)):
+            yield "route_%s_frames_%s" % (knob, where), knobbed(set_knob, u8(p.quantize_frames, at["rframes"], K, dither=True, tile_size=0, **kw))
+            yield "route_%s_rgba_%s" % (knob, where), knobbed(set_knob, u8(p.quantize_rgba, at["rrgba"], K, dither=True, tile_size=0, **kw))
+            yield "route_%s_remap_rgba_%s" % (knob, where), knobbed(set_knob, u8(p.remap_rgba, at["rrgba"], palrgba, dither=True))
+            yield "route_%s_remap_%s" % (knob, where), knobbed(set_knob, u8(p.remap, at["rimg"], pal8, dither=True))
+            yield "route_%s_remap_two_pass_%s" % (knob, where), knobbed(set_knob, two_pass(u8(p.remap, at["rimg"], pal8, dither=True)))
+    # more than 256 palette rows: the generic loop of the wavefront layout
+    yield "route_K300_u8_np", u8(p.quantize_u8, img, 300, dither=True, tile_size=0, **kw)
 
     # the chunked upload: the conversion behind the pieces
     def chunked(fn):
@@ -266,7 +318,8 @@ def enqueued(trace_dir, names):
     total = 0
     for name, ev in zip(names, cut):
         total += len(ev)
-        two_streams = name.startswith(("batch", "chunked"))     # no order of start between streams: these lists are sorted
+        # no order of start between streams: these lists are sorted (the lane layout builds its record grids on two side streams)
+        two_streams = name.startswith(("batch", "chunked", "route_lanes_", "route_gives_up_"))
         if two_streams:
             ev = sorted(ev)
         print("== %s%s" % (name, " (sorted: its work runs on more than one stream)" if two_streams else ""))
