@@ -323,7 +323,7 @@ void patolette_amd_frame_deltas_device(size_t frames, size_t width, size_t heigh
  * Kernels: k_rgba_vanish, one launch for every frame's V and the flag; then k_frame_delta_rgba once per frame on the library's
  *   stream -- rects[f - 1] is a grid-wide result that frame f's canvas needs, so the chain over frames is a chain of launches; no
  *   host turn and no wait in between.  The host unites C and V once at the end.
- * Out of scope: disposal 3, local colour tables, APNG. */
+ * Out of scope: disposal 3, local colour tables. */
 void patolette_amd_frame_deltas_rgba(size_t frames, size_t width, size_t height, const void *palette_maps, int map_elem_bytes,
                                      size_t palette_rows, const unsigned char *pixels, int channels, const double *palette,
                                      const unsigned char *palette_u8, double tolerance, int loop, void *delta_maps, void *shown_maps,
@@ -487,6 +487,47 @@ void patolette_amd_gif_lzw_lossy(size_t frames, size_t width, size_t height, con
 void patolette_amd_gif_lzw_lossy_device(size_t frames, size_t width, size_t height, const unsigned char *d_maps, const int32_t *rects,
                                         int min_code_size, size_t segment, const unsigned char *near, unsigned char *d_coded,
                                         unsigned char *out, size_t capacity, uint64_t *offsets, int *exit_code);
+
+/* ---- png_deflate: index maps deflated as an indexed PNG's image data, on the device ---------------
+ * The other way out of the pipeline: PNG and APNG.  What leaves the GPU is every frame's raw deflate stream (RFC 1951, no zlib
+ * wrapper) and the Adler-32 the zlib trailer needs; the container is a few bytes around them (Python: write_png, write_apng).
+ *   maps, rects, out, capacity, offsets: as patolette_amd_gif_lzw takes them.  Every byte value is a legal element: no min_code_size
+ *       and no flag.  Elements outside the rectangles are not read.
+ *   segment: filtered bytes per segment; 0 takes the default 16384, otherwise it must lie in [1, 32768].
+ *   adler: host memory, uint32[frames]: the Adler-32 of every frame's filtered stream (zlib's adler32).
+ * What is coded: per frame the PNG scanline stream of its rectangle at bit depth 8 with filter type 0 -- h rows, each a zero byte and
+ *   the row's w indices: the filtered stream, h * (w + 1) bytes.  It is cut into nseg = ceil(h * (w + 1) / segment) segments; a
+ *   wavefront codes a segment as ONE deflate block, the last of a frame carrying BFINAL; the blocks lie bit to bit, every frame starts
+ *   on a byte and its last byte is padded with zero bits.  zlib's inflate of out[offsets[f] : offsets[f + 1]] (raw, window 15) returns
+ *   the filtered stream byte for byte: that, not a model of the coder, is what the tests check.
+ *   - A segment is parsed on its own and gets its own code tables, but a match may start up to 32768 bytes back in the same frame's
+ *     filtered stream, before the segment's start too; no match runs beyond its segment's end.  Lengths 3 .. 258, distances 1 .. 32768.
+ *   - Candidates at every position: the distances 1, 2, 4, 8, R - 1, R, R + 1, 2R, 4R, 8R with R = w + 1 (the pixel above, its
+ *     neighbours, and the rows of an 8 x 8 ordered dither's period), up to four distances that the segment's explorations have found,
+ *     and the last earlier position of the segment with the same three bytes (a hash table; the latest position wins, never the first
+ *     lane to arrive).  The longest wins, among equals the first in that order; a match of 3 further back than 4096 is dropped; one
+ *     step of lazy evaluation (the match one byte on, if longer).
+ *   - An exploration tries EVERY distance of the window at one position (the first free one of a step of 64 positions) and keeps the
+ *     longest match, the nearest among equals; 8 bytes and more put its distance in front of the four remembered ones.  It runs when
+ *     the step before left more than 2 tokens; one that finds nothing makes the next ones wait 1, 3, 7, 15, 15, ... steps.  An
+ *     image repeats at few distances (a dither's tile, a row, a sprite's step) which a one-entry hash bucket does not find.
+ *   - Block type: dynamic Huffman with length-limited codes (15 bits; 7 for the code-length code), or the fixed code where that is
+ *     no larger.  csrc/deflate_codes.h holds the tables' routines for the host and the device alike.
+ *   The bytes are a function of the arguments alone.
+ * Capacity: a block under the fixed code takes at most 9 bits a byte and 10 more, so
+ *   sum over the frames of ceil((9 * h * (w + 1) + 10 * nseg) / 8) bytes always suffice.  With less `capacity` than the streams
+ *   need the call fails with -1, offsets (all of them; offsets[frames] = the bytes needed) and adler are written and nothing is copied.
+ * Exit codes: as patolette_amd_gif_lzw, the text starting "patolette_amd_png_deflate:"; -1 also for no adler; -4 also when the
+ *   segments number 2^31 and more.  A failed call leaves the thread's engine usable.
+ * Statistics: as patolette_amd_gif_lzw.
+ * Four kernels, one launch each for all frames, integers only: k_png_filter (the filtered streams), k_deflate_segments (parse, tables
+ *   and bits of a segment, a wavefront each), then k_lzw_offsets and k_lzw_pack as they are.
+ * Out of scope: bit depths below 8, filters other than 0, interlace, true-colour PNG, lossy coding. */
+void patolette_amd_png_deflate(size_t frames, size_t width, size_t height, const unsigned char *maps, const int32_t *rects, size_t segment,
+                               unsigned char *out, size_t capacity, uint64_t *offsets, uint32_t *adler, int *exit_code);
+void patolette_amd_png_deflate_device(size_t frames, size_t width, size_t height, const unsigned char *d_maps, const int32_t *rects,
+                                      size_t segment, unsigned char *out, size_t capacity, uint64_t *offsets, uint32_t *adler,
+                                      int *exit_code);
 
 /* The lossy coder's table for a palette.  Host code only: it never touches the device and works without one.
  *   palette / palette_u8, palette_rows: exactly one of the two, as patolette_amd_remap_u8 takes them (trailing (-1, -1, -1) rows of an

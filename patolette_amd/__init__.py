@@ -875,7 +875,7 @@ def write_gif(file, maps, palette_u8, rects=None, transparent_index=None, delay=
         `gif_lzw_lossy` and the file is smaller.  A shown entry then lies within that tolerance (ICtCp) of the MAP's entry, not of the
         source pixel: behind `frame_deltas(tolerance=t1)` within t1 + tolerance of its frame's source; nothing accumulates over the
         frames.  `measure` on the composited `coded` maps of `gif_lzw_lossy` gives the true cost.
-    Out of scope: local colour tables, interlace, APNG."""
+    Out of scope: local colour tables, interlace.  `write_apng` writes the same animations as APNG."""
     import os
     m, shape, dev = _gif_maps(maps)
     count, height, width = shape
@@ -944,6 +944,200 @@ def write_gif(file, maps, palette_u8, rects=None, transparent_index=None, delay=
             with open(os.fspath(file), "wb") as fh:
                 fh.write(blob)
     return blob
+
+
+def _png_segment(segment):
+    if segment is None:
+        return 0
+    if isinstance(segment, (bool, np.bool_)) or not isinstance(segment, (int, np.integer)) or not 1 <= int(segment) <= 32768:
+        raise ValueError("segment must be None (the default, 16384) or an integer in [1, 32768]")
+    return int(segment)
+
+
+def png_deflate_bound(rects, segment=None):
+    """Bytes that always hold the streams of `png_deflate` for these (F, 4) rectangles: per frame 9 bits for each of its h * (w + 1)
+    filtered bytes and 10 per segment (include/patolette_amd.h)."""
+    seg = _png_segment(segment) or 16384
+    r = np.asarray(rects).astype(np.int64)
+    flen = r[:, 3] * (r[:, 2] + 1)
+    nseg = (flen + seg - 1) // seg
+    return int(np.sum((9 * flen + 10 * nseg + 7) // 8))
+
+
+def png_deflate(maps, rects=None, segment=None):
+    """Index maps deflated as an indexed PNG's image data, on the device (additive; include/patolette_amd.h: patolette_amd_png_deflate).
+
+      * maps: (F, H, W) or (H, W) uint8 numpy array, or a torch uint8 CUDA tensor (the maps then never leave the GPU; only the
+        compressed streams do).  Every byte value is a legal element.
+      * rects: None, or (F, 4) rows (x0, y0, w, h) as `frame_deltas` returns them: only the rectangle is coded.  An empty rectangle
+        (an unchanged frame) is replaced by (0, 0, 1, 1), as `gif_lzw` does.
+      * segment: filtered bytes per independently parsed segment (default 16384, at most 32768): smaller is more parallel and a
+        little larger.  A match may still start before its segment.
+
+    What is coded per frame is PNG's scanline stream at bit depth 8 with filter type 0: every row of the rectangle behind a zero byte.
+    Returns (success, data uint8 numpy array, offsets (F + 1,) int64, adler (F,) uint32, message): frame f's raw deflate stream
+    (RFC 1951, no zlib wrapper) is data[offsets[f]:offsets[f + 1]] and adler[f] the Adler-32 of what it inflates to.  The result is
+    always numpy.  `write_png` and `write_apng` wrap it in the containers."""
+    m, shape, dev = _gif_maps(maps)
+    count, height, width = shape
+    seg = _png_segment(segment)
+    r = _gif_rects(rects, count, height, width)
+    name = "patolette_amd_png_deflate"
+    out = np.empty(png_deflate_bound(r, segment), dtype=np.uint8)
+    offsets = np.zeros(count + 1, dtype=np.uint64)
+    adler = np.zeros(count, dtype=np.uint32)
+    code = C.c_int(0)
+    _call(name, dev, count, width, height, _vp(m), r.ctypes.data_as(C.POINTER(C.c_int32)) if count else None, seg,
+          out.ctypes.data_as(C.c_void_p), out.size, offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
+          adler.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(code))
+    if code.value == -1 and _native.last_error().startswith(name + ":"):
+        raise ValueError(_native.last_error())
+    message = _message(code.value)
+    if code.value != 0:
+        return (False, None, None, None, message)
+    return (True, out[:int(offsets[count])], offsets.astype(np.int64), adler, message)
+
+
+def _png_chunk(kind, body):
+    import zlib
+    return len(body).to_bytes(4, "big") + kind + body + zlib.crc32(kind + body).to_bytes(4, "big")
+
+
+def _png_palette(palette, transparent_index):
+    """The PLTE and tRNS chunks of a (K, 3) or (K, 4) uint8 palette: PLTE padded with zero rows up to transparent_index; tRNS from the
+    alpha column, or opaque entries up to a transparent one."""
+    pal = np.asarray(palette.detach().cpu().numpy() if hasattr(palette, "detach") else palette)
+    if pal.ndim != 2 or pal.shape[1] not in (3, 4) or pal.dtype != np.uint8 or pal.shape[0] < 1:
+        raise ValueError("palette must be a (K, 3) or (K, 4) uint8 array")
+    if pal.shape[0] > 256:
+        raise ValueError("a PNG palette holds at most 256 rows")
+    rows = pal.shape[0]
+    if transparent_index is not None:
+        if isinstance(transparent_index, (bool, np.bool_)) or not isinstance(transparent_index, (int, np.integer)) \
+                or not 0 <= int(transparent_index) <= 255:
+            raise ValueError("transparent_index must be None or an index in [0, 255]")
+        rows = max(rows, int(transparent_index) + 1)
+    table = np.zeros((rows, 3), dtype=np.uint8)
+    table[:pal.shape[0]] = pal[:, :3]
+    alpha = np.full(rows, 255, dtype=np.uint8)
+    if pal.shape[1] == 4:
+        alpha[:pal.shape[0]] = pal[:, 3]
+    if transparent_index is not None:
+        alpha[int(transparent_index)] = 0
+    chunks = [_png_chunk(b"PLTE", table.tobytes())]
+    if np.any(alpha != 255):
+        last = int(np.max(np.nonzero(alpha != 255)[0]))                # entries behind the last one that is not opaque need no byte
+        chunks.append(_png_chunk(b"tRNS", alpha[:last + 1].tobytes()))
+    return chunks
+
+
+def _png_zlib(data, offsets, adler, f):
+    """Frame f's zlib stream: the two header bytes, its raw deflate stream, the Adler-32."""
+    return b"\x78\x9c" + data[int(offsets[f]):int(offsets[f + 1])].tobytes() + int(adler[f]).to_bytes(4, "big")
+
+
+def _png_put(file, blob):
+    import os
+    if file is not None:
+        if hasattr(file, "write"):
+            file.write(blob)
+        else:
+            with open(os.fspath(file), "wb") as fh:
+                fh.write(blob)
+    return blob
+
+
+_PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+
+
+def _png_ihdr(width, height):
+    return _png_chunk(b"IHDR", width.to_bytes(4, "big") + height.to_bytes(4, "big") + bytes([8, 3, 0, 0, 0]))
+
+
+def write_png(file, map, palette, transparent_index=None, segment=None):
+    """Write one (H, W) uint8 map as an indexed PNG: a small pure-Python container around `png_deflate`, so that
+    `quantize_u8` -> `write_png` yields the file without the map's deflate running on a CPU core.
+
+      * file: a path, an object with `write`, or None.  The bytes are always returned.
+      * map: (H, W) uint8, numpy or a torch CUDA tensor.
+      * palette: (K, 3) uint8, or (K, 4) uint8 as `quantize_rgba` returns it: tRNS then comes from the alpha column.
+      * transparent_index: None, or an index in [0, 255] written as fully transparent; PLTE is padded with zero rows up to it.
+      * segment: as `png_deflate` takes it.
+    The file: signature, IHDR (depth 8, colour type 3, no interlace), PLTE, tRNS where an entry is not opaque, one IDAT, IEND.
+    Out of scope: bit depths below 8, filters, interlace, true colour."""
+    if not hasattr(map, "shape") or len(map.shape) != 2:
+        raise ValueError("map must be an (H, W) uint8 array or a uint8 CUDA tensor")
+    m, shape, dev = _gif_maps(map)
+    _, height, width = shape
+    chunks = _png_palette(palette, transparent_index)
+    if not 1 <= width < 2 ** 31 or not 1 <= height < 2 ** 31:
+        raise ValueError("a PNG has 1 .. 2^31 - 1 pixels a side")
+    _png_segment(segment)
+    ok, data, offsets, adler, message = png_deflate(m, None, segment)
+    if not ok:
+        raise RuntimeError(message)
+    blob = b"".join([_PNG_SIGNATURE, _png_ihdr(width, height)] + chunks
+                    + [_png_chunk(b"IDAT", _png_zlib(data, offsets, adler, 0)), _png_chunk(b"IEND", b"")])
+    return _png_put(file, blob)
+
+
+def write_apng(file, maps, palette, rects=None, transparent_index=None, delay=0.04, loop=0, disposal=1, segment=None):
+    """Write an animation's maps as an APNG file: the container around `png_deflate`, for the pipelines `write_gif` serves and for
+    the RGBA one: `quantize_rgba_frames(..., dither="ordered")` -> `frame_deltas_rgba` ->
+    `write_apng(file, deltas, palette_rgba, rects, transparent_index=0, disposal=disposals)`.
+
+      * file, maps, rects, transparent_index, segment: as `write_gif` takes them; palette: as `write_png` takes it.  Frame 0 is always
+        written with the full-frame rectangle: APNG requires it of the default image.
+      * delay: seconds per frame, a number or one per frame, written as n / 100 s; loop: acTL's num_plays (0 = for ever).
+      * disposal: every frame's disposal in GIF's numbering, or one per frame, as `frame_deltas_rgba` returns them: 0 and 1 become
+        APNG_DISPOSE_OP_NONE, 2 BACKGROUND, 3 PREVIOUS.  blend_op is OVER when there is a transparent index, else SOURCE.
+    The file: signature, IHDR, acTL, PLTE, tRNS, then per frame fcTL and its data: IDAT for frame 0, fdAT for the others; IEND.
+    Out of scope: per-frame palettes, and everything `write_png` leaves out."""
+    m, shape, dev = _gif_maps(maps)
+    count, height, width = shape
+    chunks = _png_palette(palette, transparent_index)
+    if count < 1 or not 1 <= width < 2 ** 31 or not 1 <= height < 2 ** 31:
+        raise ValueError("an APNG needs at least one frame, of 1 .. 2^31 - 1 pixels a side")
+    r = _gif_rects(rects, count, height, width)
+    r[0] = (0, 0, width, height)
+    delays = np.asarray(delay, dtype=np.float64)
+    if delays.ndim == 0:
+        delays = np.full(count, float(delays))
+    if delays.shape != (count,) or not np.all(np.isfinite(delays)) or np.any(delays < 0) or np.any(np.round(delays * 100) > 65535):
+        raise ValueError("delay must be a number of seconds or one per frame, each in [0, 655.35]")
+    if isinstance(loop, (bool, np.bool_)) or not isinstance(loop, (int, np.integer)) or not 0 <= int(loop) < 2 ** 31:
+        raise ValueError("loop must be a play count in [0, 2^31 - 1]")
+    if isinstance(disposal, (list, tuple, np.ndarray)) or hasattr(disposal, "detach"):
+        disposals = np.asarray(disposal.detach().cpu().numpy() if hasattr(disposal, "detach") else disposal)
+        if disposals.shape != (count,) or disposals.dtype.kind not in "iu" or np.any(disposals < 0) or np.any(disposals > 3):
+            raise ValueError("disposal must be 0, 1, 2 or 3, or one such integer per frame")
+        disposals = [int(v) for v in disposals]
+    else:
+        if isinstance(disposal, (bool, np.bool_)) or not isinstance(disposal, (int, np.integer)) or not 0 <= int(disposal) <= 3:
+            raise ValueError("disposal must be 0, 1, 2 or 3")
+        disposals = [int(disposal)] * count
+    _png_segment(segment)
+    ok, data, offsets, adler, message = png_deflate(m, r, segment)
+    if not ok:
+        raise RuntimeError(message)
+    u32 = lambda v: int(v).to_bytes(4, "big")
+    u16 = lambda v: int(v).to_bytes(2, "big")
+    blend = 1 if transparent_index is not None else 0
+    parts = [_PNG_SIGNATURE, _png_ihdr(width, height), _png_chunk(b"acTL", u32(count) + u32(loop))] + chunks
+    sequence = 0
+    for f in range(count):
+        x0, y0, w, h = (int(v) for v in r[f])
+        dispose = (0, 0, 1, 2)[disposals[f]]
+        parts.append(_png_chunk(b"fcTL", u32(sequence) + u32(w) + u32(h) + u32(x0) + u32(y0) + u16(int(np.round(delays[f] * 100))) + u16(100)
+                                + bytes([dispose, blend])))
+        sequence += 1
+        if f == 0:
+            parts.append(_png_chunk(b"IDAT", _png_zlib(data, offsets, adler, 0)))
+        else:
+            parts.append(_png_chunk(b"fdAT", u32(sequence) + _png_zlib(data, offsets, adler, f)))
+            sequence += 1
+    parts.append(_png_chunk(b"IEND", b""))
+    return _png_put(file, b"".join(parts))
 
 
 def quantize_rgba(image, palette_size, alpha_threshold=128, dither=True, palette_only=False, color_space=ColorSpace_ICtCp,
@@ -1447,6 +1641,10 @@ __all__ = [
     "gif_lzw_lossy",
     "gif_neighbours",
     "write_gif",
+    "png_deflate",
+    "png_deflate_bound",
+    "write_png",
+    "write_apng",
     "saliency_weights",
     "ColorSpace_sRGB",
     "ColorSpace_CIELuv",

@@ -34,6 +34,13 @@ void launch_lzw(const unsigned char *d_maps, size_t frames, size_t n, size_t wid
                 size_t stride, int m, unsigned *d_stage, unsigned *d_bits, unsigned long long *d_gbit, unsigned long long *d_words,
                 unsigned *d_out, size_t out_words, hipStream_t s);
 
+// What follows a segments kernel, the deflate coder's too (deflate.hip): k_lzw_offsets and k_lzw_pack over S segments whose bit strings
+// lie LSB first at d_stage + s * stride with d_bits[s] bits each -- the frames' offsets into d_words[1 ..], the streams into d_out.
+// pack_blocks: ceil(out_words / 256).
+void lzw_offsets_and_pack(size_t frames, const LzwFrame *d_frames, size_t S, size_t stride, const unsigned *d_stage, const unsigned *d_bits,
+                          unsigned long long *d_gbit, unsigned long long *d_words, unsigned *d_out, size_t out_words, size_t pack_blocks,
+                          hipStream_t s);
+
 // bytes of the lossy coder's table: 256 rows of 16 -- the count, then up to 15 candidates in order of preference
 constexpr size_t kLzwNearBytes = 4096;
 

@@ -353,8 +353,8 @@ static size_t lzw_launch_check(const void *d_maps, size_t frames, size_t width, 
     return pack_blocks;
 }
 
-// The segments' and frames' places, then the streams: what follows either coder's segments kernel
-static void lzw_offsets_and_pack(size_t frames, const LzwFrame *d_frames, size_t S, size_t stride, const unsigned *d_stage, const unsigned *d_bits,
+// The segments' and frames' places, then the streams: what follows either coder's segments kernel, and the deflate coder's (lzw.h)
+void lzw_offsets_and_pack(size_t frames, const LzwFrame *d_frames, size_t S, size_t stride, const unsigned *d_stage, const unsigned *d_bits,
                                  unsigned long long *d_gbit, unsigned long long *d_words, unsigned *d_out, size_t out_words, size_t pack_blocks,
                                  hipStream_t s) {
     {

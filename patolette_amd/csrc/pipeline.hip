@@ -27,6 +27,7 @@
 #include "measure.h"
 #include "lzw.h"
 #include "lzw_near.h"
+#include "deflate.h"
 #include "hist.h"
 #include "saliency.h"
 #include "quant.h"
@@ -999,6 +1000,9 @@ struct Engine {
     DevBuf<unsigned> lz_stage, lz_bits, lz_out;  // ... the segments' staging areas and bit lengths; the packed streams
     DevBuf<unsigned long long> lz_gbit, lz_words;   // ... every segment's first bit in the output; the flag and the frames' offsets
     DevBuf<unsigned char> lz_near;               // gif_lzw_lossy: the table of near colours (lzw_near.h)
+    DevBuf<unsigned char> df_stream;             // png_deflate: the frames' filtered streams, back to back (deflate.h)
+    DevBuf<unsigned long long> df_base;          // ... the frames' first bytes in them
+    DevBuf<unsigned> df_tokens;                  // ... the segments' tokens between parse and emit
     // the RGBA entry (run_rgba): tile counts / offsets + the opaque count, each pixel's compact number, the opaque pixels' RGB and
     // weights, the full index map on its way to the host, the count's pinned landing place
     DevBuf<unsigned> rgba_cnt;
@@ -3269,6 +3273,63 @@ static void run_gif_lzw(Engine &E, const char *name, bool on_device, size_t fram
     run.done();
 }
 
+// --------------------------------------------------------------------------------------------
+// png_deflate: index maps deflated as an indexed PNG's image data (include/patolette_amd.h, patolette_amd_png_deflate)
+// --------------------------------------------------------------------------------------------
+// maps: frames x width x height one-byte elements, a device pointer when `on_device`; recs: the frames' rectangles with the FILTERED
+// bytes as `area` and their first segments, frames + 1 records (lzw.h); bases: the frames' first bytes in the filtered streams, frames + 1;
+// seg: a segment's filtered bytes; cap: the longest frame's.  out, offsets, adler: host memory.
+static void run_png_deflate(Engine &E, bool on_device, size_t frames, size_t width, size_t height, const unsigned char *maps,
+                            const std::vector<LzwFrame> &recs, const std::vector<unsigned long long> &bases, size_t seg, size_t cap, size_t bound,
+                            unsigned char *out, size_t capacity, uint64_t *offsets, uint32_t *adler) {
+    const size_t n = width * height, N = frames * n, S = recs[frames].seg0, stream_bytes = (size_t)bases[frames];
+    hipStream_t s = E.stream;
+    GivenRun run(E);
+    const std::string who = "patolette_amd_png_deflate: ";
+    // the workspace, before anything is enqueued
+    const size_t longest = std::min(seg, cap), stride = deflate_stage_words(longest), tok_stride = deflate_token_stride(longest);
+    const size_t words = deflate_words(frames, S), out_words = bound / 4 + 1;
+    E.lz_frames.reserve(frames + 1);
+    E.df_base.reserve(frames + 1);
+    E.df_stream.reserve(stream_bytes + 2 * kDeflateStreamPad);             // (the streams start kDeflateStreamPad bytes in)
+    E.df_tokens.reserve(S * tok_stride);
+    E.lz_stage.reserve(S * stride);
+    E.lz_bits.reserve(S);
+    E.lz_gbit.reserve(S + 1);
+    E.lz_words.reserve(words);
+    E.lz_out.reserve(out_words);
+    const unsigned char *d_maps = maps;
+    if (!on_device) {
+        std::vector<unsigned> none;
+        stage_given(E, maps, 1, 1, N, GivenSkip{}, 0, nullptr, 0, none);
+        d_maps = E.dl_maps.p;
+    }
+    run.lap(&patolette_amd__Stats::ms_upload);
+    HIP_CHECK(hipMemcpyAsync(E.lz_frames.p, recs.data(), (frames + 1) * sizeof(LzwFrame), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(E.df_base.p, bases.data(), (frames + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+    launch_deflate(d_maps, frames, n, width, E.lz_frames.p, E.df_base.p, stream_bytes, S, seg, tok_stride, stride, E.df_stream.p + kDeflateStreamPad, E.df_tokens.p,
+                   E.lz_stage.p, E.lz_bits.p, E.lz_gbit.p, E.lz_words.p, E.lz_out.p, out_words, s);
+    const std::vector<unsigned long long> w = run.words(E.lz_words.p, words);
+    run.lap(&patolette_amd__Stats::ms_map);
+    for (size_t f = 0; f <= frames; f++) offsets[f] = w[1 + f];
+    const unsigned long long *sums = w.data() + frames + 2;                // a frame's Adler-32 from its segments' sums
+    for (size_t f = 0; f < frames; f++) {
+        Adler32 a;
+        for (size_t k = recs[f].seg0; k < recs[f + 1].seg0; k++) {
+            const size_t q0 = (k - recs[f].seg0) * seg;
+            a.add(sums[2 * k], sums[2 * k + 1], std::min(seg, (size_t)recs[f].area - q0));
+        }
+        adler[f] = a.value();
+    }
+    const size_t total = (size_t)w[1 + frames];
+    if (total > bound) throw HipError(who + "the streams exceed the stated bound (internal error)");
+    if (total > capacity)
+        throw HipError(who + "capacity is too small: offsets[frames] holds the bytes needed, nothing was copied");
+    HIP_CHECK(hipMemcpy(out, E.lz_out.p, total, hipMemcpyDeviceToHost));
+    run.lap(&patolette_amd__Stats::ms_download);
+    run.done();
+}
+
 // The RGBA entry (include/patolette_amd.h, patolette_amd_rgba): the opaque pixels (alpha >= thr) are compacted in row-scan order and
 // the path runs on them as an M x 1 image with one palette row less (row 0 is the transparent entry); the dither walks the full image's
 // curve over them (DitherMask).  Every pixel opaque: the path runs on the image itself with the full palette, exactly as run_u8 does.
@@ -3980,6 +4041,42 @@ static void gif_lzw_entry(const char *name, bool on_device, size_t frames, size_
     });
 }
 
+// index maps deflated as PNG image data (include/patolette_amd.h): the arguments, then run_png_deflate
+static void png_deflate_entry(bool on_device, size_t frames, size_t width, size_t height, const unsigned char *maps, const int32_t *rects,
+                              size_t segment, unsigned char *out, size_t capacity, uint64_t *offsets, uint32_t *adler, int *exit_code) {
+    const ArgCheck arg{"patolette_amd_png_deflate", exit_code};
+    if (!arg.shape(frames, width, height)) return;
+    if (!maps) return (void)arg.fail(-1, "no maps");
+    if (!offsets) return (void)arg.fail(-1, "no offsets");
+    if (!adler) return (void)arg.fail(-1, "no adler");
+    if (!out && capacity > 0) return (void)arg.fail(-1, "no out");
+    if (segment > kDeflateSegmentMax) return (void)arg.fail(-1, "segment must be 0 (the default) or lie in [1, 32768]");
+    const size_t seg = segment ? segment : kDeflateSegment;
+    std::vector<LzwFrame> recs;
+    std::vector<unsigned long long> bases;
+    try { recs.resize(frames + 1); bases.resize(frames + 1); } catch (const std::bad_alloc &) { return (void)arg.fail(-1, "no memory for the frames' table"); }
+    size_t S = 0, cap = 0, bound = 0, at = 0;                              // (S <= 2 * frames * width * height <= 3.2e9: checked at the launch)
+    for (size_t f = 0; f < frames; f++) {
+        long long x0 = 0, y0 = 0, w = (long long)width, h = (long long)height;
+        if (rects) { x0 = rects[4 * f]; y0 = rects[4 * f + 1]; w = rects[4 * f + 2]; h = rects[4 * f + 3]; }
+        if (x0 < 0 || y0 < 0 || w < 1 || h < 1 || x0 + w > (long long)width || y0 + h > (long long)height)
+            return (void)arg.fail(-1, "every rectangle must lie inside the frame and have w, h >= 1");
+        const size_t flen = deflate_filtered((size_t)w, (size_t)h), nseg = ceil_div(flen, seg);   // (flen <= 2 * 1.6e9: 32 bits)
+        recs[f] = LzwFrame{(unsigned)x0, (unsigned)y0, (unsigned)w, (unsigned)flen, (unsigned)S};
+        bases[f] = at;
+        at += flen;
+        S += nseg;
+        cap = std::max(cap, flen);
+        bound += deflate_frame_bound(flen, nseg);
+    }
+    if (S >> 31) return (void)arg.fail(-4, "frames * width * height is too big for this segment");
+    recs[frames] = LzwFrame{0, 0, 0, 0, (unsigned)S};
+    bases[frames] = at;
+    *exit_code = guarded([&](Engine &E) {
+        run_png_deflate(E, on_device, frames, width, height, maps, recs, bases, seg, cap, bound, out, capacity, offsets, adler);
+    });
+}
+
 // the lossy coder's table for a palette (include/patolette_amd.h): host code from end to end -- no engine, no device
 static void gif_neighbours_entry(const double *palette, const unsigned char *palette_u8, size_t palette_rows, int transparent_index, double tolerance,
                                  int max_neighbours, unsigned char *near_out, int *exit_code) {
@@ -4134,6 +4231,16 @@ void patolette_amd_gif_lzw(size_t frames, size_t width, size_t height, const uns
 void patolette_amd_gif_lzw_device(size_t frames, size_t width, size_t height, const unsigned char *d_maps, const int32_t *rects, int min_code_size,
                                   size_t segment, unsigned char *out, size_t capacity, uint64_t *offsets, int *exit_code) {
     gif_lzw_entry("patolette_amd_gif_lzw", true, frames, width, height, d_maps, rects, min_code_size, segment, nullptr, out, capacity, offsets, exit_code);
+}
+
+void patolette_amd_png_deflate(size_t frames, size_t width, size_t height, const unsigned char *maps, const int32_t *rects, size_t segment,
+                               unsigned char *out, size_t capacity, uint64_t *offsets, uint32_t *adler, int *exit_code) {
+    png_deflate_entry(false, frames, width, height, maps, rects, segment, out, capacity, offsets, adler, exit_code);
+}
+
+void patolette_amd_png_deflate_device(size_t frames, size_t width, size_t height, const unsigned char *d_maps, const int32_t *rects, size_t segment,
+                                      unsigned char *out, size_t capacity, uint64_t *offsets, uint32_t *adler, int *exit_code) {
+    png_deflate_entry(true, frames, width, height, d_maps, rects, segment, out, capacity, offsets, adler, exit_code);
 }
 
 void patolette_amd_gif_lzw_lossy(size_t frames, size_t width, size_t height, const unsigned char *maps, const int32_t *rects, int min_code_size,
