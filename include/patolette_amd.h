@@ -323,7 +323,8 @@ void patolette_amd_frame_deltas_device(size_t frames, size_t width, size_t heigh
  * Kernels: k_rgba_vanish, one launch for every frame's V and the flag; then k_frame_delta_rgba once per frame on the library's
  *   stream -- rects[f - 1] is a grid-wide result that frame f's canvas needs, so the chain over frames is a chain of launches; no
  *   host turn and no wait in between.  The host unites C and V once at the end.
- * Out of scope: disposal 3, local colour tables. */
+ * Out of scope: disposal 3; a colour table per frame (patolette_amd_frame_deltas_local has them for maps without a transparent
+ *   entry of their own). */
 void patolette_amd_frame_deltas_rgba(size_t frames, size_t width, size_t height, const void *palette_maps, int map_elem_bytes,
                                      size_t palette_rows, const unsigned char *pixels, int channels, const double *palette,
                                      const unsigned char *palette_u8, double tolerance, int loop, void *delta_maps, void *shown_maps,
@@ -339,6 +340,71 @@ void patolette_amd_frame_deltas_rgba_device(size_t frames, size_t width, size_t 
  * on an MI355X); otherwise one.  1 takes four wherever sizes and addresses allow, 0 never, -1 restores that rule.  Same results
  * either way.  Process-wide; returns the previous mode. */
 int patolette_amd_debug_delta_quad(int mode);
+
+/* ---- frame deltas with a colour table per frame: colour-keyed, for GIF local colour tables -------
+ * patolette_amd_frame_deltas for a clip whose frames (or scenes) each have a palette of their own.  Indices of two tables do not
+ * compare, so the canvas is what a viewer's canvas is: a colour.
+ *   frames, width, height, pixels, channels, tolerance, rects, changed, exit_code and the host / device flavours: as
+ *       patolette_amd_frame_deltas takes them; the same pixel cap.  n = width * height.
+ *   palette_maps: m[f][p], frames x n elements of ONE byte (a GIF table has at most 256 rows: there is no map_elem_bytes).
+ *   palettes_u8: host memory, palette_count x palette_rows x 3 bytes: P = palette_count tables of K = palette_rows rows each, K in
+ *       [1, 255], P in [1, 65536].  Bytes only: a GIF stores bytes, and the exact mode compares bytes.
+ *   palette_of: host memory, int32[frames], each in [0, P): frame f is drawn with table g(f) = palette_of[f] -- a palette per scene,
+ *       per frame, or any grouping.  NULL: g(f) = f, which requires P == frames.
+ *   transparent_index T, in [K, 255]: the one index no table uses, the same in every frame.
+ *   col(f, a): the three bytes of row a of table g(f).
+ *
+ *   frame 0:      delta[0] = m[0]; the canvas colour is C[p] = col(0, m[0][p]); shown_rgb[0][p] = C[p];
+ *                 rects[0] = (0, 0, width, height), changed[0] = n.
+ *   frame f >= 1, every position p on its own, with a = m[f][p]:
+ *     keep = (col(f, a) == C[p]) || (tolerance > 0 && D <= tolerance * tolerance)        (the equality: over the three bytes)
+ *     D    = exactly the D of patolette_amd_frame_deltas: the SOURCE pixel pixels[f][p] against the colour ON THE CANVAS, both
+ *            through sRGB -> ICtCp as that entry converts a pixel and a row of a byte palette, D = (d0*d0 + d1*d1) + d2*d2 in f64,
+ *            no FMA; evaluated only where the bytes differ.  The canvas colour's ICtCp value is that of the palette row it was drawn
+ *            from, prepared as patolette_amd_frame_deltas prepares palette_u8; equal bytes give equal values, whichever row.
+ *     keep:       delta[f][p] = T, the canvas stays.       otherwise: delta[f][p] = a, C[p] = col(f, a).       Both: shown_rgb[f][p] = C[p].
+ *   rects[f], changed[f]: as patolette_amd_frame_deltas -- the tight box of delta[f] != T, (0, 0, 0, 0) when there is none; their number.
+ *
+ * Outputs, each may be NULL: delta_maps (frames x n bytes; may be palette_maps itself); shown_rgb (frames x n x 3 bytes, interleaved:
+ *   what a viewer shows after each frame -- colours, because indices of different tables do not compare); rects (int32[4 * frames]);
+ *   changed (uint64[frames]).  The *_device flavour takes device pointers for palette_maps, pixels, delta_maps and shown_rgb;
+ *   palettes_u8, palette_of, rects and changed stay host memory.
+ * tolerance == 0: pixels and channels are not read.
+ * Consequences:
+ *   (a) Drawing delta[f] with table g(f) over the canvas, skipping T, shows shown_rgb[f].
+ *   (b) tolerance == 0: shown_rgb[f][p] == col(f, m[f][p]).
+ *   (c) Every table identical: with pairwise distinct rows, delta_maps, rects and changed are those of patolette_amd_frame_deltas with
+ *       that table as palette_u8, bit for bit, at every tolerance (P == 1 is the simplest case).  With duplicate rows, a position
+ *       whose index changed but whose colour did not is kept here and drawn there.
+ *   (d) tolerance > 0: every shown colour is the frame's own choice or lies within `tolerance` of THAT frame's source pixel; nothing
+ *       accumulates.
+ * Every element must be below K: one that is not is never used as an address, the kernel raises a flag, and the call fails with -1 and
+ *   a "patolette_amd_frame_deltas_local:" text (both modes; what the outputs then hold is not defined).
+ * Exit codes: -2 and -4 as patolette_amd_frame_deltas; -1 (with a "patolette_amd_frame_deltas_local:" text in
+ *   patolette_amd_last_error) for no maps, K, P or T out of range, no palettes, a palette_of value out of range, NULL palette_of with
+ *   P != frames, a tolerance that is negative or not finite, in the lossy mode bad channels or missing pixels; or the flag above.
+ *   A failed call leaves the thread's engine usable.
+ * Statistics: as patolette_amd_frame_deltas.
+ * One kernel for all frames (k_frame_deltas_local, then k_delta_boxes as there): a lane keeps the canvas colour's packed word and, for
+ *   the lossy compare, the row it came from; the P K rows' words are staged in LDS where they are few, read from global memory
+ *   otherwise.  The outputs are a function of the arguments alone.
+ * Out of scope: maps with a transparent entry of their own and per-frame disposal (a local patolette_amd_frame_deltas_rgba). */
+void patolette_amd_frame_deltas_local(size_t frames, size_t width, size_t height, const unsigned char *palette_maps,
+                                      const unsigned char *palettes_u8, size_t palette_count, size_t palette_rows, const int32_t *palette_of,
+                                      size_t transparent_index, const unsigned char *pixels, int channels, double tolerance,
+                                      unsigned char *delta_maps, unsigned char *shown_rgb, int32_t *rects, uint64_t *changed, int *exit_code);
+void patolette_amd_frame_deltas_local_device(size_t frames, size_t width, size_t height, const unsigned char *d_palette_maps,
+                                             const unsigned char *palettes_u8, size_t palette_count, size_t palette_rows,
+                                             const int32_t *palette_of, size_t transparent_index, const unsigned char *d_pixels, int channels,
+                                             double tolerance, unsigned char *d_delta_maps, unsigned char *d_shown_rgb, int32_t *rects,
+                                             uint64_t *changed, int *exit_code);
+
+/* TESTS ONLY: where k_frame_deltas_local reads the tables' packed rows.  -1: the launcher's rule (LDS when P * K is at most 4096 and at
+ * most 256 * frames, so that a block's fill costs no more than its element loads), 0: always global memory, 1: LDS whenever P * K is
+ * at most 4096.  Same results.  Process-wide; returns the previous mode.  patolette_amd_debug_delta_local_route: what the last launch
+ * of this process took -- 1 LDS, 0 global memory, -1 before the first. */
+int patolette_amd_debug_delta_local_tables(int mode);
+int patolette_amd_debug_delta_local_route(void);
 
 /* ---- measure: what a map costs, per palette entry and per frame ---------------------------------
  * The error of any map this library (or anything else) made of 8-bit pixels on a palette, without pixels, maps or quantized images
@@ -436,7 +502,7 @@ void patolette_amd_measure_device(size_t frames, size_t width, size_t height, co
  * Statistics: the ms_* fields as for a remap (ms_map: the kernels and the offsets), every other field 0.
  * Three kernels, one launch each for all frames, integers only: k_lzw_segments (a wavefront per segment, its dictionary a hash table in
  *   LDS), k_lzw_offsets (the segments' and frames' places), k_lzw_pack (the segments' bits shifted together).
- * Out of scope: the container (Python: write_gif), interlaced images, local colour tables. */
+ * Out of scope: the container (Python: write_gif, local colour tables included: this stage reads no palette), interlaced images. */
 void patolette_amd_gif_lzw(size_t frames, size_t width, size_t height, const unsigned char *maps, const int32_t *rects,
                            int min_code_size, size_t segment, unsigned char *out, size_t capacity, uint64_t *offsets, int *exit_code);
 void patolette_amd_gif_lzw_device(size_t frames, size_t width, size_t height, const unsigned char *d_maps, const int32_t *rects,

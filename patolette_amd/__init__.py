@@ -22,6 +22,8 @@ and, for animations with transparency, `remap_rgba` (RGBA images or frames onto 
 entry) and `quantize_rgba_frames` (one shared palette and one transparent index for all frames, composed from `quantize_rgba`'s
 palette stage and `remap_rgba`) and `frame_deltas_rgba` (the deltas of such maps: 0 means "leave the canvas", every frame gets its
 own disposal, and the rectangle also covers what the next frame makes transparent);
+and `frame_deltas_local`, the deltas of a clip whose frames or scenes each have a palette of their own -- the canvas is a colour --
+which `write_gif(palette_of=...)` writes with GIF local colour tables;
 and `gif_lzw`, which LZW-compresses maps or deltas on the device, with `write_gif`, the GIF89a container around it, and `gif_lzw_lossy`
 with `gif_neighbours`, the lossy coder that lets a nearly equal colour continue a dictionary match;
 and `ColorHistogram`, for pixels that arrive in chunks (a long clip, a directory of images): an exact colour histogram kept on the
@@ -565,6 +567,84 @@ def frame_deltas(maps, palette, transparent_index=None, frames=None, tolerance=0
     return (True, d.deltas, d.rects, d.changed.astype(np.int64), d.shown, message)
 
 
+def _local_tables(palettes, palette_of, count, max_rows, name="palettes"):
+    """Per-frame palettes as the contiguous (P, K, 3) uint8 stack and the frames' tables as (count,) int32: `palette_of` None means
+    frame f takes table f, which needs P == count."""
+    pal = np.asarray(palettes.detach().cpu().numpy() if hasattr(palettes, "detach") else palettes)
+    if pal.ndim != 3 or pal.shape[2] != 3 or pal.dtype != np.uint8 or pal.shape[0] < 1 or pal.shape[1] < 1:
+        raise ValueError("%s must be a (P, K, 3) uint8 array: P tables of K rows" % name)
+    if pal.shape[1] > max_rows:
+        raise ValueError("a GIF colour table holds at most 256 rows" if max_rows == 256 else
+                         "every table may have at most %d rows: a one-byte map needs an index no table uses" % max_rows)
+    if pal.shape[0] > 65536:
+        raise ValueError("%s may hold at most 65536 tables" % name)
+    if palette_of is None:
+        if pal.shape[0] != count:
+            raise ValueError("without palette_of every frame has its own table: %d tables do not match %d frames" % (pal.shape[0], count))
+        of = np.arange(count, dtype=np.int32)
+    else:
+        of = np.asarray(palette_of.detach().cpu().numpy() if hasattr(palette_of, "detach") else palette_of)
+        if of.shape != (count,) or of.dtype.kind not in "iu" or of.dtype == np.bool_:
+            raise ValueError("palette_of must be None or %d integers, the table of every frame" % count)
+        if np.any(of < 0) or np.any(of >= pal.shape[0]):
+            raise ValueError("every palette_of value must lie in [0, %d), the number of tables" % pal.shape[0])
+        of = np.ascontiguousarray(of.astype(np.int32))
+    return np.ascontiguousarray(pal), of
+
+
+def frame_deltas_local(maps, palettes, palette_of=None, transparent_index=None, frames=None, tolerance=0.0, want_shown=False):
+    """`frame_deltas` for a clip whose frames, or scenes, each have a palette of their own (additive; include/patolette_amd.h:
+    patolette_amd_frame_deltas_local) -- what `quantize_u8_batch` or `quantize_frames` per scene return.  Indices of two tables do not
+    compare, so the canvas is a colour, as a viewer's is: a position is transparent in frame f iff its entry's three bytes equal the
+    colour on the canvas (tolerance 0), or the colour on the canvas lies within `tolerance` (ICtCp) of the frame's source pixel.
+
+      * maps: (F, H, W) uint8 numpy array, or a torch uint8 CUDA tensor (then the deltas and the shown colours stay on its device).
+      * palettes: (P, K, 3) uint8, K <= 255: P tables of K rows.
+      * palette_of: None (frame f is drawn with table f; P == F), or F integers in [0, P): the table of every frame -- a palette
+        per scene is `palette_of=[0, 0, 0, 1, 1, 1]`.
+      * transparent_index: the one index no table uses, K <= T <= 255, the same in every frame; default K.
+      * frames, tolerance: as `frame_deltas` takes them.
+      * want_shown: also return what a viewer shows after every frame, as colours.
+    Drawing deltas[f] with table palette_of[f] over the canvas, skipping the transparent index, shows shown_rgb[f]; at tolerance 0 that
+    is the frame's own colours.  With one table whose rows are all distinct the deltas are `frame_deltas`' own.
+    `write_gif(file, deltas, palettes, rects, transparent_index=T, palette_of=palette_of)` writes them with local colour tables.
+    Out of scope: maps with a transparent entry of their own and per-frame disposal (a local `frame_deltas_rgba`); APNG, which has one
+    PLTE; `measure` across tables (measure per group of frames, or compare `shown_rgb` with the source).
+
+    Returns (success, deltas (F,H,W) uint8, rects (F,4) int32, changed (F,) int64, shown_rgb (F,H,W,3) uint8 or None, message)."""
+    T, pal, of = None, None, None
+
+    def palette_rules(tol, elem, elem_max):
+        nonlocal T, pal, of
+        if elem != 1:
+            raise ValueError("maps must be uint8: a GIF colour table has at most 256 rows")
+        pal, of = _local_tables(palettes, palette_of, int(maps.shape[0]), 255)
+        rows = pal.shape[1]
+        if transparent_index is not None and (isinstance(transparent_index, (bool, np.bool_)) or not isinstance(transparent_index, (int, np.integer))):
+            raise ValueError("transparent_index must be None or an integer")
+        T = rows if transparent_index is None else int(transparent_index)
+        if not rows <= T <= 255:
+            raise ValueError("transparent_index must lie in [%d, 255]: an index no table uses, in a one-byte element" % rows)
+        return None, None, rows
+
+    d = _delta_setup(maps, tolerance, frames, False, palette_rules)
+    shown = None
+    if want_shown:
+        shape = (d.count, d.height, d.width, 3)
+        if d.dev is None:
+            shown = np.zeros(shape, dtype=np.uint8)
+        else:
+            import torch
+            shown = torch.zeros(shape, dtype=torch.uint8, device=d.dev)
+    _call("patolette_amd_frame_deltas_local", d.dev, d.count, d.width, d.height, _vp(d.m), _vp(pal), pal.shape[0], d.rows,
+          of.ctypes.data_as(C.POINTER(C.c_int32)), T, _vp(d.px), d.channels, d.tol, _vp(d.deltas), _vp(shown),
+          d.rects.ctypes.data_as(C.POINTER(C.c_int32)), d.changed.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(d.code))
+    message = _delta_message("patolette_amd_frame_deltas_local", d.code.value)
+    if d.code.value != 0:
+        return (False, None, None, None, None, message)
+    return (True, d.deltas, d.rects, d.changed.astype(np.int64), shown, message)
+
+
 def frame_deltas_rgba(maps, palette, frames=None, tolerance=0.0, loop=True, want_shown=False, transparent_index=None):
     """`frame_deltas` for maps whose index 0 is the transparent entry -- those of `remap_rgba` / `quantize_rgba_frames` (additive;
     include/patolette_amd.h: patolette_amd_frame_deltas_rgba).  In the deltas 0 means "leave the canvas as it is", which is what a GIF
@@ -859,7 +939,31 @@ def gif_lzw_lossy(maps, near, rects=None, min_code_size=8, segment=None, want_co
     return (True, data, offsets, coded.reshape(tuple(maps.shape)) if want_coded else None, message)
 
 
-def write_gif(file, maps, palette_u8, rects=None, transparent_index=None, delay=0.04, loop=0, disposal=1, segment=None, near=None):
+def _gif_lossy_by_table(m, near, tables, of, r, mcs, segment):
+    """`gif_lzw_lossy` for frames with a table each: `near` is a (tables, 256, 16) stack, the frames are grouped by their table `of`,
+    coded once per table in use, and the streams put back in frame order -> what `gif_lzw` returns."""
+    stack = np.asarray(near.detach().cpu().numpy() if hasattr(near, "detach") else near)
+    if stack.shape != (tables, 256, 16) or stack.dtype != np.uint8:
+        raise ValueError("with (P, K, 3) tables near must be a (P, 256, 16) uint8 stack: one `gif_neighbours` table per palette")
+    used = [int(g) for g in np.unique(of)]
+    checked = {g: _gif_near(stack[g], mcs) for g in used}
+    streams = [None] * len(of)
+    message = ""
+    for g in used:
+        which = np.nonzero(of == g)[0]
+        group = m[which] if not hasattr(m, "detach") else m[__import__("torch").as_tensor(which, device=m.device)]
+        ok, data, offsets, _, message = gif_lzw_lossy(group, checked[g], r[which], mcs, segment)
+        if not ok:
+            return (False, None, None, message)
+        for i, f in enumerate(which):
+            streams[f] = data[int(offsets[i]):int(offsets[i + 1])]
+    offsets = np.zeros(len(of) + 1, dtype=np.int64)
+    offsets[1:] = np.cumsum([len(x) for x in streams])
+    return (True, np.concatenate(streams), offsets, message)
+
+
+def write_gif(file, maps, palette_u8, rects=None, transparent_index=None, delay=0.04, loop=0, disposal=1, palette_of=None, segment=None,
+              near=None):
     """Write an animation's maps as a GIF89a file: a small pure-Python container around `gif_lzw`, so that
     `quantize_frames(frames, 255, dither="ordered")` -> `frame_deltas` -> `write_gif` yields a file any viewer opens.
 
@@ -875,16 +979,27 @@ def write_gif(file, maps, palette_u8, rects=None, transparent_index=None, delay=
         `gif_lzw_lossy` and the file is smaller.  A shown entry then lies within that tolerance (ICtCp) of the MAP's entry, not of the
         source pixel: behind `frame_deltas(tolerance=t1)` within t1 + tolerance of its frame's source; nothing accumulates over the
         frames.  `measure` on the composited `coded` maps of `gif_lzw_lossy` gives the true cost.
-    Out of scope: local colour tables, interlace.  `write_apng` writes the same animations as APNG."""
+      * palette_u8 may also be (P, K, 3): P tables, with palette_of the table of every frame as `frame_deltas_local` takes it (None:
+        frame f takes table f, P == F).  Table palette_of[0] is written as the global colour table, and every frame with another
+        table carries it as a local colour table behind its image descriptor.  All tables are padded to the same power of two, so
+        the file has one min_code_size and one `gif_lzw` call codes every frame.  `near` is then a (P, 256, 16) stack, one
+        `gif_neighbours` table per palette: the frames are coded by `gif_lzw_lossy` group by group, once per table in use.
+    Out of scope: interlace; a transparent entry of the maps' own together with local tables (`frame_deltas_rgba` has no local
+    variant).  `write_apng` writes the same animations as APNG, which has one PLTE and so no per-frame tables."""
     import os
     m, shape, dev = _gif_maps(maps)
     count, height, width = shape
     pal = np.asarray(palette_u8.detach().cpu().numpy() if hasattr(palette_u8, "detach") else palette_u8)
-    if pal.ndim != 2 or pal.shape[1] != 3 or pal.dtype != np.uint8 or pal.shape[0] < 1:
-        raise ValueError("palette_u8 must be a (K, 3) uint8 array")
-    if pal.shape[0] > 256:
+    of = None
+    if pal.ndim == 3:
+        pal, of = _local_tables(pal, palette_of, count, 256, "palette_u8")
+    elif palette_of is not None:
+        raise ValueError("palette_of needs palette_u8 as (P, K, 3) tables")
+    elif pal.ndim != 2 or pal.shape[1] != 3 or pal.dtype != np.uint8 or pal.shape[0] < 1:
+        raise ValueError("palette_u8 must be a (K, 3) uint8 array, or (P, K, 3) tables with palette_of")
+    if pal.shape[-2] > 256:
         raise ValueError("a GIF colour table holds at most 256 rows")
-    need = pal.shape[0]
+    need = pal.shape[-2]
     if transparent_index is not None:
         if isinstance(transparent_index, (bool, np.bool_)) or not isinstance(transparent_index, (int, np.integer)) \
                 or not 0 <= int(transparent_index) <= 255:
@@ -914,12 +1029,15 @@ def write_gif(file, maps, palette_u8, rects=None, transparent_index=None, delay=
     _gif_segment(segment)
     if near is None:
         ok, data, offsets, message = gif_lzw(m, r, mcs, segment)
-    else:
+    elif of is None:
         ok, data, offsets, _, message = gif_lzw_lossy(m, _gif_near(near, mcs), r, mcs, segment)
+    else:
+        ok, data, offsets, message = _gif_lossy_by_table(m, near, pal.shape[0], of, r, mcs, segment)
     if not ok:
         raise RuntimeError(message)
-    table = np.zeros((1 << bits, 3), dtype=np.uint8)
-    table[:pal.shape[0]] = pal
+    tables = np.zeros(((1 if of is None else pal.shape[0]), 1 << bits, 3), dtype=np.uint8)
+    tables[:, :pal.shape[-2]] = pal
+    table = tables[0 if of is None else of[0]]
     u16 = lambda v: int(v).to_bytes(2, "little")
     parts = [b"GIF89a", u16(width), u16(height), bytes([0x80 | 7 << 4 | (bits - 1), 0, 0]), table.tobytes()]
     if loop is not None:
@@ -929,7 +1047,10 @@ def write_gif(file, maps, palette_u8, rects=None, transparent_index=None, delay=
     for f in range(count):
         parts += [b"\x21\xf9\x04", bytes([disposals[f] << 2 | flag]), u16(int(np.round(delays[f] * 100))), bytes([tidx, 0])]
         x0, y0, w, h = (int(v) for v in r[f])
-        parts += [b"\x2c", u16(x0), u16(y0), u16(w), u16(h), b"\x00", bytes([mcs])]
+        if of is None or of[f] == of[0]:
+            parts += [b"\x2c", u16(x0), u16(y0), u16(w), u16(h), b"\x00", bytes([mcs])]
+        else:                                                      # a local colour table, behind the descriptor
+            parts += [b"\x2c", u16(x0), u16(y0), u16(w), u16(h), bytes([0x80 | (bits - 1)]), tables[of[f]].tobytes(), bytes([mcs])]
         stream = raw[int(offsets[f]):int(offsets[f + 1])]
         for i in range(0, len(stream), 255):
             block = stream[i:i + 255]
@@ -1634,6 +1755,7 @@ __all__ = [
     "ordered_spread",
     "frame_deltas",
     "frame_deltas_rgba",
+    "frame_deltas_local",
     "measure",
     "psnr",
     "gif_lzw",

@@ -123,6 +123,11 @@ SYMBOLS = {
                                                       dp, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32),
                                                       C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
     "patolette_amd_debug_delta_quad": (C.c_int, [C.c_int]),
+    **_pair("patolette_amd_frame_deltas_local", None, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                                       C.POINTER(C.c_int32), C.c_size_t, C.c_void_p, C.c_int, C.c_double, C.c_void_p,
+                                                       C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+    "patolette_amd_debug_delta_local_tables": (C.c_int, [C.c_int]),
+    "patolette_amd_debug_delta_local_route": (C.c_int, []),
     **_pair("patolette_amd_measure", None, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, dp, C.c_void_p,
                                             C.c_size_t, C.c_longlong, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
                                             C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), dp, dp,

@@ -1,4 +1,5 @@
-// delta.h -- launchers of the frame-delta kernels (delta.hip): plain maps, and maps whose index 0 is a transparent entry.
+// delta.h -- launchers of the frame-delta kernels (delta.hip): plain maps, plain maps with a colour table per frame, and maps whose
+// index 0 is a transparent entry.
 #pragma once
 
 #include "common.h"
@@ -27,6 +28,25 @@ inline size_t frame_deltas_masks(size_t frames, size_t n) { return frames * ceil
 void launch_frame_deltas(const void *d_maps, int elem_bytes, size_t frames, size_t width, size_t height, size_t rows, size_t T, bool lossy,
                          const unsigned char *d_px, int channels, const double *d_pal, double tol2, void *d_delta, void *d_shown,
                          unsigned long long *d_masks, unsigned long long *d_words, hipStream_t s);
+
+// colour words a block of k_frame_deltas_local holds in LDS at most (16 KB beside the lossy mode's 30 KB: five blocks a CU stay)
+constexpr int kLocalLdsRows = 4096;
+
+// The frame deltas of maps with a colour table per frame (include/patolette_amd.h, patolette_amd_frame_deltas_local): `frames` maps of
+// one-byte elements; frame f indexes table d_pof[f] (each in [0, P): the caller has checked them) of P tables of K rows, K in
+// [1, 255]; T in [K, 255].  d_rows: the P K rows' packed RGB words (given.h, given_row_words); d_pal (lossy only): the P K rows in
+// ICtCp, planar (P K,3).  d_delta (frames x n bytes, may be d_maps) and d_shown (frames x n x 3 bytes, colours) may be null.  d_masks,
+// d_words: as launch_frame_deltas takes them, and the words come out in its layout.  One launch of k_frame_deltas_local, then
+// k_delta_boxes.  The rows' words go to LDS when they number at most kLocalLdsRows and at most 256 per frame, otherwise they are
+// read from global memory; same results.
+void launch_frame_deltas_local(const unsigned char *d_maps, size_t frames, size_t width, size_t height, size_t K, size_t P, size_t T, bool lossy,
+                               const int *d_pof, const unsigned *d_rows, const unsigned char *d_px, int channels, const double *d_pal, double tol2,
+                               unsigned char *d_delta, unsigned char *d_shown, unsigned long long *d_masks, unsigned long long *d_words, hipStream_t s);
+// TESTS ONLY: where k_frame_deltas_local reads the rows' words: -1 the launcher's rule, 0 global memory, 1 LDS whenever they number at
+// most kLocalLdsRows.  Same results.  Returns the previous mode.  delta_local_route: what the last launch took, 1 LDS, 0 global
+// memory, -1 before the first one.
+int delta_debug_local_tables(int mode);
+int delta_local_route();
 
 // what the kernels of the RGBA flavour leave for the host, as unsigned long long words: per frame and slot the box of the changed
 // positions (C), then per frame and slot the box of the positions that vanish in the next frame (V), both as above and 16 bytes a

@@ -1,4 +1,5 @@
-// delta.hip -- frame deltas of an animation's index maps on gfx950: include/patolette_amd.h, patolette_amd_frame_deltas.
+// delta.hip -- frame deltas of an animation's index maps on gfx950: include/patolette_amd.h, patolette_amd_frame_deltas, its RGBA
+// flavour (further down) and the one with a colour table per frame (k_frame_deltas_local, between the two).
 //
 // The step is a chain over frames and independent per position, so a lane owns one position, walks all frames and keeps the canvas
 // entry in a register: one launch, no canvas buffer, element bytes x (1 + outputs) of traffic per pixel-frame.  The loads of a
@@ -47,6 +48,21 @@ __device__ __forceinline__ void store_elems(ElemT *at, const unsigned (&in)[V]) 
         typename Quad<ElemT>::type q;
         q.x = (ElemT)in[0]; q.y = (ElemT)in[1]; q.z = (ElemT)in[2]; q.w = (ElemT)in[3];
         *reinterpret_cast<typename Quad<ElemT>::type *>(at) = q;
+    }
+}
+
+// A frame's ballots, by every lane of the wavefront: bit i of word w of `frame_masks` = position 64 w + i changed.  changes: bit j says
+// that this lane's position p + j did.
+template <int V>
+__device__ __forceinline__ void store_ballot(unsigned changes, unsigned lane, size_t p, size_t nw, unsigned long long *frame_masks) {
+    if constexpr (V == 1) {
+        const unsigned long long moved = __ballot(changes != 0);
+        if (lane == 0 && (p >> 6) < nw) frame_masks[p >> 6] = moved;
+    } else {                                                     // sixteen lanes hold a word's 64 positions, four bits each
+        unsigned long long w = (unsigned long long)changes << (4 * (lane & 15u));
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) w |= __shfl_xor(w, o);
+        if ((lane & 15u) == 0 && (p >> 6) < nw) frame_masks[p >> 6] = w;
     }
 }
 
@@ -113,16 +129,7 @@ __global__ __launch_bounds__(256) void k_frame_deltas(const ElemT *maps, size_t 
                 if (delta) store_elems<ElemT, V>(delta + at, out);
                 if (shown) store_elems<ElemT, V>(shown + at, c);
             }
-            // the ballots: bit i of word w of a frame = position 64 w + i
-            if constexpr (V == 1) {
-                const unsigned long long moved = __ballot(changes != 0);
-                if (lane == 0 && (p >> 6) < nw) masks[(f + u) * nw + (p >> 6)] = moved;
-            } else {                                             // sixteen lanes hold a word's 64 positions, four bits each
-                unsigned long long w = (unsigned long long)changes << (4 * (lane & 15u));
-#pragma unroll
-                for (int o = 8; o > 0; o >>= 1) w |= __shfl_xor(w, o);
-                if ((lane & 15u) == 0 && (p >> 6) < nw) masks[(f + u) * nw + (p >> 6)] = w;
-            }
+            store_ballot<V>(changes, lane, p, nw, masks + (f + u) * nw);
         }
 #pragma unroll
         for (int u = 0; u < A; u++)
@@ -213,6 +220,158 @@ void launch_frame_deltas(const void *d_maps, int elem_bytes, size_t frames, size
             hipLaunchKernelGGL((k_frame_deltas<ElemT, decltype(is_lossy)::value, V>), (unsigned)ceil_div(n, (size_t)256 * V), 256, 0, s,
                                (const ElemT *)d_maps, frames, n, nw, (unsigned)rows, (ElemT)T, d_px, channels, d_pal, tol2, (ElemT *)d_delta,
                                (ElemT *)d_shown, d_masks, d_flag);
+        });
+        HIP_CHECK(hipGetLastError());
+    }
+    if (frames > 1) {
+        KTIME("k_delta_boxes", s, 8.0 * nw * (frames - 1));
+        hipLaunchKernelGGL(k_delta_boxes, (unsigned)(box_blocks * (frames - 1)), 256, 0, s, d_masks, frames, n, nw, (unsigned)width, (unsigned)height,
+                           box_blocks, d_words);
+        HIP_CHECK(hipGetLastError());
+    }
+}
+
+// --------------------------------------------------------------------------------------------
+// Per-frame palettes (include/patolette_amd.h, patolette_amd_frame_deltas_local): frame f's elements index table pof[f] of P tables of
+// K rows, so the canvas a lane keeps is a colour -- the row's packed RGB word -- and, for the lossy compare, the number g K + a of the
+// row it was drawn from.  k_frame_deltas' walk otherwise: one launch, the next group's elements loaded ahead, one ballot word per
+// wavefront and frame, k_delta_boxes behind it.  Every step looks a row's word up: the P K words lie in LDS where launch_frame_deltas_local
+// finds that worth a block's fill (Lds), in global memory otherwise -- they are L2-resident, a frame's table mostly L1-resident.
+// --------------------------------------------------------------------------------------------
+// TESTS ONLY (patolette_amd_debug_delta_local_tables): -1 the rule of launch_frame_deltas_local, 0 global memory, 1 LDS wherever they fit
+static std::atomic<int> g_local_tables{-1}, g_local_route{-1};
+int delta_debug_local_tables(int mode) { return g_local_tables.exchange(mode < 0 ? -1 : (mode ? 1 : 0)); }
+int delta_local_route() { return g_local_route.load(std::memory_order_relaxed); }
+
+// V positions' colour words (r in the low byte) as 3 V interleaved bytes; V == 4: `at` is 4-byte aligned (12 bytes, three words)
+template <int V>
+__device__ __forceinline__ void store_rgb(unsigned char *at, const unsigned (&c)[V]) {
+    if constexpr (V == 1) { at[0] = (unsigned char)c[0]; at[1] = (unsigned char)(c[0] >> 8); at[2] = (unsigned char)(c[0] >> 16); }
+    else {
+        unsigned *q = reinterpret_cast<unsigned *>(at);
+        q[0] = c[0] | c[1] << 24; q[1] = c[1] >> 8 | c[2] << 16; q[2] = c[2] >> 16 | c[3] << 8;
+    }
+}
+
+// maps, delta: one-byte elements (delta may be maps).  palw: the P K rows' words (given.h, given_row_words), PK = P K of them; pof: the
+// frames' tables, each below P (the host has checked them); pal: the P K rows in ICtCp, planar (PK,3).  shown: 3 bytes a position.
+// An element that is not below K is never an address: row 0 of its frame's table stands in, and the flag fails the call.
+// Lds: PK * 4 bytes of dynamic LDS hold palw.
+template <bool Lossy, int V, bool Lds>
+__global__ __launch_bounds__(256) void k_frame_deltas_local(const unsigned char *maps, size_t F, size_t n, size_t nw, unsigned K, unsigned PK, unsigned T,
+                                                            const int *__restrict__ pof, const unsigned *__restrict__ palw,
+                                                            const unsigned char *__restrict__ px, int ch,
+                                                            const double *__restrict__ pal /* planar (PK,3), ICtCp */, double tol2,
+                                                            unsigned char *delta, unsigned char *shown, unsigned long long *masks, unsigned *flag) {
+    extern __shared__ unsigned s_words[];
+    constexpr int A = kDeltaAhead;
+    const unsigned tid = threadIdx.x, lane = tid & 63u;
+    if constexpr (Lds) for (unsigned j = tid; j < PK; j += 256) s_words[j] = palw[j];
+    if constexpr (Lossy) DeltaLossy::fill(pal, PK);
+    if constexpr (Lds || Lossy) __syncthreads();
+    auto row_word = [&](unsigned row) -> unsigned { if constexpr (Lds) return s_words[row]; else return palw[row]; };
+    const size_t p = ((size_t)blockIdx.x * 256 + tid) * V;       // the first of this lane's V positions
+    const bool active = p < n;                                   // (a lane past the end stays for the ballots)
+    unsigned c[V], cr[V];                                        // the canvas: the colour's word, and the row it was drawn from
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < V; j++) { c[j] = 0; cr[j] = 0; }
+    if (active) {
+        unsigned e[V];
+        load_elems<unsigned char, V>(maps + p, e);
+        const unsigned base = (unsigned)pof[0] * K;
+#pragma unroll
+        for (int j = 0; j < V; j++) {
+            const bool ok = e[j] < K;
+            bad |= !ok;
+            cr[j] = base + (ok ? e[j] : 0u);
+            c[j] = row_word(cr[j]);
+        }
+        if (delta) store_elems<unsigned char, V>(delta + p, e);
+        if (shown) store_rgb<V>(shown + 3 * p, c);
+    }
+    unsigned a[A][V], b[A][V];
+#pragma unroll
+    for (int u = 0; u < A; u++) {
+#pragma unroll
+        for (int j = 0; j < V; j++) a[u][j] = 0;
+        if (active && 1 + u < F) load_elems<unsigned char, V>(maps + (1 + u) * n + p, a[u]);
+    }
+    for (size_t f = 1; f < F; f += A) {
+#pragma unroll
+        for (int u = 0; u < A; u++) {
+#pragma unroll
+            for (int j = 0; j < V; j++) b[u][j] = 0;
+            if (active && f + A + u < F) load_elems<unsigned char, V>(maps + (f + A + u) * n + p, b[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < A; u++) {
+            if (f + u >= F) break;                               // (the same for every lane)
+            const size_t at = (f + u) * n + p;
+            const unsigned base = (unsigned)pof[f + u] * K;      // (uniform: a scalar load)
+            unsigned out[V], changes = 0;                        // bit j: this lane's position p + j changed
+#pragma unroll
+            for (int j = 0; j < V; j++) {
+                const unsigned e = a[u][j];
+                const bool ok = e < K;
+                bad |= active && !ok;
+                const unsigned r = base + (ok ? e : 0u);         // (a lane past the end: row 0 of the table, a valid address)
+                const unsigned w = row_word(r);
+                bool change = active && w != c[j];
+                if constexpr (Lossy) {
+                    if (change) {
+                        const unsigned char *q = px + (at + j) * (size_t)ch;
+                        if (DeltaLossy::dist2(cr[j], q, pal, PK) <= tol2) change = false;    // the canvas colour still serves
+                    }
+                }
+                if (change) { c[j] = w; cr[j] = r; changes |= 1u << j; }
+                out[j] = change ? e : T;
+            }
+            if (active) {
+                if (delta) store_elems<unsigned char, V>(delta + at, out);
+                if (shown) store_rgb<V>(shown + 3 * at, c);
+            }
+            store_ballot<V>(changes, lane, p, nw, masks + (f + u) * nw);
+        }
+#pragma unroll
+        for (int u = 0; u < A; u++)
+#pragma unroll
+            for (int j = 0; j < V; j++) a[u][j] = b[u][j];
+    }
+    if (__ballot(bad) && lane == 0) atomicOr(flag, 1u);
+}
+
+void launch_frame_deltas_local(const unsigned char *d_maps, size_t frames, size_t width, size_t height, size_t K, size_t P, size_t T, bool lossy,
+                               const int *d_pof, const unsigned *d_rows, const unsigned char *d_px, int channels, const double *d_pal, double tol2,
+                               unsigned char *d_delta, unsigned char *d_shown, unsigned long long *d_masks, unsigned long long *d_words, hipStream_t s) {
+    const size_t n = width * height, N = frames * n, nw = ceil_div(n, 64), PK = P * K;
+    if (N == 0) return;
+    const size_t box_blocks = ceil_div(nw, 256);
+    if (width >> 31 || height >> 31 || ceil_div(n, 256) >> 31 || (box_blocks * (frames - 1)) >> 31)
+        throw HipError("patolette_amd: frame deltas: a size does not fit the kernels' 32-bit fields");
+    if (K < 1 || K > 255 || T < K || T > 255 || P < 1 || P > 65536 || !d_pof || !d_rows)
+        throw HipError("patolette_amd: the local frame deltas need 1 .. 65536 tables of 1 .. 255 rows and a free index up to 255");
+    if (lossy && (!d_px || !d_pal)) throw HipError("patolette_amd: the lossy frame deltas need pixels and a palette");
+    HIP_CHECK(hipMemsetAsync(d_words, 0, frame_deltas_words(frames) * sizeof(unsigned long long), s));
+    unsigned *d_flag = reinterpret_cast<unsigned *>(d_words + frames * (size_t)kDeltaSlots * 3);
+    {
+        // The words in LDS: every block fills all P K of them, so only where that is no more than its lanes load elements anyway
+        // (256 a frame) and the block's LDS stays small enough for the SIMDs' eight wavefronts.
+        const int mode = g_local_tables.load(std::memory_order_relaxed);
+        const bool fits = PK <= (size_t)kLocalLdsRows;
+        const bool in_lds = fits && (mode < 0 ? PK <= 256 * frames : mode == 1);
+        g_local_route.store(in_lds ? 1 : 0, std::memory_order_relaxed);
+        KTIME("k_frame_deltas_local", s, (1.0 + (d_delta ? 1 : 0) + (d_shown ? 3 : 0) + (lossy ? channels : 0) + 0.125) * N);
+        const bool quad = delta_quad(n, (uintptr_t)d_maps | (uintptr_t)d_delta | (uintptr_t)d_shown, 1);
+        delta_dispatch(1, quad, lossy, [&](auto, auto v, auto is_lossy) {
+            constexpr int V = decltype(v)::value;
+            auto go = [&](auto lds) {
+                constexpr bool Lds = decltype(lds)::value;
+                hipLaunchKernelGGL((k_frame_deltas_local<decltype(is_lossy)::value, V, Lds>), (unsigned)ceil_div(n, (size_t)256 * V), 256,
+                                   Lds ? PK * sizeof(unsigned) : 0, s, d_maps, frames, n, nw, (unsigned)K, (unsigned)PK, (unsigned)T, d_pof, d_rows, d_px,
+                                   channels, d_pal, tol2, d_delta, d_shown, d_masks, d_flag);
+            };
+            if (in_lds) go(std::true_type{}); else go(std::false_type{});
         });
         HIP_CHECK(hipGetLastError());
     }

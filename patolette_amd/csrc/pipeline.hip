@@ -993,6 +993,7 @@ struct Engine {
     DevBuf<unsigned char> lut, dmap, src8, pal8, quant8;
     DevBuf<unsigned char> dl_maps, dl_shown;     // frame deltas from host maps: the maps (the deltas replace them in place), the shown maps
     DevBuf<unsigned long long> dl_words, dl_masks;   // ... the kernels' boxes, counts and flag; the ballots between them (delta.h)
+    DevBuf<unsigned> dl_rows;                    // ... per-frame palettes: every table's rows, a word each, then the frames' tables
     DevBuf<unsigned long long> ms_words;         // measure: the entries' slots, the flag and the folded results (measure.h)
     DevBuf<MeasureTile> ms_tiles;                // ... the tiles' records between its two kernels
     DevBuf<unsigned> ms_p8;                      // ... the palette's bytes, a word per row
@@ -3059,28 +3060,35 @@ static void stage_given(Engine &E, const void *maps, int eb, int me, size_t N, G
     HIP_CHECK(hipStreamSynchronize(s));
 }
 
-// The two flavours of the frame deltas: plain maps (patolette_amd_frame_deltas) and maps whose index 0 is the transparent entry
-// (patolette_amd_frame_deltas_rgba).  delta.h lays out the words the kernels leave.
+// The flavours of the frame deltas: plain maps (patolette_amd_frame_deltas), maps whose index 0 is the transparent entry
+// (patolette_amd_frame_deltas_rgba), and plain maps with a colour table per frame (patolette_amd_frame_deltas_local).  delta.h lays
+// out the words the kernels leave.
 struct DeltaFlavour {
     const char *bad_element;       // what a raised flag says
     bool v_boxes;                  // per frame a second box, V (what vanishes in the next frame): 5 words a slot instead of 3, and a disposal
     bool first_full;               // frame 0 is the full first map whatever the kernels counted
     bool free_index;               // the caller's transparent index T, an index no entry uses, travels as given_transparent_on_device(T)
 };
+// Per-frame palettes: P tables of K rows as bytes, and the table of every frame (checked: each below P).  `shown` is then colours,
+// 3 bytes a position, and a lossy run's `pal` holds all P K rows.
+struct DeltaTables { size_t P, K; std::vector<unsigned char> p8; std::vector<int32_t> of; };
 static const DeltaFlavour kPlainDeltas{"patolette_amd_frame_deltas: a map element is not below palette_rows, or names a dropped trailing (-1, -1, -1) row",
                                        false, true, true};
 static const DeltaFlavour kRgbaDeltas{"patolette_amd_frame_deltas_rgba: a map element is not below palette_rows, or names a dropped trailing (-1, -1, -1) row",
                                       true, false, false};
+static const DeltaFlavour kLocalDeltas{"patolette_amd_frame_deltas_local: a map element is not below palette_rows", false, true, true};
 
 // maps: frames x width x height elements of `eb` bytes; rows: what every element must stay below (lossy: the used rows of pal, planar
 // (rows,3) f64 sRGB; otherwise pal is empty and neither it nor the pixels are read).  T (plain maps) and loop (RGBA maps): the
 // flavour's own argument.  `maps`, `pixels`, `delta_out`, `shown_out` are device pointers when `on_device`; rects, disposals (RGBA maps)
-// and changed are host memory.  Every output may be null; delta_out may be maps.
+// and changed are host memory.  Every output may be null; delta_out may be maps.  tables: the per-frame palettes, or null.
 static void run_frame_deltas(Engine &E, const DeltaFlavour &fl, bool on_device, size_t frames, size_t width, size_t height, const void *maps, int eb,
                              size_t rows, size_t T, int loop, const unsigned char *pixels, int channels, std::vector<double> pal, double tolerance,
-                             void *delta_out, void *shown_out, int32_t *rects, int32_t *disposals, uint64_t *changed) {
+                             void *delta_out, void *shown_out, int32_t *rects, int32_t *disposals, uint64_t *changed,
+                             const DeltaTables *tables = nullptr) {
     const bool lossy = tolerance > 0.0;
     const size_t n = width * height, N = frames * n, cells = frames * (size_t)kDeltaSlots;
+    const size_t pal_rows = tables ? tables->P * tables->K : rows, shown_bytes = N * (tables ? 3 : (size_t)given_device_elem(eb, on_device));
     hipStream_t s = E.stream;
     GivenRun run(E);
     const int me = given_device_elem(eb, on_device);
@@ -3089,9 +3097,10 @@ static void run_frame_deltas(Engine &E, const DeltaFlavour &fl, bool on_device, 
     const size_t words = fl.v_boxes ? frame_deltas_rgba_words(frames) : frame_deltas_words(frames);
     E.dl_words.reserve(words);
     if (!fl.v_boxes) E.dl_masks.reserve(frame_deltas_masks(frames, n));
-    if (!on_device && shown_out) E.dl_shown.reserve(N * (size_t)me);
+    if (!on_device && shown_out) E.dl_shown.reserve(shown_bytes);
     else if (fl.v_boxes && !shown_out) E.dl_shown.reserve(n * (size_t)me);         // the canvas between the frames' launches
-    if (lossy) { E.dpal.reserve(3 * rows); E.h_pal.reserve(3 * rows); }
+    if (lossy) { E.dpal.reserve(3 * pal_rows); E.h_pal.reserve(3 * pal_rows); }
+    if (tables) E.dl_rows.reserve(pal_rows + frames);
     const void *d_maps = maps;
     void *d_delta = delta_out, *d_shown = shown_out;
     const unsigned char *d_px = pixels;
@@ -3105,11 +3114,19 @@ static void run_frame_deltas(Engine &E, const DeltaFlavour &fl, bool on_device, 
     }
     run.lap(&patolette_amd__Stats::ms_upload);
     if (lossy) {
-        palette_rows(pal, rows, hm::color::srgb_to_ictcp);                         // as run_remap's nearest map takes its palette
-        upload_palette(E, pal, rows);
+        palette_rows(pal, pal_rows, hm::color::srgb_to_ictcp);                     // as run_remap's nearest map takes its palette
+        upload_palette(E, pal, pal_rows);
     }
     const double *d_pal = lossy ? E.dpal.p : nullptr;
-    if (fl.v_boxes)
+    std::vector<unsigned> local;                                                   // (pageable: the copy has left the host when it returns)
+    if (tables) {
+        local = given_row_words(tables->p8, pal_rows);
+        local.insert(local.end(), tables->of.begin(), tables->of.end());
+        HIP_CHECK(hipMemcpyAsync(E.dl_rows.p, local.data(), local.size() * sizeof(unsigned), hipMemcpyHostToDevice, s));
+        launch_frame_deltas_local((const unsigned char *)d_maps, frames, width, height, tables->K, tables->P, Td, lossy,
+                                  reinterpret_cast<const int *>(E.dl_rows.p + pal_rows), E.dl_rows.p, d_px, channels, d_pal, tolerance * tolerance,
+                                  (unsigned char *)d_delta, (unsigned char *)d_shown, E.dl_masks.p, E.dl_words.p, s);
+    } else if (fl.v_boxes)
         launch_frame_deltas_rgba(d_maps, me, frames, width, height, rows, loop, lossy, d_px, channels, d_pal, tolerance * tolerance, d_delta, d_shown,
                                  d_shown ? nullptr : E.dl_shown.p, E.dl_words.p, s);
     else
@@ -3133,6 +3150,7 @@ static void run_frame_deltas(Engine &E, const DeltaFlavour &fl, bool on_device, 
         const void *from[2] = {d_delta, d_shown};
         for (int o = 0; o < 2; o++) {
             if (!outs[o]) continue;
+            if (tables && o == 1) { HIP_CHECK(hipMemcpy(outs[o], from[o], shown_bytes, hipMemcpyDeviceToHost)); continue; }   // colours
             if (eb == me) { HIP_CHECK(hipMemcpy(outs[o], from[o], N * (size_t)me, hipMemcpyDeviceToHost)); continue; }
             HIP_CHECK(hipMemcpy(stage.data(), from[o], N * sizeof(unsigned), hipMemcpyDeviceToHost));   // (stage_given sized it; Td becomes T)
             given_elems_out(stage.data(), me, outs[o], eb, 0, N, fl.free_index, Td, T);
@@ -3979,6 +3997,40 @@ static void frame_deltas_rgba_entry(bool on_device, size_t frames, size_t width,
     });
 }
 
+// the deltas of maps with a colour table per frame (include/patolette_amd.h): the arguments, then run_frame_deltas
+static void frame_deltas_local_entry(bool on_device, size_t frames, size_t width, size_t height, const void *palette_maps,
+                                     const unsigned char *palettes_u8, size_t palette_count, size_t palette_rows, const int32_t *palette_of,
+                                     size_t transparent_index, const unsigned char *pixels, int channels, double tolerance, void *delta_maps,
+                                     unsigned char *shown_rgb, int32_t *rects, uint64_t *changed, int *exit_code) {
+    const ArgCheck arg{"patolette_amd_frame_deltas_local", exit_code};
+    if (!arg.shape(frames, width, height)) return;
+    if (!palette_maps) return (void)arg.fail(-1, "no maps");
+    if (palette_rows < 1 || palette_rows > 255) return (void)arg.fail(-1, "palette_rows must lie in [1, 255]: a GIF table of 256 rows leaves no free index");
+    if (palette_count < 1 || palette_count > 65536) return (void)arg.fail(-1, "palette_count must lie in [1, 65536]");
+    if (transparent_index < palette_rows || transparent_index > 255)
+        return (void)arg.fail(-1, "transparent_index must lie in [palette_rows, 255] (an index no table uses, in a one-byte element)");
+    if (!palettes_u8) return (void)arg.fail(-1, "no palettes");
+    if (!palette_of && palette_count != frames) return (void)arg.fail(-1, "without palette_of every frame has its own table: palette_count must equal frames");
+    if (!(std::isfinite(tolerance) && tolerance >= 0.0)) return (void)arg.fail(-1, "tolerance must be finite and not negative");
+    DeltaTables t{palette_count, palette_rows, {}, std::vector<int32_t>(frames)};
+    for (size_t f = 0; f < frames; f++) {
+        t.of[f] = palette_of ? palette_of[f] : (int32_t)f;
+        if (t.of[f] < 0 || (size_t)t.of[f] >= palette_count) return (void)arg.fail(-1, "a palette_of value does not lie in [0, palette_count)");
+    }
+    GivenPalette g;                                                                   // all P K rows as one byte palette
+    if (tolerance > 0.0) {
+        if (channels != 3 && channels != 4) return (void)arg.fail(-1, "channels must be 3 or 4");
+        if (!pixels) return (void)arg.fail(-1, "a tolerance above 0 needs the frames' pixels");
+    }
+    given_palette(nullptr, palettes_u8, palette_count * palette_rows, true, g);        // (bytes: nothing to reject)
+    if (!(tolerance > 0.0)) g.pal.clear();
+    t.p8 = std::move(g.p8);
+    *exit_code = guarded([&](Engine &E) {
+        run_frame_deltas(E, kLocalDeltas, on_device, frames, width, height, palette_maps, 1, palette_rows, transparent_index, 0, pixels, channels,
+                         std::move(g.pal), tolerance, delta_maps, shown_rgb, rects, nullptr, changed, &t);
+    });
+}
+
 // a map's error per entry and frame (include/patolette_amd.h): the arguments, then run_measure
 static void measure_entry(bool on_device, size_t frames, size_t width, size_t height, const unsigned char *pixels, int channels,
                           const void *palette_maps, int map_elem_bytes, const double *palette, const unsigned char *palette_u8, size_t palette_rows,
@@ -4173,6 +4225,24 @@ void patolette_amd_remap_rgba_u8_device(size_t frames, size_t width, size_t heig
 int patolette_amd_debug_rgba_stamp_quad(int mode) { return rgba_stamp_debug_quad(mode); }
 
 int patolette_amd_debug_delta_quad(int mode) { return delta_debug_quad(mode); }
+int patolette_amd_debug_delta_local_tables(int mode) { return delta_debug_local_tables(mode); }
+int patolette_amd_debug_delta_local_route(void) { return delta_local_route(); }
+
+void patolette_amd_frame_deltas_local(size_t frames, size_t width, size_t height, const unsigned char *palette_maps,
+                                      const unsigned char *palettes_u8, size_t palette_count, size_t palette_rows, const int32_t *palette_of,
+                                      size_t transparent_index, const unsigned char *pixels, int channels, double tolerance,
+                                      unsigned char *delta_maps, unsigned char *shown_rgb, int32_t *rects, uint64_t *changed, int *exit_code) {
+    frame_deltas_local_entry(false, frames, width, height, palette_maps, palettes_u8, palette_count, palette_rows, palette_of, transparent_index,
+                             pixels, channels, tolerance, delta_maps, shown_rgb, rects, changed, exit_code);
+}
+void patolette_amd_frame_deltas_local_device(size_t frames, size_t width, size_t height, const unsigned char *d_palette_maps,
+                                             const unsigned char *palettes_u8, size_t palette_count, size_t palette_rows,
+                                             const int32_t *palette_of, size_t transparent_index, const unsigned char *d_pixels, int channels,
+                                             double tolerance, unsigned char *d_delta_maps, unsigned char *d_shown_rgb, int32_t *rects,
+                                             uint64_t *changed, int *exit_code) {
+    frame_deltas_local_entry(true, frames, width, height, d_palette_maps, palettes_u8, palette_count, palette_rows, palette_of, transparent_index,
+                             d_pixels, channels, tolerance, d_delta_maps, d_shown_rgb, rects, changed, exit_code);
+}
 
 void patolette_amd_frame_deltas(size_t frames, size_t width, size_t height, const void *palette_maps, int map_elem_bytes, size_t palette_rows,
                                 size_t transparent_index, const unsigned char *pixels, int channels, const double *palette,
