@@ -907,6 +907,11 @@ int patolette_amd_debug_gq_table(const double *table, const uint32_t *counts, in
                                  uint64_t *prefix_w0, double *prefix, int *cut_table);
 /* out[i] = pow(x[i], y) as the colour conversions evaluate it on the device (x >= 0; <= 0.52 ulp) */
 int patolette_amd_pow(const double *x, double y, double *out, size_t n);
+/* Tests only: the same with the routine named.  mode 0: the general routine (any x); 1: the branch-free routine of the common domain
+ * (x positive, normal and finite, -1200 <= y log2(x) <= 1100: the caller's promise, nothing checks it); 2: what patolette_amd_pow
+ * runs -- a vote per wavefront picks 1 when every lane's x allows it and 0 otherwise.  All three return the same bits wherever 1
+ * is allowed.  Returns 0, or -1 on an unknown mode or a HIP error. */
+int patolette_amd_debug_pow(const double *x, double y, double *out, size_t n, int mode);
 
 enum {
     PAMD_SRGB_TO_ICTCP = 0,     /* patolette__COLOR_sRGB_Matrix_to_ICtCp_Matrix            color/ICtCp.c:120-146 */
@@ -919,6 +924,11 @@ enum {
 };
 /* in place on a planar (n,3) host matrix */
 int patolette_amd_convert(int which, double *planar, size_t n);
+/* Tests only: one conversion (the ids above, or 100 for the plain copy) of n pixels from a planar (n,3) f64 host matrix or from
+ * interleaved 8-bit rows with `channels` (3 or 4) bytes per pixel (exactly one of planar / bytes is non-NULL; bytes / 255 are read
+ * as coordinates of the source space whatever it is) into the planar (n,3) host matrix out.  general != 0: every pow through the
+ * general routine, whatever the wavefront's vote would say.  Returns 0, or -1 on bad arguments or a HIP error. */
+int patolette_amd_debug_convert(int which, const double *planar, const unsigned char *bytes, int channels, double *out, size_t n, int general);
 
 /* patolette__GQ_quantize + patolette__LQ_quantize + patolette__PALETTE_create
  * (quantize/global.c:388-443, quantize/local.c:318-404, palette/create.c:11-33).

@@ -160,7 +160,9 @@ SYMBOLS = {
                                       C.POINTER(QuantizationOptions), C.POINTER(dp), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int,
                                       C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
     "patolette_amd_pow": (C.c_int, [dp, C.c_double, dp, C.c_size_t]),
+    "patolette_amd_debug_pow": (C.c_int, [dp, C.c_double, dp, C.c_size_t, C.c_int]),
     "patolette_amd_convert": (C.c_int, [C.c_int, dp, C.c_size_t]),
+    "patolette_amd_debug_convert": (C.c_int, [C.c_int, dp, C.c_void_p, C.c_int, dp, C.c_size_t, C.c_int]),
     "patolette_amd_quantize_clusters": (C.c_int, [dp, dp, C.c_size_t, C.c_size_t, dp, zp]),
     "patolette_amd_kmeans_refine": (C.c_int, [dp, dp, C.c_size_t, dp, C.c_size_t, C.c_int, C.c_size_t]),
     "patolette_amd_nn_map": (C.c_int, [dp, C.c_size_t, dp, C.c_size_t, zp]),

@@ -5,8 +5,12 @@
 // the CIELuv no-dither path is three full sweeps, patolette.c:305-314); here every chain is
 // one kernel: 3 coalesced 8-byte loads per pixel, the whole chain in registers, 3 stores.
 // Arithmetic follows the reference expression by expression in f64 with contraction off;
-// only pow() differs (ocml vs glibc, last-ulp).  Bound: 48 B/px of HBM traffic; ~9 f64 pow
-// per pixel make the ICtCp chain VALU-heavy, still under the HBM time at 16 B/lane loads.
+// only pow() differs: pamd_pow (color_device.h), a table-and-series routine within 0.52 ulp,
+// 99.8 % of its results glibc's.  Bound: 48 B/px of HBM traffic would take 0.16 ms at 4096^2;
+// the nine f64 pow of an ICtCp pixel make the kernel VALU-issue-bound at three times that
+// (~860 vector instructions per pixel at ~5 cycles each, four waves per SIMD).  A pixel runs
+// its pow on the branch-free pamd_pow_pos first; one vote per pixel sends a wavefront that
+// holds an operand outside that routine's domain through the general route again.
 #define PAMD_POW_TABLES_IN_LDS
 #include "color_device.h"
 #include "common.h"
@@ -18,9 +22,12 @@ namespace pamd {
 
 // sumk.M0 != 0: also accumulate the column sums of the output (order-independent binned parts; the bound behind sumk
 // is a property of the colour space, so it is known before the pass)
+// amdgpu_waves_per_eu(4, 4): with the pow chains free of branches the scheduler overlaps them as far as registers reach (165 VGPRs
+// for the ICtCp chain, three waves per SIMD); the kernel is bound by VALU issue and wants the fourth wave more than that overlap
 template <int WHICH, class SRC>
-__global__ __launch_bounds__(256) void k_convert(SRC src, double *__restrict__ dst, size_t n, ConvertStats *stats, BinK sumk, BinK momk,
-                                                 size_t begin, size_t end) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_convert(SRC src, double *__restrict__ dst, size_t n, ConvertStats *stats, BinK sumk, BinK momk,
+                                                 size_t begin, size_t end, int general) {
+    // general != 0 (tests only): every pixel takes the general pow, whatever its wavefront holds
     // pixels [begin, end) of the n-pixel image (n = plane stride): the host entry converts an image chunk by chunk behind its upload
     // per-plane min / max of the OUTPUT (bounds for the binned accumulators downstream)
     double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
@@ -33,6 +40,7 @@ __global__ __launch_bounds__(256) void k_convert(SRC src, double *__restrict__ d
     double acc2[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     constexpr bool kLut = std::is_same<SRC, SrcU8>::value && (WHICH == PAMD_SRGB_TO_ICTCP || WHICH == PAMD_SRGB_TO_CIELUV || WHICH == PAMD_SRGB_TO_REC2020);
     __shared__ double glut[kLut ? 256 : 1];                // companding of the 256 possible 8-bit values (sRGB.c:70-89)
+    const PowMode pk = pow_fast();
     pow_tables_to_lds();
     __syncthreads();
     if constexpr (kLut) {
@@ -64,7 +72,21 @@ __global__ __launch_bounds__(256) void k_convert(SRC src, double *__restrict__ d
         if constexpr (kLut) { c[0] = glut[nr]; c[1] = glut[ng]; c[2] = glut[nb]; }
         else { c[0] = nxt[0]; c[1] = nxt[1]; c[2] = nxt[2]; }
         if (i + stride < end) { if constexpr (kLut) src.load_bytes(i + stride, nr, ng, nb); else src.load(i + stride, nxt); }
-        if constexpr (kLut) dev_convert_linear<WHICH>(c); else dev_convert<WHICH>(c);
+        // every pow on the branch-free routine; a wavefront with a lane outside its domain converts the pixel again (color_device.h)
+        // (the second turn reads its pixel from memory again: kept in registers it would cost the first turn six VGPRs)
+        pk.ok = general == 0;
+        if constexpr (kLut) dev_convert_linear<WHICH>(c, pk); else dev_convert<WHICH>(c, pk);
+        if (__builtin_expect(!__all(pk.ok), 0)) {
+            if constexpr (kLut) {
+                unsigned r, g, b;
+                src.load_bytes(i, r, g, b);
+                c[0] = glut[r]; c[1] = glut[g]; c[2] = glut[b];
+                dev_convert_linear<WHICH>(c);
+            } else {
+                src.load(i, c);
+                dev_convert<WHICH>(c);
+            }
+        }
         finish(i, c);
     }
     if (do_sum) {                                          // block-uniform
@@ -155,23 +177,24 @@ static int stream_grid(size_t n) {
     return (int)b;
 }
 
-// begin / end: the pixels to convert (the whole image by default); init_stats: clear the statistics first (the first chunk)
+// begin / end: the pixels to convert (the whole image by default); init_stats: clear the statistics first (the first chunk);
+// general (tests only): every pow through pamd_pow
 void launch_convert(int which, const double *src_p, double *dst, size_t n, ConvertStats *stats, hipStream_t s, BinK sumk, BinK momk,
-                    size_t begin, size_t end, bool init_stats) {
+                    size_t begin, size_t end, bool init_stats, bool general) {
     if (end > n) end = n;
     if (stats && init_stats) hipLaunchKernelGGL(k_init_stats, 1, 64, 0, s, stats);
     int g = stream_grid(end - begin);
     KTIME("k_convert", s, 48.0 * (end - begin));
     const SrcF64 src{src_p, n};
     switch (which) {
-        case PAMD_SRGB_TO_ICTCP: hipLaunchKernelGGL((k_convert<PAMD_SRGB_TO_ICTCP, SrcF64>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end); break;
-        case PAMD_SRGB_TO_CIELUV: hipLaunchKernelGGL((k_convert<PAMD_SRGB_TO_CIELUV, SrcF64>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end); break;
-        case PAMD_ICTCP_TO_REC2020: hipLaunchKernelGGL((k_convert<PAMD_ICTCP_TO_REC2020, SrcF64>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end); break;
-        case PAMD_CIELUV_TO_REC2020: hipLaunchKernelGGL((k_convert<PAMD_CIELUV_TO_REC2020, SrcF64>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end); break;
-        case PAMD_SRGB_TO_REC2020: hipLaunchKernelGGL((k_convert<PAMD_SRGB_TO_REC2020, SrcF64>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end); break;
-        case PAMD_REC2020_TO_SRGB: hipLaunchKernelGGL((k_convert<PAMD_REC2020_TO_SRGB, SrcF64>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end); break;
-        case PAMD_CIELUV_TO_ICTCP: hipLaunchKernelGGL((k_convert<PAMD_CIELUV_TO_ICTCP, SrcF64>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end); break;
-        case PAMD_COPY: hipLaunchKernelGGL((k_convert<PAMD_COPY, SrcF64>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end); break;
+        case PAMD_SRGB_TO_ICTCP: hipLaunchKernelGGL((k_convert<PAMD_SRGB_TO_ICTCP, SrcF64>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end, (int)general); break;
+        case PAMD_SRGB_TO_CIELUV: hipLaunchKernelGGL((k_convert<PAMD_SRGB_TO_CIELUV, SrcF64>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end, (int)general); break;
+        case PAMD_ICTCP_TO_REC2020: hipLaunchKernelGGL((k_convert<PAMD_ICTCP_TO_REC2020, SrcF64>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end, (int)general); break;
+        case PAMD_CIELUV_TO_REC2020: hipLaunchKernelGGL((k_convert<PAMD_CIELUV_TO_REC2020, SrcF64>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end, (int)general); break;
+        case PAMD_SRGB_TO_REC2020: hipLaunchKernelGGL((k_convert<PAMD_SRGB_TO_REC2020, SrcF64>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end, (int)general); break;
+        case PAMD_REC2020_TO_SRGB: hipLaunchKernelGGL((k_convert<PAMD_REC2020_TO_SRGB, SrcF64>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end, (int)general); break;
+        case PAMD_CIELUV_TO_ICTCP: hipLaunchKernelGGL((k_convert<PAMD_CIELUV_TO_ICTCP, SrcF64>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end, (int)general); break;
+        case PAMD_COPY: hipLaunchKernelGGL((k_convert<PAMD_COPY, SrcF64>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end, (int)general); break;
         default: throw HipError("patolette_amd: unknown conversion");
     }
     HIP_CHECK(hipGetLastError());
@@ -183,28 +206,34 @@ void launch_convert_rows(int which, const double *rows, double *dst, size_t n, C
     if (stats && init_stats) hipLaunchKernelGGL(k_init_stats, 1, 64, 0, s, stats);
     int g = stream_grid(end - begin);
     KTIME("k_convert", s, 48.0 * (end - begin));
+    const bool general = false;
     const SrcF64Rows src{rows};
     switch (which) {
-        case PAMD_SRGB_TO_ICTCP: hipLaunchKernelGGL((k_convert<PAMD_SRGB_TO_ICTCP, SrcF64Rows>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end); break;
-        case PAMD_SRGB_TO_CIELUV: hipLaunchKernelGGL((k_convert<PAMD_SRGB_TO_CIELUV, SrcF64Rows>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end); break;
-        case PAMD_COPY: hipLaunchKernelGGL((k_convert<PAMD_COPY, SrcF64Rows>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end); break;
+        case PAMD_SRGB_TO_ICTCP: hipLaunchKernelGGL((k_convert<PAMD_SRGB_TO_ICTCP, SrcF64Rows>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end, (int)general); break;
+        case PAMD_SRGB_TO_CIELUV: hipLaunchKernelGGL((k_convert<PAMD_SRGB_TO_CIELUV, SrcF64Rows>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end, (int)general); break;
+        case PAMD_COPY: hipLaunchKernelGGL((k_convert<PAMD_COPY, SrcF64Rows>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end, (int)general); break;
         default: throw HipError("patolette_amd: unknown conversion");
     }
     HIP_CHECK(hipGetLastError());
 }
 
 void launch_convert_u8(int which, const unsigned char *pixels, int channels, double *dst, size_t n, ConvertStats *stats,
-                       hipStream_t s, BinK sumk, BinK momk, size_t begin, size_t end, bool init_stats) {
+                       hipStream_t s, BinK sumk, BinK momk, size_t begin, size_t end, bool init_stats, bool general) {
     if (end > n) end = n;
     if (stats && init_stats) hipLaunchKernelGGL(k_init_stats, 1, 64, 0, s, stats);
     int g = stream_grid(end - begin);
     KTIME("k_convert_u8", s, (24.0 + channels) * (end - begin));
     const SrcU8 src{pixels, channels};
     switch (which) {
-        case PAMD_SRGB_TO_ICTCP: hipLaunchKernelGGL((k_convert<PAMD_SRGB_TO_ICTCP, SrcU8>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end); break;
-        case PAMD_SRGB_TO_CIELUV: hipLaunchKernelGGL((k_convert<PAMD_SRGB_TO_CIELUV, SrcU8>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end); break;
-        case PAMD_SRGB_TO_REC2020: hipLaunchKernelGGL((k_convert<PAMD_SRGB_TO_REC2020, SrcU8>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end); break;   // the remap entry's dither
-        case PAMD_COPY: hipLaunchKernelGGL((k_convert<PAMD_COPY, SrcU8>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end); break;
+        case PAMD_SRGB_TO_ICTCP: hipLaunchKernelGGL((k_convert<PAMD_SRGB_TO_ICTCP, SrcU8>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end, (int)general); break;
+        case PAMD_SRGB_TO_CIELUV: hipLaunchKernelGGL((k_convert<PAMD_SRGB_TO_CIELUV, SrcU8>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end, (int)general); break;
+        case PAMD_SRGB_TO_REC2020: hipLaunchKernelGGL((k_convert<PAMD_SRGB_TO_REC2020, SrcU8>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end, (int)general); break;   // the remap entry's dither
+        // the four below: reached by patolette_amd_debug_convert only (bytes / 255 read as that space's coordinates)
+        case PAMD_ICTCP_TO_REC2020: hipLaunchKernelGGL((k_convert<PAMD_ICTCP_TO_REC2020, SrcU8>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end, (int)general); break;
+        case PAMD_CIELUV_TO_REC2020: hipLaunchKernelGGL((k_convert<PAMD_CIELUV_TO_REC2020, SrcU8>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end, (int)general); break;
+        case PAMD_REC2020_TO_SRGB: hipLaunchKernelGGL((k_convert<PAMD_REC2020_TO_SRGB, SrcU8>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end, (int)general); break;
+        case PAMD_CIELUV_TO_ICTCP: hipLaunchKernelGGL((k_convert<PAMD_CIELUV_TO_ICTCP, SrcU8>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end, (int)general); break;
+        case PAMD_COPY: hipLaunchKernelGGL((k_convert<PAMD_COPY, SrcU8>), g, 256, 0, s, src, dst, n, stats, sumk, momk, begin, end, (int)general); break;
         default: throw HipError("patolette_amd: unknown conversion");
     }
     HIP_CHECK(hipGetLastError());
@@ -248,14 +277,23 @@ void launch_reconstruct(const void *map, int map_elem, size_t n, const unsigned 
     HIP_CHECK(hipGetLastError());
 }
 
+// MODE 0: pamd_pow; 1: pamd_pow_pos, every x inside its domain (the caller's promise); 2: pow_auto, what the conversions call
+template <int MODE>
 __global__ __launch_bounds__(256) void k_pow(const double *__restrict__ x, double y, double *__restrict__ out, size_t n) {
     pow_tables_to_lds();
     __syncthreads();
     const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = pamd_pow(x[i], y);
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        if constexpr (MODE == 0) out[i] = pamd_pow(x[i], y);
+        else if constexpr (MODE == 1) out[i] = pamd_pow_pos(x[i], y);
+        else out[i] = pow_voted([&](const PowMode &k) { return pow_auto(x[i], y, k); });
+    }
 }
-void launch_pow(const double *x, double y, double *out, size_t n, hipStream_t s) {
-    hipLaunchKernelGGL(k_pow, stream_grid(n), 256, 0, s, x, y, out, n);
+void launch_pow(const double *x, double y, double *out, size_t n, hipStream_t s, int mode) {
+    if (mode == 0) hipLaunchKernelGGL(k_pow<0>, stream_grid(n), 256, 0, s, x, y, out, n);
+    else if (mode == 1) hipLaunchKernelGGL(k_pow<1>, stream_grid(n), 256, 0, s, x, y, out, n);
+    else if (mode == 2) hipLaunchKernelGGL(k_pow<2>, stream_grid(n), 256, 0, s, x, y, out, n);
+    else throw HipError("patolette_amd: unknown pow mode");
     HIP_CHECK(hipGetLastError());
 }
 

@@ -40,17 +40,18 @@ namespace pamd {
 
 // launchers defined in color.hip
 void launch_convert(int which, const double *src, double *dst, size_t n, ConvertStats *stats, hipStream_t s, BinK sumk = BinK{0.0, 0.0},
-                    BinK momk = BinK{0.0, 0.0}, size_t begin = 0, size_t end = ~(size_t)0, bool init_stats = true);
+                    BinK momk = BinK{0.0, 0.0}, size_t begin = 0, size_t end = ~(size_t)0, bool init_stats = true,
+                    bool general = false);
 void launch_convert_rows(int which, const double *rows, double *dst, size_t n, ConvertStats *stats, hipStream_t s,
                          BinK sumk = BinK{0.0, 0.0}, BinK momk = BinK{0.0, 0.0}, size_t begin = 0, size_t end = ~(size_t)0,
                          bool init_stats = true);
 void launch_convert_u8(int which, const unsigned char *pixels, int channels, double *dst, size_t n, ConvertStats *stats,
                        hipStream_t s, BinK sumk = BinK{0.0, 0.0}, BinK momk = BinK{0.0, 0.0}, size_t begin = 0, size_t end = ~(size_t)0,
-                       bool init_stats = true);
+                       bool init_stats = true, bool general = false);
 void launch_reconstruct(const void *map, int map_elem, size_t n, const unsigned char *pal_u8, int k, unsigned char *out,
                         hipStream_t s);
 void launch_weight_stats(const double *w, size_t n, ConvertStats *stats, hipStream_t s);
-void launch_pow(const double *x, double y, double *out, size_t n, hipStream_t s);
+void launch_pow(const double *x, double y, double *out, size_t n, hipStream_t s, int mode);
 void launch_fill_image(double *d, size_t n, uint64_t seed, hipStream_t s);
 void launch_fill_weights(double *d, size_t n, uint64_t seed, hipStream_t s);
 
@@ -4656,14 +4657,36 @@ void patolette_amd_batch_rows(size_t count, size_t width, size_t height, const d
     batch_impl(true, count, width, height, rows, weights, tile_size, palette_size, options, palettes, palette_maps, exit_codes);
 }
 
-int patolette_amd_pow(const double *x, double y, double *out, size_t n) {
+static int pow_entry(const double *x, double y, double *out, size_t n, int mode) {
     return guarded([&](Engine &E) -> int {
         if (n == 0) return 0;
+        if (mode < 0 || mode > 2) return -1;
         E.src.reserve(2 * n);
         HIP_CHECK(hipMemcpyAsync(E.src.p, x, n * sizeof(double), hipMemcpyHostToDevice, E.stream));
-        launch_pow(E.src.p, y, E.src.p + n, n, E.stream);
+        launch_pow(E.src.p, y, E.src.p + n, n, E.stream, mode);
         HIP_CHECK(hipMemcpyAsync(out, E.src.p + n, n * sizeof(double), hipMemcpyDeviceToHost, E.stream));
         E.sync();
+        return 0;
+    });
+}
+int patolette_amd_pow(const double *x, double y, double *out, size_t n) { return pow_entry(x, y, out, n, 2); }
+int patolette_amd_debug_pow(const double *x, double y, double *out, size_t n, int mode) { return pow_entry(x, y, out, n, mode); }
+
+int patolette_amd_debug_convert(int which, const double *planar, const unsigned char *bytes, int channels, double *out, size_t n, int general) {
+    return guarded([&](Engine &E) -> int {
+        if (n == 0) return 0;
+        if ((planar == nullptr) == (bytes == nullptr) || (bytes && (channels < 3 || channels > 4))) return -1;
+        E.src.reserve(3 * n); E.aux.reserve(3 * n);
+        if (planar) {
+            HIP_CHECK(hipMemcpy(E.src.p, planar, 3 * n * sizeof(double), hipMemcpyHostToDevice));
+            launch_convert(which, E.src.p, E.aux.p, n, nullptr, E.stream, BinK{0.0, 0.0}, BinK{0.0, 0.0}, 0, n, true, general != 0);
+        } else {
+            HIP_CHECK(hipMemcpy(E.src.p, bytes, n * (size_t)channels, hipMemcpyHostToDevice));
+            launch_convert_u8(which, reinterpret_cast<const unsigned char *>(E.src.p), channels, E.aux.p, n, nullptr, E.stream, BinK{0.0, 0.0},
+                              BinK{0.0, 0.0}, 0, n, true, general != 0);
+        }
+        E.sync();
+        HIP_CHECK(hipMemcpy(out, E.aux.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
         return 0;
     });
 }
