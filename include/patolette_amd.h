@@ -594,6 +594,14 @@ void patolette_amd_png_deflate(size_t frames, size_t width, size_t height, const
 void patolette_amd_png_deflate_device(size_t frames, size_t width, size_t height, const unsigned char *d_maps, const int32_t *rects,
                                       size_t segment, unsigned char *out, size_t capacity, uint64_t *offsets, uint32_t *adler,
                                       int *exit_code);
+/* tests: one deflate block as the HOST writes it for a token list, by the routines the kernel shares with it (csrc/deflate_codes.h,
+ *   write_block).  Host code only: it never touches the device and works without one.
+ *   tokens[count]: a literal (0 .. 255) or 0x80000000 | (length - 3) << 16 | (distance - 1) with length 3 .. 258 and distance
+ *   1 .. 32768; the end of block is appended here.  final_block: BFINAL.  The block starts at bit 0 of out[0]; *bits = its bits, and
+ *   its ceil(bits / 8) bytes go to out when capacity holds them (the last byte's unused bits zero).
+ * Returns 0; -1 for a null argument, a token that is none of the above or too little capacity (*bits is still written then). */
+int patolette_amd_debug_deflate_block(const uint32_t *tokens, size_t count, int final_block, unsigned char *out, size_t capacity,
+                                      uint64_t *bits);
 
 /* The lossy coder's table for a palette.  Host code only: it never touches the device and works without one.
  *   palette / palette_u8, palette_rows: exactly one of the two, as patolette_amd_remap_u8 takes them (trailing (-1, -1, -1) rows of an

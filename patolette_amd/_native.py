@@ -138,6 +138,7 @@ SYMBOLS = {
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
     **_pair("patolette_amd_png_deflate", None, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.POINTER(C.c_int32), C.c_size_t,
                                                 C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
+    "patolette_amd_debug_deflate_block": (C.c_int, [C.POINTER(C.c_uint32), C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
     "patolette_amd_gif_neighbours": (None, [dp, C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
     **_pair("patolette_amd_rgba", None, [C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_size_t,
                                          C.POINTER(QuantizationOptions), dp, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,

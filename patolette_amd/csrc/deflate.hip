@@ -12,7 +12,8 @@
 //     last earlier position of the segment with the same three bytes (a hash table in LDS, read before the step's own positions enter
 //     it), and the up to four distances its explorations have found (below); every candidate within the frame and the 32 KB window
 //     counts, also before the segment's start.  Each lane extends its
-//     candidates four bytes at a time and keeps the longest (the nearest among equals).  The serial part is a wave-uniform walk over
+//     candidates four bytes at a time and keeps the longest (the first among equals in the order tried -- the order above, the
+//     remembered distances and the hashed one last --, which is not the nearest: 8 comes before R - 1).  The serial part is a wave-uniform walk over
 //     the 64 lengths: take the match at p unless the one at p + 1 is longer (one step of lazy evaluation), then jump.  It leaves two
 //     64-bit masks (token starts, matches); the lanes at the starts then write their tokens side by side (a popcount gives the
 //     place) and count them into the two histograms.

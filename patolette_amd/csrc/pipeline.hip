@@ -4314,6 +4314,25 @@ void patolette_amd_png_deflate_device(size_t frames, size_t width, size_t height
     png_deflate_entry(true, frames, width, height, d_maps, rects, segment, out, capacity, offsets, adler, exit_code);
 }
 
+// tests: the host's block for a token list (deflate_codes.h, write_block); no device, no engine
+int patolette_amd_debug_deflate_block(const uint32_t *tokens, size_t count, int final_block, unsigned char *out, size_t capacity, uint64_t *bits) {
+    if (!bits || (count && !tokens)) return -1;
+    *bits = 0;
+    for (size_t i = 0; i < count; i++) {                                // literals below 256; a match's unused bits clear, its length within 258
+        const uint32_t t = tokens[i];
+        if (dc::tok_is_match(t) ? (t & 0x7f008000u) != 0 || dc::tok_len(t) > dc::kMaxMatch : t > 255u) return -1;
+    }
+#if defined(__HIP_DEVICE_COMPILE__)                                     // (write_block exists in the host's pass alone)
+    return -1;
+#else
+    dc::BitWriter bw;
+    *bits = dc::write_block(tokens, count, final_block != 0, bw);
+    if (!out || bw.bytes.size() > capacity) return -1;
+    if (!bw.bytes.empty()) std::memcpy(out, bw.bytes.data(), bw.bytes.size());
+    return 0;
+#endif
+}
+
 void patolette_amd_gif_lzw_lossy(size_t frames, size_t width, size_t height, const unsigned char *maps, const int32_t *rects, int min_code_size,
                                  size_t segment, const unsigned char *near, unsigned char *coded, unsigned char *out, size_t capacity,
                                  uint64_t *offsets, int *exit_code) {

@@ -300,6 +300,10 @@ def test_symbols_are_declared_bound_and_exported():
         assert "void %s(" % name in header and name in _native.SYMBOLS
         restype, argtypes = _native.SYMBOLS[name]
         assert restype is None and len(argtypes) == 11 and argtypes[-1] == C.POINTER(C.c_int) and argtypes[-2] == C.POINTER(C.c_uint32)
+    assert "int patolette_amd_debug_deflate_block(" in header                      # host code only: tests/test_deflate_model.py calls it
+    restype, argtypes = _native.SYMBOLS["patolette_amd_debug_deflate_block"]
+    assert restype is C.c_int and len(argtypes) == 6 and argtypes[-1] == C.POINTER(C.c_uint64)
+    assert hasattr(_native.lib(), "patolette_amd_debug_deflate_block")
     for name in ("png_deflate", "png_deflate_bound", "write_png", "write_apng"):
         assert name in patolette_amd.__all__ and callable(getattr(patolette_amd, name))
     assert "deflate.hip" in open(os.path.join(HERE, "..", "patolette_amd", "csrc", "Makefile")).read()
